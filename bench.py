@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """ConceptHash encode-and-retrieve benchmark (BASELINE.json metric), one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without WORLD_SIZE: starts its own N ranks)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without WORLD_SIZE: starts its own N ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given, and prints the
+JSON line: nothing else runs in it.  Everything else the line can carry (roofline pass, per-batch figures, Hamming blocks, CPU
+baselines, pcie / decode / loader / evaluator / training blocks) runs only with --full, after the timed region.
 
 One STEP (per rank) = the hot path over one batch of synthetic input already resident in HBM:
   encode 256 synthetic 224x224 bf16 images with the ViT-B/16 ConceptHash model (64-bit codes, Q=4 concept tokens,
@@ -14,10 +18,10 @@ images/s = N * 256 * K / max-over-ranks time.  Weak scaling: per-rank batch and 
 
 `value` is measured in the library's default launch mode: the batch as TWO micro-batches whose launch chains run on two HIP
 streams (bit-identical codes; `--streams 1` = one chain).  Per-kernel durations stop describing single kernels once launches
-overlap, so the `roofline` numbers come from a second, single-stream pass of the same K steps (HIP events on the launch stream
+overlap, so the `roofline` numbers (--full) come from a second, single-stream pass of the same K steps (HIP events on the launch stream
 around every launch), run right after the timed region; `roofline_pass` says so and gives that pass's ms/step.
 
-Also reported (outside the timed region, same process): the Hamming scan and mAP@all on the 1M x 128-bit synthetic gallery
+Also reported with --full (outside the timed region, same process): the Hamming scan and mAP@all on the 1M x 128-bit synthetic gallery
 (BASELINE.json config 5 size; N > 1: the gallery sharded by rows across the ranks) and at the NABirds / CUB sizes, and --
 rank 0, N == 1 only -- the CPU baselines on the host cores, on bounded samples of the same workloads.
 """
@@ -65,10 +69,17 @@ def parse_args():
     ap.add_argument("--no-loader", action="store_true", help="skip the loader-inclusive block (JPEG files -> DataLoader -> decode -> encode)")
     ap.add_argument("--loader-images", type=int, default=8192, help="JPEG files the loader-inclusive block generates and reads")
     ap.add_argument("--encode-only", action="store_true",
-                    help="nothing but the timed encode + retrieve steps (and the roofline pass unless --no-roofline-pass): no "
+                    help="with --full: nothing but the timed encode + retrieve steps and the roofline pass (unless --no-roofline-pass): no "
                          "pcie / decode / evaluator / training / Hamming-scan / CPU-baseline blocks -- what the rocprofv3 passes of "
                          "tools/profile_round.sh trace, so that every kernel row of a summary is the encoder's")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the roofline pass and every extra block of the line (each still subject "
+                         "to its --no-* option and to --encode-only); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (codes float32, top-k indices and distances float64)")
     a = ap.parse_args()
+    if not a.full:      # a plain run: set-up, warm-up, the timed steps, outputs, the line
+        a.encode_only = a.no_roofline_pass = True
     if a.encode_only:
         a.no_cpu_baseline = a.no_hamming_scan = a.no_train_step = a.no_evaluator = a.no_loader = True
     return a
@@ -209,6 +220,8 @@ def main():
         dist.all_gather_object(rank_info, mine)
     assert torch.isfinite(codes).all()
     log(f"[bench r{rank}] timed region: {args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:     # N > 1: rank 0's codes; the merged top-k lists cover every rank's queries
+        dump_outputs(np, args.dump_outputs, codes=codes, topk_index=idx, topk_distance=dst)
 
     # ---- roofline pass: the same K steps as ONE launch chain on one stream, every launch bracketed by HIP events ----------
     prof, prof_ms_per_step, codes_same = None, None, None
@@ -298,6 +311,16 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(np, path, **tensors):
+    """What the caller of the timed step receives, as <name>.npy: float32 stays float32, integers become float64 (exact: indices
+    and distances are far below 2**53).  About 100 KiB at the default sizes."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a if a.dtype == np.float32 else a.astype(np.float64))
+    log(f"[bench] outputs of the last timed step written to {path}: {', '.join(tensors)}")
 
 
 def backend_name(dist):

@@ -16,6 +16,7 @@ import ctypes
 import os
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,7 @@ from concepthash_amd.encoder import ConceptHashEncoder
 
 def build_victim():
     src = os.path.join(ROOT, "tools", "repro", "pk_opsel_victim.hip")
-    out = "/tmp/libpkvictim.so"
+    out = os.path.join(tempfile.mkdtemp(prefix="pkvictim_"), "libpkvictim.so")   # a fixed path would collide with another user's copy
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", src, "-o", out], check=True)
     lib = ctypes.CDLL(out)
     lib.pk_victim_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]

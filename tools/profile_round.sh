@@ -2,7 +2,7 @@
 # Reproduces the profiles/ evidence of a round on a 1-GPU MI355X box (run from the repo root, e.g. through gpurun):
 #   bash tools/profile_round.sh r03 [enc|ham|train|probes|all]
 # rocprofv3 runs from /tmp (TMPDIR=/tmp); counters are collected in their own passes (no trace domains next to --pmc).
-# ENCODER passes trace `bench.py --encode-only --streams 1`: nothing but the encode + retrieve steps runs in the traced process
+# ENCODER passes trace `bench.py --full --encode-only --streams 1`: nothing but the encode + retrieve steps runs in the traced process
 # (no training step, no pcie / decode / evaluator blocks), one launch chain, so every GEMM row of a summary is one shape of the
 # encoder.  The training step is profiled only through tools/train_bench.py.
 set -o pipefail
@@ -12,7 +12,7 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-ENC="python3 $R/bench.py --streams 1 --encode-only"
+ENC="python3 $R/bench.py --full --streams 1 --encode-only"
 cd /tmp
 if [ "$WHAT" = all ] || [ "$WHAT" = enc ]; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/enc_trace -o enc -- $ENC --steps 10 --warmup 3 > $O/enc_trace.json 2> $O/enc_trace.err || exit 1
@@ -46,6 +46,6 @@ if [ "$WHAT" = all ] || [ "$WHAT" = probes ]; then
   python tools/error_growth.py > $O/error_growth.txt 2>&1
 fi
 if [ "$WHAT" = all ]; then
-  python bench.py > $O/bench.json 2> $O/bench.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
 fi
 echo "summaries under $O: copy the ones to be judged into profiles/ (${TAG}_*)"
