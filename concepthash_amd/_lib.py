@@ -27,6 +27,12 @@ class ImageDesc(Structure):
                [(n, c_int32) for n in ("h", "w", "nh", "nw", "top", "left", "row0", "nrows", "stride", "flip")]
 
 
+class AugmentDesc(Structure):
+    _fields_ = [("src_offset", c_int64), ("tmp_offset", c_int64), ("img_offset", c_int64)] + \
+               [(n, c_int32) for n in ("h", "w", "nh", "nw", "top", "left", "row0", "nrows", "flip", "op", "iparam", "reserved")] + \
+               [("fparam", c_double), ("m", c_double * 6)]
+
+
 class JpegDesc(Structure):
     _fields_ = [("coef_offset", c_int64), ("pix_offset", c_int64), ("plane_offset", c_int64)] + \
                [(n, c_int32) for n in ("width", "height", "ncomp", "hs", "vs", "mcu_w", "mcu_h", "status", "nblocks", "reserved")] + \
@@ -67,6 +73,9 @@ SIGNATURES = {
     "ch_preprocess": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p,
                               c_int32, c_void_p, c_void_p]),
     "ch_preprocess_max_taps": (c_int32, []),
+    "ch_augment_workspace": (c_int64, [c_int32, c_int64]),
+    "ch_preprocess_augment": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float),
+                                      c_void_p, c_int32, c_void_p, c_void_p]),
     "ch_jpeg_plan": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "ch_jpeg_entropy_decode": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32]),
     "ch_jpeg_plan_packed": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),

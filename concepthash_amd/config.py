@@ -257,7 +257,8 @@ def locate(target: str):
     try:
         return getattr(importlib.import_module(mod), attr)
     except ModuleNotFoundError:
-        # torchvision is absent in the target image: its handful of eval transforms are restated in utils.transforms
+        # torchvision is absent in the target image: the transforms the configs name (the eval chain, RandomResizedCrop,
+        # RandomHorizontalFlip, TrivialAugmentWide) are restated in utils.transforms
         if mod == "torchvision.transforms":
             return getattr(importlib.import_module("utils.transforms"), attr)
         raise

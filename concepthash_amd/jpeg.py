@@ -212,6 +212,7 @@ class GpuJpegDecoder:
     def host_stage(self, files) -> "StagedJpegBatch":
         staged = self._host_stage(files)
         staged.boxes, staged.flips = getattr(files, "boxes", None), getattr(files, "flips", None)
+        staged.ta = getattr(files, "ta", None)
         return staged
 
     def _host_stage(self, files) -> "StagedJpegBatch":
@@ -333,6 +334,7 @@ class StagedJpegBatch:
         self.decoder, self.slot, self.desc, self.fallback, self.totals, self.sizes, self.fb = decoder, slot, desc, fallback, totals, sizes, fb
         self.staged = True
         self.boxes = self.flips = None      # a training dataset's crop boxes / flips ride along (utils.datasets.RawJpegBatch)
+        self.ta = None                      # ... and its TrivialAugmentWide draws
 
     def size(self, dim=0):
         if dim != 0:

@@ -41,6 +41,19 @@ def _taps(in_size: int, out_size: int) -> int:
     return int(math.ceil(2.0 * max(scale, 1.0))) * 2 + 1
 
 
+def _row_bounds_bilinear(in_size: int, out_size: int, xx: int):
+    """(first source index, count) of output index xx of a triangle-filter (BILINEAR) resize -- Pillow precompute_coeffs bounds."""
+    scale = float(np.float32(in_size)) / out_size
+    support = 1.0 * max(scale, 1.0)
+    center = (xx + 0.5) * scale
+    xmin = max(int(center - support + 0.5), 0)
+    xmax = min(int(center + support + 0.5), in_size) - xmin
+    return xmin, xmax
+
+
+_TRANSPOSE_CODE = {"ROTATE_90": 2, "ROTATE_270": 3, "ROTATE_180": 4}     # ch_augment_desc.iparam of Rotate's fast paths
+
+
 class GpuPreprocess:
     """Resize(resize, bicubic) -> CenterCrop(crop) -> ToTensor -> Normalize(mean, std), on the GPU."""
 
@@ -68,6 +81,9 @@ class GpuPreprocess:
                             ("top", "<i4"), ("left", "<i4"), ("row0", "<i4"), ("nrows", "<i4"), ("stride", "<i4"),
                             ("flip", "<i4")])   # == ch_image_desc / _lib.ImageDesc
     _RING = 8          # pinned descriptor staging buffers in flight
+    _AUG_DTYPE = np.dtype([("src_offset", "<i8"), ("tmp_offset", "<i8"), ("img_offset", "<i8")] +
+                          [(n, "<i4") for n in ("h", "w", "nh", "nw", "top", "left", "row0", "nrows", "flip", "op", "iparam", "reserved")] +
+                          [("fparam", "<f8"), ("m", "<f8", (6,))])   # == ch_augment_desc / _lib.AugmentDesc (128 bytes)
 
     def _geometry(self, h: int, w: int):
         """(nh, nw, top, left, row0, nrows, horizontal taps) of one image size; cached -- dataset images repeat a handful of sizes."""
@@ -128,6 +144,78 @@ class GpuPreprocess:
         taps = max([_taps(int(b[3]), self.crop) for b, big in zip(bx, too_big) if not big], default=0)
         return desc, int(src.sum()), int(tmp.sum()), (int(max(1, desc["nrows"].max())) if B else 1), taps
 
+    def plan_augment(self, sizes: Sequence[tuple], flips, ta):
+        """The TrivialAugmentWide chain (configs/transforms/trivialaugment.yaml): Resize(resize, bilinear) -> RandomHorizontalFlip ->
+        TrivialAugmentWide(bicubic) -> CenterCrop(crop).  flips: [bool]; ta: [(op, signed magnitude)] drawn by the loader.  -> (descriptor
+        array (ch_augment_desc layout), total source bytes, workspace bytes, max rows, max nh, max nw).  The op scalars are
+        utils.transforms.ta_op_params of the resized image's size: what TrivialAugmentWide.apply hands Pillow."""
+        from utils.transforms import ta_op_params
+        B = len(sizes)
+        ta = np.asarray(ta, dtype=np.float64).reshape(B, 2)
+        flips = np.zeros(B, dtype=bool) if flips is None else np.asarray(flips, dtype=bool).reshape(B)
+        desc = np.zeros(B, dtype=self._AUG_DTYPE)
+        off = int(self.lib.ch_augment_workspace(B, 0))
+        src = 0
+        for i, (h, w) in enumerate(sizes):
+            h, w = int(h), int(w)
+            nw, nh = _resized_size(w, h, self.resize)
+            op, m = int(ta[i, 0]), float(ta[i, 1])
+            if not 0 <= op < 14:
+                raise ValueError(f"TrivialAugmentWide op index {op} out of range")
+            d = desc[i]
+            d["src_offset"], d["h"], d["w"], d["nh"], d["nw"] = src, h, w, nh, nw
+            d["left"], d["top"] = int(round((nw - self.crop) / 2.0)), int(round((nh - self.crop) / 2.0))
+            d["flip"], d["op"] = int(flips[i]), op
+            src += h * w * 3
+            kind, val = ta_op_params(op, m, nw, nh)
+            if kind == "affine":
+                d["m"] = val
+            elif kind == "copy":
+                d["iparam"] = 1
+            elif kind == "transpose":
+                d["iparam"] = _TRANSPOSE_CODE[val.name]
+            elif kind in ("blend", "threshold"):
+                d["fparam"] = val
+            elif kind == "bits":
+                d["iparam"] = val
+            if any(2 * math.ceil(max(n_in / n_out, 1.0)) + 1 > self.max_taps for n_in, n_out in ((w, nw), (h, nh))):
+                continue                  # nrows = 0: the kernels skip it, `_host_route_augment` runs Pillow
+            r0, _ = _row_bounds_bilinear(h, nh, 0)
+            rl, cl = _row_bounds_bilinear(h, nh, nh - 1)
+            d["row0"], d["nrows"] = r0, rl + cl - r0
+            d["tmp_offset"] = off
+            off += int(d["nrows"]) * nw * 3
+            d["img_offset"] = off
+            off += nh * nw * 3
+        routed = desc["nrows"] == 0
+        return (desc, src, off, int(max(1, desc["nrows"].max())) if B else 1, int(desc["nh"][~routed].max(initial=1)),
+                int(desc["nw"][~routed].max(initial=1)))
+
+    def _host_route_augment(self, pixels, sizes, desc, flips, ta, out, stream):
+        """`_host_route` of the TrivialAugmentWide chain: the PIL chain itself with the loader's draws."""
+        from PIL import Image
+        from utils.transforms import TrivialAugmentWide
+        aug = TrivialAugmentWide(interpolation=Image.BICUBIC)
+        mean = torch.tensor(list(self._mean)).view(3, 1, 1)
+        std = torch.tensor(list(self._std)).view(3, 1, 1)
+        offsets = np.cumsum([0] + [h * w * 3 for h, w in sizes])
+        s = stream if stream is not None else torch.cuda.current_stream(pixels.device)
+        ta = np.asarray(ta, dtype=np.float64).reshape(len(sizes), 2)
+        for i in np.nonzero(desc["nrows"] == 0)[0]:
+            h, w = sizes[i]
+            s.synchronize()
+            img = Image.fromarray(pixels[int(offsets[i]):int(offsets[i + 1])].view(h, w, 3).cpu().numpy())
+            nh, nw, top, left = (int(desc[n][i]) for n in ("nh", "nw", "top", "left"))
+            img = img.resize((nw, nh), Image.BILINEAR)
+            if int(desc["flip"][i]):
+                img = img.transpose(Image.FLIP_LEFT_RIGHT)
+            img = aug.apply(img, int(ta[i, 0]), float(ta[i, 1])).crop((left, top, left + self.crop, top + self.crop))
+            x = torch.from_numpy(np.array(img, dtype=np.uint8)).permute(2, 0, 1).float().div_(255.0)
+            x = (x - mean) / std
+            with torch.cuda.stream(s):
+                out[i].copy_(x.to(out.dtype).to(out.device, non_blocking=False))
+        self.host_routed += int((desc["nrows"] == 0).sum())
+
     def _host_route(self, pixels, sizes, desc, boxes, flips, out, stream):
         """Images the kernels skipped (nrows == 0: down-scaling beyond the tap limit) through Pillow on the host -- rare (a handful of very
         large photographs in a dataset), exact (it IS the reference's chain), slow (one device -> host copy and one PIL resize per image)."""
@@ -176,15 +264,20 @@ class GpuPreprocess:
         slot["event"] = ev
         return ddev
 
-    def __call__(self, pixels: torch.Tensor, sizes: Sequence[tuple], stream=None, boxes=None, flips=None) -> torch.Tensor:
+    def __call__(self, pixels: torch.Tensor, sizes: Sequence[tuple], stream=None, boxes=None, flips=None, ta=None) -> torch.Tensor:
         """pixels: uint8 device tensor, the images' HWC bytes back to back (image i is [h_i, w_i, 3]); sizes: [(h, w)].
-        boxes / flips given: the training chain (`plan_boxes`) instead of Resize -> CenterCrop."""
+        boxes / flips given: the training chain (`plan_boxes`) instead of Resize -> CenterCrop.  ta ([B, 2]: op, signed magnitude) /
+        flips given: the TrivialAugmentWide chain (`plan_augment`, csrc/augment.hip)."""
         if pixels.dtype != torch.uint8 or not pixels.is_cuda:
             raise TypeError("pixels must be a uint8 GPU tensor (decoded RGB bytes, images concatenated)")
         B = len(sizes)
         out = torch.empty(B, 3, self.crop, self.crop, dtype=self.out_dtype, device=pixels.device)
         if B == 0:
             return out
+        if ta is not None:
+            if boxes is not None:
+                raise ValueError("crop boxes and TrivialAugmentWide draws belong to different chains")
+            return self._augment(pixels, sizes, flips, ta, out, stream)
         desc, nbytes, ws_bytes, max_rows, max_taps = self.plan(sizes) if boxes is None else self.plan_boxes(sizes, boxes, flips)
         if pixels.numel() != nbytes:
             raise ValueError(f"pixels holds {pixels.numel()} bytes, the sizes add up to {nbytes}")
@@ -197,4 +290,19 @@ class GpuPreprocess:
                                               _lib.stream_ptr(stream)), "ch_preprocess")
             if (desc["nrows"] == 0).any():
                 self._host_route(pixels, sizes, desc, boxes, flips, out, stream)
+        return out
+
+    def _augment(self, pixels, sizes, flips, ta, out, stream):
+        desc, nbytes, ws_bytes, max_rows, max_nh, max_nw = self.plan_augment(sizes, flips, ta)
+        if pixels.numel() != nbytes:
+            raise ValueError(f"pixels holds {pixels.numel()} bytes, the sizes add up to {nbytes}")
+        pixels = pixels.contiguous()
+        with torch.cuda.device(pixels.device):
+            ddev = self._stage(desc, pixels.device, stream)
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=pixels.device)
+            _lib.check(self.lib.ch_preprocess_augment(_lib.ptr(pixels), _lib.ptr(ddev), len(sizes), max_rows, max_nh, max_nw, self.crop,
+                                                      self._mean, self._std, _lib.ptr(out), 1 if self.out_dtype == torch.bfloat16 else 0,
+                                                      _lib.ptr(ws), _lib.stream_ptr(stream)), "ch_preprocess_augment")
+            if (desc["nrows"] == 0).any():
+                self._host_route_augment(pixels, sizes, desc, flips, ta, out, stream)
         return out

@@ -237,6 +237,37 @@ int ch_preprocess(const uint8_t *pixels, const ch_image_desc *desc_device, int32
 /* largest number of filter taps per output pixel the kernels hold (down-scaling factor up to ~15.5) */
 int32_t ch_preprocess_max_taps(void);
 
+/* TrivialAugmentWide training chain (reference configs/transforms/trivialaugment.yaml): Resize(resize, BILINEAR, shorter side) ->
+ * RandomHorizontalFlip -> TrivialAugmentWide(bicubic, fill None) -> CenterCrop(crop) -> ToTensor -> normalize.  The random draws
+ * (flip, op, signed magnitude) are made on the host by the loader; the host derives each image's op scalars as torchvision / Pillow
+ * do (utils.transforms.ta_op_params).  One descriptor per image: */
+typedef struct ch_augment_desc {
+    int64_t src_offset; /* bytes from `pixels` to the image's first byte ([h, w, 3] uint8) */
+    int64_t tmp_offset; /* bytes from the workspace to the horizontal pass's rows ([nrows, nw, 3]) */
+    int64_t img_offset; /* bytes from the workspace to the resized, flipped image ([nh, nw, 3]) the op reads */
+    int32_t h, w, nh, nw;
+    int32_t top, left;  /* CenterCrop origin in the resized image */
+    int32_t row0, nrows;/* source rows of the horizontal pass; nrows = 0: the kernels skip the image (the caller's host route) */
+    int32_t flip;       /* 1: the resized image is mirrored (FLIP_LEFT_RIGHT) before the op */
+    int32_t op;         /* TrivialAugmentWide op index: 0 Identity, 1 ShearX, 2 ShearY, 3 TranslateX, 4 TranslateY, 5 Rotate, 6 Brightness,
+                           7 Color, 8 Contrast, 9 Sharpness, 10 Posterize, 11 Solarize, 12 AutoContrast, 13 Equalize */
+    int32_t iparam;     /* Posterize: bits; Rotate: 0 = affine (m), 1 = copy, 2 = ROTATE_90, 3 = ROTATE_270, 4 = ROTATE_180 (Pillow's fast paths) */
+    int32_t reserved;
+    double fparam;      /* the enhancers' factor 1 + m; Solarize's threshold */
+    double m[6];        /* the geometric ops: the inverse affine matrix Pillow's Image.transform receives */
+} ch_augment_desc;
+
+/* workspace bytes ch_preprocess_augment needs for B images whose descriptors ask for `image_bytes` = sum of (nrows + nh) * nw * 3
+ * (the tmp / img offsets are the caller's, inside that range after the first ch_augment_workspace(B, 0) bytes) */
+int64_t ch_augment_workspace(int32_t B, int64_t image_bytes);
+/* desc_device: device array of B descriptors; max_rows = max nrows, max_nh = max nh, max_nw = max nw over the batch; out: NCHW
+ * [B,3,crop,crop] fp32 (out_dtype 0) or bf16 (1), normalised as ch_preprocess does.  Resize is Pillow's two-pass 8-bit resampler with
+ * the triangle (BILINEAR) filter; the ops restate Pillow's arithmetic (ImageEnhance's blend, ImageOps' tables, the bicubic affine
+ * sampler, the 3x3 SMOOTH filter): the output equals the PIL chain's. */
+int ch_preprocess_augment(const uint8_t *pixels, const ch_augment_desc *desc_device, int32_t B, int32_t max_rows, int32_t max_nh,
+                          int32_t max_nw, int32_t crop, const float *mean3_host, const float *std3_host, void *out, int32_t out_dtype,
+                          uint8_t *workspace, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * JPEG decode split  (replaces the decode half of the loader workers: `Image.open(path).convert("RGB")` in the dataset classes
  * that engine.dataloader drives, engine.py:41-54 -- PIL = libjpeg-turbo with its default settings: islow IDCT, fancy upsampling)

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--backbone", default="openai/clip-vit-base-patch16")
     ap.add_argument("--modes", default="gpu_decode,cpu_loader")
     ap.add_argument("--out", default="")
+    ap.add_argument("--transforms", default="", help="a transform group for the training split (e.g. trivialaugment); default: the dataset's")
     ap.add_argument("--extra", default="", help="extra command-line overrides for every run, comma separated (e.g. meter_stream=false)")
     a = ap.parse_args()
     import numpy as np
@@ -57,10 +58,12 @@ def main():
             open(os.path.join(data, name), "w").write(lines)
         open(os.path.join(data, "test.txt"), "w").write("".join(f"images/{i}.jpg {i % 200}\n" for i in range(min(n, 256))))
         env = dict(os.environ, PYTHONPATH=ROOT)
-        result = {"train_images": n, "epochs": a.epochs, "batch_size": a.batch_size, "backbone": a.backbone, "host_cpu_quota": cpu_budget(), "runs": {}}
+        result = {"train_images": n, "transforms": a.transforms or "dataset", "epochs": a.epochs, "batch_size": a.batch_size, "backbone": a.backbone, "host_cpu_quota": cpu_budget(), "runs": {}}
         for mode in a.modes.split(","):
             logdir = os.path.join(work, "run_" + mode)
             flags = ["dataset.gpu_decode=true"] if mode == "gpu_decode" else ["dataset.gpu_decode=false", "dataset.gpu_preprocess=false"]
+            if a.transforms:
+                flags.append("transforms=" + a.transforms)
             t0 = time.perf_counter()
             subprocess.run([sys.executable, os.path.join(ROOT, "main_v2.py"), "exp=hashing", "dataset=cub200", "data_dir=" + work, "optim=sgd",
                             "model.backbone.name=" + a.backbone, "model.nbit=64", f"epochs={a.epochs}", "eval_interval=0",

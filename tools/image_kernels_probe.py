@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The GPU half of the loader alone: 256 JPEG files of 500 x 375 (the common CUB-200 size) -> ch_jpeg_reconstruct -> ch_preprocess, a few
 times, with nothing else on the GPU -- the command to put behind `rocprofv3 --kernel-trace --stats` for the per-kernel times of
-`jpeg_idct`, `jpeg_color`, `resize_h*`, `resize_v*`.  Also checks one image against Pillow / the PIL chain.
+`jpeg_idct`, `jpeg_color`, `resize_h*`, `resize_v*` -- with --train-ta, the TrivialAugmentWide chain's
+`ta_resize_h`, `ta_resize_v`, `ta_lut`, `ta_output` (section 4b).  Also checks one image against Pillow / the PIL chain.
 
-    python3 tools/image_kernels_probe.py [--images 256] [--reps 12] [--train]"""
+    python3 tools/image_kernels_probe.py [--images 256] [--reps 12] [--train | --train-ta]"""
 import argparse
 import io
 import os
@@ -18,6 +19,7 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--reps", type=int, default=12)
     ap.add_argument("--train", action="store_true", help="training geometry: a random crop box and flip per image")
+    ap.add_argument("--train-ta", action="store_true", help="the TrivialAugmentWide chain: a flip and an op drawn per image")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -38,8 +40,13 @@ def main():
     dev = torch.device("cuda:0")
     dec = GpuJpegDecoder(device=dev)
     pre = GpuPreprocess(256, 224, device=dev)      # bf16 output, as the trainer uses it
-    boxes = flips = None
-    if a.train:
+    boxes = flips = ta = None
+    if a.train_ta:
+        torch.manual_seed(1)
+        aug = T.TrivialAugmentWide(interpolation=Image.BICUBIC)
+        flips = [bool(torch.rand(1) < 0.5) for _ in range(a.images)]
+        ta = torch.tensor([aug.draw() for _ in range(a.images)], dtype=torch.float64)
+    elif a.train:
         rng = np.random.default_rng(1)
         boxes, flips = [], []
         for i in range(a.images):
@@ -52,13 +59,25 @@ def main():
         if rep == a.reps // 2:
             ev[0].record()
         pixels, sizes = dec.decode(files)
-        out = pre(pixels, sizes, boxes=boxes, flips=flips)
+        out = pre(pixels, sizes, boxes=boxes, flips=flips, ta=ta)
     ev[1].record()
     torch.cuda.synchronize()
     print(f"decode + pre-process of {a.images} images: {ev[0].elapsed_time(ev[1]) / (a.reps - a.reps // 2):.3f} ms per batch "
-          f"(host entropy decode included; max taps {(pre.plan(sizes) if boxes is None else pre.plan_boxes(sizes, boxes, flips))[4]})")
+          f"(host entropy decode included" + ("" if ta is not None else
+                                            f"; max taps {(pre.plan(sizes) if boxes is None else pre.plan_boxes(sizes, boxes, flips))[4]}") + ")")
     i = 3
     ref = Image.open(io.BytesIO(files[i])).convert("RGB")
+    if ta is not None:
+        ok = True
+        for i in range(min(a.images, 32)):          # every op class is among the first images' draws
+            img = Image.open(io.BytesIO(files[i])).convert("RGB")
+            img = T.Resize(256)(img)
+            img = img.transpose(Image.FLIP_LEFT_RIGHT) if flips[i] else img
+            img = aug.apply(img, int(ta[i, 0]), float(ta[i, 1]))
+            want = T.normalize_transform(3)(T.ToTensor()(T.CenterCrop(224)(img)))
+            ok = ok and bool(torch.equal(out[i].cpu(), want.to(torch.bfloat16)))
+        print("bit-equal to the PIL chain (bf16 of it), first 32 images:", ok)
+        return
     if a.train:
         t, l, bh, bw = boxes[i]
         ref = ref.crop((l, t, l + bw, t + bh)).resize((224, 224), Image.BICUBIC)

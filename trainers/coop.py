@@ -76,6 +76,15 @@ class COOPTrainer(BaseTrainer):
             ds = self.config.dataset
             mean, std = _NORMS[int(ds.get("norm", 3))]
             self._gpu_pre = GpuPreprocess(int(ds.get("resize", 256)), int(ds.get("crop", 224)), mean, std, device=self.device)
+        ta = getattr(raw, "ta", None)
+        if ta is not None:
+            # the TrivialAugmentWide chain (configs/transforms/trivialaugment.yaml): its flips / op draws go to csrc/augment.hip, with
+            # the geometry of the list's Resize / CenterCrop, which must be the dataset config's
+            chain = getattr(self.dataset.get("train"), "augment", None) if isinstance(self.dataset, dict) else None
+            if hasattr(chain, "resize") and (chain.resize, chain.crop) != (self._gpu_pre.resize, self._gpu_pre.crop):
+                raise ValueError(f"the training list's Resize({chain.resize}) / CenterCrop({chain.crop}) differ from the dataset config's "
+                                 f"resize={self._gpu_pre.resize} / crop={self._gpu_pre.crop}")
+            return self._gpu_pre(raw.pixels, raw.sizes, flips=getattr(raw, "flips", None), ta=ta)
         # a training dataset's batches carry the crop boxes / flips its workers drew (RandomResizedCrop -> RandomHorizontalFlip,
         # configs/dataset/cub200.yaml:13-23): the same kernels resize the box instead of Resize -> CenterCrop
         return self._gpu_pre(raw.pixels, raw.sizes, boxes=getattr(raw, "boxes", None), flips=getattr(raw, "flips", None))
@@ -92,7 +101,7 @@ class COOPTrainer(BaseTrainer):
         a RawJpegBatch (undecoded files) or, from `iterate_loader`, a StagedJpegBatch whose host half already ran on the prefetch thread."""
         from utils.datasets import RawImageBatch
         pixels, sizes = raw.finish() if hasattr(raw, "staged") else self._jpeg_decoder().decode(raw)
-        return RawImageBatch(pixels, sizes, getattr(raw, "boxes", None), getattr(raw, "flips", None))
+        return RawImageBatch(pixels, sizes, getattr(raw, "boxes", None), getattr(raw, "flips", None), getattr(raw, "ta", None))
 
     def iterate_loader(self, loader):
         """A `gpu_decode` loader is iterated with the host half of the JPEG decode one or two batches ahead, on a background thread."""

@@ -67,6 +67,8 @@ def gpu_augmentation(transform):
     from utils import transforms as T
     from PIL import Image
     items = list(getattr(transform, "transforms", transform) or [])
+    if any(isinstance(t, T.TrivialAugmentWide) for t in items):
+        return _trivialaugment_chain(items)
     rrc = [t for t in items if isinstance(t, T.RandomResizedCrop)]
     if not rrc:
         return None
@@ -80,15 +82,50 @@ def gpu_augmentation(transform):
     return rrc[0], (flips[0] if flips else None)
 
 
+class TrivialAugmentChain:
+    """What the GPU path takes over from Resize(resize, bilinear) -> [RandomHorizontalFlip] -> TrivialAugmentWide(bicubic, fill None) ->
+    CenterCrop(crop) -> ToTensor -> normalize (the reference's configs/transforms/trivialaugment.yaml): the geometry, and the two random
+    transforms whose draws the loader makes."""
+
+    def __init__(self, resize: int, flip, ta, crop: int):
+        self.resize, self.flip, self.ta, self.crop = int(resize), flip, ta, int(crop)
+
+    def draw(self):
+        """(flip, (op, signed magnitude)) with the CPU chain's random calls in its order: RandomHorizontalFlip's torch.rand, then
+        TrivialAugmentWide's torch.randint calls"""
+        flip = bool(float(torch.rand(1)) < self.flip.p) if self.flip is not None else False
+        return flip, self.ta.draw()
+
+
+def _trivialaugment_chain(items):
+    from utils import transforms as T
+    from PIL import Image
+    err = ValueError("gpu_preprocess / gpu_decode: a transform list with TrivialAugmentWide must be Resize(int size, bilinear) "
+                     "[-> RandomHorizontalFlip] -> TrivialAugmentWide(interpolation=bicubic, fill=None) -> CenterCrop(square) -> ToTensor -> "
+                     "normalize; set dataset.gpu_decode=false dataset.gpu_preprocess=false to run any other list on CPU workers")
+    flip = items[1] if len(items) > 1 and isinstance(items[1], T.RandomHorizontalFlip) else None
+    rest = items[2:] if flip is not None else items[1:]
+    kinds = (T.TrivialAugmentWide, T.CenterCrop, T.ToTensor, T.Normalize)
+    if len(items) < 1 or type(items[0]) is not T.Resize or len(rest) != len(kinds) or \
+            any(type(t) is not k for t, k in zip(rest, kinds)):
+        raise err
+    resize, ta, crop = items[0], rest[0], rest[1]
+    if not isinstance(resize.size, int) or resize.interp != Image.BILINEAR or ta.interpolation != Image.BICUBIC or ta.fill is not None \
+            or crop.size[0] != crop.size[1]:
+        raise err
+    return TrivialAugmentChain(resize.size, flip, ta, crop.size[0])
+
+
 class RawImageBatch:
     """Decoded, untransformed images of one batch for the GPU pre-processing path: `pixels` = the uint8 RGB bytes of all images
     back to back (image i is [h_i, w_i, 3]), `sizes` = [(h, w)].  Quacks enough like a tensor for the trainer's plumbing.
     `boxes` [B, 4] (top, left, height, width) / `flips` [B]: the draws of the training transforms, made in the loader worker with the
-    CPU chain's own random calls; None for the evaluation chain."""
+    CPU chain's own random calls; None for the evaluation chain.  `ta` [B, 2] float64 (op index, signed magnitude): the
+    TrivialAugmentWide draws of that chain (utils.datasets.TrivialAugmentChain; boxes is None then), or None."""
 
-    def __init__(self, pixels: torch.Tensor, sizes, boxes=None, flips=None):
+    def __init__(self, pixels: torch.Tensor, sizes, boxes=None, flips=None, ta=None):
         self.pixels, self.sizes = pixels, list(sizes)
-        self.boxes, self.flips = boxes, flips
+        self.boxes, self.flips, self.ta = boxes, flips, ta
 
     def size(self, dim=0):
         if dim != 0:
@@ -96,24 +133,31 @@ class RawImageBatch:
         return len(self.sizes)
 
     def to(self, device, non_blocking=False):
-        return RawImageBatch(self.pixels.to(device, non_blocking=non_blocking), self.sizes, self.boxes, self.flips)
+        return RawImageBatch(self.pixels.to(device, non_blocking=non_blocking), self.sizes, self.boxes, self.flips, self.ta)
 
     def pin_memory(self):
-        return RawImageBatch(self.pixels.pin_memory(), self.sizes, self.boxes, self.flips)
+        return RawImageBatch(self.pixels.pin_memory(), self.sizes, self.boxes, self.flips, self.ta)
+
+
+def _collate_draws(items):
+    """(boxes, flips, ta) of a training batch's items (x, box, flip) or (x, None, flip, (op, magnitude))"""
+    if len(items[0]) == 4:
+        return (None, torch.as_tensor([it[2] for it in items], dtype=torch.bool),
+                torch.as_tensor([it[3] for it in items], dtype=torch.float64).reshape(len(items), 2))
+    return torch.as_tensor([it[1] for it in items], dtype=torch.int32), torch.as_tensor([it[2] for it in items], dtype=torch.bool), None
 
 
 def raw_collate(batch):
     """collate_fn of a `gpu_preprocess` dataset: images stay decoded uint8 of their own sizes (no CPU resize), targets and
     indices are stacked as usual."""
     imgs, targets, idxs = zip(*batch)
-    boxes = flips = None
-    if isinstance(imgs[0], tuple):         # (image, box, flip): a training dataset
-        boxes = torch.as_tensor([im[1] for im in imgs], dtype=torch.int32)
-        flips = torch.as_tensor([im[2] for im in imgs], dtype=torch.bool)
+    boxes = flips = ta = None
+    if isinstance(imgs[0], tuple):         # (image, box, flip) or (image, None, flip, ta): a training dataset
+        boxes, flips, ta = _collate_draws(imgs)
         imgs = [im[0] for im in imgs]
     pixels = torch.cat([im.reshape(-1) for im in imgs])
     targets = torch.stack([t if torch.is_tensor(t) else torch.as_tensor(t) for t in targets])
-    return RawImageBatch(pixels, [tuple(im.shape[:2]) for im in imgs], boxes, flips), targets, torch.as_tensor(idxs)
+    return RawImageBatch(pixels, [tuple(im.shape[:2]) for im in imgs], boxes, flips, ta), targets, torch.as_tensor(idxs)
 
 
 class RawJpegBatch:
@@ -122,10 +166,10 @@ class RawJpegBatch:
     Stays on the host -- the entropy decode runs on host threads -- until the trainer hands `files` to
     `concepthash_amd.jpeg.GpuJpegDecoder`, which returns the RawImageBatch the GPU pre-processing takes."""
 
-    def __init__(self, data: torch.Tensor, lengths, boxes=None, flips=None):
+    def __init__(self, data: torch.Tensor, lengths, boxes=None, flips=None, ta=None):
         self.data = data
         self.lengths = [int(n) for n in lengths]
-        self.boxes, self.flips = boxes, flips      # training transforms' draws (see RawImageBatch), or None
+        self.boxes, self.flips, self.ta = boxes, flips, ta      # training transforms' draws (see RawImageBatch), or None
 
     @property
     def files(self):
@@ -150,13 +194,12 @@ class RawJpegBatch:
 def jpeg_collate(batch):
     """collate_fn of a `gpu_decode` dataset: the items are file bytes; nothing is decoded or resized on the CPU."""
     files, targets, idxs = zip(*batch)
-    boxes = flips = None
+    boxes = flips = ta = None
     if isinstance(files[0], tuple):
-        boxes = torch.as_tensor([f[1] for f in files], dtype=torch.int32)
-        flips = torch.as_tensor([f[2] for f in files], dtype=torch.bool)
+        boxes, flips, ta = _collate_draws(files)
         files = [f[0] for f in files]
     targets = torch.stack([t if torch.is_tensor(t) else torch.as_tensor(t) for t in targets])
-    return RawJpegBatch(torch.cat(files), [f.numel() for f in files], boxes, flips), targets, torch.as_tensor(idxs)
+    return RawJpegBatch(torch.cat(files), [f.numel() for f in files], boxes, flips, ta), targets, torch.as_tensor(idxs)
 
 
 class HashingDataset(Dataset):
@@ -208,7 +251,11 @@ class HashingDataset(Dataset):
 
     def _draw(self, h, w):
         """One image's training draws, with the random calls and in the order of the CPU chain (RandomResizedCrop.get_params, then
-        RandomHorizontalFlip's torch.rand): the same worker seed gives the same boxes and flips as the reference's loader."""
+        RandomHorizontalFlip's torch.rand): the same worker seed gives the same boxes and flips as the reference's loader.
+        A TrivialAugmentWide chain: (None, flip, (op, signed magnitude)) -- the flip's torch.rand, then TrivialAugmentWide's calls."""
+        if isinstance(self.augment, TrivialAugmentChain):
+            flip, ta = self.augment.draw()
+            return None, flip, ta
         rrc, flip = self.augment
         box = rrc.get_params(w, h)
         return box, (bool(float(torch.rand(1)) < flip.p) if flip is not None else False)
@@ -252,15 +299,14 @@ class HashingDataset(Dataset):
         view = memoryview(data.numpy())
         targets = [self.target_transform(self.items[i][1]) if self.target_transform is not None else self.items[i][1] for i in indices]
         targets = torch.stack([t if torch.is_tensor(t) else torch.as_tensor(t) for t in targets])
-        boxes = flips = None
         if self.augment is not None:
             draws, o = [], 0
             for n in lengths:
                 draws.append(self._draw(*self._file_size(view[o:o + n])))
                 o += n
-            boxes = torch.as_tensor([d[0] for d in draws], dtype=torch.int32)
-            flips = torch.as_tensor([d[1] for d in draws], dtype=torch.bool)
-        return RawJpegBatch(data, lengths, boxes, flips), targets, torch.as_tensor(list(indices))
+            boxes, flips, ta = _collate_draws([(None,) + tuple(d) for d in draws])
+            return RawJpegBatch(data, lengths, boxes, flips, ta), targets, torch.as_tensor(list(indices))
+        return RawJpegBatch(data, lengths), targets, torch.as_tensor(list(indices))
 
     def __getitem__(self, index):
         from PIL import Image
@@ -292,6 +338,10 @@ class SyntheticHashingDataset(Dataset):
     in_memory = True
 
     def __init__(self, nclass, size=0, root=None, filename=None, image_size=224, seed=0, dtype="float32", limit=0, **kwargs):
+        if kwargs.get("transform"):
+            # a transform group (e.g. transforms=trivialaugment) selected over a synthetic dataset: there are no images to apply it to
+            raise ValueError("SyntheticHashingDataset: a transform list was given (transforms=...), but synthetic datasets hold "
+                             "post-normalisation tensors, not images; use an image dataset (dataset=cub200 ...) with a transform group")
         self.nclass = int(nclass)
         if root is not None and filename is not None and os.path.exists(os.path.join(root, filename)):
             labels = torch.tensor([lab for _, lab in read_list(os.path.join(root, filename))], dtype=torch.int64)

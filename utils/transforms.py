@@ -119,3 +119,155 @@ class RandomHorizontalFlip:
 
     def __call__(self, img):
         return img.transpose(Image.FLIP_LEFT_RIGHT) if float(torch.rand(1)) < self.p else img
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# TrivialAugmentWide (torchvision >= 0.13, v1 API) as the reference's configs/transforms/trivialaugment.yaml uses it.  The random
+# draws (`draw`) and the PIL arithmetic (`apply`) are split so that a GPU-path loader makes exactly these random calls and the host
+# planner derives the same per-image parameters (`op_params`) that `apply` hands Pillow.
+# ---------------------------------------------------------------------------------------------------------------------------------
+TA_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness",
+          "Posterize", "Solarize", "AutoContrast", "Equalize")
+
+
+def ta_augmentation_space(num_bins: int = 31):
+    """op name -> (magnitudes, signed): torchvision's TrivialAugmentWide._augmentation_space, float32 torch tensors."""
+    return {
+        "Identity": (torch.tensor(0.0), False),
+        "ShearX": (torch.linspace(0.0, 0.99, num_bins), True),
+        "ShearY": (torch.linspace(0.0, 0.99, num_bins), True),
+        "TranslateX": (torch.linspace(0.0, 32.0, num_bins), True),
+        "TranslateY": (torch.linspace(0.0, 32.0, num_bins), True),
+        "Rotate": (torch.linspace(0.0, 135.0, num_bins), True),
+        "Brightness": (torch.linspace(0.0, 0.99, num_bins), True),
+        "Color": (torch.linspace(0.0, 0.99, num_bins), True),
+        "Contrast": (torch.linspace(0.0, 0.99, num_bins), True),
+        "Sharpness": (torch.linspace(0.0, 0.99, num_bins), True),
+        "Posterize": (8 - (torch.arange(num_bins) / ((num_bins - 1) / 6)).round().int(), False),
+        "Solarize": (torch.linspace(255.0, 0.0, num_bins), False),
+        "AutoContrast": (torch.tensor(0.0), False),
+        "Equalize": (torch.tensor(0.0), False),
+    }
+
+
+def inverse_affine_matrix(center, angle, translate, scale, shear):
+    """torchvision.transforms.functional._get_inverse_affine_matrix (inverted=True), Python doubles."""
+    import math
+    rot = math.radians(angle)
+    sx, sy = math.radians(shear[0]), math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [d, -b, 0.0, -c, a, 0.0]
+    m = [x / scale for x in m]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def rotate_plan(angle, w, h):
+    """What Pillow's Image.rotate(angle, expand=False) does to a w x h image: ("copy", None), ("transpose", ROTATE_90 / ROTATE_270) or
+    ("affine", the 6 doubles it hands Image.transform) -- its own fast paths and its matrix, restated."""
+    import math
+    angle = angle % 360.0
+    if angle == 0:
+        return "copy", None
+    if angle == 180:
+        return "transpose", Image.Transpose.ROTATE_180
+    if angle in (90, 270) and w == h:
+        return "transpose", Image.Transpose.ROTATE_90 if angle == 90 else Image.Transpose.ROTATE_270
+    cx, cy = w / 2, h / 2
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return "affine", m
+
+
+def ta_op_params(op: int, m: float, w: int, h: int):
+    """(kind, value) of TrivialAugmentWide op `op` with signed magnitude `m` on a w x h image, as `TrivialAugmentWide.apply` hands them to
+    Pillow: ("affine", M) for the geometric ops (the inverse matrix of torchvision's PIL branch of F.affine, or Pillow's rotate matrix),
+    ("copy" | "transpose", ...) for rotate's fast paths, ("blend", 1 + m) for the four enhancers, ("bits", int(m)), ("threshold", m),
+    ("none", None) for Identity / AutoContrast / Equalize."""
+    import math
+    name = TA_OPS[op]
+    if name == "ShearX":
+        return "affine", inverse_affine_matrix([0, 0], 0.0, [0, 0], 1.0, [math.degrees(math.atan(m)), 0.0])
+    if name == "ShearY":
+        return "affine", inverse_affine_matrix([0, 0], 0.0, [0, 0], 1.0, [0.0, math.degrees(math.atan(m))])
+    if name == "TranslateX":
+        return "affine", inverse_affine_matrix([w * 0.5, h * 0.5], 0.0, [int(m), 0], 1.0, [0.0, 0.0])
+    if name == "TranslateY":
+        return "affine", inverse_affine_matrix([w * 0.5, h * 0.5], 0.0, [0, int(m)], 1.0, [0.0, 0.0])
+    if name == "Rotate":
+        return rotate_plan(m, w, h)
+    if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+        return "blend", 1.0 + m
+    if name == "Posterize":
+        return "bits", int(m)
+    if name == "Solarize":
+        return "threshold", m
+    return "none", None
+
+
+class TrivialAugmentWide:
+    """torchvision.transforms.TrivialAugmentWide on PIL images: one op of `TA_OPS` drawn uniformly, one of `num_magnitude_bins`
+    magnitudes, a random sign for the signed ops; Pillow does the arithmetic (`apply`).  `fill=None` is black, as torchvision's
+    _parse_fill makes it."""
+
+    def __init__(self, num_magnitude_bins: int = 31, interpolation=Image.NEAREST, fill=None):
+        self.num_magnitude_bins = int(num_magnitude_bins)
+        self.interpolation = interpolation
+        self.fill = fill
+        self.space = ta_augmentation_space(self.num_magnitude_bins)
+
+    def draw(self):
+        """(op index, signed magnitude): torchvision's random calls, in its order."""
+        op = int(torch.randint(len(TA_OPS), (1,)).item())
+        mags, signed = self.space[TA_OPS[op]]
+        m = float(mags[torch.randint(len(mags), (1,), dtype=torch.long)].item()) if mags.ndim > 0 else 0.0
+        if signed and torch.randint(2, (1,)):
+            m *= -1.0
+        return op, m
+
+    def _fillcolor(self, img):
+        fill = 0 if self.fill is None else self.fill
+        if isinstance(fill, (int, float)) and len(img.getbands()) > 1:
+            return tuple([fill] * len(img.getbands()))
+        return tuple(fill) if isinstance(fill, (list, tuple)) else fill
+
+    def apply(self, img, op: int, m: float):
+        from PIL import ImageEnhance, ImageOps
+        name = TA_OPS[op]
+        fillcolor = self._fillcolor(img)
+        if name in ("ShearX", "ShearY", "TranslateX", "TranslateY"):
+            M = ta_op_params(op, m, *img.size)[1]
+            return img.transform(img.size, Image.AFFINE, M, self.interpolation, fillcolor=fillcolor)
+        if name == "Rotate":
+            return img.rotate(m, self.interpolation, expand=False, fillcolor=fillcolor)
+        if name == "Brightness":
+            return ImageEnhance.Brightness(img).enhance(1.0 + m)
+        if name == "Color":
+            return ImageEnhance.Color(img).enhance(1.0 + m)
+        if name == "Contrast":
+            return ImageEnhance.Contrast(img).enhance(1.0 + m)
+        if name == "Sharpness":
+            return ImageEnhance.Sharpness(img).enhance(1.0 + m)
+        if name == "Posterize":
+            return ImageOps.posterize(img, int(m))
+        if name == "Solarize":
+            return ImageOps.solarize(img, m)
+        if name == "AutoContrast":
+            return ImageOps.autocontrast(img)
+        if name == "Equalize":
+            return ImageOps.equalize(img)
+        return img
+
+    def __call__(self, img):
+        return self.apply(img, *self.draw())
