@@ -749,6 +749,185 @@ __global__ __launch_bounds__(256) void hist_prefix_kernel(const uint32_t *__rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// tie bracket: the smallest / largest AP@R over EVERY order of the rows that share a distance
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_incl_scan64(unsigned long long v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+// AP of a candidate, the float64 the host computes from the same integers (ap_from_fixed): S / (nrel * 2^32), 0 without a relevant row
+__device__ __forceinline__ double ap_value(unsigned long long S, uint32_t nrel) {
+    return nrel ? (double)S / ((double)nrel * 4294967296.0) : 0.0;
+}
+__device__ __forceinline__ uint32_t limit_at(const RankLimits &lims, int l) {   // wave-uniform l: a chain of scalar selects
+    uint32_t v = lims.lim[0];
+#pragma unroll
+    for (int i = 1; i < MAX_LIMITS; ++i) v = (l == i) ? lims.lim[i] : v;
+    return v;
+}
+// sum over i < cnt of fixdiv32(rel0 + i + 1, rank0 + i + 1): `cnt` relevant rows on consecutive ranks from rank0 + 1, lanes striding
+// over the rows; the trip count is wave-uniform and the sum is an integer, so every lane returns the same value
+__device__ __forceinline__ unsigned long long run_sum(uint32_t rel0, uint32_t rank0, uint32_t cnt, int lane) {
+    unsigned long long acc = 0ull;
+    for (uint32_t i0 = 0; i0 < cnt; i0 += 64u) {
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool on = i < cnt;
+        const unsigned long long t = fixdiv32(on ? rel0 + i + 1u : 1u, on ? rank0 + i + 1u : 1u);
+        acc += on ? t : 0ull;
+    }
+    return wave_sum64(acc);
+}
+
+struct TieOut {
+    unsigned long long *S_low, *S_high;
+    uint32_t *n_low, *n_high;
+};
+
+// One walk over a query's buckets, ascending distance; (dn, dr) rows / relevant rows are taken out of the first non-empty bucket (the
+// row remove_first drops).  Every bucket in front of the one a limit cuts lies inside that limit whole, and limits ascend, so ONE
+// running pair of sums -- relevant rows first (SH) / last (SL) inside every bucket so far -- serves all limits; a limit is settled,
+// and its outputs written, at the bucket that cuts it (or at the end).  merge: an earlier walk (the other kind of dropped row) has
+// written the outputs; this one replaces them only where it is strictly better.  Everything here is wave-uniform.
+__device__ void tie_walk(const uint2 *__restrict__ cnt, int nb, uint32_t dn, uint32_t dr, const RankLimits &lims, int nlim, int64_t Qn,
+                         int64_t qi, int lane, bool merge, const TieOut &o) {
+    uint32_t B = 0, K = 0;                  // rows / relevant rows ranked before the bucket
+    unsigned long long SH = 0ull, SL = 0ull;
+    int lcur = 0;
+    bool first = true;
+    auto settle = [&](int l, unsigned long long s_hi, uint32_t n_hi, unsigned long long s_lo, uint32_t n_lo) {
+        if (lane == 0) {
+            const size_t at = (size_t)l * Qn + qi;
+            if (merge) {
+                if (!(ap_value(s_hi, n_hi) > ap_value(o.S_high[at], o.n_high[at]))) {
+                    s_hi = o.S_high[at];
+                    n_hi = o.n_high[at];
+                }
+                if (!(ap_value(s_lo, n_lo) < ap_value(o.S_low[at], o.n_low[at]))) {
+                    s_lo = o.S_low[at];
+                    n_lo = o.n_low[at];
+                }
+            }
+            o.S_high[at] = s_hi;
+            o.n_high[at] = n_hi;
+            o.S_low[at] = s_lo;
+            o.n_low[at] = n_lo;
+        }
+    };
+    for (int d = 0; d < nb; ++d) {
+        const uint2 v = cnt[d];
+        uint32_t n = v.x, r = v.y;
+        if (n == 0u) continue;
+        if (first) {
+            n -= dn;
+            r -= dr;
+            first = false;
+            if (n == 0u) continue;
+        }
+        // limits that end inside this bucket (B <= limit < B + n): `take` of its rows are ranked, t of them relevant -- any feasible t
+        while (lcur < nlim && limit_at(lims, lcur) < B + n) {
+            const uint32_t take = limit_at(lims, lcur) - B;
+            const uint32_t irr = n - r;
+            const uint32_t tmin = take > irr ? take - irr : 0u, tmax = min(r, take);
+            // high: the t relevant rows lead the bucket, so candidate t is the length-t prefix of one run of terms.  Lanes hold
+            // consecutive t; ties keep the smaller t (a lane's own t ascend, and the reduction prefers the smaller on equal values).
+            double bv = -1.0;
+            uint32_t bt = 0xFFFFFFFFu;
+            unsigned long long bs = 0ull;
+            if (tmin == 0u && lane == 0) {
+                bv = ap_value(SH, K);
+                bt = 0u;
+                bs = SH;
+            }
+            unsigned long long carry = 0ull;
+            for (uint32_t i0 = 0; i0 < tmax; i0 += 64u) {
+                const uint32_t i = i0 + (uint32_t)lane;
+                const bool on = i < tmax;
+                const unsigned long long term = fixdiv32(on ? K + i + 1u : 1u, on ? B + i + 1u : 1u);
+                const unsigned long long p = carry + wave_incl_scan64(on ? term : 0ull, lane);
+                carry = __shfl(p, 63, 64);
+                const uint32_t t = i + 1u;
+                const double val = ap_value(SH + p, K + t);
+                if (on && t >= tmin && val > bv) {
+                    bv = val;
+                    bt = t;
+                    bs = SH + p;
+                }
+            }
+#pragma unroll
+            for (int s = 32; s > 0; s >>= 1) {
+                const double ov = __shfl_xor(bv, s, 64);
+                const uint32_t ot = __shfl_xor(bt, s, 64);
+                const unsigned long long os = __shfl_xor(bs, s, 64);
+                if (ov > bv || (ov == bv && ot < bt)) {
+                    bv = ov;
+                    bt = ot;
+                    bs = os;
+                }
+            }
+            // low: the t relevant rows close the `take` positions, on ranks B + take - t + 1 ..: the ranks move with t, so every
+            // candidate is a sum of its own (the plain O(t^2) form)
+            double wv = 0.0;
+            uint32_t wt = 0u;
+            unsigned long long ws = 0ull;
+            for (uint32_t t = tmin; t <= tmax; ++t) {
+                const unsigned long long s = SL + run_sum(K, B + take - t, t, lane);
+                const double val = ap_value(s, K + t);
+                if (t == tmin || val < wv) {
+                    wv = val;
+                    wt = t;
+                    ws = s;
+                }
+            }
+            settle(lcur, bs, K + bt, ws, K + wt);
+            ++lcur;
+        }
+        if (r > 0u) {
+            SH += run_sum(K, B, r, lane);
+            SL += run_sum(K, B + (n - r), r, lane);
+        }
+        B += n;
+        K += r;
+    }
+    for (; lcur < nlim; ++lcur) settle(lcur, SH, K, SL, K);   // limits the ranking never reaches
+}
+
+// One wave per query, four queries per workgroup.  remove_first: rank 1 of a tie order is any row of the lowest non-empty bucket, so
+// both kinds of dropped row are walked (the irrelevant one first: on equal AP it stays).
+__global__ __launch_bounds__(256) void tie_bracket_kernel(const uint32_t *__restrict__ counts, int64_t Qn, int nb, RankLimits lims,
+                                                          int nlim, int remove_first, TieOut o) {
+    const int64_t qi = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (qi >= Qn) return;   // wave-uniform
+    const uint2 *cnt = (const uint2 *)counts + (size_t)qi * nb;
+    if (!remove_first) {
+        tie_walk(cnt, nb, 0u, 0u, lims, nlim, Qn, qi, lane, false, o);
+        return;
+    }
+    uint32_t n0 = 0, r0 = 0;
+    for (int d = 0; d < nb && n0 == 0u; ++d) {
+        const uint2 v = cnt[d];
+        n0 = v.x;
+        r0 = v.y;
+    }
+    if (n0 == 0u) {         // no gallery row at all: nothing to drop
+        tie_walk(cnt, nb, 0u, 0u, lims, nlim, Qn, qi, lane, false, o);
+        return;
+    }
+    const bool can_irr = n0 > r0, can_rel = r0 > 0u;
+    if (can_irr) tie_walk(cnt, nb, 1u, 0u, lims, nlim, Qn, qi, lane, false, o);
+    if (can_rel) tie_walk(cnt, nb, 1u, 1u, lims, nlim, Qn, qi, lane, can_irr, o);
+}
+
 struct ScanArgs {   // everything a map_scan_kernel launch takes
     const uint64_t *q;
     int64_t Qn;
@@ -1009,6 +1188,25 @@ extern "C" int ch_hamming_hist_prefix(const uint32_t *hist, int32_t nseg, int64_
     CH_REQUIRE(hist && out_base, "hist_prefix: null pointer");
     hipLaunchKernelGGL(hist_prefix_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, (hipStream_t)stream, hist, nseg, Qn, nb,
                        out_base, out_totals);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- tie bracket: AP over every order inside the distance buckets ------------------------------------
+extern "C" int ch_hamming_tie_bracket(const uint32_t *bucket_counts, int64_t Qn, int32_t nb, const int64_t *rank_limits,
+                                      int32_t nlimits, int32_t remove_first, unsigned long long *out_S_low, uint32_t *out_nrel_low,
+                                      unsigned long long *out_S_high, uint32_t *out_nrel_high, void *stream) {
+    CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, "hamming_tie_bracket: 1 <= nlimits <= 16");
+    CH_REQUIRE(Qn >= 0 && nb >= 1 && nb <= 257, "hamming_tie_bracket: bad sizes (nb = 64 W + 1, W <= 4)");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(bucket_counts && out_S_low && out_nrel_low && out_S_high && out_nrel_high, "hamming_tie_bracket: null pointer");
+    CH_REQUIRE((((uintptr_t)bucket_counts | (uintptr_t)out_S_low | (uintptr_t)out_S_high) & 7u) == 0,
+               "hamming_tie_bracket: bucket_counts (read as pairs), out_S_low and out_S_high must be 8-byte aligned");
+    RankLimits lims;
+    CH_REQUIRE(fill_limits(rank_limits, nlimits, lims), "hamming_tie_bracket: rank limits must ascend (<= 0 = unlimited, last)");
+    TieOut o{out_S_low, out_S_high, out_nrel_low, out_nrel_high};
+    hipLaunchKernelGGL(tie_bracket_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, (hipStream_t)stream, bucket_counts, Qn,
+                       (int)nb, lims, (int)nlimits, (int)remove_first, o);
     CH_LAUNCH_CHECK();
     return 0;
 }

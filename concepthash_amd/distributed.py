@@ -190,10 +190,13 @@ class ShardedRetrieval:
 
     # ---- mAP / P@k / R@k -----------------------------------------------------------------------------------------
     def evaluate(self, q_all: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Sequence[int] = (1, 5, 10),
-                 remove_first: bool = False, seg_rows: Optional[int] = None, skip_queries_without_relevant: bool = False) -> dict:
+                 remove_first: bool = False, seg_rows: Optional[int] = None, skip_queries_without_relevant: bool = False,
+                 tie_bracket: bool = False) -> dict:
         """Same statistics as ``retrieval.evaluate`` (R an int or a list; `skip_queries_without_relevant` as there), gallery sharded by rows: per-shard histograms are
         all-gathered, every rank builds the same global bases, ONE local AP pass accumulates every rank limit (each R and each
-        k), and the integer sums are all-reduced -- bit-identical to the single-GPU result for any shard count."""
+        k), and the integer sums are all-reduced -- bit-identical to the single-GPU result for any shard count.
+        tie_bracket: as ``retrieval.evaluate``: the whole-gallery bucket counts are the sum over ranks of the per-shard totals that were
+        all-gathered anyway, and every rank runs the bracket kernel on the same integers (replicated; no further collective)."""
         if self.labels is None:
             raise ValueError("gallery labels are required for evaluate()")
         ops = self.ops
@@ -247,8 +250,10 @@ class ShardedRetrieval:
             after = tot_all[self.rank + 1:].sum(0, dtype=hist.dtype)
             base_s, totals = ops.hist_prefix(torch.cat([before.unsqueeze(0), hist, after.unsqueeze(0)], dim=0))
             base = base_s[1:1 + hist.shape[0]].contiguous()
+            counts = tot_all.sum(0, dtype=hist.dtype) if tie_bracket else None
         else:
             base, totals = ops.hist_prefix(hist)
+            counts = hist.sum(0, dtype=hist.dtype) if tie_bracket else None
         limits, idx_of = ops.normalize_limits(Rs + ks)
         if use_rec:
             S, nrel = ops.hamming_ap_rec(q_all, self.gallery, q_lab, g_lab, LW, seg, base, recs, limits, first_rel=first_rel)
@@ -267,4 +272,6 @@ class ShardedRetrieval:
                        ap=sm["aps"])
         else:
             out.update(mAP=sm["mAPs"][0], S=S[idx_of[0]], nrel=nrel[idx_of[0]], ap=sm["aps"][0])
+        if tie_bracket:
+            out.update(ops.tie_results(counts, Rs, ks, remove_first, many, skip_queries_without_relevant))
         return out

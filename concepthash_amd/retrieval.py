@@ -238,6 +238,108 @@ def hamming_ap_multi(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Ten
     return S, nrel
 
 
+def tie_bracket(bucket_counts: torch.Tensor, limits: Sequence[int], remove_first: bool = False, stream=None):
+    """Smallest / largest AP over every order of the rows that share a distance ("tie bracket").
+    bucket_counts: [Qn, 64W+1, 2] int32 -- rows / relevant rows per (query, distance) over the whole gallery, i.e. the histogram of
+    hamming_hist / hamming_hist_rec summed over its segments (and shards).  limits: ascending, <= 0 = unlimited, last (normalize_limits).
+    -> (S_low int64 [n, Qn], nrel_low int32 [n, Qn], S_high, nrel_high): AP = ap_from_fixed(S, nrel)."""
+    lib = _lib.load()
+    if bucket_counts.dim() != 3 or bucket_counts.shape[2] != 2 or bucket_counts.dtype != torch.int32:
+        raise TypeError("bucket_counts must be an int32 tensor [Qn, nb, 2]")
+    bc = bucket_counts.contiguous()
+    Qn, nb, _ = bc.shape
+    lim = [int(r) for r in limits]
+    n = len(lim)
+    S_lo = torch.zeros(n, Qn, dtype=torch.int64, device=bc.device)
+    S_hi = torch.zeros(n, Qn, dtype=torch.int64, device=bc.device)
+    n_lo = torch.zeros(n, Qn, dtype=torch.int32, device=bc.device)
+    n_hi = torch.zeros(n, Qn, dtype=torch.int32, device=bc.device)
+    with _dev_guard(bc):
+        for c0 in range(0, n, MAX_LIMITS):
+            chunk = lim[c0:c0 + MAX_LIMITS]
+            arr = (ctypes.c_int64 * len(chunk))(*chunk)
+            c1 = c0 + len(chunk)
+            _lib.check(lib.ch_hamming_tie_bracket(_lib.ptr(bc), Qn, nb, arr, len(chunk), int(bool(remove_first)), _lib.ptr(S_lo[c0:c1]),
+                                                  _lib.ptr(n_lo[c0:c1]), _lib.ptr(S_hi[c0:c1]), _lib.ptr(n_hi[c0:c1]),
+                                                  _lib.stream_ptr(stream)), "ch_hamming_tie_bracket")
+    return S_lo, n_lo, S_hi, n_hi
+
+
+def tie_hits(bucket_counts: torch.Tensor, ks: Sequence[int], remove_first: bool = False) -> dict:
+    """Bracket of hits@k (relevant rows in the top k), P@k and R@k over the tie orders: the two extreme numbers of relevant rows of
+    the bucket that k cuts.  A few elementwise launches on [Qn, nb] integers.  With remove_first the dropped row is any row of the
+    lowest non-empty bucket: hits and R@k (whose denominator loses a dropped relevant row) take their extremes over both kinds."""
+    bc = bucket_counts.to(torch.int64)
+    Qn, dev = bc.shape[0], bc.device
+    ks = [int(k) for k in ks]
+
+    def extremes(b):
+        n, r = b[..., 0], b[..., 1]
+        before = n.cumsum(1) - n
+        lo, hi = [], []
+        for k in ks:
+            take = torch.minimum((k - before).clamp_min(0), n)
+            hi.append(torch.minimum(r, take).sum(1))
+            lo.append((take - (n - r)).clamp_min(0).sum(1))
+        z = torch.zeros(Qn, 0, dtype=torch.int64, device=dev)
+        return (torch.stack(lo, 1) if ks else z), (torch.stack(hi, 1) if ks else z), r.sum(1)
+
+    def recall(h, tot):
+        return torch.where(tot[:, None] > 0, h.double() / tot.clamp_min(1).double()[:, None], torch.zeros_like(h, dtype=torch.float64))
+
+    if not remove_first or Qn == 0:
+        lo, hi, tot = extremes(bc)
+        rlo, rhi = recall(lo, tot), recall(hi, tot)
+    else:
+        nz = bc[..., 0] > 0
+        rows = torch.arange(Qn, device=dev)
+        d0 = nz.to(torch.int8).argmax(1)                       # the lowest non-empty bucket (first maximum)
+        n0, r0 = bc[rows, d0, 0], bc[rows, d0, 1]
+        can_irr, can_rel = n0 > r0, r0 > 0
+        b_irr, b_rel = bc.clone(), bc.clone()
+        b_irr[rows, d0, 0] -= can_irr.to(torch.int64)
+        b_rel[rows, d0, 0] -= can_rel.to(torch.int64)
+        b_rel[rows, d0, 1] -= can_rel.to(torch.int64)
+        lo_i, hi_i, tot_i = extremes(b_irr)
+        lo_r, hi_r, tot_r = extremes(b_rel)
+        only_i, only_r = (~can_rel)[:, None], (~can_irr)[:, None]   # a query with no row at all: both walks see the same zeros
+        lo = torch.where(only_i, lo_i, torch.where(only_r, lo_r, torch.minimum(lo_i, lo_r)))
+        hi = torch.where(only_i, hi_i, torch.where(only_r, hi_r, torch.maximum(hi_i, hi_r)))
+        rl_i, rl_r, rh_i, rh_r = recall(lo_i, tot_i), recall(lo_r, tot_r), recall(hi_i, tot_i), recall(hi_r, tot_r)
+        rlo = torch.where(only_i, rl_i, torch.where(only_r, rl_r, torch.minimum(rl_i, rl_r)))
+        rhi = torch.where(only_i, rh_i, torch.where(only_r, rh_r, torch.maximum(rh_i, rh_r)))
+    out = dict(hits_low=lo.to(torch.int32), hits_high=hi.to(torch.int32))
+    if not Qn or not ks:
+        z = [0.0] * len(ks)
+        out.update(precisions_low=z, precisions_high=list(z), recalls_low=list(z), recalls_high=list(z))
+        return out
+    kf = torch.tensor(ks, dtype=torch.float64, device=dev)
+    vals = torch.stack([(lo.double() / kf).mean(0), (hi.double() / kf).mean(0), rlo.mean(0), rhi.mean(0)]).tolist()
+    out.update(precisions_low=vals[0], precisions_high=vals[1], recalls_low=vals[2], recalls_high=vals[3])
+    return out
+
+
+TIE_KEYS = ("mAP_low", "mAP_high", "ap_low", "ap_high", "S_low", "S_high", "nrel_low", "nrel_high", "precisions_low", "precisions_high",
+            "recalls_low", "recalls_high", "hits_low", "hits_high")
+
+
+def tie_results(bucket_counts: torch.Tensor, Rs: Sequence[int], ks: Sequence[int], remove_first: bool, many: bool,
+                skip_queries_without_relevant: bool = False) -> dict:
+    """The TIE_KEYS of evaluate(tie_bracket=True) from the whole-gallery bucket counts [Qn, nb, 2] (one kernel launch per 16 R)."""
+    limits, idx_of = normalize_limits(Rs)
+    S_lo, n_lo, S_hi, n_hi = tie_bracket(bucket_counts, limits, remove_first)
+    Qn = bucket_counts.shape[0]
+    total = torch.zeros(Qn, dtype=torch.int32, device=bucket_counts.device)      # no k here: summarize() uses it for R@k only
+    lo = summarize(S_lo, n_lo, total, idx_of, Rs, [], skip_queries_without_relevant)
+    hi = summarize(S_hi, n_hi, total, idx_of, Rs, [], skip_queries_without_relevant)
+    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    first = (lambda x: x) if many else (lambda x: x[0])
+    out = dict(mAP_low=first(lo["mAPs"]), mAP_high=first(hi["mAPs"]), ap_low=first(lo["aps"]), ap_high=first(hi["aps"]),
+               S_low=pick(S_lo), S_high=pick(S_hi), nrel_low=pick(n_lo), nrel_high=pick(n_hi))
+    out.update(tie_hits(bucket_counts, ks, remove_first))
+    return out
+
+
 REC_BUDGET_BYTES = 4 << 30     # upper bound of the record buffer of one evaluation
 REC_COMFORT_BYTES = 1 << 30    # ... and what is spent without need, for long lists (class-sorted galleries)
 
@@ -380,7 +482,8 @@ def summarize(S, nrel, total, idx_of, Rs: Sequence[int], ks: Sequence[int], skip
 
 def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
              ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, seg_rows: Optional[int] = None,
-             records: Optional[bool] = None, rec_cap: Optional[int] = None, skip_queries_without_relevant: bool = False) -> dict:
+             records: Optional[bool] = None, rec_cap: Optional[int] = None, skip_queries_without_relevant: bool = False,
+             tie_bracket: bool = False) -> dict:
     """Single-GPU mAP@R + P@k + R@k on packed codes: histogram pass, prefix, ONE AP pass whose rank limits are R (an int or
     a list) and every k -- the number of relevant rows inside limit k is exactly hits@k, for any k.  Returns python
     floats/lists plus the raw integer statistics (S, nrel, hits, total) that the parity tests compare bit-for-bit with the
@@ -389,7 +492,10 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
     the AP pass walks those records instead of scanning the gallery again; rec_cap overrides the list capacity (tests).  Left to the
     default, large single-label problems first predict (exactly, from the labels) how many workgroups' lists would overflow and run
     the two-scan form where most would (`predicted_overflow`).
-    skip_queries_without_relevant: which queries the mean of AP runs over (`summarize`); the integers S / nrel do not depend on it."""
+    skip_queries_without_relevant: which queries the mean of AP runs over (`summarize`); the integers S / nrel do not depend on it.
+    tie_bracket: also report, for every statistic, the smallest and the largest value any order of equal-distance rows can give
+    (TIE_KEYS: mAP_low / mAP_high ... hits_low / hits_high) -- one more small kernel on the histogram this
+    call holds anyway.  Off: exactly the keys, integers and launches of before."""
     q, g = _check_packed(q, g)
     Qn, W = q.shape
     G = g.shape[0]
@@ -408,6 +514,11 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
                    hits=torch.zeros(Qn, len(ks), dtype=torch.int32, device=dev), total=z32, ap=z64.double())
         if many:
             out.update(mAP=[0.0] * len(Rs), S=[z64] * len(Rs), nrel=[z32] * len(Rs), ap=[z64.double()] * len(Rs))
+        if tie_bracket:
+            for side in ("low", "high"):
+                out.update({"mAP_" + side: out["mAP"], "ap_" + side: out["ap"], "S_" + side: out["S"], "nrel_" + side: out["nrel"],
+                            "precisions_" + side: list(out["precisions"]), "recalls_" + side: list(out["recalls"]),
+                            "hits_" + side: out["hits"]})
         return out
     first_rel = None
     if remove_first:   # relevance of every query's rank-1 row (the self-match when the test set is the database)
@@ -437,4 +548,6 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
                    ap=sm["aps"])
     else:
         out.update(mAP=sm["mAPs"][0], S=S[idx_of[0]], nrel=nrel[idx_of[0]], ap=sm["aps"][0])
+    if tie_bracket:
+        out.update(tie_results(hist.sum(0, dtype=hist.dtype), Rs, ks, remove_first, many, skip_queries_without_relevant))
     return out

@@ -402,6 +402,26 @@ int ch_hamming_ap_rec(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t 
 int ch_hamming_hist_prefix(const uint32_t *hist, int32_t nseg, int64_t Qn, int32_t nb, uint32_t *out_base,
                            uint32_t *out_totals, void *stream);
 
+/* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
+ * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
+ * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the
+ * histogram of ch_hamming_hist / ch_hamming_hist_rec summed over its segments (and over gallery shards) by the caller; there is no
+ * nseg argument.  rank_limits as for ch_hamming_ap_multi (host array, ascending, <= 0 = no limit, last, at most 16).  remove_first != 0:
+ * rank 1 of the tie order is dropped first -- any row of the lowest non-empty bucket, relevant or not; the bracket covers both.
+ * out_* [nlimits, Qn], WRITTEN (not accumulated): AP_low = S_low / (nrel_low * 2^32), AP_high likewise, in the fixed point of
+ * ch_hamming_ap.  Inside the bucket a limit cuts every feasible number t of relevant rows inside the limit is a candidate (relevant
+ * rows first is NOT always the maximum there, the denominator moves with t); candidates are compared as float64 AP, equal values
+ * keep the smaller t, and an irrelevant dropped row is kept over a relevant one -- so the integers are deterministic.
+ * bucket_counts (read as (rows, relevant) pairs), out_S_low and out_S_high must be 8-byte aligned (checked).
+ * Cost: one fixed-point division per (query, relevant row, order), plus, for every limit that cuts a bucket holding both relevant and
+ * irrelevant rows, about min(r, take)^2 / 2 more on the low side (r relevant rows in that bucket, take = rows of it inside the limit; every
+ * candidate t is a sum of its own, run by ONE wave per query).  Measured up to r = 676 (0.9 ms for 16,384 queries x 1M rows).  A large
+ * finite limit over few classes -- r and take in the tens of thousands -- is 1e7 .. 1e9 serial divisions per query and NOT measured:
+ * split such a call, or ask for the unlimited bracket (<= 0: no bucket is cut, the cost is linear). */
+int ch_hamming_tie_bracket(const uint32_t *bucket_counts, int64_t Qn, int32_t nb, const int64_t *rank_limits, int32_t nlimits,
+                           int32_t remove_first, unsigned long long *out_S_low, uint32_t *out_nrel_low,
+                           unsigned long long *out_S_high, uint32_t *out_nrel_high, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

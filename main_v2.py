@@ -28,7 +28,7 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream")
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket")
 
 
 def run(config):
@@ -53,6 +53,8 @@ def run(config):
         load_config["exp"] = "validation"
         load_config["seed"] = config.get("seed", load_config.get("seed", 42))
         load_config["device"] = config.get("device", "cuda")
+        if load_config.get("tie_bracket"):      # the evaluator + the mAP bracket over tie orders
+            from experiments.tie_bracket_eval import TieBracketEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp in ("descriptor", "extract"):
         experiment = RetrievalEvaluation(config)

@@ -44,7 +44,12 @@ def _sharded():
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
 
-def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False):
+# The tie bracket of the last calculate_mAP(..., tie_bracket=True) call: {"mAP_low", "mAP_high", "precisions_low", "precisions_high",
+# "recalls_low", "recalls_high"} (the return arity of calculate_mAP is the reference's and cannot grow); None after any other call.
+last_tie_bracket = None
+
+
+def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False):
     dev = _device()
     from concepthash_amd.distributed import RowShard
     if isinstance(db_codes, RowShard) or isinstance(test_codes, RowShard):
@@ -66,7 +71,7 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
             ql, _ = _all_gather_ragged(tl.contiguous(), sr.group)
         else:
             ql = _labels(test_labels, dev)
-        return sr.evaluate(q, ql, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
+        return sr.evaluate(q, ql, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip, tie_bracket=tie)
     q = rt.pack_sign(torch.as_tensor(test_codes).to(dev, torch.float32))
     if _sharded():
         # replicated inputs under an initialised process group (a caller that gathered its codes): every rank takes its block
@@ -76,29 +81,39 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
         lo, hi = b[dist.get_rank()], b[dist.get_rank() + 1]
         g = rt.pack_sign(torch.as_tensor(db_codes[lo:hi]).to(dev, torch.float32))
         sr = ShardedRetrieval(g, _labels(db_labels[lo:hi], dev))
-        return sr.evaluate(q, _labels(test_labels, dev), R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
+        return sr.evaluate(q, _labels(test_labels, dev), R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip,
+                           tie_bracket=tie)
     g = rt.pack_sign(torch.as_tensor(db_codes).to(dev, torch.float32))
     return rt.evaluate(q, g, _labels(test_labels, dev), _labels(db_labels, dev), R=R, ks=ks, remove_first=remove_first,
-                       skip_queries_without_relevant=skip)
+                       skip_queries_without_relevant=skip, tie_bracket=tie)
 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False):
+                  skip_queries_without_relevant=False, tie_bracket=False):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
     skip_queries_without_relevant (not a reference argument; the reference's un-vendored `utils.hashing` cannot be read, so the one
     convention that changes numbers at R < database size is a switch): False (default) = a query with no relevant row inside its top
     R contributes AP = 0 to the mean; True = such queries are left out of the mean, as the HashNet /
-    OrthoHash family of evaluators does.  mAP@all on CUB-200 / Cars196 / NABirds is the same under both."""
+    OrthoHash family of evaluators does.  mAP@all on CUB-200 / Cars196 / NABirds is the same under both.
+    tie_bracket (not a reference argument): also compute the smallest / largest value of every statistic over all orders of the
+    database rows that share a Hamming distance -- the one thing another implementation's sort may do
+    differently.  The triple returned is unchanged; the bracket is left in the module attribute `last_tie_bracket` (a dict with
+    mAP_low, mAP_high, precisions_low/high, recalls_low/high; lists where the triple has lists), which is None after a call without it."""
+    global last_tie_bracket
+    last_tie_bracket = None
     _check(dist_metric, threshold, landmark_gt)
     ks = [int(k) for k in (PRs or [])]
     many = isinstance(R, (list, tuple)) or (hasattr(R, "__iter__") and not isinstance(R, (int, float)))
     Rs = [int(r) for r in R] if many else int(R)
     if many and not Rs:
         return [], [], []
-    res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant))
+    res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
+                    bool(tie_bracket))
+    if tie_bracket:
+        last_tie_bracket = {k: res[k] for k in ("mAP_low", "mAP_high", "precisions_low", "precisions_high", "recalls_low", "recalls_high")}
     return res["mAP"], res["recalls"], res["precisions"]
 
 
