@@ -67,6 +67,8 @@ SIGNATURES = {
     "ch_debug_copy_buffer": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "ch_debug_adapter": (c_int, [c_void_p] * 2 + [c_int32] * 3 + [c_void_p] * 10 + [c_int32, c_void_p]),
     "ch_debug_attention": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_attention_ex": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "ch_debug_attention_dispatch_count": (c_int64, [c_int32]),
     "ch_encode": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "ch_encode_hidden": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
@@ -111,6 +113,7 @@ SIGNATURES = {
     "ch_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int32, c_int32, c_void_p]),
     "ch_debug_attention_bwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "ch_debug_attention_bwd_ex": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ch_debug_wgrad": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_debug_ln_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_debug_act": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
@@ -122,7 +125,7 @@ SIGNATURES = {
 
 # ch_model_set_option keys (include/concepthash_hip.h) and the DEBUG environment overrides the Python wrapper maps onto them when a
 # handle is created.  The library itself reads no environment variable; code that needs a setting passes `options=` / set_option().
-OPTION_KEYS = ("streams", "chain_auto", "ln_fold", "prune_last", "pp_min_k", "small_kernel", "serpentine", "pp_sched", "fused_adapter", "resid_nt",
+OPTION_KEYS = ("streams", "chain_auto", "ln_fold", "prune_last", "pp_min_k", "attn_stream", "small_kernel", "serpentine", "pp_sched", "fused_adapter", "resid_nt",
                "nt_out", "group_n", "splitk", "gemm_rows", "wide_kernel", "graph_max_batch", "train_chains", "train_chain_min_rows", "train_prune_last",
                "train_batched_grads")
 _ENV_OVERRIDES = {  # env name -> (option key, value map)

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libconcepthash_hip.so")
 SOURCES = ["model.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_r4.hip", "attention.hip", "rowops.hip", "head.hip", "small_f32.hip", "hamming.hip",
-           "preprocess.hip", "augment.hip", "train_kernels.hip", "attention_bwd.hip", "train.hip", "jpeg.hip", "jpeg_host.cpp", "errors.cpp"]
+           "preprocess.hip", "augment.hip", "train_kernels.hip", "attention_bwd.hip", "attention_stream.hip", "train.hip", "jpeg.hip", "jpeg_host.cpp", "errors.cpp"]
 # plain C++ sources (no HIP): compiled by the same driver as host code; tests/test_jpeg.py also builds them with g++ -fsanitize=address,undefined
 HOST_SOURCES = ["jpeg_host.cpp", "errors.cpp"]
 # kernels that lost to the dispatched ones (DESIGN.md sections 3.8-3.9): kept in csrc/experiments/ with their parity tests, compiled
@@ -22,7 +22,7 @@ HEADERS = ["ch_common.h", "ch_host.h", "kernels.h", "gemm_epilogue.h", "model_in
            os.path.join("..", "..", "include", "concepthash_hip_debug.h")]
 # attention post-processes every MFMA result on the VALU: keep accumulators in VGPRs (no v_accvgpr_read round trips)
 # preprocess / augment reproduce Pillow's double-precision filter coefficients (and its samplers) bit for bit: no fused multiply-adds there
-EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "preprocess.hip": ["-ffp-contract=off"],
+EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention_stream.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "preprocess.hip": ["-ffp-contract=off"],
                "augment.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

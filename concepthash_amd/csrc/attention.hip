@@ -1,4 +1,5 @@
 // Multi-head self-attention for the ConceptHash ViT encoder (gfx950): head_dim 64, sequence 54..288 tokens, no mask.
+// (Longer sequences: attention_stream.hip; ch_attention below chooses by length.)
 //
 // Restates HF CLIPAttention's eager path (transformers modeling_clip.py eager_attention_forward: softmax(q k^T / sqrt(d)) v)
 // as called from the reference's CLIPEncoderLayerWithAdapter.forward (models/layers/adapter.py:146-152).  The reference
@@ -252,9 +253,15 @@ int launch_attn(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, floa
 }  // namespace
 
 int ch_attention(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s, float *cattn, int ncon, bool compact,
-                 bool rev) {
+                 bool rev, int kernel) {
     CH_REQUIRE(B > 0 && ntok > 0 && heads > 0, "attention: empty problem");
     CH_REQUIRE(!compact || (ncon >= 1 && ncon < ntok), "attention: compact mode needs 1 <= ncon < ntok");
+    CH_REQUIRE(kernel >= 0 && kernel <= 2, "attention: kernel must be 0 (by length), 1 (resident) or 2 (streaming)");
+    if (kernel == 2 || (kernel == 0 && ntok > CH_ATTN_RESIDENT_MAX_TOKENS)) {   // attention_stream.hip
+        ch_attention_count_launch(1);
+        return ch_attention_stream(qkv, B, ntok, heads, out, s, cattn, ncon, compact, rev);
+    }
+    if (ntok <= CH_ATTN_RESIDENT_MAX_TOKENS) ch_attention_count_launch(0);
     const int KB = (ntok + 31) / 32;
     switch (KB) {
         case 1: return launch_attn<1>(qkv, B, ntok, heads, out, cattn, ncon, compact, rev ? 1 : 0, s);
@@ -267,6 +274,6 @@ int ch_attention(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hip
         case 8: return launch_attn<8>(qkv, B, ntok, heads, out, cattn, ncon, compact, rev ? 1 : 0, s);
         case 9: return launch_attn<9>(qkv, B, ntok, heads, out, cattn, ncon, compact, rev ? 1 : 0, s);
     }
-    ch_set_error("attention: more than 288 tokens per image is not supported");
+    ch_set_error("attention: the LDS-resident kernel holds at most 288 tokens per image");
     return 2;
 }

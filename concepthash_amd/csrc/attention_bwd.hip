@@ -318,9 +318,15 @@ int launch_bwd(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, 
 // qkv [B*ntok, 3D] bf16 (q | k | v), dO [B*ntok, D] bf16 -> dqkv [B*ntok, 3D] bf16 (dq | dk | dv); head_dim 64
 // dpext (optional): [B, heads, ncon, ntok - ncon - 1] fp32 cotangent of the concept tokens' attention rows over the patch tokens
 int ch_attention_bwd(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, bf16_t *dqkv, hipStream_t s, const float *dpext,
-                     int ncon) {
+                     int ncon, int kernel) {
     CH_REQUIRE(B > 0 && ntok > 0 && heads > 0, "attention backward: empty problem");
     CH_REQUIRE(!dpext || (ncon >= 1 && ncon < ntok - 1), "attention backward: the probability cotangent needs 1 <= ncon < ntok - 1");
+    CH_REQUIRE(kernel >= 0 && kernel <= 2, "attention backward: kernel must be 0 (by length), 1 (resident) or 2 (streaming)");
+    if (kernel == 2 || (kernel == 0 && ntok > CH_ATTN_RESIDENT_MAX_TOKENS)) {   // attention_stream.hip
+        ch_attention_count_launch(3);
+        return ch_attention_bwd_stream(qkv, dO, B, ntok, heads, dqkv, s, dpext, ncon);
+    }
+    if (ntok <= CH_ATTN_RESIDENT_MAX_TOKENS) ch_attention_count_launch(2);
     const int KB = (ntok + 31) / 32;
     switch (KB) {
         case 1: return launch_bwd<1>(qkv, dO, B, ntok, heads, dqkv, dpext, ncon, s);
@@ -333,6 +339,6 @@ int ch_attention_bwd(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int h
         case 8: return launch_bwd<8>(qkv, dO, B, ntok, heads, dqkv, dpext, ncon, s);
         case 9: return launch_bwd<9>(qkv, dO, B, ntok, heads, dqkv, dpext, ncon, s);
     }
-    ch_set_error("attention backward: more than 288 tokens per image is not built (LDS-resident Q/K/V/dO)");
+    ch_set_error("attention backward: the LDS-resident kernel holds at most 288 tokens per image");
     return 2;
 }

@@ -167,8 +167,20 @@ int ch_gather_head_rows(const float *H, int B, int ntok, int ncon, int D, float 
 // cattn (optional): [B, heads, ncon, ntok - ncon - 1] fp32 softmax rows of the last `ncon` tokens over tokens 1 .. ntok-ncon-1
 // compact: queries are only CLS + the last `ncon` (concept) tokens of every image; out is [B * (1 + ncon), heads * 64]
 // rev: process the (image, head) pairs from the last image to the first (serpentine launch order)
+// kernel: 0 = by length (up to 288 tokens the LDS-resident kernel, past them the streaming one), 1 = resident, 2 = streaming
 int ch_attention(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s, float *cattn = nullptr,
-                 int ncon = 0, bool compact = false, bool rev = false);
+                 int ncon = 0, bool compact = false, bool rev = false, int kernel = 0);
+
+// ---- attention_stream.hip ------------------------------------------------------------------------------------
+// The same two operations for any length up to CH_ATTN_MAX_TOKENS: K / V (Q / dO) walked in 64-row blocks through a two-deep
+// LDS ring, online softmax.  Reached through ch_attention / ch_attention_bwd (`kernel`), which count every launch.
+constexpr int CH_ATTN_RESIDENT_MAX_TOKENS = 288;
+constexpr int CH_ATTN_MAX_TOKENS = 1 + 32 * 32 + 64;   // CLS + a 32 x 32 patch grid + the most concept tokens a model may have
+int ch_attention_stream(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s, float *cattn, int ncon, bool compact,
+                        bool rev);
+int ch_attention_bwd_stream(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, bf16_t *dqkv, hipStream_t s, const float *dpext,
+                            int ncon);
+void ch_attention_count_launch(int which);   // 0 forward resident, 1 forward streaming, 2 backward resident, 3 backward streaming
 
 // ---- head.hip ------------------------------------------------------------------------------------------------
 struct HeadParams {
@@ -268,5 +280,6 @@ int ch_small_ln_bwd(const float *dy, const float *x, const float *gamma, int row
 int ch_gather_concept_rows(const float *H, int B, int ntok, int Q, int D, float *out, hipStream_t s);
 // qkv [B*ntok, 3D] (q | k | v), dO [B*ntok, D] -> dqkv [B*ntok, 3D]; head_dim 64
 // dpext (optional): [B, heads, ncon, ntok - ncon - 1] fp32 cotangent of the last `ncon` tokens' attention rows over tokens 1 .. ntok-ncon-1
+// kernel: as ch_attention
 int ch_attention_bwd(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, bf16_t *dqkv, hipStream_t s,
-                     const float *dpext = nullptr, int ncon = 0);
+                     const float *dpext = nullptr, int ncon = 0, int kernel = 0);

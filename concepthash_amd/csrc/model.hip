@@ -494,7 +494,7 @@ int run_chain(ch_model *mm, int pi, const void *images_all, int image_dtype, int
         float *cattn = !concept_attn ? nullptr
                        : attn_all_layers ? concept_attn + (size_t)i * Btot * c.heads * c.ncontext * np
                        : i == nlayers - 1 ? concept_attn : nullptr;
-        if (int e = ch_attention(m->QKV, B, ntok, c.heads, m->AO, s, cattn, c.ncontext, pruned, next_dir() != 0))
+        if (int e = ch_attention(m->QKV, B, ntok, c.heads, m->AO, s, cattn, c.ncontext, pruned, next_dir() != 0, mm->attn_stream ? 2 : 0))
             return e;
         if (pruned) {
             // from here on every buffer holds B * (1 + Q) compact rows (image-major: CLS, then the concept tokens)
@@ -581,7 +581,8 @@ int validate(const ch_model_config *c) {
     CH_REQUIRE(c->max_batch >= 1, "max_batch must be >= 1");
     CH_REQUIRE(c->act == 0 || c->act == 1, "act must be 0 (quick_gelu) or 1 (gelu)");
     const int grid = c->image_size / c->patch;
-    CH_REQUIRE(1 + grid * grid + c->ncontext <= 288, "more than 288 tokens per image is not supported");
+    CH_REQUIRE(grid <= 32, "more than a 32 x 32 patch grid (1,024 patch tokens per image) is not supported");
+    static_assert(1 + 32 * 32 + 64 <= CH_ATTN_MAX_TOKENS, "the streaming attention kernels cover every admissible model");
     return 0;
 }
 
@@ -660,6 +661,7 @@ const OptionRef g_options[] = {
     {"ln_fold", 1, CH_OPT_FIELD(ln_fold), 0, 1},
     {"prune_last", 1, CH_OPT_FIELD(prune_last), 0, 1},
     {"pp_min_k", 0, CH_OPT_FIELD(pp_min_k), 0, 1 << 20},
+    {"attn_stream", 0, CH_OPT_FIELD(attn_stream), 0, 1},
     {"small_kernel", 0, CH_OPT_FIELD(small_kernel), 0, 2},
     {"serpentine", 1, CH_OPT_FIELD(serpentine), 0, 1},
     {"pp_sched", 0, CH_OPT_FIELD(pp_sched), 0, 2},
@@ -1039,6 +1041,11 @@ extern "C" int32_t ch_debug_experiments_built(void) {
 extern "C" int ch_debug_attention(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, void *stream) {
     CH_REQUIRE(qkv && out, "debug_attention: null pointer");
     return ch_attention((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_attention_ex(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, float *cattn, int32_t ncon,
+                                     int32_t compact, int32_t kernel, void *stream) {
+    CH_REQUIRE(qkv && out, "debug_attention_ex: null pointer");
+    return ch_attention((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream, cattn, ncon, compact != 0, false, kernel);
 }
 
 extern "C" int ch_debug_adapter(const void *A, float *H, int32_t M, int32_t D, int32_t b, const float *Wd, const float *bd,

@@ -80,6 +80,7 @@ struct ch_model {
     int pp_sched = 0;  // option "pp_sched": schedule of the 256x256 GEMM (gemm_pp.hip)
     int small_kernel = 0;  // option "small_kernel": 0 = dispatcher (ring up to CH_RING_MAX_ROWS rows), 1 = 128x128x64 two-phase always, 2 = ring always
     int pp_min_k = 0;  // option "pp_min_k" (tests: sends small-K GEMMs of a small fixture to the 256x256 kernel)
+    int attn_stream = 0;  // option "attn_stream" (tests: 1 sends attention of <= 288 tokens, forward and backward, to the streaming kernels)
     // ---- per-handle tuning / test options (ch_model_set_option; the library reads no environment variable)
     int resid_nt = 0, nt_out = 0;   // cache policy of the fp32 residual read-modify-write / of large bf16 outputs: 0 = by tensor size, 1 = on, -1 = off
     int group_n = 0;                // n-tiles per L2-resident weight group of the GEMM tile order (0 = host heuristic)

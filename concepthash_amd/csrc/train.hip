@@ -210,7 +210,7 @@ int forward_chain(ch_trainer *t, int ch, const void *images_all, int image_dtype
         float *cattn = !out_cattn_all ? nullptr
                        : t->attn_all_layers ? out_cattn_all + ((size_t)l * t->B + img0) * c.heads * Q * np
                        : l == L - 1 ? out_cattn_all + (size_t)img0 * c.heads * Q * np : nullptr;
-        if (int e = ch_attention(R.d3(v.QKV), B, ntok, c.heads, R.d(v.AO), s, cattn, Q, pruned)) return e;
+        if (int e = ch_attention(R.d3(v.QKV), B, ntok, c.heads, R.d(v.AO), s, cattn, Q, pruned, false, m->attn_stream ? 2 : 0)) return e;
         if (pruned) {      // from here on every buffer of this layer holds B * (1 + Q) compact rows (CLS, then the concept tokens)
             cur = B * nq;
             if (int e = ch_gather_head_rows(H, B, ntok, Q, D, Hc, s)) return e;
@@ -348,7 +348,7 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
         const float *dpext = !dcattn_all ? nullptr
                              : t->attn_all_layers ? dcattn_all + ((size_t)l * t->B + img0) * c.heads * Q * (ntok - Q - 1)
                              : l == L - 1 ? dcattn_all + (size_t)img0 * c.heads * Q * (ntok - Q - 1) : nullptr;
-        if (int e = ch_attention_bwd(R.d3(v.QKV), dctx, B, ntok, c.heads, tQKV, s, dpext, Q)) return e;
+        if (int e = ch_attention_bwd(R.d3(v.QKV), dctx, B, ntok, c.heads, tQKV, s, dpext, Q, m->attn_stream ? 2 : 0)) return e;
         g = GemmCall{D, 3 * D, tQKV, x.qkv_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
@@ -579,6 +579,11 @@ extern "C" int ch_debug_attention_bwd(const void *qkv, const void *dO, int32_t B
                                       int32_t ncon, void *stream) {
     CH_REQUIRE(qkv && dO && dqkv, "debug_attention_bwd: null argument");
     return ch_attention_bwd((const bf16_t *)qkv, (const bf16_t *)dO, B, ntok, heads, (bf16_t *)dqkv, (hipStream_t)stream, dpext, ncon);
+}
+extern "C" int ch_debug_attention_bwd_ex(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
+                                         int32_t ncon, int32_t kernel, void *stream) {
+    CH_REQUIRE(qkv && dO && dqkv, "debug_attention_bwd_ex: null argument");
+    return ch_attention_bwd((const bf16_t *)qkv, (const bf16_t *)dO, B, ntok, heads, (bf16_t *)dqkv, (hipStream_t)stream, dpext, ncon, kernel);
 }
 extern "C" int ch_debug_wgrad(const void *A, int32_t lda, const void *Bm, int32_t ldb, int64_t rows, int64_t rows_alloc, int32_t N,
                               int32_t K, float *out, void *stream) {

@@ -84,11 +84,13 @@ size_t ch_model_device_bytes(const ch_model *m);
 
 /* Tuning / test options of ONE model handle ("no hidden global state except an opaque handle").  Every call
  * made on the handle afterwards uses the new value; outputs are bit-identical for every setting except "ln_fold" (rounding points
- * move) and "splitk" (summation order).  Unknown keys and out-of-range values are errors.
+ * move), "splitk" (summation order) and "attn_stream" (another kernel's rounding).  Unknown keys and out-of-range values are errors.
  *   "streams"       1..4   micro-batch launch chains of ch_encode on as many HIP streams (default 2; 1 = what a per-kernel profile wants)
  *   "ln_fold"       0/1    LayerNorm folded into the consumer GEMMs (default 1)
  *   "prune_last"    0/1    final layer past its attention on the rows the hashing head reads only (default 1)
  *   "pp_min_k"      >= 0   smallest K that goes to the 256x256 ping-pong GEMM (0 = dispatcher default: 512 and >= 128 tiles)
+ *   "attn_stream"   0/1    1 = attention of <= 288 tokens also runs the streaming kernels, forward and backward (tests; default 0: up to 288
+ *                          tokens per image the LDS-resident kernels, past them -- up to a 32 x 32 patch grid -- the streaming ones)
  *   "resid_nt"      -1/0/1 non-temporal read-modify-write of the fp32 residual: off / by tensor size (default) / on
  *   "nt_out"        -1/0/1 non-temporal stores of large bf16 GEMM outputs: off / by tensor size (default) / on
  *   "group_n"       >= 0   n-tiles per L2-resident weight group of the GEMM tile order (0 = host heuristic)

@@ -51,6 +51,15 @@ int ch_debug_adapter(const void *A, float *H, int32_t M, int32_t D, int32_t b, c
                      void *work_wdf, float *work_c, float *work_d, int32_t dbg, void *stream);
 /* qkv [B*ntok, 3*heads*64] bf16 (q | k | v) -> out [B*ntok, heads*64] bf16: softmax(q k^T / 8) v per (image, head). */
 int ch_debug_attention(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, void *stream);
+/* The same launch with every mode of the kernels (attention.hip, attention_stream.hip): cattn (optional) [B, heads, ncon, ntok - ncon - 1]
+ * fp32 receives the softmax rows of the last `ncon` tokens over tokens 1 .. ntok - ncon - 1 (attn_cache[-1][:, :, -Q:, 1:-Q],
+ * models/arch/coop.py:481-482); compact = 1: only token 0 and the last `ncon` tokens are queries, out is [B * (1 + ncon), heads*64];
+ * kernel: 0 = by length (<= 288 tokens the LDS-resident kernel, longer the streaming one), 1 = resident, 2 = streaming. */
+int ch_debug_attention_ex(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, float *cattn, int32_t ncon, int32_t compact,
+                          int32_t kernel, void *stream);
+/* Attention launches since the library was loaded: which = 0 forward resident, 1 forward streaming, 2 backward resident, 3 backward
+ * streaming -- lets a test prove which kernel produced the output it compared. */
+int64_t ch_debug_attention_dispatch_count(int32_t which);
 
 /* 1 = the mAP scan passes read the gallery through scalar loads (the round-1 form) instead of 16-row VMEM blocks + DPP row broadcast:
  * same results bit for bit, kept as a cross-check of the row loops (tests/test_hamming_gpu.py).  Process-wide, tests only. */
@@ -59,6 +68,9 @@ void ch_debug_set_hamming_scalar_loads(int32_t on);
 /* Kernel taps of the training step: see train_kernels.hip / attention_bwd.hip. */
 int ch_debug_attention_bwd(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
                            int32_t ncon, void *stream);
+/* ... with the kernel chosen as in ch_debug_attention_ex. */
+int ch_debug_attention_bwd_ex(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
+                              int32_t ncon, int32_t kernel, void *stream);
 int ch_debug_wgrad(const void *A, int32_t lda, const void *Bm, int32_t ldb, int64_t rows, int64_t rows_alloc, int32_t N, int32_t K,
                    float *out, void *stream);
 int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int32_t D, float eps, const float *dres_in, float *dres_out,

@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--ab", default="", help="A/B of model options in one process, interleaved: 'name:key=v,key=v;name2:key=v' "
                     "(ch_model_set_option keys; an empty option list = the defaults); one engine per variant, --cycles rounds over them")
     ap.add_argument("--cycles", type=int, default=1)
+    ap.add_argument("--image-size", type=int, default=0, help="square input size other than the config's pretrain resolution (position table "
+                    "interpolated; e.g. 448 = 789 tokens of ViT-B/16, which run the streaming attention kernels)")
+    ap.add_argument("--encode", action="store_true", help="also time ch_encode (evaluation) at the same batches and input size")
     a = ap.parse_args()
     if a.ab:
         return ab(a)
@@ -83,12 +86,14 @@ def main():
     sd = synthetic.synthetic_state_dict(cfg, nbit=64, nclass=200)
     adapters = adapters_from_state_dict(sd, cfg["L"], cfg["D"], cfg["b"])
     batches = [int(x) for x in a.batches.split(",")]
-    eng = TrainEngine(sd, adapters, heads=cfg["heads"], max_batch=max(batches), device=torch.device("cuda", torch.cuda.current_device()))
+    size = a.image_size or cfg["image"]
+    eng = TrainEngine(sd, adapters, heads=cfg["heads"], max_batch=max(batches), device=torch.device("cuda", torch.cuda.current_device()),
+                      image_size=size)
     fwd_f, bwd_f = encoder_step_flops(eng.cfg)
     Q, D = 4, cfg["D"]
     ctx = torch.randn(Q, D, device="cuda") * 0.02
     for B in batches:
-        x = synthetic.synthetic_images(B, cfg["image"]).to("cuda", torch.bfloat16)
+        x = synthetic.synthetic_images(B, size).to("cuda", torch.bfloat16)
         dhf = torch.randn(B, Q, D, device="cuda") * 0.01
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         tf = tb = 0.0
@@ -105,12 +110,29 @@ def main():
                 tb += ev[1].elapsed_time(ev[2])
         tf /= a.steps
         tb /= a.steps
-        print(json.dumps({"config": a.config, "batch": B, "forward_ms": round(tf, 3), "backward_ms": round(tb, 3),
+        print(json.dumps({"config": a.config, "image_size": size, "tokens": eng.encoder.ntok, "batch": B, "forward_ms": round(tf, 3), "backward_ms": round(tb, 3),
                           "step_ms": round(tf + tb, 3), "images_per_s": round(B / (tf + tb) * 1e3, 1),
                           "forward_tflops": round(fwd_f * B / tf / 1e9, 1), "backward_tflops": round(bwd_f * B / tb / 1e9, 1),
                           "trainer_gib": round(eng.device_bytes / 2 ** 30, 2)}))
 
 
+    if a.encode:
+        eng.close()
+        from concepthash_amd.encoder import ConceptHashEncoder
+        enc = ConceptHashEncoder(sd, heads=cfg["heads"], max_batch=max(batches), image_size=size)
+        for B in batches:
+            x = synthetic.synthetic_images(B, size).to("cuda", torch.bfloat16)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for it in range(a.warmup + a.steps):
+                if it == a.warmup:
+                    e0.record()
+                enc.encode(x, want=("codes", "packed"))
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / a.steps
+            print(json.dumps({"config": a.config, "image_size": size, "tokens": enc.ntok, "batch": B, "encode_ms": round(ms, 3),
+                              "encode_images_per_s": round(B / ms * 1e3, 1)}))
+        enc.close()
     if a.full:
         eng.close()
         full_step(a, cfg, sd, batches)
