@@ -106,12 +106,17 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "ch_adapter_arena_numel": (c_int64, [c_void_p]),
     "ch_trainer_create": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, POINTER(c_void_p)]),
+    "ch_backbone_arena_numel": (c_int64, [POINTER(ModelConfig)]),
+    "ch_backbone_arena_offset": (c_int64, [POINTER(ModelConfig), c_char_p, POINTER(c_int64)]),
+    "ch_trainer_create_ex": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p)]),
     "ch_trainer_destroy": (None, [c_void_p]),
     "ch_trainer_bytes": (c_int64, [c_void_p]),
     "ch_trainer_refresh": (c_int, [c_void_p, c_void_p]),
     "ch_train_forward": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "ch_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_int32, c_int32, c_void_p]),
+    "ch_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_double, c_int32, c_int64,
+                             c_void_p]),
     "ch_debug_attention_bwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "ch_debug_attention_bwd_ex": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ch_debug_wgrad": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),

@@ -272,6 +272,23 @@ int ch_adapter_refresh(const float *params, int64_t stride, int nad, int D, int 
                        bf16_t *up_w, bf16_t *up_wT, bf16_t *down_wgT, hipStream_t s);
 int ch_sgd_step_launch(float *p, const float *g, float *buf, int64_t n, float lr, float momentum, float wd, float dampening, int nesterov,
                        int first, hipStream_t s);
+// torch.optim.Adam (decoupled = 0: weight decay added to the gradient) / AdamW (1: p *= 1 - lr * wd first), amsgrad False; step = t >= 1
+int ch_adam_step_launch(float *p, const float *g, float *m, float *v, int64_t n, double lr, double beta1, double beta2, double eps, double wd,
+                        int decoupled, int64_t step, hipStream_t s);
+// ---- trainable backbone: gradients of a Linear with a folded input LayerNorm, made of up to three row blocks (q | k | v)
+struct ChFoldGradParts {
+    const float *W[3];   // fp32 master weights [rows_each, D] of every block
+    float *dW[3], *db[3];
+    int nparts, rows_each;
+};
+// T [nparts * rows_each, D] = dpre^T x_hat, c = column sums of dpre: dW = T o gamma + c (x) beta, db = c, dgamma = sum_j T o W, dbeta = sum_j c_j W_j
+int ch_fold_grads(const float *T, const float *c, const float *gamma, const float *beta, int D, const ChFoldGradParts &parts, float *dgamma,
+                  float *dbeta, hipStream_t s);
+// backward of embeddings + pre_layrnorm: X (patch rows = the patch GEMM's output) <- dy o x_hat, dY <- dx, patch rows of dx compact as bf16
+int ch_embed_bwd(float *X, float *dY, int B, int ntok, int np, int D, const float *cls_pos0, const float *ctx, const float *gamma, float eps,
+                 bf16_t *dx_patch, hipStream_t s);
+// out[j][:] = sum_b dX[b*ntok + j][:], j < nrows
+int ch_token_rows_sum(const float *dX, int B, int ntok, int nrows, int D, float *out, hipStream_t s);
 int ch_concept_rows_sum(const float *dH, int B, int ntok, int Q, int D, float *out, hipStream_t s);
 int ch_scatter_concept_rows(const float *dhf, int B, int ntok, int Q, int D, float *dH, bf16_t *dHb, hipStream_t s);
 // compact head rows [B*(1+Q), D] (CLS, concept tokens) -> full token rows [B*ntok, D], zeros elsewhere; fp32 (is_f32) or bf16

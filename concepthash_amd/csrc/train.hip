@@ -25,6 +25,7 @@
 // Parameter arena (fp32, caller-owned, device): adapters in (layer, adapter) order, each
 //   [ln_w D][ln_b D][down_w b*D][down_b b][up_w D*b][up_b D][scale 1];  the gradient arena has the same layout.
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "model_internal.h"
@@ -37,6 +38,19 @@ struct AdWork {
 };
 struct LayerT {
     bf16_t *qkv_wgT = nullptr, *out_wT = nullptr, *fc1_wgT = nullptr, *fc2_wT = nullptr;
+};
+// trainable backbone: the forward's working copies of one layer, derived from the fp32 arena by ch_trainer_refresh (biases and
+// LayerNorm vectors are read from the arena itself)
+struct BbWork {
+    bf16_t *qkv_wf = nullptr, *out_w = nullptr, *fc1_wf = nullptr, *fc2_w = nullptr;
+    float *qkv_c = nullptr, *qkv_d = nullptr, *fc1_c = nullptr, *fc1_d = nullptr;
+};
+// one layer's tensors inside the backbone arena (parameters or gradients): the layout written in include/concepthash_hip.h
+struct BbPtr {
+    float *ln1_w, *ln1_b, *qkv_w[3], *qkv_b[3], *out_w, *out_b, *ln2_w, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+};
+struct BbEmb {
+    float *cls, *patch_w, *pos, *pre_w, *pre_b;
 };
 struct Saved {
     bf16_t *Xn1, *QKV, *AO, *A, *P1, *G1, *Xn2, *F1pre, *A2, *P2, *G2;
@@ -85,6 +99,19 @@ struct ch_trainer {
     bool batched_grads = true;
     float *ws_wgradT[TR_CHAINS] = {}, *ws_colsumD[TR_CHAINS] = {}, *Gs[TR_CHAINS] = {}, *Ts[TR_CHAINS] = {}, *cus[TR_CHAINS] = {},
           *cds[TR_CHAINS] = {}, *ws_ag[TR_CHAINS] = {};
+    // ---- trainable backbone (ch_trainer_create_ex with a second arena pair; everything below is unused, and nothing of it allocated,
+    // for a trainer created by ch_trainer_create).  The forward reads `lw` / `patch_w` / `pos` / ...: the model's frozen weights, or --
+    // trainable -- the working copies in `bw` and the arena's own biases and LayerNorm vectors.
+    bool bb = false;
+    float *bparams = nullptr, *bgrads = nullptr, *bgrads1 = nullptr;
+    int64_t bb_numel = 0, bb_layer_numel = 0;
+    std::vector<LayerW> lw;     // [L]
+    std::vector<BbWork> bw;     // [L]
+    const bf16_t *patch_w = nullptr;
+    const float *pos = nullptr, *cls_pos0 = nullptr, *pre_w = nullptr, *pre_b = nullptr;
+    bf16_t *bb_patch_w = nullptr;
+    float *bb_cls_pos0 = nullptr;
+    float *ws_bb[TR_CHAINS] = {}, *ws_bbcol[TR_CHAINS] = {}, *Tbb[TR_CHAINS] = {}, *cbb[TR_CHAINS] = {};
     bool forward_done = false;
     bool attn_all_layers = false;   // layout of the concept-attention tap, latched by ch_train_forward for the matching ch_train_backward
 };
@@ -108,6 +135,41 @@ void *talloc(ch_trainer *t, size_t bytes, bool &ok) {
 int64_t adapter_numel(const ch_model_config &c) {
     const int64_t D = c.dim, b = c.adapter_dim;
     return 2 * D + b * D + b + D * b + D + 1;
+}
+
+// backbone arena layout (include/concepthash_hip.h): per layer
+//   [ln1.w D][ln1.b D][q.w D*D][q.b D][k.w D*D][k.b D][v.w D*D][v.b D][out.w D*D][out.b D][ln2.w D][ln2.b D][fc1.w M*D][fc1.b M][fc2.w D*M][fc2.b D]
+// then [class_embedding D][patch_embedding.weight D*3*p*p][position_embedding.weight (np+1)*D][pre_layrnorm.weight D][.bias D]
+int64_t bb_layer_numel(const ch_model_config &c) {
+    const int64_t D = c.dim, M = c.ffn;
+    return 4 * D * D + 2 * D * M + 9 * D + M;
+}
+int64_t bb_emb_numel(const ch_model_config &c) {
+    const int64_t D = c.dim, g = c.image_size / c.patch;
+    return D + D * 3 * c.patch * c.patch + (g * g + 1) * D + 2 * D;
+}
+BbPtr bb_ptrs(float *base, const ch_model_config &c) {
+    const int64_t D = c.dim, M = c.ffn;
+    BbPtr p;
+    float *q = base;
+    auto take = [&](int64_t n) { float *r = q; q += n; return r; };
+    p.ln1_w = take(D); p.ln1_b = take(D);
+    for (int j = 0; j < 3; ++j) { p.qkv_w[j] = take(D * D); p.qkv_b[j] = take(D); }
+    p.out_w = take(D * D); p.out_b = take(D);
+    p.ln2_w = take(D); p.ln2_b = take(D);
+    p.fc1_w = take(M * D); p.fc1_b = take(M);
+    p.fc2_w = take(D * M); p.fc2_b = take(D);
+    return p;
+}
+BbEmb bb_emb_ptrs(float *arena, const ch_model_config &c) {
+    const int64_t D = c.dim, g = c.image_size / c.patch;
+    BbEmb e;
+    e.cls = arena + bb_layer_numel(c) * c.layers;
+    e.patch_w = e.cls + D;
+    e.pos = e.patch_w + D * 3 * c.patch * c.patch;
+    e.pre_w = e.pos + (g * g + 1) * D;
+    e.pre_b = e.pre_w + D;
+    return e;
 }
 
 struct AdPtr {
@@ -184,12 +246,12 @@ int forward_chain(ch_trainer *t, int ch, const void *images_all, int image_dtype
     if (int e = ch_im2col(images, image_dtype, B, c.image_size, c.patch, m->Kp, PATCH, s)) return e;
     {
         GemmParams p{};
-        p.X = PATCH; p.W = m->patch_w; p.M = B * np; p.N = D; p.K = m->Kp; p.X_rows_alloc = t->region_prows[ch];
-        p.resid = H; p.ldr = D; p.pos = m->pos; p.tokens_per_img = ntok; p.patches_per_img = np; p.pp_min_k = m->pp_min_k;
+        p.X = PATCH; p.W = t->patch_w; p.M = B * np; p.N = D; p.K = m->Kp; p.X_rows_alloc = t->region_prows[ch];
+        p.resid = H; p.ldr = D; p.pos = t->pos; p.tokens_per_img = ntok; p.patches_per_img = np; p.pp_min_k = m->pp_min_k;
         if (int e = ch_gemm_bf16(p, EPI_PATCH, s)) return e;
     }
-    const LayerW &w0 = m->layers[0];
-    if (int e = ch_assemble_preln(H, B, ntok, np, D, m->cls_pos0, t->ctx, m->pre_w, m->pre_b, w0.ln1_w, w0.ln1_b, c.ln_eps,
+    const LayerW &w0 = t->lw[0];
+    if (int e = ch_assemble_preln(H, B, ntok, np, D, t->cls_pos0, t->ctx, t->pre_w, t->pre_b, w0.ln1_w, w0.ln1_b, c.ln_eps,
                                   R.d(t->XnDummy), s))
         return e;
     if (int e = ch_hb_stats(H, rows, D, R.d(t->sv[0].Xn1), R.st(t->sv[0].st1), s)) return e;
@@ -197,7 +259,7 @@ int forward_chain(ch_trainer *t, int ch, const void *images_all, int image_dtype
     float *Hc = t->Hc + (size_t)ch * t->hc_rows * D;
     int cur = rows;          // rows carried: all tokens, or B * (1 + Q) past the last layer's attention
     for (int l = 0; l < L; ++l) {
-        const LayerW &w = m->layers[l];
+        const LayerW &w = t->lw[l];
         Saved &v = t->sv[l];
         GemmCall g;
         // attention block
@@ -265,6 +327,11 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
     const Rows R{t->row_off[ch], D, M, bpad};
     const float *zero = m->zero_bias;
     float *grads = ch == 0 ? t->grads : t->grads1;
+    // trainable backbone: this chain's gradient arena, and the fp32 copy of d(branch input) the bias gradients are summed from (the
+    // forward's residual buffer is free during backward)
+    const bool bb = t->bb;
+    float *bgrads = ch == 0 ? t->bgrads : t->bgrads1;
+    float *dMf = bb ? R.d(t->H) : nullptr;
     bf16_t *dMb = R.d(t->dMb), *tD = R.d(t->tD), *tD2 = R.d(t->tD2), *tB = R.b(t->tB), *tM = R.m(t->tM), *tQKV = R.d3(t->tQKV);
     const int64_t ralloc = t->region_rows[ch];
     // gradient of the residual stream: fp32 + its bf16 copy.  Full token rows, or -- inside the pruned last layer -- the compact
@@ -302,7 +369,7 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
         g = GemmCall{D, bpad, tB, aw.down_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
-        if (int e = ch_ln_bwd(tD, in, stin, cur, D, 1e-5f, dH, nullptr, dMb, s, tD2)) return e;
+        if (int e = ch_ln_bwd(tD, in, stin, cur, D, 1e-5f, dH, dMf, dMb, s, tD2)) return e;
         if (int e = ch_wgrad_tn(tB, bpad, tD2, D, cur, ralloc, bpad, D, t->T[ch], bg ? t->ws_wgradT[ch] : t->ws_wgrad[ch], s, bg ? &nchunk[2] : nullptr))
             return e;
         if (int e = ch_colsum(tB, 0, bpad, cur, bpad, t->cd[ch], bg ? t->ws_colsumD[ch] : t->ws_colsum[ch], s, bg ? &nchunk[3] : nullptr)) return e;
@@ -317,20 +384,45 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
                                 t->ws_colsum[ch], s);
     };
 
+    // ---- trainable backbone: weight gradients from the operands the chain has in hand anyway (all of it behind `bb`)
+    // plain Linear: dW [N, K] = dy^T x straight into the arena, db = fp32 column sums of dy (a cancelled sum: train.hip adapter_bwd)
+    auto plain_grads = [&](bf16_t *dy_b, const float *dy_f, const bf16_t *xin, int N, int K, int64_t dyalloc, float *dW, float *db) -> int {
+        if (int e = ch_wgrad_tn(dy_b, N, xin, K, cur, dyalloc, N, K, dW, t->ws_bb[ch], s)) return e;
+        return ch_colsum(dy_f, 1, N, cur, N, db, t->ws_bbcol[ch], s);
+    };
+    // Linear with its input LayerNorm folded in: T = dpre^T x_hat, c = colsum(dpre), assembled by ch_fold_grads
+    auto folded_grads = [&](bf16_t *dpre, const bf16_t *xhat, int N, const ChFoldGradParts &parts, const float *gamma, const float *beta,
+                            float *dgamma, float *dbeta) -> int {
+        if (int e = ch_wgrad_tn(dpre, N, xhat, D, cur, ralloc, N, D, t->Tbb[ch], t->ws_bb[ch], s)) return e;
+        if (int e = ch_colsum(dpre, 0, N, cur, N, t->cbb[ch], t->ws_bbcol[ch], s)) return e;
+        return ch_fold_grads(t->Tbb[ch], t->cbb[ch], gamma, beta, D, parts, dgamma, dbeta, s);
+    };
     for (int l = L - 1; l >= 0; --l) {
         const Saved &v = t->sv[l];
         const LayerT &x = t->lt[l];
+        const BbPtr bp = bb ? bb_ptrs(t->bparams + (int64_t)l * t->bb_layer_numel, c) : BbPtr{};
+        const BbPtr bg = bb ? bb_ptrs(bgrads + (int64_t)l * t->bb_layer_numel, c) : BbPtr{};
         // ---- x_out = x_mid + m + adapter_2(m),  m = fc2(act(fc1(LN2(x_mid))))
         if (int e = adapter_bwd(l, 1)) return e;
+        if (bb) {   // fc2: dM^T act(F1); act(F1) is recomputed from the saved pre-activation (no extra saved bytes)
+            if (int e = ch_act_fwd(R.m(v.F1pre), (int64_t)cur * M, c.act == 0 ? 0 : 1, R.m(t->F1act), s)) return e;
+            if (int e = plain_grads(dMb, dMf, R.m(t->F1act), D, M, ralloc, bg.fc2_w, bg.fc2_b)) return e;
+        }
         GemmCall g{M, D, dMb, x.fc2_wT, zero, c.act == 0 ? EPI_BIAS_DACT_QUICK : EPI_BIAS_DACT_GELU};
         g.out = tM; g.ldo = M; g.aux = R.m(v.F1pre);
         if (int e = gemm(t, ch, cur, g, s)) return e;
         g = GemmCall{D, M, tM, x.fc1_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
-        if (int e = ch_ln_bwd(tD, R.d(v.Xn2), R.st(v.st2), cur, D, c.ln_eps, dH, dH, dHb, s)) return e;
+        if (int e = ch_ln_bwd(tD, R.d(v.Xn2), R.st(v.st2), cur, D, c.ln_eps, dH, dH, dHb, s, bb ? tD2 : nullptr)) return e;
+        if (bb) {   // fc1 with layer_norm2 folded: tM^T x_hat_2
+            ChFoldGradParts parts{{bp.fc1_w, nullptr, nullptr}, {bg.fc1_w, nullptr, nullptr}, {bg.fc1_b, nullptr, nullptr}, 1, M};
+            if (int e = folded_grads(tM, tD2, M, parts, bp.ln2_w, bp.ln2_b, bg.ln2_w, bg.ln2_b)) return e;
+        }
         // ---- x_mid = x_in + a + adapter_1(a),  a = out_proj(attention(qkv(LN1(x_in))))
         if (int e = adapter_bwd(l, 0)) return e;
+        if (bb)     // out_proj: dA^T ctx (the saved attention output; compact rows inside the pruned last layer, as dA is)
+            if (int e = plain_grads(dMb, dMf, R.d(v.AO), D, D, ralloc, bg.out_w, bg.out_b)) return e;
         g = GemmCall{D, D, dMb, x.out_wT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
@@ -352,13 +444,42 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
         g = GemmCall{D, 3 * D, tQKV, x.qkv_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
-        if (int e = ch_ln_bwd(tD, R.d(v.Xn1), R.st(v.st1), cur, D, c.ln_eps, dH, dH, dHb, s)) return e;
+        if (int e = ch_ln_bwd(tD, R.d(v.Xn1), R.st(v.st1), cur, D, c.ln_eps, dH, dH, dHb, s, bb ? tD2 : nullptr)) return e;
+        if (bb) {   // q | k | v with layer_norm1 folded: tQKV^T x_hat_1
+            ChFoldGradParts parts{{bp.qkv_w[0], bp.qkv_w[1], bp.qkv_w[2]}, {bg.qkv_w[0], bg.qkv_w[1], bg.qkv_w[2]},
+                                  {bg.qkv_b[0], bg.qkv_b[1], bg.qkv_b[2]}, 3, D};
+            if (int e = folded_grads(tQKV, tD2, 3 * D, parts, bp.ln1_w, bp.ln1_b, bg.ln1_w, bg.ln1_b)) return e;
+        }
     }
     if (t->batched_grads)   // every adapter's reduced products are in their slots: one launch pair assembles all the gradients
         if (int e = ch_adapter_grads(t->Gs[ch], t->cus[ch], t->Ts[ch], t->cds[ch], t->params, D, b, bpad, grads, t->ws_ag[ch], s, 2 * L, t->ad_numel))
             return e;
     // ---- concept tokens: rows ntok-Q.. of every image are pre_layrnorm(ctx[q]) (models/arch/coop.py:470-472)
-    return ch_concept_rows_sum(dH, B, ntok, Q, D, t->dctx_sum[ch], s);
+    if (int e = ch_concept_rows_sum(dH, B, ntok, Q, D, t->dctx_sum[ch], s)) return e;
+    if (!bb) return 0;
+    // ---- trainable backbone, embedding side (models/arch/coop.py:452-472).  dH is the gradient of pre_layrnorm's output on every row.
+    const int np = m->np, Kp = m->Kp, K = 3 * c.patch * c.patch;
+    const BbEmb eg = bb_emb_ptrs(bgrads, c);
+    if (int e = ch_colsum(dH, 1, D, rows, D, eg.pre_b, t->ws_bbcol[ch], s)) return e;
+    // the pre-LayerNorm input is not kept (the forward normalises in place): its patch rows are the patch GEMM once more, on the im2col
+    // matrix the forward left in PATCH
+    float *X = R.d(t->H);
+    bf16_t *PATCH = t->PATCH + t->prow_off[ch] * Kp;
+    {
+        GemmParams p{};
+        p.X = PATCH; p.W = t->patch_w; p.M = B * np; p.N = D; p.K = Kp; p.X_rows_alloc = t->region_prows[ch];
+        p.resid = X; p.ldr = D; p.pos = t->pos; p.tokens_per_img = ntok; p.patches_per_img = np; p.pp_min_k = m->pp_min_k;
+        if (int e = ch_gemm_bf16(p, EPI_PATCH, s)) return e;
+    }
+    if (int e = ch_embed_bwd(X, dH, B, ntok, np, D, t->cls_pos0, t->ctx, t->pre_w, c.ln_eps, tD, s)) return e;
+    if (int e = ch_colsum(X, 1, D, rows, D, eg.pre_w, t->ws_bbcol[ch], s)) return e;
+    // position table (the table the forward added: rows 0 .. np); the class embedding enters row 0 only
+    if (int e = ch_token_rows_sum(dH, B, ntok, np + 1, D, eg.pos, s)) return e;
+    CH_CHECK_HIP(hipMemcpyAsync(eg.cls, eg.pos, sizeof(float) * D, hipMemcpyDeviceToDevice, s));
+    // patch weight: (patch rows of dx)^T im2col -> [D, Kp], of which the first K columns are the parameter's
+    if (int e = ch_wgrad_tn(tD, D, PATCH, Kp, (int64_t)B * np, std::min(ralloc, t->region_prows[ch]), D, Kp, t->Tbb[ch], t->ws_bb[ch], s)) return e;
+    CH_CHECK_HIP(hipMemcpy2DAsync(eg.patch_w, sizeof(float) * K, t->Tbb[ch], sizeof(float) * Kp, sizeof(float) * K, D, hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 }  // namespace
@@ -381,15 +502,103 @@ extern "C" int ch_trainer_refresh(ch_trainer *t, void *stream) {
     CH_REQUIRE(t != nullptr, "null trainer");
     const ch_model_config &c = t->m->cfg;
     const AdWork &w = t->ad[0];   // slot 0 of the contiguous per-field arrays
-    return ch_adapter_refresh(t->params, t->ad_numel, c.layers * 2, c.dim, c.adapter_dim, t->m->bpad, w.down_wf, w.fold_c, w.fold_d, w.up_w,
-                              w.up_wT, w.down_wgT, (hipStream_t)stream);
+    hipStream_t s = (hipStream_t)stream;
+    if (int e = ch_adapter_refresh(t->params, t->ad_numel, c.layers * 2, c.dim, c.adapter_dim, t->m->bpad, w.down_wf, w.fold_c, w.fold_d, w.up_w,
+                                   w.up_wT, w.down_wgT, s))
+        return e;
+    if (!t->bb) return 0;
+    // trainable backbone: bf16 / LayerNorm-folded copies for the forward, (W o gamma)^T and W^T for the input-gradient GEMMs
+    const int D = c.dim, M = c.ffn, K = 3 * c.patch * c.patch;
+    for (int l = 0; l < c.layers; ++l) {
+        const BbPtr p = bb_ptrs(t->bparams + (int64_t)l * t->bb_layer_numel, c);
+        const BbWork &b = t->bw[l];
+        const LayerT &x = t->lt[l];
+        for (int j = 0; j < 3; ++j) {
+            if (int e = ch_fold_ln(p.qkv_w[j], p.qkv_b[j], p.ln1_w, p.ln1_b, D, D, D, b.qkv_wf + (size_t)j * D * D, b.qkv_c + j * D, b.qkv_d + j * D, s))
+                return e;
+            if (int e = ch_transpose_f32_to_bf16(p.qkv_w[j], D, D, D, p.ln1_w, x.qkv_wgT + j * D, 3 * D, s)) return e;
+        }
+        if (int e = ch_fold_ln(p.fc1_w, p.fc1_b, p.ln2_w, p.ln2_b, M, M, D, b.fc1_wf, b.fc1_c, b.fc1_d, s)) return e;
+        if (int e = ch_transpose_f32_to_bf16(p.fc1_w, M, D, D, p.ln2_w, x.fc1_wgT, M, s)) return e;
+        if (int e = ch_convert_bf16(p.out_w, D, D, D, b.out_w, s)) return e;
+        if (int e = ch_transpose_f32_to_bf16(p.out_w, D, D, D, nullptr, x.out_wT, D, s)) return e;
+        if (int e = ch_convert_bf16(p.fc2_w, D, M, M, b.fc2_w, s)) return e;
+        if (int e = ch_transpose_f32_to_bf16(p.fc2_w, D, M, M, nullptr, x.fc2_wT, D, s)) return e;
+    }
+    const BbEmb e = bb_emb_ptrs(t->bparams, c);
+    if (int r = ch_convert_bf16(e.patch_w, D, K, t->m->Kp, t->bb_patch_w, s)) return r;
+    return ch_small_add(e.cls, e.pos, D, t->bb_cls_pos0, s);
+}
+
+extern "C" int64_t ch_backbone_arena_numel(const ch_model_config *cfg) {
+    if (!cfg || cfg->dim <= 0 || cfg->patch <= 0 || cfg->layers <= 0) return 0;
+    return bb_layer_numel(*cfg) * cfg->layers + bb_emb_numel(*cfg);
+}
+
+// name: a state-dict key below `vision_model.` ("encoder.layers.3.self_attn.q_proj.weight", "embeddings.class_embedding", ...)
+extern "C" int64_t ch_backbone_arena_offset(const ch_model_config *cfg, const char *name, int64_t *numel) {
+    if (!cfg || !name || cfg->dim <= 0 || cfg->patch <= 0 || cfg->layers <= 0) return -1;
+    const ch_model_config &c = *cfg;
+    const int64_t D = c.dim, M = c.ffn;
+    const std::string n(name);
+    int64_t off = -1, cnt = 0;
+    const std::string lp = "encoder.layers.";
+    if (n.compare(0, lp.size(), lp) == 0) {
+        const size_t dot = n.find('.', lp.size());
+        if (dot == std::string::npos || dot == lp.size()) return -1;
+        int64_t l = 0;
+        for (size_t i = lp.size(); i < dot; ++i) {
+            if (n[i] < '0' || n[i] > '9' || l > c.layers) return -1;
+            l = l * 10 + (n[i] - '0');
+        }
+        if (l >= c.layers) return -1;
+        const std::string f = n.substr(dot + 1);
+        static const char *names[16] = {"layer_norm1.weight", "layer_norm1.bias", "self_attn.q_proj.weight", "self_attn.q_proj.bias",
+                                        "self_attn.k_proj.weight", "self_attn.k_proj.bias", "self_attn.v_proj.weight", "self_attn.v_proj.bias",
+                                        "self_attn.out_proj.weight", "self_attn.out_proj.bias", "layer_norm2.weight", "layer_norm2.bias",
+                                        "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"};
+        const int64_t sizes[16] = {D, D, D * D, D, D * D, D, D * D, D, D * D, D, D, D, M * D, M, D * M, D};
+        int64_t o = l * bb_layer_numel(c);
+        for (int i = 0; i < 16; ++i) {
+            if (f == names[i]) {
+                off = o;
+                cnt = sizes[i];
+                break;
+            }
+            o += sizes[i];
+        }
+    } else {
+        const int64_t g = c.image_size / c.patch;
+        static const char *names[5] = {"embeddings.class_embedding", "embeddings.patch_embedding.weight", "embeddings.position_embedding.weight",
+                                       "pre_layrnorm.weight", "pre_layrnorm.bias"};
+        const int64_t sizes[5] = {D, D * 3 * c.patch * c.patch, (g * g + 1) * D, D, D};
+        int64_t o = bb_layer_numel(c) * c.layers;
+        for (int i = 0; i < 5; ++i) {
+            if (n == names[i]) {
+                off = o;
+                cnt = sizes[i];
+                break;
+            }
+            o += sizes[i];
+        }
+    }
+    if (off >= 0 && numel) *numel = cnt;
+    return off;
 }
 
 extern "C" int ch_trainer_create(ch_model *m, int32_t max_batch, float *params, float *grads, ch_trainer **out) {
+    return ch_trainer_create_ex(m, max_batch, params, grads, nullptr, nullptr, out);
+}
+
+extern "C" int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *params, float *grads, float *backbone_params, float *backbone_grads,
+                                    ch_trainer **out) {
     CH_REQUIRE(out != nullptr, "null out pointer");
     *out = nullptr;
     CH_REQUIRE(m != nullptr && params != nullptr && grads != nullptr, "trainer: null model / parameter arena / gradient arena");
+    CH_REQUIRE((backbone_params == nullptr) == (backbone_grads == nullptr), "trainer: the backbone arenas come as a pair (both or neither)");
     const ch_model_config &c = m->cfg;
+    CH_REQUIRE(backbone_params == nullptr || (m->Kp % 128 == 0 && c.ffn % 128 == 0 && c.dim % 128 == 0),
+               "trainer: a trainable backbone needs dim, ffn and the padded patch length 3*patch^2 to be multiples of 128");
     CH_REQUIRE(c.adapter_dim > 0, "trainer: the model has no adapters (nothing to train in the encoder)");
     CH_REQUIRE(max_batch >= 1, "trainer: max_batch must be >= 1");
     CH_REQUIRE(m->layers[0].qkv_wf != nullptr, "trainer: the model was built without the LayerNorm-folded weights");
@@ -399,6 +608,13 @@ extern "C" int ch_trainer_create(ch_model *m, int32_t max_batch, float *params, 
     t->params = params;
     t->grads = grads;
     t->ad_numel = adapter_numel(c);
+    t->bb = backbone_params != nullptr;
+    t->bparams = backbone_params;
+    t->bgrads = backbone_grads;
+    t->bb_layer_numel = bb_layer_numel(c);
+    t->bb_numel = t->bb_layer_numel * c.layers + bb_emb_numel(c);
+    t->lw = m->layers;
+    t->patch_w = m->patch_w; t->pos = m->pos; t->cls_pos0 = m->cls_pos0; t->pre_w = m->pre_w; t->pre_b = m->pre_b;
     // options of the model the trainer is created on (ch_model_set_option "train_chains" / "train_chain_min_rows" / "train_prune_last")
     t->nchains = std::max(1, std::min(m->train_chains, TR_CHAINS));
     t->chain_min_rows = std::max<int64_t>(0, m->train_chain_min_rows);
@@ -447,12 +663,14 @@ extern "C" int ch_trainer_create(ch_model *m, int32_t max_batch, float *params, 
         x.fc1_wgT = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)D * M, ok);
         x.fc2_wT = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)M * D, ok);
         if (!ok) break;
-        // the folded weights already carry gamma: W' = bf16(W * gamma) [N, D] -> (W')^T [D, N]
-        int e = ch_transpose_bf16(w.qkv_wf, 3 * D, D, D, x.qkv_wgT, 3 * D, s);
-        e |= ch_transpose_bf16(w.out_w, D, D, D, x.out_wT, D, s);
-        e |= ch_transpose_bf16(w.fc1_wf, M, D, D, x.fc1_wgT, M, s);
-        e |= ch_transpose_bf16(w.fc2_w, D, M, M, x.fc2_wT, D, s);
-        if (e) ok = false;
+        if (!t->bb) {
+            // the folded weights already carry gamma: W' = bf16(W * gamma) [N, D] -> (W')^T [D, N]
+            int e = ch_transpose_bf16(w.qkv_wf, 3 * D, D, D, x.qkv_wgT, 3 * D, s);
+            e |= ch_transpose_bf16(w.out_w, D, D, D, x.out_wT, D, s);
+            e |= ch_transpose_bf16(w.fc1_wf, M, D, D, x.fc1_wgT, M, s);
+            e |= ch_transpose_bf16(w.fc2_w, D, M, M, x.fc2_wT, D, s);
+            if (e) ok = false;
+        }
         Saved &v = t->sv[l];
         v.Xn1 = bf(D); v.QKV = bf(3 * D); v.AO = bf(D); v.A = bf(D); v.P1 = bf(bpad); v.G1 = bf(bpad); v.Xn2 = bf(D);
         v.F1pre = bf(M); v.A2 = bf(D); v.P2 = bf(bpad); v.G2 = bf(bpad);
@@ -490,6 +708,41 @@ extern "C" int ch_trainer_create(ch_model *m, int32_t max_batch, float *params, 
         t->dctx_sum[ch] = (float *)talloc(t, sizeof(float) * Q * D, ok);
     }
     if (t->nchains > 1) t->grads1 = (float *)talloc(t, sizeof(float) * t->ad_numel * L * 2, ok);
+    if (t->bb) {   // working copies (filled by ch_trainer_refresh below), weight-gradient scratch, the second chain's gradient arena
+        t->bw.resize(L);
+        for (int l = 0; l < L; ++l) {
+            BbWork &b = t->bw[l];
+            b.qkv_wf = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)3 * D * D, ok);
+            b.out_w = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)D * D, ok);
+            b.fc1_wf = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)M * D, ok);
+            b.fc2_w = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)D * M, ok);
+            b.qkv_c = (float *)talloc(t, sizeof(float) * 3 * D, ok);
+            b.qkv_d = (float *)talloc(t, sizeof(float) * 3 * D, ok);
+            b.fc1_c = (float *)talloc(t, sizeof(float) * M, ok);
+            b.fc1_d = (float *)talloc(t, sizeof(float) * M, ok);
+            if (!ok) break;
+            const BbPtr p = bb_ptrs(t->bparams + (int64_t)l * t->bb_layer_numel, c);
+            LayerW &w = t->lw[l];
+            w.ln1_w = p.ln1_w; w.ln1_b = p.ln1_b; w.ln2_w = p.ln2_w; w.ln2_b = p.ln2_b;
+            w.qkv_w = nullptr; w.fc1_w = nullptr; w.qkv_b = nullptr; w.fc1_b = nullptr;      // the folded forms are what the chain reads
+            w.qkv_wf = b.qkv_wf; w.qkv_c = b.qkv_c; w.qkv_d = b.qkv_d; w.out_w = b.out_w; w.out_b = p.out_b;
+            w.fc1_wf = b.fc1_wf; w.fc1_c = b.fc1_c; w.fc1_d = b.fc1_d; w.fc2_w = b.fc2_w; w.fc2_b = p.fc2_b;
+        }
+        t->bb_patch_w = (bf16_t *)talloc(t, sizeof(bf16_t) * (size_t)D * m->Kp, ok);
+        t->bb_cls_pos0 = (float *)talloc(t, sizeof(float) * D, ok);
+        const BbEmb e = bb_emb_ptrs(t->bparams, c);
+        t->patch_w = t->bb_patch_w; t->pos = e.pos; t->cls_pos0 = t->bb_cls_pos0; t->pre_w = e.pre_w; t->pre_b = e.pre_b;
+        const int Kp = m->Kp;
+        const size_t wsf = std::max({ch_wgrad_ws_floats(max_rows, D, M), ch_wgrad_ws_floats(max_rows, M, D), ch_wgrad_ws_floats(max_rows, 3 * D, D),
+                                     ch_wgrad_ws_floats(max_rows, D, D), ch_wgrad_ws_floats(max_rows, D, Kp)});
+        for (int ch = 0; ch < t->nchains; ++ch) {
+            t->ws_bb[ch] = (float *)talloc(t, sizeof(float) * wsf, ok);
+            t->ws_bbcol[ch] = (float *)talloc(t, sizeof(float) * ch_colsum_ws_floats(std::max(3 * D, M)), ok);
+            t->Tbb[ch] = (float *)talloc(t, sizeof(float) * (size_t)D * std::max({3 * D, M, Kp}), ok);
+            t->cbb[ch] = (float *)talloc(t, sizeof(float) * std::max(3 * D, M), ok);
+        }
+        if (t->nchains > 1) t->bgrads1 = (float *)talloc(t, sizeof(float) * t->bb_numel, ok);
+    }
     if (ok && ch_trainer_refresh(t, nullptr) != 0) ok = false;
     if (ok && hipDeviceSynchronize() != hipSuccess) {
         ch_set_error("trainer: device error while preparing the working copies");
@@ -561,9 +814,11 @@ extern "C" int ch_train_backward(ch_trainer *t, const float *d_hash_features, co
         CH_CHECK_HIP(hipStreamWaitEvent(s, t->ev_join, 0));
         // the two chains' contributions: parameter gradients and concept-token rows (both linear in the per-row products)
         if (int e = ch_small_add(t->grads, t->grads1, t->ad_numel * c.layers * 2, t->grads, s)) return e;
+        if (t->bb)
+            if (int e = ch_small_add(t->bgrads, t->bgrads1, t->bb_numel, t->bgrads, s)) return e;
         if (int e = ch_small_add(t->dctx_sum[0], t->dctx_sum[1], (int64_t)Q * D, t->dctx_sum[0], s)) return e;
     }
-    return ch_small_ln_bwd(t->dctx_sum[0], t->ctx, t->m->pre_w, Q, D, c.ln_eps, d_concept_tokens, s);
+    return ch_small_ln_bwd(t->dctx_sum[0], t->ctx, t->pre_w, Q, D, c.ln_eps, d_concept_tokens, s);
 }
 
 // torch.optim.SGD semantics (maximize False) over a flat fp32 array, e.g. the adapter arena: see include/concepthash_hip.h
@@ -572,6 +827,14 @@ extern "C" int ch_sgd_step(float *params, const float *grads, float *momentum_bu
     CH_REQUIRE(params && grads && (momentum == 0.f || momentum_buf), "sgd_step: null argument");
     CH_REQUIRE(n > 0, "sgd_step: empty array");
     return ch_sgd_step_launch(params, grads, momentum_buf, n, lr, momentum, weight_decay, dampening, nesterov, first_step, (hipStream_t)stream);
+}
+
+// torch.optim.Adam / AdamW semantics (amsgrad False, maximize False) over a flat fp32 array: see include/concepthash_hip.h
+extern "C" int ch_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                            double eps, double weight_decay, int32_t decoupled, int64_t step, void *stream) {
+    CH_REQUIRE(params && grads && exp_avg && exp_avg_sq, "adam_step: null argument");
+    CH_REQUIRE(n > 0 && step >= 1, "adam_step: empty array, or step < 1 (the first step is 1)");
+    return ch_adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, (hipStream_t)stream);
 }
 
 // ---- kernel taps for the tests -------------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 //   * colsum:          bias gradients, same two-stage reduction
 //   * transposes:      [N, K] weights -> [K, N] bf16 (optionally scaled per input column by the LayerNorm gamma) for the dgrad GEMMs
 //   * adapter_grads:   assembles the gradients of one adapter's parameters from the two weight-gradient products
+#include <cmath>
+
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
@@ -577,6 +579,143 @@ __global__ __launch_bounds__(256) void sgd_step_kernel(float *__restrict__ p, co
     }
 }
 
+// ---- trainable backbone (train.hip, ch_trainer_create_ex) ---------------------------------------------------------------------
+// Gradients of a Linear whose input LayerNorm is folded into it (qkv with layer_norm1, fc1 with layer_norm2), from
+//   T [n, D] = dpre^T x_hat  and  c [n] = column sums of dpre     (pre = W (gamma o x_hat + beta) + b),
+// the adapters' construction (adapter_grads_*):  dW = T o gamma + c (x) beta, db = c, dgamma[k] = sum_j T[j][k] W[j][k],
+// dbeta[k] = sum_j c[j] W[j][k].  The Linear is `nparts` row blocks of `rows_each` rows (q | k | v) with their own arena slots.
+__global__ __launch_bounds__(256) void fold_grads_elem_kernel(const float *__restrict__ T, const float *__restrict__ c,
+                                                              const float *__restrict__ gamma, const float *__restrict__ beta, int D,
+                                                              ChFoldGradParts a) {
+    const int64_t n4 = (int64_t)a.nparts * a.rows_each * (D / 4);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const int j = (int)(i / (D / 4)), k = (int)(i - (int64_t)j * (D / 4)) * 4;
+        const int part = j / a.rows_each, jj = j - part * a.rows_each;
+        const f32x4 t = *(const f32x4 *)(T + (size_t)j * D + k), g = *(const f32x4 *)(gamma + k), bt = *(const f32x4 *)(beta + k);
+        const float cj = c[j];
+        *(f32x4 *)(a.dW[part] + (size_t)jj * D + k) = t * g + bt * cj;
+        if (k == 0) a.db[part][jj] = cj;
+    }
+}
+// 16 columns k per block, 64 row lanes over j, lanes added in lane order (fixed association)
+__global__ __launch_bounds__(1024) void fold_grads_red_kernel(const float *__restrict__ T, const float *__restrict__ c, int D, ChFoldGradParts a,
+                                                              float *__restrict__ dgamma, float *__restrict__ dbeta) {
+    __shared__ float ra[64][17], rc[64][17];
+    const int kl = threadIdx.x & 15, jl = threadIdx.x >> 4;
+    const int k = blockIdx.x * 16 + kl;
+    float sa = 0.f, sc = 0.f;
+    if (k < D)
+        for (int part = 0; part < a.nparts; ++part) {
+            const float *W = a.W[part];
+            for (int jj = jl; jj < a.rows_each; jj += 64) {
+                const int j = part * a.rows_each + jj;
+                const float w = W[(size_t)jj * D + k];
+                sa += T[(size_t)j * D + k] * w;
+                sc += c[j] * w;
+            }
+        }
+    ra[jl][kl] = sa;
+    rc[jl][kl] = sc;
+    __syncthreads();
+    if (jl == 0 && k < D) {
+        float ta = 0.f, tc = 0.f;
+        for (int j = 0; j < 64; ++j) {
+            ta += ra[j][kl];
+            tc += rc[j][kl];
+        }
+        dgamma[k] = ta;
+        dbeta[k] = tc;
+    }
+}
+
+// Backward of the embedding assembly + pre_layrnorm (rowops.hip assemble_preln_kernel) for one row per wave.  X holds the patch rows of the
+// pre-LayerNorm input (the patch GEMM run again); the CLS row is cls_pos0, the concept rows are ctx.  dY = gradient of the pre-LayerNorm
+// OUTPUT (fp32 rows) is replaced by dx, the gradient of its input; X is replaced by dy o x_hat (whose column sums are d gamma); the patch
+// rows of dx also go out compact, [B * np, D] bf16, as the operand of the patch weight's gradient product.
+__global__ __launch_bounds__(256) void embed_bwd_kernel(float *__restrict__ X, float *__restrict__ dY, int64_t rows, int ntok, int np, int D,
+                                                        const float *__restrict__ cls_pos0, const float *__restrict__ ctx,
+                                                        const float *__restrict__ gamma, float eps, bf16_t *__restrict__ dxp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int t = (int)(row % ntok);
+    const int64_t bimg = row / ntok;
+    const int npass = D >> 7;
+    const float *src = t == 0 ? cls_pos0 : (t > np ? ctx + (size_t)(t - np - 1) * D : X + row * D);
+    float2 x[MAXP], g[MAXP];
+    float sm = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j)
+        if (j < npass) {
+            x[j] = *(const float2 *)(src + (j * 64 + lane) * 2);
+            sm += x[j].x + x[j].y;
+        }
+    const float mean = wave_sum(sm) / (float)D;
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j)
+        if (j < npass) {
+            x[j].x -= mean;
+            x[j].y -= mean;
+            sq += x[j].x * x[j].x + x[j].y * x[j].y;
+        }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j)
+        if (j < npass) {
+            const int k = (j * 64 + lane) * 2;
+            const float2 dy = *(const float2 *)(dY + row * D + k), gm = *(const float2 *)(gamma + k);
+            x[j].x *= rstd;
+            x[j].y *= rstd;
+            *(float2 *)(X + row * D + k) = make_float2(dy.x * x[j].x, dy.y * x[j].y);
+            g[j] = make_float2(dy.x * gm.x, dy.y * gm.y);
+            s1 += g[j].x + g[j].y;
+            s2 += g[j].x * x[j].x + g[j].y * x[j].y;
+        }
+    s1 = wave_sum(s1) / (float)D;
+    s2 = wave_sum(s2) / (float)D;
+#pragma unroll
+    for (int j = 0; j < MAXP; ++j)
+        if (j < npass) {
+            const int k = (j * 64 + lane) * 2;
+            const float2 d = make_float2(rstd * (g[j].x - s1 - x[j].x * s2), rstd * (g[j].y - s1 - x[j].y * s2));
+            *(float2 *)(dY + row * D + k) = d;
+            if (t >= 1 && t <= np) *(uint32_t *)(dxp + (bimg * np + (t - 1)) * D + k) = pack_bf16x2(d.x, d.y);
+        }
+}
+// out[j][:] = sum_b dX[b*ntok + j][:], j < nrows (CLS + patch token rows: the gradient of the position table that was added), images in order
+__global__ __launch_bounds__(256) void token_rows_sum_kernel(const float *__restrict__ dX, int B, int ntok, int D, float *__restrict__ out) {
+    const int j = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= D) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += dX[((size_t)b * ntok + j) * D + k];
+    out[(size_t)j * D + k] = s;
+}
+
+// torch.optim.Adam / AdamW, single-tensor form (amsgrad False, maximize False) over one flat fp32 array:
+//   g' = g + wd * p (Adam, coupled)  |  p *= 1 - lr * wd (AdamW, decoupled);  m += (g' - m) * (1 - beta1);  v = v * beta2 + (1 - beta2) g' g';
+//   p -= step_size * m / (sqrt(v) / bc2_sqrt + eps),  step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
+__global__ __launch_bounds__(256) void adam_step_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                        float *__restrict__ v, int64_t n4, float one_minus_b1, float b2, float one_minus_b2,
+                                                        float eps, float wd, float decay_mul, int decoupled, float step_size, float bc2_sqrt) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pv = *(const f32x4 *)(p + i * 4), gv = *(const f32x4 *)(g + i * 4), mv = *(const f32x4 *)(m + i * 4), vv = *(const f32x4 *)(v + i * 4);
+        if (decoupled)
+            pv = pv * decay_mul;
+        else if (wd != 0.f)
+            gv = gv + pv * wd;
+        mv = mv + (gv - mv) * one_minus_b1;
+        vv = vv * b2 + gv * gv * one_minus_b2;
+        f32x4 out;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[c] = pv[c] - step_size * (mv[c] / (sqrtf(vv[c]) / bc2_sqrt + eps));
+        *(f32x4 *)(m + i * 4) = mv;
+        *(f32x4 *)(v + i * 4) = vv;
+        *(f32x4 *)(p + i * 4) = out;
+    }
+}
+
 // rows of the concept tokens: out[q][:] = sum_b dH[b*ntok + ntok - Q + q][:]   (one block per (q, 256-column slab))
 __global__ __launch_bounds__(256) void concept_rows_sum_kernel(const float *__restrict__ dH, int B, int ntok, int Q, int D,
                                                                float *__restrict__ out) {
@@ -814,6 +953,43 @@ int ch_sgd_step_launch(float *p, const float *g, float *buf, int64_t n, float lr
     const int64_t n4 = n / 4;
     hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 4096)), dim3(256), 0, s, p, g, buf, n4, lr,
                        momentum, wd, dampening, nesterov, first);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+int ch_fold_grads(const float *T, const float *c, const float *gamma, const float *beta, int D, const ChFoldGradParts &parts, float *dgamma,
+                  float *dbeta, hipStream_t s) {
+    CH_REQUIRE(parts.nparts >= 1 && parts.nparts <= 3 && D % 4 == 0, "fold_grads: 1..3 row blocks, D a multiple of 4");
+    const int64_t n4 = (int64_t)parts.nparts * parts.rows_each * (D / 4);
+    hipLaunchKernelGGL(fold_grads_elem_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 4096)), dim3(256), 0, s, T, c, gamma, beta, D,
+                       parts);
+    CH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fold_grads_red_kernel, dim3((D + 15) / 16), dim3(1024), 0, s, T, c, D, parts, dgamma, dbeta);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+int ch_embed_bwd(float *X, float *dY, int B, int ntok, int np, int D, const float *cls_pos0, const float *ctx, const float *gamma, float eps,
+                 bf16_t *dx_patch, hipStream_t s) {
+    CH_REQUIRE(D % 128 == 0 && D <= 128 * MAXP, "embed_bwd: D must be a multiple of 128, <= 1280");
+    const int64_t rows = (int64_t)B * ntok;
+    hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, s, X, dY, rows, ntok, np, D, cls_pos0, ctx, gamma, eps,
+                       dx_patch);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+int ch_token_rows_sum(const float *dX, int B, int ntok, int nrows, int D, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(token_rows_sum_kernel, dim3((D + 255) / 256, nrows), dim3(256), 0, s, dX, B, ntok, D, out);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+int ch_adam_step_launch(float *p, const float *g, float *m, float *v, int64_t n, double lr, double beta1, double beta2, double eps, double wd,
+                        int decoupled, int64_t step, hipStream_t s) {
+    CH_REQUIRE(n % 4 == 0, "adam_step: element count must be a multiple of 4 (pad the arena)");
+    const int64_t n4 = n / 4;
+    // the scalar factors in double, as torch's Python-side arithmetic has them (torch/optim/adam.py _single_tensor_adam)
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64(n4, 256), 4096)), dim3(256), 0, s, p, g, m, v, n4,
+                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)wd, (float)(1.0 - lr * wd), decoupled,
+                       (float)(lr / bc1), (float)std::sqrt(bc2));
     CH_LAUNCH_CHECK();
     return 0;
 }

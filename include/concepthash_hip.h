@@ -158,8 +158,29 @@ int64_t ch_adapter_arena_numel(const ch_model *m);
 int ch_trainer_create(ch_model *m, int32_t max_batch, float *params, float *grads, ch_trainer **out);
 void ch_trainer_destroy(ch_trainer *t);
 int64_t ch_trainer_bytes(const ch_trainer *t);
-/* Re-derive the bf16 / LayerNorm-folded / transposed working copies from the parameter arena: call after every optimizer step. */
+/* Re-derive the bf16 / LayerNorm-folded / transposed working copies from the parameter arena(s): call after every optimizer step. */
 int ch_trainer_refresh(ch_trainer *t, void *stream);
+/* ---- Trainable backbone (`backbone_lr_scale != 0`, reference trainers/base.py:133-152: the whole vision_model in param group 0).
+ * A second caller-owned fp32 device arena pair holds the backbone's master weights and receives their gradients.  Layout, per encoder
+ * layer (state-dict names below `vision_model.encoder.layers.<l>.`):
+ *   [layer_norm1.weight D][layer_norm1.bias D][self_attn.q_proj.weight D*D][.bias D][self_attn.k_proj.weight D*D][.bias D]
+ *   [self_attn.v_proj.weight D*D][.bias D][self_attn.out_proj.weight D*D][.bias D][layer_norm2.weight D][layer_norm2.bias D]
+ *   [mlp.fc1.weight ffn*D][.bias ffn][mlp.fc2.weight D*ffn][.bias D]
+ * then the embedding side (names below `vision_model.`):
+ *   [embeddings.class_embedding D][embeddings.patch_embedding.weight D*3*patch*patch]
+ *   [embeddings.position_embedding.weight (Np+1)*D][pre_layrnorm.weight D][pre_layrnorm.bias D]
+ * The position table is the one the forward ADDS, (image_size/patch)^2 + 1 rows: at a resolution other than the pretrain one the caller
+ * stores the interpolated table there and applies the interpolation's adjoint to the gradient it gets back.  post_layernorm and
+ * visual_projection are not part of the arena: no term of the training loss reads them (their gradient is None in the reference).
+ * Both functions need only the configuration (no device): numel of the arena; offset (floats) and numel of one tensor, -1 = no such name. */
+int64_t ch_backbone_arena_numel(const ch_model_config *cfg);
+int64_t ch_backbone_arena_offset(const ch_model_config *cfg, const char *name, int64_t *numel);
+/* ch_trainer_create with the backbone arena pair (both NULL = ch_trainer_create: frozen backbone, nothing more allocated or computed).
+ * With them the forward reads working copies derived from `backbone_params` (ch_trainer_refresh; the model's own frozen weights are not
+ * read), and ch_train_backward also OVERWRITES `backbone_grads` with the gradient of every tensor of the arena.  Needs dim, ffn and
+ * the 64-padded 3*patch^2 to be multiples of 128. */
+int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *params, float *grads, float *backbone_params, float *backbone_grads,
+                         ch_trainer **out);
 /* Forward in training mode (adapter dropout 0, as the reference configs have it).
  *   concept_tokens    [Q,D] fp32 device: forward_hash_query() output (models/arch/coop.py:413-427), before pre_layrnorm
  *   out_hash_features [B,Q,D] fp32: last-layer states of the concept tokens (coop.py:503-509)
@@ -180,6 +201,13 @@ int ch_train_backward(ch_trainer *t, const float *d_hash_features, const float *
  * n must be a multiple of 4 (ch_adapter_arena_numel is padded by the caller if not). */
 int ch_sgd_step(float *params, const float *grads, float *momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
                 float dampening, int32_t nesterov, int32_t first_step, void *stream);
+/* torch.optim.Adam.step / AdamW.step (single-tensor form, amsgrad False, maximize False) over ONE flat fp32 array, `step` = 1 on the first
+ * call: decoupled 0 (Adam): g += weight_decay * p;  decoupled 1 (AdamW): p *= 1 - lr * weight_decay;  then
+ * exp_avg += (g - exp_avg) * (1 - beta1);  exp_avg_sq = beta2 * exp_avg_sq + (1 - beta2) * g * g;
+ * p -= lr / (1 - beta1^step) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps)      (eps outside the square root).
+ * The scalar factors are formed in double, as torch's host code does.  n must be a multiple of 4. */
+int ch_adam_step(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
+                 double eps, double weight_decay, int32_t decoupled, int64_t step, void *stream);
 /* Launch profiler for bench.py's roofline: between begin and end every kernel launch of ch_encode is bracketed by
  * HIP events on the caller's stream (capacity max_launches events; launches beyond it are not recorded).
  * ch_model_profile_end waits for the last recorded event and returns, per category, the summed launch durations

@@ -160,8 +160,8 @@ class LGHWithoutText(nn.Module):
     def _drop_train_engine(self):
         eng = getattr(self, "_train_engine", None)
         if eng is not None:
-            if eng.momentum_buf is not None:      # the fused arena step's momentum outlives the engine (rebuilds: a larger batch,
-                self._carried_momentum = eng.momentum_buf   # .to(), load_state_dict), as torch's optimizer state does
+            if eng.fused_state is not None:       # the fused arena step's state (momentum, Adam's moments) outlives the engine (rebuilds:
+                self._carried_fused = eng.fused_state   # a larger batch, .to(), load_state_dict), as torch's optimizer state does
             eng.close()
         self._train_engine = None
 
@@ -191,7 +191,10 @@ class LGHWithoutText(nn.Module):
         from concepthash_amd.training import TrainEngine, adapter_modules
         if not self.has_adapter:
             raise NotImplementedError("training on the MI355X path trains the adapters + head (has_adapter=True, the shipped config)")
-        key = (str(device), image_size)
+        # a trainable backbone (`backbone_lr_scale != 0`: the optimizer holds vision_model's parameters) gets the second arena pair
+        vm = self.backbone.vision_model
+        train_backbone = bool(vm.pre_layrnorm.weight.requires_grad)
+        key = (str(device), image_size, train_backbone)
         eng = getattr(self, "_train_engine", None)
         if eng is not None and (self._train_engine_key != key or eng.max_batch < batch):
             self._drop_train_engine()
@@ -199,11 +202,9 @@ class LGHWithoutText(nn.Module):
         if eng is None:
             eng = TrainEngine(self._projected_state_dict(), adapter_modules(self.backbone.vision_model), heads=self._heads,
                               upt_heads=self._upt_heads, act=self._act, max_batch=max(batch, getattr(self, "train_max_batch", 0)),
-                              device=device, image_size=image_size)
-            carried = getattr(self, "_carried_momentum", None)
-            if carried is not None and carried.numel() == eng.params.numel():
-                eng.momentum_buf = carried.to(eng.device)
-            self._carried_momentum = None
+                              device=device, image_size=image_size, backbone=vm if train_backbone else None)
+            eng.adopt_fused_state(getattr(self, "_carried_fused", None))
+            self._carried_fused = None
             self._train_engine, self._train_engine_key = eng, key
         return eng
 

@@ -78,6 +78,9 @@ def main():
     ap.add_argument("--cycles", type=int, default=1)
     ap.add_argument("--image-size", type=int, default=0, help="square input size other than the config's pretrain resolution (position table "
                     "interpolated; e.g. 448 = 789 tokens of ViT-B/16, which run the streaming attention kernels)")
+    ap.add_argument("--train-backbone", action="store_true", help="trainable backbone (backbone_lr_scale != 0): the engine owns the second arena "
+                    "pair, backward also fills the backbone's gradients; also prints the working-copy refresh and the optimizer step (fused "
+                    "ch_adam_step over the arenas against torch.optim.Adam over their views)")
     ap.add_argument("--encode", action="store_true", help="also time ch_encode (evaluation) at the same batches and input size")
     a = ap.parse_args()
     if a.ab:
@@ -87,9 +90,16 @@ def main():
     adapters = adapters_from_state_dict(sd, cfg["L"], cfg["D"], cfg["b"])
     batches = [int(x) for x in a.batches.split(",")]
     size = a.image_size or cfg["image"]
+    backbone = None
+    if a.train_backbone:
+        from concepthash_amd.training import backbone_from_state_dict
+        backbone = backbone_from_state_dict(sd)
     eng = TrainEngine(sd, adapters, heads=cfg["heads"], max_batch=max(batches), device=torch.device("cuda", torch.cuda.current_device()),
-                      image_size=size)
+                      image_size=size, backbone=backbone)
     fwd_f, bwd_f = encoder_step_flops(eng.cfg)
+    if a.train_backbone:   # the weight-gradient products of the four backbone GEMMs equal the forward's linears
+        D_, M_, N_ = eng.cfg["dim"], eng.cfg["ffn"], eng.encoder.ntok
+        bwd_f += eng.cfg["layers"] * 2.0 * N_ * (4 * D_ * D_ + 2 * D_ * M_)
     Q, D = 4, cfg["D"]
     ctx = torch.randn(Q, D, device="cuda") * 0.02
     for B in batches:
@@ -113,8 +123,18 @@ def main():
         print(json.dumps({"config": a.config, "image_size": size, "tokens": eng.encoder.ntok, "batch": B, "forward_ms": round(tf, 3), "backward_ms": round(tb, 3),
                           "step_ms": round(tf + tb, 3), "images_per_s": round(B / (tf + tb) * 1e3, 1),
                           "forward_tflops": round(fwd_f * B / tf / 1e9, 1), "backward_tflops": round(bwd_f * B / tb / 1e9, 1),
-                          "trainer_gib": round(eng.device_bytes / 2 ** 30, 2)}))
-
+                          "trainer_gib": round(eng.device_bytes / 2 ** 30, 2), "trainer_bytes": int(eng.lib.ch_trainer_bytes(eng._t)),
+                          "train_backbone": bool(a.train_backbone)}))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    eng.refresh()
+    e0.record()
+    for _ in range(a.steps):
+        eng.refresh()
+    e1.record()
+    torch.cuda.synchronize()
+    print(json.dumps({"config": a.config, "train_backbone": bool(a.train_backbone), "refresh_ms": round(e0.elapsed_time(e1) / a.steps, 3)}))
+    if a.train_backbone:
+        optimizer_step(a, eng)
 
     if a.encode:
         eng.close()
@@ -136,6 +156,31 @@ def main():
     if a.full:
         eng.close()
         full_step(a, cfg, sd, batches)
+
+
+def optimizer_step(a, eng):
+    """Adam over the two arenas: one ch_adam_step launch each, against torch.optim.Adam over the views (the gradients of the last backward)."""
+    import time
+
+    from concepthash_amd import _lib
+    params = eng.adapter_parameters() + eng.backbone_parameters()
+    opt = torch.optim.Adam(params, lr=1e-5, weight_decay=5e-4)
+    res = {}
+    for name in ("torch", "fused"):
+        state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in (eng.params, eng.bparams)]
+        for it in range(a.warmup + a.steps):
+            if it == a.warmup:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            if name == "torch":
+                opt.step()
+            else:
+                for (m, v), pa, ga in zip(state, (eng.params, eng.bparams), (eng.grads, eng.bgrads)):
+                    _lib.check(eng.lib.ch_adam_step(_lib.ptr(pa), _lib.ptr(ga), _lib.ptr(m), _lib.ptr(v), pa.numel(), 1e-5, 0.9, 0.999, 1e-8, 5e-4,
+                                                    0, it + 1, _lib.stream_ptr()), "ch_adam_step")
+        torch.cuda.synchronize()
+        res[name + "_adam_step_ms"] = round((time.perf_counter() - t0) / a.steps * 1e3, 3)
+    print(json.dumps(dict(config=a.config, parameters=int(eng.params.numel() + eng.bparams.numel()), **res)))
 
 
 def full_step(a, cfg, sd, batches):

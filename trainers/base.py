@@ -6,7 +6,8 @@ Kept: method names, argument meaning, return shapes -- `inference_one_epoch(data
 Changed on purpose: per-batch outputs stay on the GPU and are copied to the host once per epoch (the reference does a
 synchronising `.cpu()` per batch, trainers/base.py:291-296), and so do the loss / accuracy meters (utils.misc.DeviceMeters: the
 reference reads every term back with `.item()` per batch, trainers/coop.py:80-101).  Training: the adapters + get_training_modules() with the backbone frozen
-(`backbone_lr_scale: 0`, the shipped ConceptHash config); a trainable backbone is not built.
+(`backbone_lr_scale: 0`, the shipped ConceptHash config), or -- `backbone_lr_scale != 0` -- the whole vision_model at that multiple of the
+learning rate (reference :136-139).
 """
 from __future__ import annotations
 
@@ -20,6 +21,20 @@ import yaml
 
 from concepthash_amd.config import DictConfig, instantiate, to_container
 from utils.misc import AverageMeter, DeviceMeters
+
+
+def param_groups(model, backbone_lr_scale, lr, has_adapter):
+    """The reference's rule (trainers/base.py:136-145): `backbone_lr_scale != 0` -> group 0 is the whole backbone (`get_backbone()`: the
+    vision_model, adapters included) at `backbone_lr_scale * optim.lr`; otherwise the adapters (when the model has them) at the optimizer's
+    own rate.  The last group is always `get_training_modules()`."""
+    if backbone_lr_scale != 0:
+        groups = [{"params": list(model.get_backbone().parameters()), "lr": backbone_lr_scale * lr}]
+    elif has_adapter:
+        groups = [{"params": list(model.get_adapter().parameters())}]
+    else:
+        groups = []
+    groups.append({"params": [p for p in model.get_training_modules().parameters() if p is not None]})
+    return groups
 
 
 class BaseTrainer:
@@ -160,13 +175,11 @@ class BaseTrainer:
     # ---- training (reference :133-175, :340-358) --------------------------------------------------------------------------
     def load_optimizer_and_scheduler(self):
         assert self.model is not None
-        if self.config.get("backbone_lr_scale", 0) != 0:
-            raise NotImplementedError("backbone_lr_scale != 0 (a trainable backbone) is not built on the MI355X path: the shipped "
-                                      "ConceptHash config freezes it (configs/model/concept_hash_final_v1_nosa_apt.yaml)")
-        groups = []
-        if self.config.model.get("has_adapter", False):
-            groups.append({"params": list(self.model.get_adapter().parameters())})
-        groups.append({"params": [p for p in self.model.get_training_modules().parameters() if p is not None]})
+        scale = self.config.get("backbone_lr_scale", 0)
+        has_adapter = self.config.model.get("has_adapter", False)
+        if scale != 0 and not has_adapter:
+            raise NotImplementedError("training on the MI355X path trains the adapters + head (has_adapter=True, the shipped config)")
+        groups = param_groups(self.model, scale, self.config.optim.get("lr"), has_adapter)
         self.model.requires_grad_(False)          # only what the optimizer holds is trainable (reference :147-152)
         count = 0
         for g in groups:
@@ -175,10 +188,11 @@ class BaseTrainer:
                 count += p.numel()
         logging.info("Number of trainable params: %.3f%s", count / (1e6 if count >= 1e6 else 1e3), "M" if count >= 1e6 else "K")
         self.optimizer = instantiate(self.config.optim, groups)
-        if self.config.model.get("has_adapter", False):
-            # the adapters are 168 views of one arena: update them with one launch instead of torch's per-tensor kernels
-            from concepthash_amd.training import fuse_adapter_sgd
-            self.optimizer = fuse_adapter_sgd(self.optimizer, self.model)
+        if has_adapter:
+            # group 0 is views of one arena (the adapters) or two (the whole backbone): one launch per arena instead of torch's per-tensor
+            # kernels, for SGD, Adam and AdamW
+            from concepthash_amd.training import fuse_arena_step
+            self.optimizer = fuse_arena_step(self.optimizer, self.model)
         self.scheduler = instantiate(self.config.scheduler, self.optimizer)
 
     def get_learning_rate(self):
@@ -191,15 +205,17 @@ class BaseTrainer:
         os.makedirs(os.path.dirname(fn) or ".", exist_ok=True)
         state = {"optim": self.optimizer.state_dict(), "scheduler": self.scheduler.state_dict()}
         eng = getattr(self.model, "_train_engine", None)
-        if eng is not None and eng.momentum_buf is not None:      # the adapters' momentum lives in the fused arena step, not in torch's state
-            state["adapter_momentum"] = eng.momentum_buf.cpu()
+        if eng is not None and eng.fused_state is not None:       # group 0's state lives in the fused arena step, not in torch's: momentum,
+            # or Adam's moments and step count, per arena
+            state["fused_state"] = {k: ([t.cpu() for t in v] if isinstance(v, list) else v) for k, v in eng.fused_state.items()}
         torch.save(state, fn)
 
     def load_training_state(self, fn):
         sd = torch.load(fn, map_location="cpu")
         self.optimizer.load_state_dict(sd["optim"])
         self.scheduler.load_state_dict(sd["scheduler"])
-        self.optimizer.restored_adapter_momentum = sd.get("adapter_momentum")   # picked up by the fused arena step on its first call
+        self.optimizer.restored_fused_state = sd.get("fused_state")             # picked up by the fused arena step on its first call
+        self.optimizer.restored_adapter_momentum = sd.get("adapter_momentum")   # the form earlier checkpoints carry
 
     def train_one_batch(self, *args, **kwargs):
         raise NotImplementedError
