@@ -22,6 +22,10 @@ class ModelConfig(Structure):
                [("ln_eps", c_float), ("bn_eps", c_float)]
 
 
+class TextConfig(Structure):
+    _fields_ = [(n, c_int32) for n in ("vocab", "max_positions", "dim", "layers", "heads", "ffn", "act", "max_batch")] + [("ln_eps", c_float)]
+
+
 class ImageDesc(Structure):
     _fields_ = [("src_offset", c_int64), ("tmp_offset", c_int64)] + \
                [(n, c_int32) for n in ("h", "w", "nh", "nw", "top", "left", "row0", "nrows", "stride", "flip")]
@@ -126,6 +130,10 @@ SIGNATURES = {
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "ch_text_create": (c_int, [POINTER(TextConfig), POINTER(Tensor), c_int32, POINTER(c_void_p)]),
+    "ch_text_destroy": (None, [c_void_p]),
+    "ch_text_device_bytes": (c_size_t, [c_void_p]),
+    "ch_text_encode": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
 # ch_model_set_option keys (include/concepthash_hip.h) and the DEBUG environment overrides the Python wrapper maps onto them when a

@@ -34,8 +34,9 @@ typedef short v4s __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 // KB: number of 32-key blocks (keys padded to KB*32); TAP: write the concept-token attention rows; COMPACT: only the rows the
-// hashing head reads -- CLS and the `ncon` concept tokens -- are queries, and the output is [B * (1 + ncon), D] (final layer)
-template <int KB, bool TAP, bool COMPACT>
+// hashing head reads -- CLS and the `ncon` concept tokens -- are queries, and the output is [B * (1 + ncon), D] (final layer);
+// CAUSAL: query q sees keys 0..q only (the CLIP text tower, text_model.hip; never with TAP or COMPACT)
+template <int KB, bool TAP, bool COMPACT, bool CAUSAL = false>
 __global__ __launch_bounds__(NW * 64, 4) void attention_kernel(const bf16_t *__restrict__ qkv, int ntok, int heads, float scale_log2e,
                                                         bf16_t *__restrict__ out, float *__restrict__ cattn, int ncon, int rev) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -144,6 +145,15 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_kernel(const bf16_t *__r
                 for (int r = 0; r < 4; ++r)
                     if (kt * 16 + fq * 4 + r >= ntok) st[kt][r] = -1e30f;
             }
+        // causal: one select per score (query = lane & 15), straight-line so that register allocation stays the plain instance's;
+        // key 0 is never masked, so every row keeps a finite maximum and the masked keys get probability exactly 0
+        if constexpr (CAUSAL) {
+            const int lim = cur_q - fq * 4;
+#pragma unroll
+            for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) st[kt][r] = kt * 16 + r > lim ? -1e30f : st[kt][r];
+        }
         float mx = -1e30f;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
@@ -228,15 +238,15 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_kernel(const bf16_t *__r
     }
 }
 
-template <int KB, bool TAP, bool COMPACT>
+template <int KB, bool TAP, bool COMPACT, bool CAUSAL = false>
 int launch_attn_inst(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, float *cattn, int ncon, int rev, hipStream_t s) {
     const int KP = KB * 32;
     const size_t lds = (size_t)KP * 128 * 2;
     CH_REQUIRE(lds <= 160 * 1024, "attention: sequence too long for the LDS-resident K/V kernel");
     static ch_once_per_device lds_once;
-    if (int e = ch_func_max_lds((const void *)attention_kernel<KB, TAP, COMPACT>, (int)lds, lds_once)) return e;
+    if (int e = ch_func_max_lds((const void *)attention_kernel<KB, TAP, COMPACT, CAUSAL>, (int)lds, lds_once)) return e;
     const float scale_log2e = 0.125f * 1.4426950408889634f;  // head_dim^-0.5 * log2(e), head_dim = 64
-    CH_LAUNCH((attention_kernel<KB, TAP, COMPACT>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, ntok, heads, scale_log2e,
+    CH_LAUNCH((attention_kernel<KB, TAP, COMPACT, CAUSAL>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, ntok, heads, scale_log2e,
                        out, cattn, ncon, rev);
     CH_LAUNCH_CHECK();
     return 0;
@@ -276,4 +286,21 @@ int ch_attention(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hip
     }
     ch_set_error("attention: the LDS-resident kernel holds at most 288 tokens per image");
     return 2;
+}
+
+// Causal self-attention of the CLIP text tower (text_model.hip): the resident kernel's CAUSAL instance, no tap, no compact mode.
+int ch_attention_causal(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s) {
+    CH_REQUIRE(B > 0 && ntok > 0 && heads > 0, "causal attention: empty problem");
+    CH_REQUIRE(ntok <= CH_ATTN_RESIDENT_MAX_TOKENS, "causal attention: the LDS-resident kernel holds at most 288 tokens per sequence");
+    switch ((ntok + 31) / 32) {
+        case 1: return launch_attn_inst<1, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 2: return launch_attn_inst<2, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 3: return launch_attn_inst<3, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 4: return launch_attn_inst<4, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 5: return launch_attn_inst<5, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 6: return launch_attn_inst<6, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 7: return launch_attn_inst<7, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        case 8: return launch_attn_inst<8, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+        default: return launch_attn_inst<9, false, false, true>(qkv, B, ntok, heads, out, nullptr, 0, 0, s);
+    }
 }

@@ -170,6 +170,8 @@ int ch_gather_head_rows(const float *H, int B, int ntok, int ncon, int D, float 
 // kernel: 0 = by length (up to 288 tokens the LDS-resident kernel, past them the streaming one), 1 = resident, 2 = streaming
 int ch_attention(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s, float *cattn = nullptr,
                  int ncon = 0, bool compact = false, bool rev = false, int kernel = 0);
+// the same with a causal mask (query q attends keys 0..q), 1 <= ntok <= 288: the CLIP text tower (text_model.hip)
+int ch_attention_causal(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, hipStream_t s);
 
 // ---- attention_stream.hip ------------------------------------------------------------------------------------
 // The same two operations for any length up to CH_ATTN_MAX_TOKENS: K / V (Q / dO) walked in 64-row blocks through a two-deep

@@ -16,79 +16,11 @@ thread_local ch_prof_pair g_ch_prof_pair;   // (the last-error string lives in e
 extern "C" int ch_abi_version(void) { return CH_ABI_VERSION; }
 
 #include "model_internal.h"
+#include "weight_builder.h"
 
 namespace {
 
-struct Builder {
-    ch_model *m;
-    std::map<std::string, const ch_tensor *> tab;
-    hipStream_t s = nullptr;
-    bool ok = true;
-
-    void *alloc(size_t bytes) {
-        void *p = nullptr;
-        if (bytes == 0) bytes = 16;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            ch_set_error("hipMalloc failed for " + std::to_string(bytes) + " bytes");
-            ok = false;
-            return nullptr;
-        }
-        m->allocs.push_back(p);
-        m->bytes += bytes;
-        return p;
-    }
-    const ch_tensor *find(const std::string &name, int64_t numel) {
-        auto it = tab.find(name);
-        if (it == tab.end()) {
-            ch_set_error("missing tensor '" + name + "'");
-            ok = false;
-            return nullptr;
-        }
-        if (it->second->numel != numel) {
-            ch_set_error("tensor '" + name + "' has " + std::to_string(it->second->numel) + " elements, expected " +
-                         std::to_string(numel));
-            ok = false;
-            return nullptr;
-        }
-        return it->second;
-    }
-    bool has(const std::string &name) { return tab.count(name) != 0; }
-    // fp32 host -> fp32 device
-    float *f32(const std::string &name, int64_t numel) {
-        const ch_tensor *t = find(name, numel);
-        if (!t) return nullptr;
-        float *d = (float *)alloc(sizeof(float) * numel);
-        if (!d) return nullptr;
-        if (hipMemcpy(d, t->data, sizeof(float) * numel, hipMemcpyDefault) != hipSuccess) {
-            ch_set_error("hipMemcpy failed for '" + name + "'");
-            ok = false;
-        }
-        return d;
-    }
-    float *f32_zeros(int64_t numel) {
-        float *d = (float *)alloc(sizeof(float) * numel);
-        if (d && hipMemset(d, 0, sizeof(float) * numel) != hipSuccess) ok = false;
-        return d;
-    }
-    // fp32 host [rows, cols] -> bf16 device [rows, cols_pad] written at row offset into dst (or fresh alloc)
-    bf16_t *bf16(const std::string &name, int64_t rows, int cols, int cols_pad, bf16_t *dst = nullptr) {
-        const ch_tensor *t = find(name, rows * cols);
-        if (!t) return nullptr;
-        float *tmp = nullptr;
-        if (hipMalloc((void **)&tmp, sizeof(float) * rows * cols) != hipSuccess) {
-            ch_set_error("hipMalloc failed (staging)");
-            ok = false;
-            return nullptr;
-        }
-        if (!dst) dst = (bf16_t *)alloc(sizeof(bf16_t) * rows * cols_pad);
-        if (dst) {
-            if (hipMemcpy(tmp, t->data, sizeof(float) * rows * cols, hipMemcpyDefault) != hipSuccess) ok = false;
-            if (ch_convert_bf16(tmp, rows, cols, cols_pad, dst, s) != 0) ok = false;
-            if (hipStreamSynchronize(s) != hipSuccess) ok = false;
-        }
-        (void)hipFree(tmp);
-        return dst;
-    }
+struct Builder : ChWeightBuilder {
     // LayerNorm fold of a Linear made of `nparts` row blocks ([rows_each, D] weights + [rows_each] biases, host fp32):
     // wf = bf16(W * gamma) [n_pad, D] (rows past the true ones zero), c[n] = sum_k wf[n][k], d[n] = bias[n] + sum_k W[n][k] beta[k]
     bool fold(const std::string *wnames, const std::string *bnames, int nparts, int rows_each, int n_pad, int D,
@@ -126,7 +58,8 @@ struct Builder {
 int build_model(ch_model *m, const ch_tensor *tensors, int ntensors) {
     const ch_model_config &c = m->cfg;
     Builder B;
-    B.m = m;
+    B.allocs = &m->allocs;
+    B.bytes = &m->bytes;
     for (int i = 0; i < ntensors; ++i) {
         CH_REQUIRE(tensors[i].name && tensors[i].data, "tensor entry with null name/data");
         B.tab[tensors[i].name] = &tensors[i];

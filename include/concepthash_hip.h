@@ -452,6 +452,45 @@ int ch_hamming_tie_bracket(const uint32_t *bucket_counts, int64_t Qn, int32_t nb
                            int32_t remove_first, unsigned long long *out_S_low, uint32_t *out_nrel_low,
                            unsigned long long *out_S_high, uint32_t *out_nrel_high, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * CLIP text tower (language-guided class centres)
+ * ------------------------------------------------------------------------------------------------------------- */
+
+/* Replaces: `CLIPModel.from_pretrained(model_id).text_model` as trainers/orthohash.py:94-145 (language_guided_codebook) runs it:
+ * input_ids only (no attention mask: causality keeps the padding behind EOS away from it), `pooler_output` = the EOS token's row
+ * after final_layer_norm, no text projection.  Forward only, once per training run. */
+typedef struct ch_text ch_text; /* opaque: text-tower weights (bf16 GEMM operands, fp32 the rest) + activation workspace */
+
+typedef struct ch_text_config {
+    int32_t vocab;         /* rows of token_embedding */
+    int32_t max_positions; /* rows of position_embedding (77); at most 288.  CLIP's 77 positions run the attention kernel's 96-key causal
+                              instance (same occupancy as the image tower's); models with more than 128 positions are accepted but their
+                              causal instances hold one wave per SIMD fewer (129-160) or spill as the plain 257-288 instance does */
+    int32_t dim;           /* width (multiple of 128, at most 1280) */
+    int32_t layers;
+    int32_t heads;         /* dim / heads must be 64 */
+    int32_t ffn;           /* MLP hidden width (multiple of 128) */
+    int32_t act;           /* 0 = quick_gelu (OpenAI CLIP), 1 = exact gelu */
+    int32_t max_batch;     /* largest B accepted by ch_text_encode (workspace is sized for max_batch * max_positions rows) */
+    float ln_eps;          /* LayerNorm eps (1e-5) */
+} ch_text_config;
+
+/* Tensor names are the HF state_dict keys `text_model.embeddings.{token,position}_embedding.weight`,
+ * `text_model.encoder.layers.N.{layer_norm1,layer_norm2,self_attn.{q,k,v,out}_proj,mlp.fc1,mlp.fc2}.{weight,bias}` and
+ * `text_model.final_layer_norm.{weight,bias}` (`text_model.embeddings.position_ids`, an index buffer, is accepted and ignored).
+ * Unknown or missing names are an error.  The config is validated before any device call. */
+int ch_text_create(const ch_text_config *cfg, const ch_tensor *tensors, int32_t ntensors, ch_text **out);
+void ch_text_destroy(ch_text *m);
+size_t ch_text_device_bytes(const ch_text *m);
+/* ids [B, T] and eos_pos [B] are HOST int32 arrays, validated here (0 <= id < vocab, 0 <= eos_pos < T, 1 <= B <= max_batch,
+ * 1 <= T <= max_positions: a bad value is a status and a message, never an out-of-range read on the GPU) and copied to the device on
+ * `stream` through a pinned buffer of the handle: the caller may free or reuse both arrays as soon as the call returns.  The staging
+ * buffers and the activation workspace belong to the handle, so ONE handle must not be used from two streams (or threads) at the same
+ * time; calls on one stream queue up as usual (a call waits on the host until the previous call's copy of its arrays has executed).  out_pooled [B, dim] fp32 (device) = final_layer_norm of row eos_pos[b] of prompt b; out_hidden (optional, device,
+ * [B, T, dim] fp32) = final_layer_norm of every row (HF `last_hidden_state`). */
+int ch_text_encode(ch_text *m, const int32_t *ids, const int32_t *eos_pos, int32_t B, int32_t T, float *out_pooled, float *out_hidden,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,8 +297,8 @@ class LGHWithFixedPrompt(LGHWithoutText):
                  upt_config=None, fixed_center: Optional[torch.Tensor] = None, additional_blocks: int = 0,
                  text_projection: Optional[nn.Module] = None, **kwargs):
         if fixed_center is None:
-            raise ValueError("LGHWithFixedPrompt needs `fixed_center` (C, 512); it is checkpoint data on this path "
-                             "(building it needs the CLIP text tower, trainers/orthohash.py:94-260)")
+            raise ValueError("LGHWithFixedPrompt needs `fixed_center` (C, 512): a tensor, e.g. from concepthash_amd.centers.class_centers "
+                             "or trainers.orthohash.get_codebook (language-guided: CLIP text tower over the class names)")
         super().__init__(backbone, nbit, nclass, ncontext, add_bn, use_before_projection, upt_config, fixed_center,
                          additional_blocks, **kwargs)
         cd = int(self.center.shape[1])
