@@ -64,6 +64,10 @@ SIGNATURES = {
     "ch_debug_gemm_ln": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                  c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                  c_void_p]),
+    "ch_debug_gemm_train": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                    c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
+    "ch_debug_gemm_patch": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                    c_int32, c_int32, c_void_p]),
     "ch_debug_set_gemm_variant": (None, [c_int32]),
     "ch_debug_gemm_dispatch_count": (c_int64, [c_int32]),
     "ch_debug_experiments_built": (c_int32, []),
@@ -72,6 +76,7 @@ SIGNATURES = {
     "ch_debug_adapter": (c_int, [c_void_p] * 2 + [c_int32] * 3 + [c_void_p] * 10 + [c_int32, c_void_p]),
     "ch_debug_attention": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_debug_attention_ex": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "ch_debug_attention_causal": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_debug_attention_dispatch_count": (c_int64, [c_int32]),
     "ch_encode": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),

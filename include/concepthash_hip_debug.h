@@ -28,6 +28,18 @@ int ch_debug_gemm_ln(int32_t variant, const void *X, int64_t X_rows_alloc, const
                      int32_t N, int32_t K, int32_t epi, void *out_bf16, int32_t ldo, float *resid, int32_t ldr,
                      const float *scale_ptr, const void *addend, const float *stats_in, const float *fold_c, float ln_eps,
                      float *stats_out, void *hb_out, void *stream);
+/* The training-step epilogues on caller buffers.  epi 11 / 12 = out_bf16 = s * bf16(acc + bias) * act'(aux) with act = quick_gelu
+ * (11, s = 1) / exact GELU (12, s = *scale_ptr, or 1 when scale_ptr is null); aux [M, ldo] bf16 shares the layout of out_bf16 and must
+ * not overlap it.  epi 13 / 14 = out_bf16 = the LayerNorm-folded linear of epi 8 and hb_out [M, ld_hb] = quick_gelu / GELU of the
+ * rounded out_bf16.  variant: 0 = dispatcher, 1 = 128x128 two-phase, 2 / 4 = 256x256 ping-pong schedules, 7 = ring (which does not
+ * carry these epilogues: an error). */
+int ch_debug_gemm_train(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M, int32_t N,
+                        int32_t K, int32_t epi, void *out_bf16, int32_t ldo, const void *aux, const float *scale_ptr,
+                        const float *stats_in, const float *fold_c, float ln_eps, void *hb_out, int32_t ld_hb, void *stream);
+/* The patch-embedding epilogue (epi 5): row m = img * patches_per_img + patch of X W^T, plus pos[1 + patch] (pos [1 + patches_per_img, N]
+ * fp32), goes to row img * tokens_per_img + 1 + patch of resid [*, ldr] fp32; every other row of resid is left alone. */
+int ch_debug_gemm_patch(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, int32_t M, int32_t N, int32_t K, float *resid,
+                        int32_t ldr, const float *pos, int32_t tokens_per_img, int32_t patches_per_img, void *stream);
 void ch_debug_set_gemm_variant(int32_t variant);
 /* 1 when the library was built with CH_BUILD_EXPERIMENTS=1: the non-dispatched experiment kernels (GEMM variants 3 / 5 / 6 of
  * the taps above, the fused adapter kernel behind CH_FUSED_ADAPTER=1 and ch_debug_adapter) exist; 0 in the product build, where
@@ -57,6 +69,8 @@ int ch_debug_attention(const void *qkv, int32_t B, int32_t ntok, int32_t heads, 
  * kernel: 0 = by length (<= 288 tokens the LDS-resident kernel, longer the streaming one), 1 = resident, 2 = streaming. */
 int ch_debug_attention_ex(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, float *cattn, int32_t ncon, int32_t compact,
                           int32_t kernel, void *stream);
+/* The causal instance of the resident kernel (the text tower's): query q attends keys 0 .. q; 1 <= ntok <= 288. */
+int ch_debug_attention_causal(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, void *stream);
 /* Attention launches since the library was loaded: which = 0 forward resident, 1 forward streaming, 2 backward resident, 3 backward
  * streaming -- lets a test prove which kernel produced the output it compared. */
 int64_t ch_debug_attention_dispatch_count(int32_t which);
