@@ -68,7 +68,6 @@ SIGNATURES = {
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
     "ch_debug_gemm_patch": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                     c_int32, c_int32, c_void_p]),
-    "ch_debug_set_gemm_variant": (None, [c_int32]),
     "ch_debug_gemm_dispatch_count": (c_int64, [c_int32]),
     "ch_debug_experiments_built": (c_int32, []),
     "ch_debug_set_gemm_splitk": (None, [c_int32]),

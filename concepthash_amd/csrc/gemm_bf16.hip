@@ -212,8 +212,6 @@ int ch_gemm_group_n(int M, int N, int K, int bm, int bn, int forced) {
 // ---- dispatcher: the 256x256 ping-pong kernel when the shape allows it, this file's 128x128 kernel otherwise ---------
 static std::atomic<int64_t> g_dispatch_count[5];   // 128x128 | 256x256 | non-temporal residual instance | non-temporal output instance | 256x384
 void ch_gemm_count_nt_launch(int kind) { g_dispatch_count[2 + (kind != 0)].fetch_add(1, std::memory_order_relaxed); }
-static int g_gemm_variant = 0;  // 0 auto, 1 force v1 (128x128 two-phase), 2 force pp (256x256 ping-pong), 3 force dp
-void ch_gemm_set_variant(int v) { g_gemm_variant = v; }
 // residual tensors from this size up are streamed past the caches by the scale+residual epilogues (gemm_epilogue.h: ld_resid);
 // the model option "resid_nt" (1 / -1) forces the choice
 static int resid_nt_choice(const GemmParams &p, int epi) {
@@ -231,7 +229,33 @@ static int out_nt_choice(const GemmParams &p, int epi) {
     if (p.nt_out_opt) return p.nt_out_opt > 0;
     return std::max<int64_t>(p.M, p.footprint_rows) * p.N * 2 >= (128ll << 20);
 }
-int ch_gemm_bf16(const GemmParams &p0, int epi, hipStream_t s) {
+// The one table from variant number to kernel (test taps, and the dispatcher when a caller forces a choice): the named launcher
+// itself -- no cache-policy choice, no dispatcher argument checks, not counted.
+int ch_gemm_launch_variant(int variant, const GemmParams &p, int epi, hipStream_t s) {
+    switch (variant) {
+        case 1: return ch_gemm_bf16_v1(p, epi, s);
+        case 2: return ch_gemm_bf16_pp(p, epi, s);
+        case 4:     // 256x256 kernel, coarse schedule
+        case 8: {   // 256x256 kernel, free tail
+            GemmParams q = p;
+            q.pp_sched = variant == 4 ? 1 : 2;
+            return ch_gemm_bf16_pp(q, epi, s);
+        }
+        case 3: return ch_gemm_bf16_dp(p, epi, s);
+        case 5: return ch_gemm_bf16_ppp(p, epi, s);
+        case 6: return ch_gemm_bf16_pq(p, epi, s);
+        case 7: return ch_gemm_bf16_r4(p, epi, s);
+        case 9: return ch_gemm_bf16_rows(p, epi, s);
+        case 10: return ch_gemm_bf16_wide(p, epi, s);
+    }
+    if (variant >= 21 && variant <= 29) return ch_gemm_bf16_pp_dbg(p, variant - 20, s);    // timing-only / stamped builds
+    if (variant >= 41 && variant <= 47) return ch_gemm_bf16_wide_dbg(p, variant - 40, s);  // timing-only builds of the 256x384 kernel
+    ch_set_error("gemm: variant must be 1 .. 10, 21 .. 29 (256x256 timing builds) or 41 .. 47 (256x384 timing builds)");
+    return 2;
+}
+// variant: 0 = the rule below; 7 = the rule with the ring kernel wherever it is supported; any other number = that kernel of
+// ch_gemm_launch_variant after the cache-policy choice and the argument checks, not counted (test taps only: product callers pass nothing)
+int ch_gemm_bf16(const GemmParams &p0, int epi, hipStream_t s, int variant) {
     GemmParams p = p0;
     p.nt_resid = resid_nt_choice(p, epi);
     p.nt_out = out_nt_choice(p, epi);
@@ -242,21 +266,7 @@ int ch_gemm_bf16(const GemmParams &p0, int epi, hipStream_t s) {
                    "gemm: LN-folded epilogue needs stats_in, fold_c, ln_eps and K % 128 == 0, K <= 1280");
     if (epi == EPI_BIAS_STATS || epi == EPI_SCALE_RESID_STATS)
         CH_REQUIRE(p.stats_out && (epi == EPI_BIAS_STATS || p.hb_out), "gemm: statistics epilogue needs stats_out (and hb_out)");
-    if (g_gemm_variant == 1) return ch_gemm_bf16_v1(p, epi, s);
-    if (g_gemm_variant == 2) return ch_gemm_bf16_pp(p, epi, s);
-    if (g_gemm_variant == 4) {  // 256x256 kernel, coarse schedule
-        GemmParams q = p;
-        q.pp_sched = 1;
-        return ch_gemm_bf16_pp(q, epi, s);
-    }
-    if (g_gemm_variant == 9) return ch_gemm_bf16_rows(p, epi, s);
-    if (g_gemm_variant == 8) {  // 256x256 kernel, free tail
-        GemmParams q = p;
-        q.pp_sched = 2;
-        return ch_gemm_bf16_pp(q, epi, s);
-    }
-    if (g_gemm_variant == 3) return ch_gemm_bf16_dp(p, epi, s);
-    if (g_gemm_variant == 10) return ch_gemm_bf16_wide(p, epi, s);
+    if (variant != 0 && variant != 7) return ch_gemm_launch_variant(variant, p, epi, s);
     // Short-K GEMMs (the adapter up-projection, K = 384) are epilogue/HBM bound: two 128x128 workgroups per CU overlap one's
     // read-modify-write epilogue with the other's K loop and win there (measured: 152 -> 97 us per launch in the pipeline);
     // the 256x256 ping-pong kernel wins from K = 512 up.
@@ -279,7 +289,7 @@ int ch_gemm_bf16(const GemmParams &p0, int epi, hipStream_t s) {
     // Small grids (batch <= 40 of ViT-B/16): every launch is one workgroup per CU walking a chain of L2 round trips; the four-stage ring
     // (gemm_r4.hip, bit-identical) keeps three K-steps in flight: -7 % per step at batch 8, -2.5 % at batch 32; slower at 51,456 rows.
     // (a non-temporal residual instance, chosen by size or forced by the option "resid_nt", exists in the two-phase kernel only and wins)
-    const bool ring = (p.small_kernel == 2 || g_gemm_variant == 7 || (p.small_kernel == 0 && g_gemm_variant == 0 && p.M <= CH_RING_MAX_ROWS && !p.nt_resid)) &&
+    const bool ring = (p.small_kernel == 2 || variant == 7 || (p.small_kernel == 0 && variant == 0 && p.M <= CH_RING_MAX_ROWS && !p.nt_resid)) &&
                       ch_gemm_r4_supported(p, epi);
     return ring ? ch_gemm_bf16_r4(p, epi, s) : ch_gemm_bf16_v1(p, epi, s);
 }

@@ -78,7 +78,8 @@ struct GemmParams {
 constexpr size_t CH_SPLITK_WS_BYTES = (size_t)256 * 256 * 256 * 4;  // 64 MiB: at most 256 tail units of one 256x256 fp32 slab
 constexpr size_t CH_SPLITK_CNT_BYTES = 256 * sizeof(unsigned);
 constexpr int CH_FOLD_LDS_BYTES = 2048;  // per-row (mean, rstd) table of a <= 256-row block tile
-int ch_gemm_bf16(const GemmParams &p, int epi, hipStream_t s);      // dispatcher
+int ch_gemm_bf16(const GemmParams &p, int epi, hipStream_t s, int variant = 0);  // dispatcher; variant != 0 (test taps): that kernel instead of the rule
+int ch_gemm_launch_variant(int variant, const GemmParams &p, int epi, hipStream_t s);  // gemm_bf16.hip: the table from variant number to launcher
 int ch_gemm_bf16_v1(const GemmParams &p, int epi, hipStream_t s);   // gemm_bf16.hip: 128x128x64, two-phase
 int ch_gemm_bf16_pp(const GemmParams &p, int epi, hipStream_t s);   // gemm_pp.hip: 256x256x64, ping-pong 8-phase
 bool ch_gemm_pp_supported(const GemmParams &p);
@@ -116,7 +117,6 @@ static inline int ch_gemm_bf16_wide_dbg(const GemmParams &, int, hipStream_t) { 
 #endif
 int ch_gemm_bf16_pp_dbg(const GemmParams &p, int dbg, hipStream_t s);  // timing-only builds (garbage results)
 void ch_gemm_count_nt_launch(int kind);  // test tap counters: 0 = non-temporal residual instance, 1 = non-temporal output instance
-void ch_gemm_set_variant(int v);
 // n-tiles per weight group for a block tile of bn columns: minimises X re-fetches + W re-fetches
 int ch_gemm_group_n(int M, int N, int K, int bm, int bn, int forced = 0);
 

@@ -8,7 +8,6 @@
 #include <vector>
 
 #include "../../include/concepthash_hip.h"
-#include "../../include/concepthash_hip_debug.h"
 #include "ch_common.h"
 #include "kernels.h"
 
@@ -815,27 +814,6 @@ extern "C" int ch_encode_hidden(ch_model *m, const void *images, int32_t image_d
     return 0;
 }
 
-// test tap: copy the first nbytes of one workspace buffer (as the last ch_encode / ch_encode_hidden left it) to `out`
-extern "C" int ch_debug_copy_buffer(ch_model *m, int32_t which, void *out, int64_t nbytes, void *stream) {
-    CH_REQUIRE(m != nullptr && out != nullptr && nbytes >= 0, "debug_copy_buffer: null pointer");
-    const int64_t rows = m->rows_alloc, D = m->cfg.dim;
-    const void *src = nullptr;
-    int64_t size = 0;
-    switch (which) {
-        case 0: src = m->H; size = rows * D * 4; break;
-        case 1: src = m->Xn; size = rows * D * 2; break;
-        case 2: src = m->QKV; size = rows * 3 * D * 2; break;
-        case 3: src = m->AO; size = rows * D * 2; break;
-        case 4: src = m->A; size = rows * D * 2; break;
-        case 5: src = m->AD; size = rows * std::max(m->bpad, 128) * 2; break;
-        case 6: src = m->F1; size = rows * (int64_t)m->cfg.ffn * 2; break;
-        default: CH_REQUIRE(false, "debug_copy_buffer: which must be 0..6 (H, Xn, QKV, AO, A, AD, F1)");
-    }
-    CH_REQUIRE(nbytes <= size, "debug_copy_buffer: more bytes requested than the buffer holds");
-    CH_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
-}
-
 extern "C" int ch_pack_sign(const float *codes, int64_t rows, int32_t nbit, float threshold, uint64_t *out_packed,
                             void *stream) {
     CH_REQUIRE(rows >= 0 && nbit > 0, "pack_sign: rows must be >= 0 and nbit > 0");
@@ -894,164 +872,4 @@ extern "C" int ch_model_profile_end(ch_model *m, int32_t ncat, double *ms_per_ca
         P.n = 0;
     }
     return 0;
-}
-
-// split-K workspace of the debug taps (off by default so that the 256x256 kernel stays bit-identical to the 128x128 one)
-static bool g_debug_splitk = false;
-static float *g_debug_ws = nullptr;
-static unsigned *g_debug_cnt = nullptr;
-static int debug_attach_splitk(GemmParams &p) {
-    if (!g_debug_splitk) return 0;
-    if (!g_debug_ws) {
-        CH_CHECK_HIP(hipMalloc((void **)&g_debug_ws, CH_SPLITK_WS_BYTES));
-        CH_CHECK_HIP(hipMalloc((void **)&g_debug_cnt, CH_SPLITK_CNT_BYTES));
-        CH_CHECK_HIP(hipMemset(g_debug_cnt, 0, CH_SPLITK_CNT_BYTES));
-    }
-    p.splitk_ws = g_debug_ws;
-    p.splitk_cnt = g_debug_cnt;
-    p.force_split = 1;
-    return 0;
-}
-extern "C" void ch_debug_set_gemm_splitk(int32_t on) { g_debug_splitk = on != 0; }
-
-// ---- test / bench tap: one GEMM launch on caller buffers (tests/test_gemm_gpu.py, tools/gemm_bench.py) -----------------
-extern "C" int ch_debug_gemm(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias,
-                             int32_t M, int32_t N, int32_t K, int32_t epi, void *out_bf16, int32_t ldo, float *resid,
-                             int32_t ldr, const float *scale_ptr, const void *addend, void *stream) {
-    CH_REQUIRE(X && W, "debug_gemm: null operand");
-    CH_REQUIRE(epi >= EPI_BIAS && epi <= EPI_SCALE_RESID, "debug_gemm: epilogue must be one of the non-patch modes");
-    GemmParams p{};
-    p.X = (const bf16_t *)X; p.W = (const bf16_t *)W; p.M = M; p.N = N; p.K = K; p.X_rows_alloc = X_rows_alloc;
-    p.bias = bias; p.out_bf16 = (bf16_t *)out_bf16; p.ldo = ldo; p.resid = resid; p.ldr = ldr; p.scale_ptr = scale_ptr; p.addend = (const bf16_t *)addend; p.ld_addend = N;
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = debug_attach_splitk(p)) return e;
-    if (variant == 1) return ch_gemm_bf16_v1(p, epi, s);
-    if (variant == 2) return ch_gemm_bf16_pp(p, epi, s);
-    if (variant == 4 || variant == 8) {
-        p.pp_sched = variant == 4 ? 1 : 2;
-        return ch_gemm_bf16_pp(p, epi, s);
-    }
-    if (variant == 3) return ch_gemm_bf16_dp(p, epi, s);
-    if (variant == 10) return ch_gemm_bf16_wide(p, epi, s);
-    if (variant == 9) return ch_gemm_bf16_rows(p, epi, s);
-    if (variant == 5) return ch_gemm_bf16_ppp(p, epi, s);
-    if (variant == 6) return ch_gemm_bf16_pq(p, epi, s);
-    if (variant == 7) return ch_gemm_bf16_r4(p, epi, s);
-    if (variant >= 21 && variant <= 29) return ch_gemm_bf16_pp_dbg(p, variant - 20, s);  // timing-only / stamped builds
-    if (variant >= 41 && variant <= 47) return ch_gemm_bf16_wide_dbg(p, variant - 40, s);  // timing-only builds of the 256x384 kernel
-    return ch_gemm_bf16(p, epi, s);
-}
-extern "C" int ch_debug_gemm_ln(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias,
-                                int32_t M, int32_t N, int32_t K, int32_t epi, void *out_bf16, int32_t ldo, float *resid,
-                                int32_t ldr, const float *scale_ptr, const void *addend, const float *stats_in,
-                                const float *fold_c, float ln_eps, float *stats_out, void *hb_out, void *stream) {
-    CH_REQUIRE(X && W, "debug_gemm_ln: null operand");
-    CH_REQUIRE(epi >= EPI_BIAS_STATS && epi <= EPI_FOLD_GELU, "debug_gemm_ln: epilogue must be one of the LayerNorm-fold modes");
-    GemmParams p{};
-    p.X = (const bf16_t *)X; p.W = (const bf16_t *)W; p.M = M; p.N = N; p.K = K; p.X_rows_alloc = X_rows_alloc;
-    p.bias = bias; p.out_bf16 = (bf16_t *)out_bf16; p.ldo = ldo; p.resid = resid; p.ldr = ldr; p.scale_ptr = scale_ptr;
-    p.addend = (const bf16_t *)addend; p.ld_addend = N;
-    p.stats_in = stats_in; p.fold_c = fold_c; p.ln_eps = ln_eps; p.stats_out = stats_out; p.hb_out = (bf16_t *)hb_out; p.ld_hb = N;
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = debug_attach_splitk(p)) return e;
-    if (variant == 5) return ch_gemm_bf16_ppp(p, epi, s);
-    if (variant == 6) return ch_gemm_bf16_pq(p, epi, s);
-    if (variant == 7) return ch_gemm_bf16_r4(p, epi, s);
-    if (variant == 1 || variant == 2 || variant == 4 || variant == 8 || variant == 9 || variant == 10) ch_gemm_set_variant(variant);
-    const int rc = ch_gemm_bf16(p, epi, s);
-    if (variant == 1 || variant == 2 || variant == 4 || variant == 8 || variant == 9 || variant == 10) ch_gemm_set_variant(0);
-    return rc;
-}
-// variant routing of the two taps below, as in ch_debug_gemm: 0 = dispatcher, 1 = 128x128 two-phase, 2 / 4 = 256x256 ping-pong
-// (fine / coarse schedule), 7 = ring
-static int debug_gemm_route(int32_t variant, GemmParams &p, int epi, hipStream_t s, const char *what) {
-    if (variant == 0) return ch_gemm_bf16(p, epi, s);
-    if (variant == 1) return ch_gemm_bf16_v1(p, epi, s);
-    if (variant == 2) return ch_gemm_bf16_pp(p, epi, s);
-    if (variant == 4) {
-        p.pp_sched = 1;
-        return ch_gemm_bf16_pp(p, epi, s);
-    }
-    if (variant == 7) return ch_gemm_bf16_r4(p, epi, s);
-    ch_set_error(std::string(what) + ": variant must be 0 (dispatcher), 1, 2, 4 or 7");
-    return 2;
-}
-// The training-step epilogues (kernels.h): 11 / 12 = (*scale_ptr, 12 only) * bf16(acc + bias) * act'(aux), aux [M, ldo] bf16 in the layout
-// of out_bf16; 13 / 14 = out_bf16 = the LN-folded linear (stats_in, fold_c, ln_eps as ch_debug_gemm_ln), hb_out [M, ld_hb] = act(out_bf16).
-extern "C" int ch_debug_gemm_train(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M,
-                                   int32_t N, int32_t K, int32_t epi, void *out_bf16, int32_t ldo, const void *aux, const float *scale_ptr,
-                                   const float *stats_in, const float *fold_c, float ln_eps, void *hb_out, int32_t ld_hb, void *stream) {
-    CH_REQUIRE(X && W && bias && out_bf16, "debug_gemm_train: null operand");
-    CH_REQUIRE(epi >= EPI_BIAS_DACT_QUICK && epi <= EPI_FOLD_ACT2_GELU, "debug_gemm_train: epilogue must be one of the training modes (11 .. 14)");
-    CH_REQUIRE(M > 0 && N > 0 && K > 0, "debug_gemm_train: empty problem");
-    CH_REQUIRE(ldo >= N && ldo % 8 == 0, "debug_gemm_train: ldo must be >= N and a multiple of 8 (16-byte row chunks)");
-    const bool dact = epi == EPI_BIAS_DACT_QUICK || epi == EPI_BIAS_DACT_GELU;
-    if (dact) {
-        CH_REQUIRE(aux != nullptr, "debug_gemm_train: the derivative epilogues need aux");
-        // a workgroup reads the aux rows of its tile while other workgroups store theirs: in place is not what the training step does
-        const char *a0 = (const char *)aux, *o0 = (const char *)out_bf16;
-        const size_t span = ((size_t)(M - 1) * ldo + N) * sizeof(bf16_t);
-        CH_REQUIRE(a0 + span <= o0 || o0 + span <= a0, "debug_gemm_train: aux and out_bf16 must not overlap");
-    } else {
-        CH_REQUIRE(hb_out != nullptr && stats_in && fold_c, "debug_gemm_train: the two-output epilogues need hb_out, stats_in and fold_c");
-        CH_REQUIRE(ld_hb >= N && ld_hb % 8 == 0, "debug_gemm_train: ld_hb must be >= N and a multiple of 8 (16-byte row chunks)");
-        CH_REQUIRE(K % 128 == 0 && K <= 1280 && ln_eps > 0.f, "debug_gemm_train: LN-folded epilogue needs K % 128 == 0, K <= 1280, ln_eps > 0");
-        CH_REQUIRE(hb_out != out_bf16, "debug_gemm_train: hb_out and out_bf16 must be distinct");
-    }
-    GemmParams p{};
-    p.X = (const bf16_t *)X; p.W = (const bf16_t *)W; p.M = M; p.N = N; p.K = K; p.X_rows_alloc = X_rows_alloc;
-    p.bias = bias; p.out_bf16 = (bf16_t *)out_bf16; p.ldo = ldo; p.aux = (const bf16_t *)aux; p.scale_ptr = scale_ptr;
-    p.stats_in = stats_in; p.fold_c = fold_c; p.ln_eps = ln_eps; p.hb_out = (bf16_t *)hb_out; p.ld_hb = ld_hb;
-    return debug_gemm_route(variant, p, epi, (hipStream_t)stream, "debug_gemm_train");
-}
-// The patch-embedding epilogue: resid[(img * tokens_per_img + 1 + patch) * ldr + n] = acc + pos[(1 + patch) * N + n] for row
-// m = img * patches_per_img + patch of X W^T (no bias); every other row of resid is left alone.
-extern "C" int ch_debug_gemm_patch(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, int32_t M, int32_t N, int32_t K,
-                                   float *resid, int32_t ldr, const float *pos, int32_t tokens_per_img, int32_t patches_per_img,
-                                   void *stream) {
-    CH_REQUIRE(X && W && resid && pos, "debug_gemm_patch: null operand");
-    CH_REQUIRE(M > 0 && N > 0 && K > 0, "debug_gemm_patch: empty problem");
-    CH_REQUIRE(ldr >= N && ldr % 4 == 0, "debug_gemm_patch: ldr must be >= N and a multiple of 4 (16-byte row chunks)");
-    CH_REQUIRE(patches_per_img >= 1 && tokens_per_img >= 1 + patches_per_img, "debug_gemm_patch: tokens_per_img must be >= 1 + patches_per_img");
-    CH_REQUIRE(M % patches_per_img == 0, "debug_gemm_patch: M must be a whole number of images");
-    GemmParams p{};
-    p.X = (const bf16_t *)X; p.W = (const bf16_t *)W; p.M = M; p.N = N; p.K = K; p.X_rows_alloc = X_rows_alloc;
-    p.resid = resid; p.ldr = ldr; p.pos = pos; p.tokens_per_img = tokens_per_img; p.patches_per_img = patches_per_img;
-    return debug_gemm_route(variant, p, EPI_PATCH, (hipStream_t)stream, "debug_gemm_patch");
-}
-extern "C" void ch_debug_set_gemm_variant(int32_t v) { ch_gemm_set_variant(v); }
-extern "C" int32_t ch_debug_experiments_built(void) {
-#ifdef CH_EXPERIMENTS
-    return 1;
-#else
-    return 0;
-#endif
-}
-
-extern "C" int ch_debug_attention(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, void *stream) {
-    CH_REQUIRE(qkv && out, "debug_attention: null pointer");
-    return ch_attention((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream);
-}
-extern "C" int ch_debug_attention_ex(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, float *cattn, int32_t ncon,
-                                     int32_t compact, int32_t kernel, void *stream) {
-    CH_REQUIRE(qkv && out, "debug_attention_ex: null pointer");
-    return ch_attention((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream, cattn, ncon, compact != 0, false, kernel);
-}
-
-extern "C" int ch_debug_attention_causal(const void *qkv, int32_t B, int32_t ntok, int32_t heads, void *out, void *stream) {
-    CH_REQUIRE(qkv && out, "debug_attention_causal: null pointer");
-    return ch_attention_causal((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream);
-}
-
-extern "C" int ch_debug_adapter(const void *A, float *H, int32_t M, int32_t D, int32_t b, const float *Wd, const float *bd,
-                                const float *gamma, const float *beta, const void *Wu_bf16_padded, const float *bu,
-                                const float *scale, void *work_wdf, float *work_c, float *work_d, int32_t dbg, void *stream) {
-    // Wd [b, D] fp32, Wu [D, bpad] bf16 (already padded); work_*: caller scratch for the folded weights ([bpad, D] bf16, [bpad] x2)
-    const int bpad = (int)round_up64(b, 128);
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = ch_fold_ln(Wd, bd, gamma, beta, b, bpad, D, (bf16_t *)work_wdf, work_c, work_d, s)) return e;
-    AdapterParams p{};
-    p.A = (const bf16_t *)A; p.H = H; p.M = M; p.D = D; p.bpad = bpad; p.Wd = (const bf16_t *)work_wdf; p.c = work_c; p.d = work_d;
-    p.Wu = (const bf16_t *)Wu_bf16_padded; p.bu = bu; p.scale = scale; p.eps = 1e-5f; p.dbg = dbg;
-    return ch_adapter_fused(p, s);
 }

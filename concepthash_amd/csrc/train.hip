@@ -29,7 +29,6 @@
 #include <vector>
 
 #include "model_internal.h"
-#include "../../include/concepthash_hip_debug.h"
 
 namespace {
 struct AdWork {
@@ -835,57 +834,4 @@ extern "C" int ch_adam_step(float *params, const float *grads, float *exp_avg, f
     CH_REQUIRE(params && grads && exp_avg && exp_avg_sq, "adam_step: null argument");
     CH_REQUIRE(n > 0 && step >= 1, "adam_step: empty array, or step < 1 (the first step is 1)");
     return ch_adam_step_launch(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, (hipStream_t)stream);
-}
-
-// ---- kernel taps for the tests -------------------------------------------------------------------------------------------------
-extern "C" int ch_debug_attention_bwd(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
-                                      int32_t ncon, void *stream) {
-    CH_REQUIRE(qkv && dO && dqkv, "debug_attention_bwd: null argument");
-    return ch_attention_bwd((const bf16_t *)qkv, (const bf16_t *)dO, B, ntok, heads, (bf16_t *)dqkv, (hipStream_t)stream, dpext, ncon);
-}
-extern "C" int ch_debug_attention_bwd_ex(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
-                                         int32_t ncon, int32_t kernel, void *stream) {
-    CH_REQUIRE(qkv && dO && dqkv, "debug_attention_bwd_ex: null argument");
-    return ch_attention_bwd((const bf16_t *)qkv, (const bf16_t *)dO, B, ntok, heads, (bf16_t *)dqkv, (hipStream_t)stream, dpext, ncon, kernel);
-}
-extern "C" int ch_debug_wgrad(const void *A, int32_t lda, const void *Bm, int32_t ldb, int64_t rows, int64_t rows_alloc, int32_t N,
-                              int32_t K, float *out, void *stream) {
-    CH_REQUIRE(A && Bm && out, "debug_wgrad: null argument");
-    float *ws = nullptr;
-    CH_CHECK_HIP(hipMalloc((void **)&ws, sizeof(float) * ch_wgrad_ws_floats(rows, N, K)));
-    const int e = ch_wgrad_tn((bf16_t *)A, lda, (const bf16_t *)Bm, ldb, rows, rows_alloc, N, K, out, ws, (hipStream_t)stream);
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(ws);
-    return e;
-}
-// row statistics of x are computed here (hb_stats on an fp32 copy is what the chain does; the tap takes bf16 x and derives the
-// partials from it through an fp32 round trip), then ln_bwd; xhat_out (optional) receives normalize(x)
-extern "C" int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int32_t D, float eps, const float *dres_in, float *dres_out,
-                               void *out_b, void *xhat_out, void *stream) {
-    CH_REQUIRE(dyg && x && dres_in, "debug_ln_bwd: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    float *st = nullptr, *xf = nullptr;
-    bf16_t *hb = nullptr;
-    CH_CHECK_HIP(hipMalloc((void **)&st, sizeof(float) * rows * (D / 64) * 2));
-    CH_CHECK_HIP(hipMalloc((void **)&xf, sizeof(float) * rows * D));
-    CH_CHECK_HIP(hipMalloc((void **)&hb, sizeof(bf16_t) * rows * D));
-    int e = 0;
-    {   // bf16 -> fp32 (exact) by a strided 2-byte copy into the high halves
-        CH_CHECK_HIP(hipMemsetAsync(xf, 0, sizeof(float) * rows * D, s));
-        CH_CHECK_HIP(hipMemcpy2DAsync((char *)xf + 2, 4, x, 2, 2, (size_t)rows * D, hipMemcpyDeviceToDevice, s));
-    }
-    e = ch_hb_stats(xf, rows, D, hb, st, s);
-    if (!e) e = ch_ln_bwd((const bf16_t *)dyg, (const bf16_t *)x, st, rows, D, eps, dres_in, dres_out, (bf16_t *)out_b, s);
-    if (!e && xhat_out) e = ch_normalize_bf16((const bf16_t *)x, st, rows, D, eps, (bf16_t *)xhat_out, s);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(st);
-    (void)hipFree(xf);
-    (void)hipFree(hb);
-    return e;
-}
-extern "C" int ch_debug_act(const void *g, const void *pre, int64_t n, int32_t act, const float *scale_ptr, int32_t backward, void *out,
-                            void *stream) {
-    CH_REQUIRE(pre && out, "debug_act: null argument");
-    if (backward) return ch_act_bwd((const bf16_t *)g, (const bf16_t *)pre, n, act, scale_ptr, (bf16_t *)out, (hipStream_t)stream);
-    return ch_act_fwd((const bf16_t *)pre, n, act, (bf16_t *)out, (hipStream_t)stream);
 }

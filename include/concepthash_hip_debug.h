@@ -1,8 +1,8 @@
 /*
  * concepthash_hip_debug.h -- test / bench taps of libconcepthash_hip.so (MI355X / gfx950).
  *
- * NOT part of the drop-in boundary (include/concepthash_hip.h): single-kernel launches on caller buffers, kernel-selection
- * overrides and workspace copies that tests/ and tools/ use to pin each kernel by itself.  Same conventions as the main header
+ * NOT part of the drop-in boundary (include/concepthash_hip.h): single-kernel launches on caller buffers with the kernel
+ * chosen per call, and workspace copies that tests/ and tools/ use to pin each kernel by itself.  Same conventions as the main header
  * (0 on success, ch_last_error(), device pointers, `stream` = hipStream_t as void*).
  */
 #ifndef CONCEPTHASH_HIP_DEBUG_H
@@ -14,8 +14,9 @@
 extern "C" {
 #endif
 
-/* Test / bench taps (not part of the product path): one fused-epilogue GEMM launch on caller buffers, and a global
- * override of the GEMM kernel selection (0 auto, 1 = 128x128 two-phase kernel, 2 = 256x256 ping-pong kernel).
+/* Test / bench taps (not part of the product path): one fused-epilogue GEMM launch on caller buffers.  `variant` chooses the
+ * kernel of that call alone (0 = the dispatcher's rule, 1 = 128x128 two-phase kernel, 2 = 256x256 ping-pong kernel, ...: the
+ * table is ch_gemm_launch_variant in csrc/gemm_bf16.hip); no call changes what another call runs.
  * X [X_rows_alloc, K] bf16, W [N, K] bf16, bias [N] fp32; epi: 0 bias, 1 bias+quick_gelu, 2 bias+gelu,
  * 3 bias + (resid += v) + bf16 out, 4 resid += [addend bf16 [M,N]] + *scale_ptr * (acc + bias). */
 int ch_debug_gemm(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M,
@@ -40,7 +41,6 @@ int ch_debug_gemm_train(int32_t variant, const void *X, int64_t X_rows_alloc, co
  * fp32), goes to row img * tokens_per_img + 1 + patch of resid [*, ldr] fp32; every other row of resid is left alone. */
 int ch_debug_gemm_patch(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, int32_t M, int32_t N, int32_t K, float *resid,
                         int32_t ldr, const float *pos, int32_t tokens_per_img, int32_t patches_per_img, void *stream);
-void ch_debug_set_gemm_variant(int32_t variant);
 /* 1 when the library was built with CH_BUILD_EXPERIMENTS=1: the non-dispatched experiment kernels (GEMM variants 3 / 5 / 6 of
  * the taps above, the fused adapter kernel behind CH_FUSED_ADAPTER=1 and ch_debug_adapter) exist; 0 in the product build, where
  * those taps return an error. */

@@ -452,3 +452,52 @@ def test_256x128_pingpong_equals_two_phase_bitwise_and_is_race_free(M, N, K):
             torch.cuda.synchronize()
             assert torch.equal(out.view(torch.int16), ref.view(torch.int16)), epi
             assert torch.equal(st, st_ref), epi
+
+
+def test_forced_kernel_choice_does_not_leak_into_concurrent_calls():
+    """The kernel choice of a tap is an argument of that call.  One host thread forces the 128x128 kernel through the dispatcher
+    (ch_debug_gemm_ln, variant 1; forced launches are not counted) while a second one runs a GEMM that the dispatcher's rule sends to the
+    256x256 kernel (128 tiles of 256x256, K = 512; 16 MB of output: no non-temporal instance).  ctypes releases the GIL during the calls,
+    so with a process-wide choice some of the second thread's launches would run the forced kernel and go uncounted."""
+    import threading
+
+    from concepthash_amd import _lib
+    lib = _lib.load()
+    calls = 200
+    Ma, Na, Ka = 300, 256, 256
+    Xa, Wa, bias_a, _ = _inputs(Ma, Na, Ka, seed=11)
+    stats_a = _slice_stats(Xa, Xa.shape[0]).float()
+    fold_c = torch.randn(Na, device="cuda")
+    out_a = torch.zeros(Xa.shape[0], Na, dtype=torch.bfloat16, device="cuda")
+    Mb, Nb, Kb = 8192, 1024, 512
+    Xb, Wb, bias_b, _ = _inputs(Mb, Nb, Kb, seed=12)
+    ref_b = torch.zeros(Mb, Nb, dtype=torch.bfloat16, device="cuda")
+    out_b = torch.zeros_like(ref_b)
+    _gemm(0, Xb, Wb, bias_b, Mb, EPI_BIAS, out=ref_b)
+    torch.cuda.synchronize()
+    count = lambda: [int(lib.ch_debug_gemm_dispatch_count(i)) for i in (0, 1)]
+    before = count()
+    errors = []
+
+    def run(stream, call):
+        try:
+            with torch.cuda.stream(stream):
+                for _ in range(calls):
+                    call()
+        except Exception as e:   # noqa: BLE001 -- reported by the asserting thread
+            errors.append(e)
+
+    forced = lambda: _gemm_ln(1, Xa, Wa, bias_a, Ma, EPI_FOLD_BIAS, out=out_a, stats_in=stats_a, fold_c=fold_c, eps=1e-5)
+    by_rule = lambda: _gemm(0, Xb, Wb, bias_b, Mb, EPI_BIAS, out=out_b)
+    threads = [threading.Thread(target=run, args=(torch.cuda.Stream(), call)) for call in (forced, by_rule)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    torch.cuda.synchronize()
+    assert not errors, errors
+    after = count()
+    print(f"dispatch counters before {before} after {after}")
+    assert after[1] - before[1] == calls      # every call of the second thread was dispatched, to the 256x256 kernel
+    assert after[0] == before[0]              # ... and the forced calls of the first were not
+    assert torch.equal(out_b.view(torch.int16), ref_b.view(torch.int16))
