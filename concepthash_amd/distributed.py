@@ -11,6 +11,10 @@ per-shard results are exchanged:
 
 The per-shard compute is injected (``ops``): on GPUs it is ``concepthash_amd.retrieval`` (HIP kernels); the gloo
 tests inject a CPU stand-in so that the collective choreography itself is covered without a GPU.
+
+Data-parallel training ("Training") adds three helpers: `all_reduce_flat` (many small tensors through ONE
+collective), `all_reduce_param_grads` (the torch-side parameters' gradients, key set agreed between the ranks) and
+`sync_batch_norm` (batch statistics over the GLOBAL batch).
 """
 from __future__ import annotations
 
@@ -51,6 +55,134 @@ def _all_gather_ragged(t: torch.Tensor, group=None):
     bufs = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(bufs, pad, group=group)
     return torch.cat([b[:c] for b, c in zip(bufs, counts)], dim=0), counts
+
+
+def collectives_on(group=None) -> bool:
+    """True when collectives have to run: a group of more than one rank, or CH_FORCE_COLLECTIVES=1 with an initialised one-rank group
+    (every collective is then an identity -- lets a single GPU exercise the RCCL backend with this module's dtypes and shapes)."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return False
+    return dist.get_world_size(group) > 1 or os.environ.get("CH_FORCE_COLLECTIVES") == "1"
+
+
+def all_reduce_flat(tensors: Sequence[torch.Tensor], group=None) -> None:
+    """SUM all-reduce of many tensors (one dtype, one device) IN PLACE through one flat buffer: one flatten, ONE collective, one foreach
+    copy back -- not one collective per tensor."""
+    tensors = list(tensors)
+    if not tensors:
+        return
+    flat = torch.cat([t.reshape(-1) for t in tensors])
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+    torch._foreach_copy_(tensors, [v.view(t.shape) for v, t in zip(flat.split([t.numel() for t in tensors]), tensors)])
+
+
+def agree_grad_keys(named_params, group=None):
+    """Which of `named_params` ([(name, parameter)], the same list in the same order on every rank) carry a gradient on ANY rank: one
+    small MAX all-reduce of a 0/1 mask -> the names, identical on every rank."""
+    named_params = list(named_params)
+    if not named_params:
+        return []
+    dev = named_params[0][1].device
+    mask = torch.tensor([0 if p.grad is None else 1 for _, p in named_params], dtype=torch.int32, device=dev)
+    dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=group)
+    return [name for (name, _), m in zip(named_params, mask.tolist()) if m]
+
+
+def all_reduce_param_grads(named_params, group=None, keys=None):
+    """SUM all-reduce of the `.grad`s of `named_params` through one flat buffer per dtype.  The ranks must enter the same collectives
+    with the same sizes, so the key set is agreed first (`agree_grad_keys`; pass `keys` = an earlier agreement to skip that exchange): a
+    parameter some rank has a gradient for and this rank has not (`grad is None`) contributes zeros and receives the sum; one that no rank
+    has a gradient for keeps `None`, so the optimizer skips it as it does in a single process.  Returns the agreed keys."""
+    named_params = list(named_params)
+    if keys is None:
+        keys = agree_grad_keys(named_params, group)
+    want = set(keys)
+    by_dtype = {}
+    for name, p in named_params:
+        if name not in want:
+            if p.grad is not None:
+                raise RuntimeError(f"all_reduce_param_grads: {name} has a gradient on this rank but is not among the agreed keys; the "
+                                   f"set of parameters with gradients changed since the ranks agreed on it")
+            continue
+        if p.grad is None:
+            p.grad = torch.zeros_like(p)
+        by_dtype.setdefault(p.grad.dtype, []).append(p.grad)
+    for dt in sorted(by_dtype, key=str):
+        all_reduce_flat(by_dtype[dt], group)
+    return keys
+
+
+def broadcast_module_state(module: torch.nn.Module, src=0, group=None) -> None:
+    """Every parameter and buffer of `module` from rank `src`, one broadcast per dtype (flattened).  The values are copied into the
+    parameters themselves (in place, under no_grad), so their versions move and whatever caches derived copies by version -- the training
+    engine's arenas' working copies, the evaluation engine -- re-derives them."""
+    by_dtype = {}
+    for t in list(module.parameters()) + list(module.buffers()):
+        by_dtype.setdefault(t.dtype, []).append(t)
+    with torch.no_grad():
+        for dt in sorted(by_dtype, key=str):
+            ts = by_dtype[dt]
+            flat = torch.cat([t.detach().reshape(-1) for t in ts])
+            dist.broadcast(flat, src=src, group=group)
+            torch._foreach_copy_(ts, [v.view(t.shape) for v, t in zip(flat.split([t.numel() for t in ts]), ts)])
+
+
+class _SyncBatchNorm(torch.autograd.Function):
+    """Training-mode batch normalisation of [n_local, C] rows with the statistics of ALL ranks' rows.  Forward all-reduces
+    [count, sum x, sum x^2] per channel, backward [sum dy, sum dy * xhat]; both in float64 whatever the input's type (2C + 1 numbers: the
+    difference sum x^2 / N - mean^2 then loses nothing an fp32 input had).  Weighted by count: ranks may hold different numbers of rows,
+    zero included.  The gradients of weight and bias are this rank's LOCAL sums -- they join the all-reduce of every other parameter's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, group, collective):
+        C = x.shape[1]
+        xd = x.detach().double()
+        stats = torch.cat([torch.full((1,), float(x.shape[0]), dtype=torch.float64, device=x.device), xd.sum(0), (xd * xd).sum(0)])
+        if collective:
+            dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)
+        n = stats[0]
+        mean = stats[1:1 + C] / n
+        var = (stats[1 + C:] / n - mean * mean).clamp_min(0)          # biased, what normalises
+        invstd = torch.rsqrt(var + eps)
+        xhat = (xd - mean) * invstd
+        ctx.save_for_backward(xhat, weight, invstd, n)
+        ctx.group, ctx.collective = group, collective
+        ctx.mark_non_differentiable(mean, var, n)
+        y = xhat * weight.detach().double() + bias.detach().double() if weight is not None else xhat
+        return y.to(x.dtype), mean, var, n
+
+    @staticmethod
+    def backward(ctx, dy, _dm, _dv, _dn):
+        xhat, weight, invstd, n = ctx.saved_tensors
+        C = xhat.shape[1]
+        dyd = dy.double()
+        local = torch.cat([dyd.sum(0), (dyd * xhat).sum(0)])
+        sums = local.clone()
+        if ctx.collective:
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=ctx.group)
+        w = weight.detach().double() if weight is not None else 1.0
+        dx = w * invstd * (dyd - sums[:C] / n - xhat * (sums[C:] / n))
+        dw = local[C:].to(weight.dtype) if weight is not None else None
+        db = local[:C].to(weight.dtype) if weight is not None else None
+        return dx.to(dy.dtype), dw, db, None, None, None
+
+
+def sync_batch_norm(x: torch.Tensor, bn: torch.nn.BatchNorm1d, group=None, collective=None) -> torch.Tensor:
+    """`bn(x)` in train mode with the batch statistics taken over every rank's rows (x: [n_local, C]).  Running mean / variance are
+    updated from the GLOBAL statistics with the global count by torch's rule (unbiased variance N / (N - 1), `momentum`, or the
+    cumulative average when momentum is None).  collective: None = `collectives_on(group)`; False runs the same arithmetic on the local
+    rows alone."""
+    if collective is None:
+        collective = collectives_on(group)
+    y, mean, var, n = _SyncBatchNorm.apply(x, bn.weight, bn.bias, float(bn.eps), group, bool(collective))
+    if bn.track_running_stats and bn.running_mean is not None:
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+            m = bn.momentum if bn.momentum is not None else 1.0 / bn.num_batches_tracked.double()
+            unbiased = var * (n / (n - 1).clamp_min(1))
+            bn.running_mean.copy_(((1 - m) * bn.running_mean.double() + m * mean).to(bn.running_mean.dtype))
+            bn.running_var.copy_(((1 - m) * bn.running_var.double() + m * unbiased).to(bn.running_var.dtype))
+    return y
 
 
 class RowShard:

@@ -222,6 +222,20 @@ class TrainEngine:
     def backbone_parameters(self) -> List[torch.nn.Parameter]:
         return [p for p, _ in self._bviews]
 
+    def gradient_arenas(self) -> List[tuple]:
+        """[(name, flat fp32 gradient arena)] the last backward filled: what a data-parallel step all-reduces in place, one collective per
+        arena ("adapter", and "backbone" when the backbone trains)."""
+        out = [("adapter", self.grads)]
+        if self.bgrads is not None:
+            out.append(("backbone", self.bgrads))
+        return out
+
+    def parameter_arenas(self) -> List[tuple]:
+        out = [("adapter", self.params)]
+        if self.bparams is not None:
+            out.append(("backbone", self.bparams))
+        return out
+
     def close(self):
         if getattr(self, "_t", None) is not None and self._t.value:
             self.lib.ch_trainer_destroy(self._t)
@@ -346,6 +360,39 @@ class EncoderFunction(torch.autograd.Function):
                                "library keeps the saved activations of the last forward only (one forward -> one backward)")
         dct = ctx.engine.backward(d_hf, d_attn if ctx.want_attn else None)
         return dct.view(ctx.ct_shape), None, None, None, None
+
+
+def torch_side_parameters(model) -> List[tuple]:
+    """[(name, parameter)] of the trainable parameters that are NOT views of the training engine's arenas: the concept-token generator, the
+    hash head, `hash_bn`'s affine, the centre / text projection, the concept classifier (and `post_layernorm` under a trainable backbone,
+    which no loss term reaches).  Deduplicated by identity (the `trainable_params.*` aliases), in `named_parameters` order -- the same on
+    every rank."""
+    eng = getattr(model, "_train_engine", None)
+    in_arena = {id(p) for p, _ in (eng._views + eng._bviews)} if eng is not None else set()
+    return [(n, p) for n, p in model.named_parameters() if p.requires_grad and id(p) not in in_arena]
+
+
+def all_reduce_gradients(model, group=None, keys=None):
+    """The gradient exchange of one data-parallel step, after `backward()` and before `optimizer.step()`: SUM all-reduce of the adapter
+    gradient arena, of the backbone gradient arena (when the backbone trains), and of ONE flat buffer with the gradients of every
+    torch-side trainable tensor -- three collectives.  Each rank scaled its loss by 1 / world_size before backward, so the sums are the
+    gradients of the global-batch mean.  keys: an earlier return value (the agreed set of torch-side parameters that carry gradients), to
+    skip the agreement exchange.  Returns {"keys", "bytes"}."""
+    import torch.distributed as dist
+
+    from .distributed import all_reduce_param_grads
+    eng = getattr(model, "_train_engine", None)
+    if eng is None:
+        raise RuntimeError("all_reduce_gradients: the model has no training engine (no training forward has run)")
+    nbytes = 0
+    for _, arena in eng.gradient_arenas():
+        dist.all_reduce(arena, op=dist.ReduceOp.SUM, group=group)
+        nbytes += arena.numel() * arena.element_size()
+    named = torch_side_parameters(model)
+    keys = all_reduce_param_grads(named, group, keys)
+    want = set(keys)
+    nbytes += sum(p.numel() * p.element_size() for n, p in named if n in want)
+    return {"keys": keys, "bytes": nbytes}
 
 
 def fuse_adapter_sgd(optimizer, model):
@@ -493,14 +540,11 @@ def adapter_modules(vision_model) -> list:
     return [(layer.adapt_mlp_1, layer.adapt_mlp_2) for layer in vision_model.encoder.layers]
 
 
-def benchmark_full_step(cfg: dict, state_dict, batches, steps: int = 10, warmup: int = 3) -> dict:
-    """Wall clock of the whole training step through the drop-in surface -- the reference's train_one_batch (trainers/coop.py:107-131):
-    `LGHWithFixedPrompt` in train mode, `LGHLoss` (shipped terms), `loss.backward()`, `torch.optim.SGD.step()` with the adapters' group
-    fused (fuse_adapter_sgd), synchronised once per measurement.  cfg: a concepthash_amd.synthetic.CONFIGS entry."""
-    import time
-
+def full_step_setup(cfg: dict, state_dict, max_batch: int, train_backbone: bool = False):
+    """(model, criterion, optimizer) of the whole training step through the drop-in surface -- the reference's train_one_batch
+    (trainers/coop.py:107-131): `LGHWithFixedPrompt` in train mode, `LGHLoss` (shipped terms), torch.optim.SGD with the arena group fused.
+    cfg: a concepthash_amd.synthetic.CONFIGS entry."""
     from concepthash_amd import config as cfglib
-    from concepthash_amd import synthetic
     from models.arch.coop import LGHWithFixedPrompt
     from models.backbone.clip import CLIP
     from models.loss.coop import LGHLoss
@@ -514,14 +558,25 @@ def benchmark_full_step(cfg: dict, state_dict, batches, steps: int = 10, warmup:
                                text_projection=tp, has_adapter=True, adapter_bottleneck_dim=cfg["b"], concept_reg=True)
     model.load_state_dict(state_dict)
     model = model.cuda().train()
-    model.train_max_batch = max(batches)
+    model.train_max_batch = max_batch
     crit = LGHLoss(margin=0.2, scale=8, loss_scales=dict(bin_logits=1, cont_logits=1, concept_logits=1), ncontext=4)
-    groups = [{"params": list(model.get_adapter().parameters())}, {"params": list(model.get_training_modules().parameters())}]
+    first = model.get_backbone() if train_backbone else model.get_adapter()
+    groups = [{"params": list(first.parameters())}, {"params": list(model.get_training_modules().parameters())}]
     model.requires_grad_(False)
     for g in groups:
         for p in g["params"]:
             p.requires_grad_(True)
     opt = fuse_adapter_sgd(torch.optim.SGD(groups, lr=1e-3, momentum=0.9, weight_decay=5e-4), model)
+    return model, crit, opt, C
+
+
+def benchmark_full_step(cfg: dict, state_dict, batches, steps: int = 10, warmup: int = 3) -> dict:
+    """Wall clock of the whole training step through the drop-in surface (`full_step_setup`): forward, `LGHLoss`, `loss.backward()`,
+    `torch.optim.SGD.step()` with the adapters' group fused (fuse_adapter_sgd), synchronised once per measurement."""
+    import time
+
+    from concepthash_amd import synthetic
+    model, crit, opt, C = full_step_setup(cfg, state_dict, max(batches))
     out = {}
     for B in batches:
         x = synthetic.synthetic_images(B, cfg["image"]).to("cuda", torch.bfloat16)
@@ -539,3 +594,43 @@ def benchmark_full_step(cfg: dict, state_dict, batches, steps: int = 10, warmup:
                   "what": "model.train() forward + LGHLoss + backward + SGD step (adapter group fused), wall clock"}
     model._drop_train_engine()
     return out
+
+
+def benchmark_ddp_step(cfg: dict, state_dict, global_batch: int, steps: int = 10, warmup: int = 3, train_backbone: bool = False) -> dict:
+    """This rank's view of the data-parallel step (an initialised process group is required): global_batch / world_size images per rank,
+    loss scaled by 1 / world_size, `all_reduce_gradients`, fused SGD step.  Wall clock of the whole step, and -- measured apart, on the
+    gradients of the last backward -- of the gradient all-reduce alone."""
+    import time
+
+    import torch.distributed as dist
+
+    from concepthash_amd import synthetic
+    world, rank = dist.get_world_size(), dist.get_rank()
+    if global_batch % world:
+        raise ValueError(f"batch {global_batch} is not divisible by world_size {world}")
+    B = global_batch // world
+    model, crit, opt, C = full_step_setup(cfg, state_dict, B, train_backbone)
+    x = synthetic.synthetic_images(global_batch, cfg["image"])[rank * B:(rank + 1) * B].to("cuda", torch.bfloat16)
+    y = torch.randint(0, C, (global_batch,), generator=torch.Generator().manual_seed(0))[rank * B:(rank + 1) * B].cuda()
+    keys, nbytes = None, 0
+    for it in range(warmup + steps):
+        if it == warmup:
+            torch.cuda.synchronize()
+            dist.barrier()
+            t0 = time.perf_counter()
+        opt.zero_grad()
+        (crit(model(x)[1], y) / world).backward()
+        red = all_reduce_gradients(model, keys=keys)
+        keys, nbytes = red["keys"], red["bytes"]
+        opt.step()
+    torch.cuda.synchronize()
+    step_ms = (time.perf_counter() - t0) / steps * 1e3
+    dist.barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        all_reduce_gradients(model, keys=keys)
+    torch.cuda.synchronize()
+    ar_ms = (time.perf_counter() - t0) / steps * 1e3
+    model._drop_train_engine()
+    return {"global_batch": global_batch, "images_per_rank": B, "step_ms": round(step_ms, 3), "all_reduce_ms": round(ar_ms, 3),
+            "bytes_reduced_per_step": int(nbytes), "images_per_s": round(global_batch / step_ms * 1e3, 1), "train_backbone": bool(train_backbone)}

@@ -71,7 +71,61 @@ class FileBatchLoader:
             yield self.dataset[list(indices)]
 
 
-def dataloader(d, bs=256, shuffle=False, workers=-1, drop_last=False, sampler=None):
+class GlobalBatchSampler(torch.utils.data.Sampler):
+    """Batch sampler of data-parallel training ("Training"): `batch_size` is the GLOBAL batch.  Every rank derives
+    the same permutation of the dataset from (seed, epoch) alone -- no process, worker or rank state -- cuts it into global batches with
+    the last partial one dropped, as `DataLoader(shuffle=True, drop_last=True)` cuts its own, and yields rows
+    [rank * b, (rank + 1) * b) of each, b = batch_size / world_size.  The ranks' step-i batches, concatenated in rank order, are global
+    batch i; every rank has `len(dataset) // batch_size` steps."""
+
+    def __init__(self, n: int, batch_size: int, seed: int, rank: int = 0, world_size: int = 1, shuffle: bool = True):
+        n, batch_size, world_size, rank = int(n), int(batch_size), int(world_size), int(rank)
+        if world_size < 1 or batch_size < 1 or batch_size % world_size:
+            raise ValueError(f"batch_size {batch_size} (the global batch) is not divisible by world_size {world_size}: every rank "
+                             f"must process the same number of images per step")
+        if not 0 <= rank < world_size:
+            raise ValueError(f"rank {rank} outside world_size {world_size}")
+        self.n, self.batch_size, self.seed, self.rank, self.world_size, self.shuffle = n, batch_size, int(seed), rank, world_size, shuffle
+        self.per_rank = batch_size // world_size
+        self.epoch = 0
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def global_batches(self, epoch=None):
+        """the epoch's global batches as index lists (the same on every rank)"""
+        epoch = self.epoch if epoch is None else int(epoch)
+        if self.shuffle:
+            g = torch.Generator().manual_seed(epoch_seed(self.seed, epoch))
+            perm = torch.randperm(self.n, generator=g).tolist()
+        else:
+            perm = list(range(self.n))
+        B = self.batch_size
+        return [perm[i * B:(i + 1) * B] for i in range(self.n // B)]
+
+    def __iter__(self):
+        lo = self.rank * self.per_rank
+        for batch in self.global_batches():
+            yield batch[lo:lo + self.per_rank]
+
+    def __len__(self):
+        return self.n // self.batch_size
+
+
+def epoch_seed(seed: int, epoch: int, index: int = -1) -> int:
+    """One 63-bit seed from (seed, epoch[, dataset index]): splitmix64 steps over the three numbers, so neighbouring epochs / images do not
+    get neighbouring generator states."""
+    x = 0
+    for v in (int(seed), int(epoch), int(index) + 1):
+        x = (x + 0x9E3779B97F4A7C15 + (v & 0xFFFFFFFFFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
+        x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+        x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+        x ^= x >> 31
+    return x & 0x7FFFFFFFFFFFFFFF
+
+
+def dataloader(d, bs=256, shuffle=False, workers=-1, drop_last=False, sampler=None, batch_sampler=None):
+    """batch_sampler: an iterable of index lists (GlobalBatchSampler) instead of bs / shuffle / drop_last / sampler."""
     if len(d) == 0:
         return []
     limit_torch_threads()                   # torch's CPU pool inside the container's quota before any loader thread starts (hostcpu.py)
@@ -84,14 +138,23 @@ def dataloader(d, bs=256, shuffle=False, workers=-1, drop_last=False, sampler=No
         # FileBatchLoader.  (`workers` > 0 with `file_workers=True` on the dataset keeps the earlier arrangement -- DataLoader workers
         # that only read files, persistent across epochs -- for storage where a read blocks for long.)
         from torch.utils.data import BatchSampler, RandomSampler, SequentialSampler
-        base = sampler if sampler is not None else (RandomSampler(d) if shuffle else SequentialSampler(d))
+        batches = batch_sampler
+        if batches is None:
+            base = sampler if sampler is not None else (RandomSampler(d) if shuffle else SequentialSampler(d))
+            batches = BatchSampler(base, bs, drop_last)
         if not getattr(d, "file_workers", False):
-            return FileBatchLoader(d, BatchSampler(base, bs, drop_last))
+            return FileBatchLoader(d, batches)
+        if batch_sampler is not None:
+            # persistent file-reading workers keep the dataset copy of their first epoch: the per-epoch seed of the draws would not reach them
+            raise NotImplementedError("dataset.file_workers with a batch sampler (multi-rank training) is not built; use the in-process reads")
         workers = min(workers, 6)
-        return DataLoader(d, batch_size=None, sampler=BatchSampler(base, bs, drop_last), num_workers=workers, pin_memory=False,
+        return DataLoader(d, batch_size=None, sampler=batches, num_workers=workers, pin_memory=False,
                           multiprocessing_context=_worker_context(workers), persistent_workers=workers > 0)
-    return DataLoader(d, bs, shuffle, drop_last=drop_last, num_workers=workers, sampler=sampler,
-                      pin_memory=workers > 0, collate_fn=getattr(d, "collate_fn", None), multiprocessing_context=_worker_context(workers))
+    common = dict(num_workers=workers, pin_memory=workers > 0, collate_fn=getattr(d, "collate_fn", None),
+                  multiprocessing_context=_worker_context(workers))
+    if batch_sampler is not None:
+        return DataLoader(d, batch_sampler=batch_sampler, **common)
+    return DataLoader(d, bs, shuffle, drop_last=drop_last, sampler=sampler, **common)
 
 
 class _SequentialSubset(torch.utils.data.Sampler):

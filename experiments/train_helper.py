@@ -3,6 +3,9 @@ build the trainer, datasets, model, optimizer + scheduler and criterion from the
 `trainer.train_one_epoch`, every `eval_interval` epochs encode query + database and score retrieval, keep `models/best.pth` /
 `models/last.pth`, `train_history.json` / `test_history.json`.
 
+Launched as N ranks (torchrun) the same command trains data-parallel: the global batch is sharded over the ranks, gradients are all-reduced
+once per step, rank 0 writes the run directory ("Training").
+
 What trains: the adapters + the hashing head + the concept-token generator with the CLIP backbone frozen -- the shipped
 ConceptHash setting.  The encoder's forward and backward of every step run in the HIP library (ch_train_forward /
 ch_train_backward); evaluation runs the HIP encode + Hamming kernels as `experiments.test_hashing` does.
@@ -32,26 +35,49 @@ class RetrievalExperiment:
         for key in ("resume_logdir", "finetune_path"):
             if config.get(key) is not None:
                 raise NotImplementedError(f"{key} is not built on the MI355X path")
-        self.config, self.logdir = config, str(config.logdir)
-        for sub in ("models", "optims", "outputs"):
-            os.makedirs(os.path.join(self.logdir, sub), exist_ok=True)
         trainer = instantiate(config.trainer, config)
-        trainer.save_config(self.logdir)
+        self.rank, self.world_size = trainer.rank, trainer.world_size
+        if trainer.distributed:
+            # one process per GPU: `logdir` defaults to a time-stamped directory (configs/train.yaml), which every rank would resolve to
+            # another name -- rank 0 decides, and rank 0 alone writes the run directory (checkpoints, histories, config)
+            import torch.distributed as dist
+            box = [str(config.logdir)]
+            dist.broadcast_object_list(box, src=0)
+            config["logdir"] = box[0]
+            self._refuse_batch_coupled_options(config)
+        self.config, self.logdir = config, str(config.logdir)
+        if self.rank == 0:
+            for sub in ("models", "optims", "outputs"):
+                os.makedirs(os.path.join(self.logdir, sub), exist_ok=True)
+            trainer.save_config(self.logdir)
         trainer.load_dataset()
         trainer.load_dataloader()
         trainer.load_model()
         trainer.load_optimizer_and_scheduler()
         trainer.load_criterion()
         trainer.to_device()
+        trainer.broadcast_model()
         self.trainer = trainer
         self.train_history, self.test_history = [], []
         self.best, self.best_ep, self.curr_metric = 0.0, 0, 0.0
         self.nepochs, self.neval, self.nsave = int(config.epochs), int(config.get("eval_interval", 10)), int(config.get("save_interval", 0))
         logging.info("Training Start")
 
+    @staticmethod
+    def _refuse_batch_coupled_options(config):
+        """Data parallelism keeps the optimisation problem only for terms that are per-image means (every term of models/loss/coop.py is:
+        the cross-entropies, the mixture form, the attention-diversity term's batch mean) around a model whose one batch-coupled layer,
+        `hash_bn`, is synchronised.  A criterion of another class is not known to be one: refused by name."""
+        target = str(config.criterion.get("_target_", ""))
+        if not target.endswith("models.loss.coop.LGHLoss"):
+            raise NotImplementedError(f"multi-rank training: criterion {target} is not known to be a per-image mean over the batch; only "
+                                      f"models.loss.coop.LGHLoss is built for data-parallel runs")
+
     def record_history(self, stage, stats):
         hist = self.train_history if stage == "train" else self.test_history
         hist.append(stats)
+        if self.rank != 0:
+            return
         with open(os.path.join(self.logdir, f"{stage}_history.json"), "w") as f:
             json.dump(hist, f, indent=True)
 
@@ -85,6 +111,11 @@ class RetrievalExperiment:
             logging.info("mAP%s: %.6f  R@10 %.6f  P@10 %.6f", postfix, mAP, recalls[-1], precisions[-1])
         return res, test_out, db_out
 
+    def _save(self, fn, path):
+        """checkpoints are written by rank 0 alone (the ranks hold bit-identical parameters and optimizer state after every step)"""
+        if self.rank == 0:
+            fn(path)
+
     def main(self):
         tr = self.trainer
         for ep in range(self.nepochs):
@@ -99,6 +130,7 @@ class RetrievalExperiment:
             for k, v in meters.items():
                 res["train_" + k] = v.avg
             res["train_seconds"] = time.time() - t0
+            res["world_size"], res["images_per_rank"] = self.world_size, int(self.config.batch_size) // self.world_size
             self.record_history("train", res)
             if (ep + 1) == self.nepochs or (self.neval != 0 and (ep + 1) % self.neval == 0):
                 res, test_out, db_out = self.evaluation(ep)
@@ -106,12 +138,12 @@ class RetrievalExperiment:
                 self.record_history("test", res)
                 if self.best < self.curr_metric:
                     self.best, self.best_ep = self.curr_metric, ep + 1
-                    tr.save_model_state(f"{self.logdir}/models/best.pth")
+                    self._save(tr.save_model_state, f"{self.logdir}/models/best.pth")
             if self.nsave != 0 and (ep + 1) % self.nsave == 0:
-                tr.save_model_state(f"{self.logdir}/models/ep{ep + 1}.pth")
-            tr.save_model_state(f"{self.logdir}/models/last.pth")
+                self._save(tr.save_model_state, f"{self.logdir}/models/ep{ep + 1}.pth")
+            self._save(tr.save_model_state, f"{self.logdir}/models/last.pth")
             if self.config.get("save_training_state"):
-                tr.save_training_state(f"{self.logdir}/optims/last.pth")
+                self._save(tr.save_training_state, f"{self.logdir}/optims/last.pth")
         io.join_save_queue()
         logging.info("Training End at %s; total %.2f hours; best mAP %.6f at %d; Done: %s", datetime.today().strftime("%Y-%m-%d %H:%M:%S"),
                      (time.time() - self.start_time) / 3600, self.best, self.best_ep, self.logdir)

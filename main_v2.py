@@ -38,8 +38,6 @@ def run(config):
                                   "use exp=hashing with eval_interval=0")
     if config.exp == "hashing":                  # reference main_v2.py:17-19
         from experiments.train_helper import RetrievalExperiment
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("exp=hashing is single-process (the reference trains on one GPU); launch one process")
         return RetrievalExperiment(config).main()
     if config.exp == "validation":
         load_config = cfglib.load(os.path.join(config.logdir, "config.yaml"))
@@ -73,7 +71,7 @@ def main(argv=None):
     torch.multiprocessing.set_sharing_strategy("file_system")
     config = cfglib.compose(args.config_path, args.config_name, args.overrides, cwd=os.getcwd())
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1:                                 # one process per GPU: gallery-sharded retrieval
+    if world > 1:                                 # one process per GPU: data-parallel training, gallery-sharded retrieval
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
         torch.cuda.set_device(local)

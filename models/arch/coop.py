@@ -114,6 +114,9 @@ class LGHWithoutText(nn.Module):
         # the encode-and-retrieve path reads them, so they are produced on request only -- by the per-layer parity tap
         # ch_encode_hidden, one partial run of the encoder per layer (L + 1 runs: for inspection, not for throughput)
         self.return_hidden_states = bool(kwargs.get("return_hidden_states", False))
+        # train-mode `hash_bn` on the statistics of every rank's rows (concepthash_amd.distributed.sync_batch_norm): None = whenever
+        # collectives run (a multi-rank group); True = that arithmetic also without a group (on the local rows); False = torch's BatchNorm1d
+        self.hash_bn_sync: Optional[bool] = kwargs.get("hash_bn_sync", None)
         self._engine: Optional[ConceptHashEncoder] = None
         self._engine_key = None
         self.eval()
@@ -224,7 +227,13 @@ class LGHWithoutText(nn.Module):
             hash_features = EncoderFunction.apply(ctx, x, eng, eng.anchor)   # (B, Q, D): HIP forward, HIP backward
         B = x.shape[0]
         vision_hash = self.hash_fc(hash_features + self.hash_pe).reshape(B, -1)      # reference :544-553
-        vision_hash = self.hash_bn(vision_hash)                                      # BatchNorm1d on the batch statistics
+        from concepthash_amd.distributed import collectives_on, sync_batch_norm
+        sync = collectives_on() if self.hash_bn_sync is None else self.hash_bn_sync
+        if sync and isinstance(self.hash_bn, nn.BatchNorm1d) and self.hash_bn.training:
+            # multi-rank training: statistics of the GLOBAL batch (per-rank statistics of batch_size / world_size rows would be another model)
+            vision_hash = sync_batch_norm(vision_hash, self.hash_bn)
+        else:
+            vision_hash = self.hash_bn(vision_hash)                                  # BatchNorm1d on the batch statistics
         center = self.get_center()
         v_l2 = F.normalize(vision_hash, dim=-1, p=2)
         c_l2 = F.normalize(center, dim=-1, p=2)

@@ -4,7 +4,10 @@ activations + backward in the HIP library, timed with HIP events around `ch_trai
 whole step through the drop-in surface (model.train() forward, LGHLoss, backward, SGD step).
 
     python tools/train_bench.py [--config vit_b16] [--batches 32,64,128,256] [--steps 10]
-Prints one JSON line per batch size.  FLOPs: forward 2 * params-touched * tokens; the backward's dgrad products equal the
+    python tools/train_bench.py --gpus N [--global-batch 256] [--train-backbone]      the data-parallel step on N ranks (one JSON line)
+Prints one JSON line per batch size.  --gpus N starts N fresh rank processes BEFORE any GPU call of its own, as bench.py --gpus does
+(at most 16); with fewer visible GPUs than ranks the ranks share GPUs and the collectives run over gloo -- a rehearsal of the layout, which
+the line says (`collective_backend`, `rehearsal`), never a scaling figure.  FLOPs: forward 2 * params-touched * tokens; the backward's dgrad products equal the
 forward's, the adapters' weight-gradient products add 4 N D b per layer per adapter pair, attention backward 2.5x its forward.
 """
 import argparse
@@ -17,6 +20,60 @@ import torch
 
 from concepthash_amd import synthetic
 from concepthash_amd.training import TrainEngine, adapters_from_state_dict, encoder_step_flops
+
+MAX_RANKS = 16
+
+
+def ddp_launch(a) -> int:
+    """start the ranks: fresh processes, before this one touches the GPU (device_count() does not initialise it)"""
+    import socket
+    import subprocess
+    if not 1 <= a.gpus <= MAX_RANKS:
+        raise SystemExit(f"--gpus {a.gpus}: between 1 and {MAX_RANKS} ranks")
+    ndev = torch.cuda.device_count()
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, WORLD_SIZE=str(a.gpus), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    if ndev < a.gpus and "CH_DIST_BACKEND" not in env:
+        print(f"[train_bench] {a.gpus} ranks requested but {ndev} GPU(s) visible: REHEARSAL -- ranks share GPUs, collectives over gloo",
+              file=sys.stderr)
+        env["CH_DIST_BACKEND"] = "gloo"
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=dict(env, RANK=str(r), LOCAL_RANK=str(r)),
+                              stdout=None if r == 0 else subprocess.DEVNULL) for r in range(a.gpus)]
+    bad = [(r, rc) for r, rc in enumerate(p.wait() for p in procs) if rc != 0]
+    if bad:
+        print(f"[train_bench] ranks failed: {bad}", file=sys.stderr)
+    return 1 if bad else 0
+
+
+def ddp_rank(a):
+    """one rank of `--gpus N`: the whole data-parallel step (concepthash_amd.training.benchmark_ddp_step); rank 0 prints the line"""
+    import torch.distributed as dist
+
+    from concepthash_amd.training import benchmark_ddp_step
+    world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ["RANK"])
+    ndev = torch.cuda.device_count()
+    local = int(os.environ.get("LOCAL_RANK", "0")) % max(1, ndev)
+    torch.cuda.set_device(local)
+    backend = os.environ.get("CH_DIST_BACKEND", "nccl")     # nccl = RCCL over xGMI; gloo only for rehearsals on fewer GPUs than ranks
+    if backend == "nccl":
+        dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    else:
+        dist.init_process_group(backend)
+    try:
+        cfg = synthetic.CONFIGS[a.config]
+        sd = synthetic.synthetic_state_dict(cfg, nbit=64, nclass=200)
+        res = benchmark_ddp_step(cfg, sd, a.global_batch, a.steps, a.warmup, a.train_backbone)
+        t = torch.tensor([res["step_ms"], res["all_reduce_ms"]], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)             # the slowest rank's times
+        if rank == 0:
+            res.update(step_ms=round(float(t[0]), 3), all_reduce_ms=round(float(t[1]), 3),
+                       images_per_s=round(a.global_batch / float(t[0]) * 1e3, 1))
+            print(json.dumps(dict(config=a.config, n_ranks=world, n_gpus=min(world, ndev), collective_backend=dist.get_backend(),
+                                  rehearsal=bool(ndev < world), **res)), flush=True)
+    finally:
+        dist.destroy_process_group()
 
 
 def _measure(eng, x, ctx, dhf, warmup, steps):
@@ -81,8 +138,15 @@ def main():
     ap.add_argument("--train-backbone", action="store_true", help="trainable backbone (backbone_lr_scale != 0): the engine owns the second arena "
                     "pair, backward also fills the backbone's gradients; also prints the working-copy refresh and the optimizer step (fused "
                     "ch_adam_step over the arenas against torch.optim.Adam over their views)")
+    ap.add_argument("--gpus", type=int, default=0, help="N >= 1: the data-parallel training step on N ranks (started here as fresh processes, or "
+                    "by a launcher that sets WORLD_SIZE / RANK): step time, the gradient all-reduce on its own, bytes reduced per step")
+    ap.add_argument("--global-batch", type=int, default=256, help="with --gpus: the global batch, split evenly over the ranks")
     ap.add_argument("--encode", action="store_true", help="also time ch_encode (evaluation) at the same batches and input size")
     a = ap.parse_args()
+    if a.gpus:
+        if "WORLD_SIZE" not in os.environ:
+            sys.exit(ddp_launch(a))
+        return ddp_rank(a)
     if a.ab:
         return ab(a)
     cfg = synthetic.CONFIGS[a.config]

@@ -53,6 +53,11 @@ class BaseTrainer:
         self.distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         self.rank = dist.get_rank() if self.distributed else 0
         self.world_size = dist.get_world_size() if self.distributed else 1
+        # collectives run in a multi-rank group, and -- CH_FORCE_COLLECTIVES=1 -- in a one-rank group too (identities: a single GPU can then
+        # drive the RCCL backend through the training step's collectives)
+        self.collectives = self.distributed or (dist.is_available() and dist.is_initialized()
+                                                and os.environ.get("CH_FORCE_COLLECTIVES") == "1")
+        self._grad_keys = None
         if self.distributed and self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda" and torch.cuda.is_available():
@@ -161,16 +166,48 @@ class BaseTrainer:
                     res[key] = torch.cat(vals).cpu()  # one device->host copy per output per epoch
                 else:
                     res[key] = np.concatenate(vals)
-        if self.distributed:                      # meters: sample-weighted average over ranks
-            import torch.distributed as dist
-            names = [None] * self.world_size
-            dist.all_gather_object(names, sorted(meters))          # a rank without batches has no meters of its own
-            for k in sorted(set().union(*names)):
-                v = torch.tensor([meters[k].sum, float(meters[k].count)], dtype=torch.float64, device=self.device)
-                dist.all_reduce(v)
-                meters[k].sum, meters[k].count = float(v[0]), int(v[1])
-                meters[k].avg = meters[k].sum / max(meters[k].count, 1)
+        self._reduce_meters(meters)
         return meters, res
+
+    def _reduce_meters(self, meters):
+        """meters: sample-weighted average over ranks (sums and counts all-reduced, in place)"""
+        if not self.distributed:
+            return
+        import torch.distributed as dist
+        names = [None] * self.world_size
+        dist.all_gather_object(names, sorted(meters))          # a rank without batches has no meters of its own
+        for k in sorted(set().union(*names)):
+            v = torch.tensor([meters[k].sum, float(meters[k].count)], dtype=torch.float64, device=self.device)
+            dist.all_reduce(v)
+            meters[k].sum, meters[k].count = float(v[0]), int(v[1])
+            meters[k].avg = meters[k].sum / max(meters[k].count, 1)
+
+    def shared_seed(self) -> int:
+        """The seed every rank derives the training permutation and the per-image draws from: `config.seed`, or -- unseeded runs,
+        seed = -1 -- a number rank 0 draws once and broadcasts."""
+        if getattr(self, "_shared_seed", None) is None:
+            seed = int(self.config.get("seed", -1))
+            if seed == -1:
+                box = [int(torch.empty((), dtype=torch.int64).random_().item())]
+                if self.distributed:
+                    import torch.distributed as dist
+                    dist.broadcast_object_list(box, src=0)
+                seed = box[0]
+            self._shared_seed = seed
+        return self._shared_seed
+
+    def broadcast_model(self):
+        """Rank 0's parameters and buffers to every rank, once, before the first step.  Same seed + same checkpoint already give identical
+        copies; this also covers any start that does not."""
+        if self.collectives and self.model is not None:
+            from concepthash_amd.distributed import broadcast_module_state
+            broadcast_module_state(self.model, src=0)
+
+    def all_reduce_gradients(self):
+        """concepthash_amd.training.all_reduce_gradients with the agreed key set kept for the epoch (one agreement exchange per epoch, not
+        per step; a rank whose set changes in between raises)"""
+        from concepthash_amd.training import all_reduce_gradients
+        self._grad_keys = all_reduce_gradients(self.model, keys=self._grad_keys)["keys"]
 
     # ---- training (reference :133-175, :340-358) --------------------------------------------------------------------------
     def load_optimizer_and_scheduler(self):
@@ -227,10 +264,29 @@ class BaseTrainer:
         dmeters = DeviceMeters(self.device)       # as in inference_one_epoch: nothing is read back inside the batch loop
         loader = self.dataloader["train"]
         n = len(loader) if hasattr(loader, "__len__") else 0
+        epoch = int(kwargs.get("ep", self.current_epoch))
+        sampler = getattr(loader, "batch_sampler", None)
+        if hasattr(sampler, "set_epoch"):             # GlobalBatchSampler: permutation and per-image draws are functions of (seed, epoch)
+            sampler.set_epoch(epoch)
+            if hasattr(loader.dataset, "set_draw_seed"):
+                loader.dataset.set_draw_seed(sampler.seed, epoch)
+        if self.distributed:
+            # every rank enters the same collectives the same number of times: equal step counts (drop_last + the divisibility rule)
+            import torch.distributed as dist
+            steps = torch.tensor([n, -n], dtype=torch.int64, device=self.device)
+            dist.all_reduce(steps, op=dist.ReduceOp.MAX)
+            if int(steps[0]) != -int(steps[1]):
+                raise RuntimeError(f"ranks disagree on the steps of epoch {epoch}: between {-int(steps[1])} and {int(steps[0])}")
+        self._grad_keys = None
+        done = 0
         for i, data in enumerate(loader):
             self.train_one_batch(data, dmeters, bidx=i, **kwargs)
+            done += 1
             if n and (i + 1) % max(1, n // 5) == 0:
                 logging.info("train: batch %d/%d %s", i + 1, n, dmeters.latest() or "")
                 dmeters.snapshot()
+        assert not self.distributed or done == n, (done, n)
         self.scheduler.step()
-        return defaultdict(AverageMeter, dmeters.finalize())
+        meters = defaultdict(AverageMeter, dmeters.finalize())
+        self._reduce_meters(meters)
+        return meters

@@ -60,7 +60,14 @@ class COOPTrainer(BaseTrainer):
                 ebs = max(bs, int(self.config.get("eval_batch_min", 256) or 0))
             self.dataloader[k] = engine.dataloader(ds, ebs, shuffle=False, drop_last=False, sampler=sampler)
         train = self.dataset.get("train") or []
-        self.dataloader["train"] = engine.dataloader(train, bs, shuffle=True, drop_last=True) if len(train) else []
+        if len(train) and (self.world_size > 1 or self.config.get("global_batch_sampler")):
+            # data-parallel training: `batch_size` stays the GLOBAL batch; every rank cuts the same (seed, epoch)
+            # permutation into the same global batches and takes its rows of each.  `global_batch_sampler: true` selects the same batches
+            # in a single process (the default single-process loader draws from the process generator, as the reference's does).
+            sampler = engine.GlobalBatchSampler(len(train), bs, self.shared_seed(), self.rank, self.world_size)
+            self.dataloader["train"] = engine.dataloader(train, batch_sampler=sampler)
+        else:
+            self.dataloader["train"] = engine.dataloader(train, bs, shuffle=True, drop_last=True) if len(train) else []
 
     def parse_model_output(self, output):
         codes, logits = output
@@ -152,7 +159,14 @@ class COOPTrainer(BaseTrainer):
         (image, labels, index), output = self.compute_features_one_batch(data)
         target = labels if self.config.dataset.get("multiclass") else labels.argmax(1)
         loss = self.criterion(output, target)
-        loss.backward()
+        if self.world_size > 1:
+            # the global-batch mean is the mean of the (equal-sized) ranks' means: 1 / world_size here, SUM in the all-reduce.  The factor
+            # passes linearly through the head's autograd and ch_train_backward into every gradient
+            (loss / self.world_size).backward()
+        else:
+            loss.backward()
+        if self.collectives:
+            self.all_reduce_gradients()
         self.optimizer.step()
         n = image.size(0)
         vals = {"loss": loss.detach()}

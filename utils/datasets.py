@@ -3,6 +3,7 @@ datasets with one-hot targets, plus a synthetic variant for machines without the
 reference snapshot)."""
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -239,9 +240,31 @@ class HashingDataset(Dataset):
         self.read_threads = int(kwargs.get("read_threads", 8))
         self.file_workers = bool(kwargs.get("file_workers", False))   # gpu_decode: DataLoader worker processes instead of in-process reads     # gpu_decode: threads of one batch's file reads (ch_io_read_files)
         self._paths = {}          # index -> resolved path (a worker resolves each file once)
+        self.draw_seed = None     # (seed, epoch) in multi-rank training: see set_draw_seed
 
     def __len__(self):
         return len(self.items)
+
+    def set_draw_seed(self, seed, epoch):
+        """Multi-rank training: the random draws of image `index` in this epoch (crop box, flip, TrivialAugment op -- or a CPU transform
+        list's own calls) come from a generator state that is a function of (seed, epoch, index) alone, not of the worker or rank that loads
+        the image, so N ranks draw for their rows what one process would draw for the whole global batch.  None = the process generator as
+        it stands (the single-process stream)."""
+        self.draw_seed = None if seed is None else (int(seed), int(epoch))
+
+    @contextlib.contextmanager
+    def _image_rng(self, index):
+        if self.draw_seed is None:
+            yield
+            return
+        from engine import epoch_seed
+        gen = torch.default_generator          # the CPU generator alone: torch.manual_seed would also reseed the GPU's (dropout masks)
+        state = gen.get_state()
+        gen.manual_seed(epoch_seed(self.draw_seed[0], self.draw_seed[1], int(index)))
+        try:
+            yield
+        finally:
+            gen.set_state(state)
 
     def _resolve(self, rel):
         for cand in (rel, os.path.join(self.root, rel), os.path.join(os.path.dirname(os.path.dirname(self.root)), rel)):
@@ -301,8 +324,9 @@ class HashingDataset(Dataset):
         targets = torch.stack([t if torch.is_tensor(t) else torch.as_tensor(t) for t in targets])
         if self.augment is not None:
             draws, o = [], 0
-            for n in lengths:
-                draws.append(self._draw(*self._file_size(view[o:o + n])))
+            for i, n in zip(indices, lengths):
+                with self._image_rng(i):
+                    draws.append(self._draw(*self._file_size(view[o:o + n])))
                 o += n
             boxes, flips, ta = _collate_draws([(None,) + tuple(d) for d in draws])
             return RawJpegBatch(data, lengths, boxes, flips, ta), targets, torch.as_tensor(list(indices))
@@ -319,16 +343,19 @@ class HashingDataset(Dataset):
             buf = np.fromfile(self._resolve(rel), dtype=np.uint8)      # read only: no decode on the CPU
             item = torch.from_numpy(buf)
             if self.augment is not None:
-                item = (item,) + self._draw(*self._file_size(memoryview(buf)))
+                with self._image_rng(index):
+                    item = (item,) + self._draw(*self._file_size(memoryview(buf)))
             return item, target, index
         img = Image.open(self._resolve(rel)).convert("RGB")
         if self.gpu_preprocess:
             import numpy as np
             img = torch.from_numpy(np.array(img, dtype=np.uint8))          # decode only; resize / crop / normalise on the GPU
             if self.augment is not None:
-                img = (img,) + self._draw(img.shape[0], img.shape[1])
+                with self._image_rng(index):
+                    img = (img,) + self._draw(img.shape[0], img.shape[1])
         elif self.transform is not None:
-            img = self.transform(img)
+            with self._image_rng(index):
+                img = self.transform(img)
         return img, target, index
 
 
