@@ -186,11 +186,10 @@ extern "C" int ch_debug_attention_bwd_ex(const void *qkv, const void *dO, int32_
 extern "C" int ch_debug_wgrad(const void *A, int32_t lda, const void *Bm, int32_t ldb, int64_t rows, int64_t rows_alloc, int32_t N,
                               int32_t K, float *out, void *stream) {
     CH_REQUIRE(A && Bm && out, "debug_wgrad: null argument");
-    float *ws = nullptr;
-    CH_CHECK_HIP(hipMalloc((void **)&ws, sizeof(float) * ch_wgrad_ws_floats(rows, N, K)));
-    const int e = ch_wgrad_tn((bf16_t *)A, lda, (const bf16_t *)Bm, ldb, rows, rows_alloc, N, K, out, ws, (hipStream_t)stream);
+    ChDeviceTemp ws;
+    if (ws.get(sizeof(float) * ch_wgrad_ws_floats(rows, N, K))) return 1;
+    const int e = ch_wgrad_tn((bf16_t *)A, lda, (const bf16_t *)Bm, ldb, rows, rows_alloc, N, K, out, ws.as<float>(), (hipStream_t)stream);
     (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(ws);
     return e;
 }
 // row statistics of x are computed here (hb_stats on an fp32 copy is what the chain does; the tap takes bf16 x and derives the
@@ -199,11 +198,10 @@ extern "C" int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int
                                void *out_b, void *xhat_out, void *stream) {
     CH_REQUIRE(dyg && x && dres_in, "debug_ln_bwd: null argument");
     hipStream_t s = (hipStream_t)stream;
-    float *st = nullptr, *xf = nullptr;
-    bf16_t *hb = nullptr;
-    CH_CHECK_HIP(hipMalloc((void **)&st, sizeof(float) * rows * (D / 64) * 2));
-    CH_CHECK_HIP(hipMalloc((void **)&xf, sizeof(float) * rows * D));
-    CH_CHECK_HIP(hipMalloc((void **)&hb, sizeof(bf16_t) * rows * D));
+    ChDeviceTemp tst, txf, thb;
+    if (tst.get(sizeof(float) * rows * (D / 64) * 2) || txf.get(sizeof(float) * rows * D) || thb.get(sizeof(bf16_t) * rows * D)) return 1;
+    float *st = tst.as<float>(), *xf = txf.as<float>();
+    bf16_t *hb = thb.as<bf16_t>();
     int e = 0;
     {   // bf16 -> fp32 (exact) by a strided 2-byte copy into the high halves
         CH_CHECK_HIP(hipMemsetAsync(xf, 0, sizeof(float) * rows * D, s));
@@ -213,9 +211,6 @@ extern "C" int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int
     if (!e) e = ch_ln_bwd((const bf16_t *)dyg, (const bf16_t *)x, st, rows, D, eps, dres_in, dres_out, (bf16_t *)out_b, s);
     if (!e && xhat_out) e = ch_normalize_bf16((const bf16_t *)x, st, rows, D, eps, (bf16_t *)xhat_out, s);
     (void)hipStreamSynchronize(s);
-    (void)hipFree(st);
-    (void)hipFree(xf);
-    (void)hipFree(hb);
     return e;
 }
 extern "C" int ch_debug_act(const void *g, const void *pre, int64_t n, int32_t act, const float *scale_ptr, int32_t backward, void *out,

@@ -20,19 +20,15 @@ extern "C" int ch_abi_version(void) { return CH_ABI_VERSION; }
 namespace {
 
 struct Builder : ChWeightBuilder {
+    using ChWeightBuilder::ChWeightBuilder;
     // LayerNorm fold of a Linear made of `nparts` row blocks ([rows_each, D] weights + [rows_each] biases, host fp32):
     // wf = bf16(W * gamma) [n_pad, D] (rows past the true ones zero), c[n] = sum_k wf[n][k], d[n] = bias[n] + sum_k W[n][k] beta[k]
     bool fold(const std::string *wnames, const std::string *bnames, int nparts, int rows_each, int n_pad, int D,
               const float *gamma, const float *beta, const bf16_t **wf, const float **cc, const float **dd) {
         const int n_true = nparts * rows_each;
-        float *w32 = nullptr, *b32 = nullptr;
-        if (hipMalloc((void **)&w32, sizeof(float) * (size_t)n_true * D) != hipSuccess ||
-            hipMalloc((void **)&b32, sizeof(float) * n_true) != hipSuccess) {
-            ch_set_error("hipMalloc failed (LayerNorm fold staging)");
-            ok = false;
-            (void)hipFree(w32);
-            return false;
-        }
+        ChDeviceTemp tw, tb;
+        if (tw.get(sizeof(float) * (size_t)n_true * D) || tb.get(sizeof(float) * n_true)) return ok = false;
+        float *w32 = tw.as<float>(), *b32 = tb.as<float>();
         for (int j = 0; j < nparts && ok; ++j) {
             const ch_tensor *wt = find(wnames[j], (int64_t)rows_each * D), *bt = find(bnames[j], rows_each);
             if (!wt || !bt) break;
@@ -45,8 +41,6 @@ struct Builder : ChWeightBuilder {
         float *c = (float *)alloc(sizeof(float) * n_pad), *d = (float *)alloc(sizeof(float) * n_pad);
         if (ok && ch_fold_ln(w32, b32, gamma, beta, n_true, n_pad, D, w, c, d, s) != 0) ok = false;
         if (hipStreamSynchronize(s) != hipSuccess) ok = false;
-        (void)hipFree(w32);
-        (void)hipFree(b32);
         *wf = w;
         *cc = c;
         *dd = d;
@@ -56,9 +50,7 @@ struct Builder : ChWeightBuilder {
 
 int build_model(ch_model *m, const ch_tensor *tensors, int ntensors) {
     const ch_model_config &c = m->cfg;
-    Builder B;
-    B.allocs = &m->allocs;
-    B.bytes = &m->bytes;
+    Builder B(m->own);
     for (int i = 0; i < ntensors; ++i) {
         CH_REQUIRE(tensors[i].name && tensors[i].data, "tensor entry with null name/data");
         B.tab[tensors[i].name] = &tensors[i];
@@ -474,16 +466,15 @@ int run_encoder(ch_model *m, const void *images, int image_dtype, int B, int nla
     m->last_chains = ns;
     if (ns < 2) return run_chain(m, 0, images, image_dtype, 0, B, nlayers, s, concept_attn, attn_all_layers, prune, B);
     // micro-batch i = images [i*B/ns, (i+1)*B/ns); chain 0 on the caller's stream, the others fork from / join it
-    CH_CHECK_HIP(hipEventRecord(m->ev_fork, s));
+    if (int e = m->fj.fork(s)) return e;
     for (int i = 0; i < ns; ++i) {
         const int b0 = (int)((int64_t)B * i / ns), b1 = (int)((int64_t)B * (i + 1) / ns);
-        hipStream_t si = i == 0 ? s : m->aux_stream[i - 1];
-        if (i > 0) CH_CHECK_HIP(hipStreamWaitEvent(si, m->ev_fork, 0));
-        if (int e = run_chain(m, i, images, image_dtype, b0, b1 - b0, nlayers, si, concept_attn, attn_all_layers, prune, B)) return e;
-        if (i > 0) {
-            CH_CHECK_HIP(hipEventRecord(m->ev_join[i - 1], si));
-            CH_CHECK_HIP(hipStreamWaitEvent(s, m->ev_join[i - 1], 0));
-        }
+        if (i > 0)
+            if (int e = m->fj.start(i)) return e;
+        if (int e = run_chain(m, i, images, image_dtype, b0, b1 - b0, nlayers, i == 0 ? s : m->fj.aux[i], concept_attn, attn_all_layers, prune, B))
+            return e;
+        if (i > 0)
+            if (int e = m->fj.finish(i, s)) return e;
     }
     return 0;
 }
@@ -533,11 +524,7 @@ extern "C" int ch_model_create(const ch_model_config *cfg, const ch_tensor *tens
     m->np = grid * grid;
     m->ntok = 1 + m->np + cfg->ncontext;
     m->Kp = (int)round_up64(3 * cfg->patch * cfg->patch, 64);
-    bool aux_ok = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; aux_ok && i < CH_MAX_STREAMS - 1; ++i)
-        aux_ok = hipStreamCreateWithFlags(&m->aux_stream[i], hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming) == hipSuccess;
-    if (!aux_ok) {
+    if (!m->fj.init(m->own, CH_MAX_STREAMS)) {
         ch_set_error("cannot create the auxiliary streams / events");
         ch_model_destroy(m);
         return 4;
@@ -558,24 +545,11 @@ extern "C" int ch_model_create(const ch_model_config *cfg, const ch_tensor *tens
 
 extern "C" void ch_model_destroy(ch_model *m) {
     if (!m) return;
-    drop_graphs(m);
-    if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
-    for (auto &P : m->prof) {
-        for (hipEvent_t e : P.ev) (void)hipEventDestroy(e);
-        for (hipEvent_t e : P.kstart) (void)hipEventDestroy(e);
-        for (hipEvent_t e : P.kstop) (void)hipEventDestroy(e);
-    }
-    for (hipStream_t a : m->aux_stream)
-        if (a) (void)hipStreamDestroy(a);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    for (hipEvent_t e : m->ev_join)
-        if (e) (void)hipEventDestroy(e);
-    for (void *p : m->allocs)
-        if (p) (void)hipFree(p);
+    drop_graphs(m);   // the graphs reference the owner's memory and events: they go first
     delete m;
 }
 
-extern "C" size_t ch_model_device_bytes(const ch_model *m) { return m ? m->bytes : 0; }
+extern "C" size_t ch_model_device_bytes(const ch_model *m) { return m ? m->own.bytes() : 0; }
 
 // ---- per-handle options (include/concepthash_hip.h: ch_model_set_option).  The library reads no environment variable: every knob of the
 // launch chain is state of ONE opaque handle, set through this entry point (the Python wrapper maps its debug environment overrides onto it).
@@ -641,12 +615,13 @@ extern "C" int ch_model_set_option(ch_model *m, const char *key, int64_t value) 
     if (std::string(key) == "splitk" && value != 0) {   // the tail's slabs + tickets, one set per chain: allocated on first use
         for (int i = 0; i < CH_MAX_STREAMS; ++i) {
             if (m->splitk_ws[i]) continue;
-            CH_CHECK_HIP(hipMalloc((void **)&m->splitk_ws[i], CH_SPLITK_WS_BYTES));
-            m->allocs.push_back(m->splitk_ws[i]);
-            CH_CHECK_HIP(hipMalloc((void **)&m->splitk_cnt[i], CH_SPLITK_CNT_BYTES));
-            m->allocs.push_back(m->splitk_cnt[i]);
-            CH_CHECK_HIP(hipMemset(m->splitk_cnt[i], 0, CH_SPLITK_CNT_BYTES));
-            m->bytes += CH_SPLITK_WS_BYTES + CH_SPLITK_CNT_BYTES;
+            void *ws = m->own.alloc(CH_SPLITK_WS_BYTES), *cnt = ws ? m->own.alloc(CH_SPLITK_CNT_BYTES, true) : nullptr;
+            if (!cnt) {   // both or neither: a slab without its tickets must not look allocated to the next call
+                if (ws) (void)m->own.release(ws);
+                return 1;
+            }
+            m->splitk_ws[i] = (float *)ws;
+            m->splitk_cnt[i] = (unsigned *)cnt;
         }
     }
     void *f = o->field(m);
@@ -716,18 +691,13 @@ int encode_impl(ch_model *m, const void *images, int image_dtype, int B, float *
 int ensure_bytes(ch_model *m, void **buf, size_t *have, size_t need) {
     if (*have >= need) return 0;
     drop_graphs(m);                      // cached graphs hold the old pointer
-    if (*buf) {
-        CH_CHECK_HIP(hipDeviceSynchronize());
-        for (void *&p : m->allocs)
-            if (p == *buf) p = nullptr;
-        CH_CHECK_HIP(hipFree(*buf));
-        m->bytes -= *have;
+    if (*buf && hipDeviceSynchronize() != hipSuccess) {
+        *buf = nullptr;                  // still the owner's (freed with the handle), no longer used
+        *have = 0;
+        ch_set_error("hipDeviceSynchronize failed before a staging buffer could grow");
+        return 1;
     }
-    CH_CHECK_HIP(hipMalloc(buf, need));
-    m->allocs.push_back(*buf);
-    m->bytes += need;
-    *have = need;
-    return 0;
+    return m->own.regrow(buf, have, need);   // release, then alloc; nullptr / 0 on any failure
 }
 
 // B <= graph_max_batch: images -> staging, one graph replay, requested outputs <- staging
@@ -759,7 +729,7 @@ int encode_graph(ch_model *m, const void *images, int image_dtype, int B, void *
         // first call of this shape: run it eagerly (this call's result; also performs every once-per-device function attribute
         // setting outside the capture), then capture the same chain on the library's own stream and keep the instantiated graph
         if (int e = chain(s)) return e;
-        if (!m->cap_stream) CH_CHECK_HIP(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
+        if (!m->cap_stream && !(m->cap_stream = m->own.stream(hipStreamNonBlocking))) return 1;
         ch_model::GraphEntry ge;
         CH_CHECK_HIP(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeThreadLocal));
         const int e = chain(m->cap_stream);
@@ -825,10 +795,8 @@ extern "C" int ch_model_profile_begin(ch_model *m, int32_t max_launches) {
     CH_REQUIRE(m != nullptr && max_launches > 0, "profile_begin: null model or non-positive capacity");
     for (auto &P : m->prof) {
         while (P.ev.size() < (size_t)max_launches + 1) {
-            hipEvent_t e, a, b;
-            CH_CHECK_HIP(hipEventCreate(&e));
-            CH_CHECK_HIP(hipEventCreate(&a));
-            CH_CHECK_HIP(hipEventCreate(&b));
+            hipEvent_t e = m->own.event(), a = m->own.event(), b = m->own.event();
+            if (!e || !a || !b) return 1;   // (the owner keeps whichever it did create)
             P.ev.push_back(e);
             P.kstart.push_back(a);
             P.kstop.push_back(b);

@@ -8,6 +8,7 @@
 
 #include "../../include/concepthash_hip.h"
 #include "ch_common.h"
+#include "device_owner.h"
 #include "kernels.h"
 
 constexpr int CH_MAX_STREAMS = 4;  // micro-batch chains that may run concurrently (option "streams")
@@ -28,11 +29,36 @@ struct LayerW {
     AdapterW ad[2];
 };
 
+// Fork / join of micro-batch chains (ch_encode: model.hip run_encoder; the training step: train.hip): chain 0 runs on the caller's
+// stream s, chain i > 0 on aux stream i.  The streams and events belong to the handle's owner.
+struct ChForkJoin {
+    hipStream_t aux[CH_MAX_STREAMS] = {};   // [i] for chain i; [0] unused
+    hipEvent_t ev_fork = nullptr, ev_join[CH_MAX_STREAMS] = {};
+    bool init(ChDeviceOwner &own, int nchains) {
+        bool ok = (ev_fork = own.event(hipEventDisableTiming)) != nullptr;
+        for (int i = 1; ok && i < nchains; ++i)
+            ok = (aux[i] = own.stream(hipStreamNonBlocking)) != nullptr && (ev_join[i] = own.event(hipEventDisableTiming)) != nullptr;
+        return ok;
+    }
+    int fork(hipStream_t s) {   // the point on s behind which the other chains may start
+        CH_CHECK_HIP(hipEventRecord(ev_fork, s));
+        return 0;
+    }
+    int start(int i) {
+        CH_CHECK_HIP(hipStreamWaitEvent(aux[i], ev_fork, 0));
+        return 0;
+    }
+    int finish(int i, hipStream_t s) {   // s goes on only when chain i is through
+        CH_CHECK_HIP(hipEventRecord(ev_join[i], aux[i]));
+        CH_CHECK_HIP(hipStreamWaitEvent(s, ev_join[i], 0));
+        return 0;
+    }
+};
+
 struct ch_model {
     ch_model_config cfg;
     int np = 0, ntok = 0, Kp = 0, bpad = 0;
-    std::vector<void *> allocs;
-    size_t bytes = 0;
+    ChDeviceOwner own;   // every device block, stream and event of the handle (ch_model_device_bytes = own.bytes())
     // weights
     const bf16_t *patch_w = nullptr;
     const float *pos = nullptr, *cls_pos0 = nullptr, *ctx = nullptr, *pre_w = nullptr, *pre_b = nullptr;
@@ -64,8 +90,7 @@ struct ch_model {
     // 1 -> 2 streams +8 % images/s, 3 and 4 no better.  streams = 1 is what a per-kernel profile wants:
     // per-launch durations stop describing single kernels once launches overlap.
     int nstreams = 2;
-    hipStream_t aux_stream[CH_MAX_STREAMS - 1] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[CH_MAX_STREAMS - 1] = {};
+    ChForkJoin fj;
     // workspace
     int64_t rows_alloc = 0, prow_alloc = 0;
     float *H = nullptr;

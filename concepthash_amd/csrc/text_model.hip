@@ -23,8 +23,7 @@ struct TextLayerW {
 
 struct ch_text {
     ch_text_config cfg;
-    std::vector<void *> allocs;
-    size_t bytes = 0;
+    ChDeviceOwner own;                                // every device block, the pinned `stage` and the `staged` event
     const float *tok = nullptr, *pos = nullptr;       // [vocab, D], [max_positions, D] fp32
     const float *fln_w = nullptr, *fln_b = nullptr;   // final_layer_norm
     std::vector<TextLayerW> layers;
@@ -110,17 +109,9 @@ int validate(const ch_text_config *c) {
     return 0;
 }
 
-void *zeros(ChWeightBuilder &B, size_t bytes) {
-    void *p = B.alloc(bytes);
-    if (p && hipMemset(p, 0, bytes) != hipSuccess) B.ok = false;
-    return p;
-}
-
 int build_text(ch_text *m, const ch_tensor *tensors, int ntensors) {
     const ch_text_config &c = m->cfg;
-    ChWeightBuilder B;
-    B.allocs = &m->allocs;
-    B.bytes = &m->bytes;
+    ChWeightBuilder B(m->own);
     for (int i = 0; i < ntensors; ++i) {
         CH_REQUIRE(tensors[i].name && tensors[i].data, "tensor entry with null name/data");
         B.tab[tensors[i].name] = &tensors[i];
@@ -164,17 +155,18 @@ int build_text(ch_text *m, const ch_tensor *tensors, int ntensors) {
         }
     const int64_t rows = round_up64((int64_t)c.max_batch * c.max_positions, 256) + 256;   // +256: a last tile's over-read
     m->rows_alloc = rows;
-    m->H = (float *)zeros(B, sizeof(float) * rows * D);
-    m->Xn = (bf16_t *)zeros(B, sizeof(bf16_t) * rows * D);
-    m->QKV = (bf16_t *)zeros(B, sizeof(bf16_t) * rows * 3 * D);
-    m->AO = (bf16_t *)zeros(B, sizeof(bf16_t) * rows * D);
-    m->A = (bf16_t *)zeros(B, sizeof(bf16_t) * rows * D);
-    m->F1 = (bf16_t *)zeros(B, sizeof(bf16_t) * rows * M);
-    m->ids = (int32_t *)zeros(B, sizeof(int32_t) * (size_t)c.max_batch * c.max_positions);
-    m->eos = (int32_t *)zeros(B, sizeof(int32_t) * (size_t)c.max_batch);
+    m->H = (float *)B.alloc(sizeof(float) * rows * D, true);
+    m->Xn = (bf16_t *)B.alloc(sizeof(bf16_t) * rows * D, true);
+    m->QKV = (bf16_t *)B.alloc(sizeof(bf16_t) * rows * 3 * D, true);
+    m->AO = (bf16_t *)B.alloc(sizeof(bf16_t) * rows * D, true);
+    m->A = (bf16_t *)B.alloc(sizeof(bf16_t) * rows * D, true);
+    m->F1 = (bf16_t *)B.alloc(sizeof(bf16_t) * rows * M, true);
+    m->ids = (int32_t *)B.alloc(sizeof(int32_t) * (size_t)c.max_batch * c.max_positions, true);
+    m->eos = (int32_t *)B.alloc(sizeof(int32_t) * (size_t)c.max_batch, true);
     if (!B.ok) return 4;
-    CH_CHECK_HIP(hipHostMalloc((void **)&m->stage, sizeof(int32_t) * ((size_t)c.max_batch * c.max_positions + c.max_batch), hipHostMallocDefault));
-    CH_CHECK_HIP(hipEventCreateWithFlags(&m->staged, hipEventDisableTiming));
+    m->stage = (int32_t *)m->own.host_alloc(sizeof(int32_t) * ((size_t)c.max_batch * c.max_positions + c.max_batch));
+    m->staged = m->own.event(hipEventDisableTiming);
+    if (!m->stage || !m->staged) return 1;
     CH_CHECK_HIP(hipDeviceSynchronize());
     return 0;
 }
@@ -230,15 +222,10 @@ extern "C" int ch_text_create(const ch_text_config *cfg, const ch_tensor *tensor
 }
 
 extern "C" void ch_text_destroy(ch_text *m) {
-    if (!m) return;
-    for (void *p : m->allocs)
-        if (p) (void)hipFree(p);
-    if (m->stage) (void)hipHostFree(m->stage);
-    if (m->staged) (void)hipEventDestroy(m->staged);
     delete m;
 }
 
-extern "C" size_t ch_text_device_bytes(const ch_text *m) { return m ? m->bytes : 0; }
+extern "C" size_t ch_text_device_bytes(const ch_text *m) { return m ? m->own.bytes() : 0; }
 
 extern "C" int ch_text_encode(ch_text *m, const int32_t *ids, const int32_t *eos_pos, int32_t B, int32_t T, float *out_pooled,
                               float *out_hidden, void *stream) {

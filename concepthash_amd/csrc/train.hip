@@ -62,21 +62,18 @@ constexpr int TR_CHAINS = 2;
 struct ch_trainer {
     ch_model *m = nullptr;
     int max_batch = 0, B = 0;
-    // Two micro-batch chains on two streams (as ch_encode does), model option "train_chains" = 2: chain 1 owns its own row
-    // region of every activation buffer (so that padding rows never alias the other chain's data), its own weight-gradient
+    // Two micro-batch chains on two streams (as ch_encode does), model option "train_chains" (default 2): chain 1 owns
+    // its own row region of every activation buffer (so that padding rows never alias the other chain's data), its own weight-gradient
     // scratch and its own gradient arena; the two arenas are added once at the end (the assembly is linear in the weight-gradient
-    // products).  Correct (tests run both), but MEASURED SLOWER than one chain for training -- 47.2 vs 42.5 ms at batch 256, 27.0
-    // vs 23.6 ms at batch 128: the half-size GEMMs lose more than the overlap of the HBM-bound launches returns, and the
-    // per-adapter reductions have fixed costs that double -- so one chain is the default.
+    // products).  A trainer created with two chains decides per step: two when one chain's N = D GEMMs would need more than one round
+    // of tiles (or by "train_chain_min_rows"), else one -- the rule and its measurements are at ch_train_forward.
     int nchains = 1, nc = 1, Bc[TR_CHAINS] = {0, 0};
     int64_t chain_min_rows = 12000;
     int64_t row_off[TR_CHAINS] = {0, 0}, prow_off[TR_CHAINS] = {0, 0}, region_rows[TR_CHAINS] = {0, 0}, region_prows[TR_CHAINS] = {0, 0};
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    ChDeviceOwner own;   // every device block, the aux stream and the fork / join events (ch_trainer_bytes = own.bytes())
+    ChForkJoin fj;
     float *params = nullptr, *grads = nullptr, *grads1 = nullptr;
     int64_t ad_numel = 0;
-    std::vector<void *> allocs;
-    size_t bytes = 0;
     std::vector<AdWork> ad;     // [L * 2]
     std::vector<LayerT> lt;     // [L]
     std::vector<Saved> sv;      // [L]
@@ -118,16 +115,9 @@ struct ch_trainer {
 namespace {
 
 void *talloc(ch_trainer *t, size_t bytes, bool &ok) {
-    void *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    if (!ok) return nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess || hipMemset(p, 0, bytes) != hipSuccess) {
-        ch_set_error("trainer: hipMalloc/hipMemset failed for " + std::to_string(bytes) + " bytes");
-        ok = false;
-        return nullptr;
-    }
-    t->allocs.push_back(p);
-    t->bytes += bytes;
+    if (!ok) return nullptr;   // after a failure nothing more is allocated; the first error string stands
+    void *p = t->own.alloc(bytes, true);
+    if (!p) ok = false;
     return p;
 }
 
@@ -489,11 +479,6 @@ extern "C" int64_t ch_adapter_arena_numel(const ch_model *m) {
 }
 
 extern "C" void ch_trainer_destroy(ch_trainer *t) {
-    if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
-    if (t->aux) (void)hipStreamDestroy(t->aux);
-    if (t->ev_fork) (void)hipEventDestroy(t->ev_fork);
-    if (t->ev_join) (void)hipEventDestroy(t->ev_join);
     delete t;
 }
 
@@ -630,11 +615,9 @@ extern "C" int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *param
     t->prow_off[1] = t->region_prows[0];
     const int64_t rows = t->region_rows[0] + t->region_rows[1], prows = t->region_prows[0] + t->region_prows[1];
     bool ok = true;
-    if (t->nchains > 1) {
-        ok = hipStreamCreateWithFlags(&t->aux, hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&t->ev_fork, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&t->ev_join, hipEventDisableTiming) == hipSuccess;
-        if (!ok) ch_set_error("trainer: cannot create the auxiliary stream / events");
+    if (t->nchains > 1 && !t->fj.init(t->own, 2)) {
+        ch_set_error("trainer: cannot create the auxiliary stream / events");
+        ok = false;
     }
     auto bf = [&](int64_t cols) { return (bf16_t *)talloc(t, sizeof(bf16_t) * rows * cols, ok); };
     auto st = [&]() { return (float *)talloc(t, sizeof(float) * rows * (D / 64) * 2, ok); };
@@ -755,7 +738,7 @@ extern "C" int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *param
     return 0;
 }
 
-extern "C" int64_t ch_trainer_bytes(const ch_trainer *t) { return t ? (int64_t)t->bytes : 0; }
+extern "C" int64_t ch_trainer_bytes(const ch_trainer *t) { return t ? (int64_t)t->own.bytes() : 0; }
 
 extern "C" int ch_train_forward(ch_trainer *t, const void *images, int32_t image_dtype, int32_t B, const float *concept_tokens,
                                 float *out_hash_features, float *out_cls, float *out_concept_attn, int32_t concept_attn_all_layers,
@@ -784,12 +767,11 @@ extern "C" int ch_train_forward(ch_trainer *t, const void *images, int32_t image
         if (int e = forward_chain(t, 0, images, image_dtype, 0, B, out_hash_features, out_cls, out_concept_attn, s)) return e;
     } else {
         t->Bc[0] = B - B / 2; t->Bc[1] = B / 2;      // chain 1 <= ceil(max_batch / 2) images: fits its region
-        CH_CHECK_HIP(hipEventRecord(t->ev_fork, s));
-        CH_CHECK_HIP(hipStreamWaitEvent(t->aux, t->ev_fork, 0));
+        if (int e = t->fj.fork(s)) return e;
+        if (int e = t->fj.start(1)) return e;
         if (int e = forward_chain(t, 0, images, image_dtype, 0, t->Bc[0], out_hash_features, out_cls, out_concept_attn, s)) return e;
-        if (int e = forward_chain(t, 1, images, image_dtype, t->Bc[0], t->Bc[1], out_hash_features, out_cls, out_concept_attn, t->aux)) return e;
-        CH_CHECK_HIP(hipEventRecord(t->ev_join, t->aux));
-        CH_CHECK_HIP(hipStreamWaitEvent(s, t->ev_join, 0));
+        if (int e = forward_chain(t, 1, images, image_dtype, t->Bc[0], t->Bc[1], out_hash_features, out_cls, out_concept_attn, t->fj.aux[1])) return e;
+        if (int e = t->fj.finish(1, s)) return e;
     }
     t->forward_done = true;
     return 0;
@@ -805,12 +787,11 @@ extern "C" int ch_train_backward(ch_trainer *t, const float *d_hash_features, co
     if (t->nc == 1) {
         if (int e = backward_chain(t, 0, d_hash_features, d_concept_attn, 0, t->Bc[0], s)) return e;
     } else {
-        CH_CHECK_HIP(hipEventRecord(t->ev_fork, s));
-        CH_CHECK_HIP(hipStreamWaitEvent(t->aux, t->ev_fork, 0));
+        if (int e = t->fj.fork(s)) return e;
+        if (int e = t->fj.start(1)) return e;
         if (int e = backward_chain(t, 0, d_hash_features, d_concept_attn, 0, t->Bc[0], s)) return e;
-        if (int e = backward_chain(t, 1, d_hash_features, d_concept_attn, t->Bc[0], t->Bc[1], t->aux)) return e;
-        CH_CHECK_HIP(hipEventRecord(t->ev_join, t->aux));
-        CH_CHECK_HIP(hipStreamWaitEvent(s, t->ev_join, 0));
+        if (int e = backward_chain(t, 1, d_hash_features, d_concept_attn, t->Bc[0], t->Bc[1], t->fj.aux[1])) return e;
+        if (int e = t->fj.finish(1, s)) return e;
         // the two chains' contributions: parameter gradients and concept-token rows (both linear in the per-row products)
         if (int e = ch_small_add(t->grads, t->grads1, t->ad_numel * c.layers * 2, t->grads, s)) return e;
         if (t->bb)

@@ -1,6 +1,6 @@
 // Weight ingestion shared by the handles that are built from named fp32 tensors (ch_model_create: model.hip, ch_text_create:
-// text_model.hip): look a tensor up by its state_dict key, check its size, copy or convert it to the device, and keep the allocation
-// and the byte count on the owning handle.  ch_tensor.data may be a host or a device pointer (hipMemcpyDefault).
+// text_model.hip): look a tensor up by its state_dict key, check its size, copy or convert it to the device, into memory of the
+// handle's owner (device_owner.h).  ch_tensor.data may be a host or a device pointer (hipMemcpyDefault).
 #pragma once
 #include <map>
 #include <set>
@@ -9,26 +9,20 @@
 
 #include "../../include/concepthash_hip.h"
 #include "ch_common.h"
+#include "device_owner.h"
 #include "kernels.h"
 
 struct ChWeightBuilder {
-    std::vector<void *> *allocs = nullptr;   // the owning handle's allocation list and byte count
-    size_t *bytes = nullptr;
+    ChDeviceOwner &owner;                    // the handle's: every weight and workspace block comes from it
     std::map<std::string, const ch_tensor *> tab;
     std::set<std::string> used;              // names that find() has handed out (what is left over is unknown to the model)
     hipStream_t s = nullptr;
     bool ok = true;
 
-    void *alloc(size_t nbytes) {
-        void *p = nullptr;
-        if (nbytes == 0) nbytes = 16;
-        if (hipMalloc(&p, nbytes) != hipSuccess) {
-            ch_set_error("hipMalloc failed for " + std::to_string(nbytes) + " bytes");
-            ok = false;
-            return nullptr;
-        }
-        allocs->push_back(p);
-        *bytes += nbytes;
+    explicit ChWeightBuilder(ChDeviceOwner &o) : owner(o) {}
+    void *alloc(size_t nbytes, bool zero = false) {
+        void *p = owner.alloc(nbytes, zero);
+        if (!p) ok = false;
         return p;
     }
     const ch_tensor *find(const std::string &name, int64_t numel) {
@@ -60,28 +54,22 @@ struct ChWeightBuilder {
         }
         return dst;
     }
-    float *f32_zeros(int64_t numel) {
-        float *d = (float *)alloc(sizeof(float) * numel);
-        if (d && hipMemset(d, 0, sizeof(float) * numel) != hipSuccess) ok = false;
-        return d;
-    }
+    float *f32_zeros(int64_t numel) { return (float *)alloc(sizeof(float) * numel, true); }
     // fp32 [rows, cols] -> bf16 device [rows, cols_pad] written into dst (or a fresh allocation)
     bf16_t *bf16(const std::string &name, int64_t rows, int cols, int cols_pad, bf16_t *dst = nullptr) {
         const ch_tensor *t = find(name, rows * cols);
         if (!t) return nullptr;
-        float *tmp = nullptr;
-        if (hipMalloc((void **)&tmp, sizeof(float) * rows * cols) != hipSuccess) {
-            ch_set_error("hipMalloc failed (staging)");
+        ChDeviceTemp tmp;
+        if (tmp.get(sizeof(float) * rows * cols)) {
             ok = false;
             return nullptr;
         }
         if (!dst) dst = (bf16_t *)alloc(sizeof(bf16_t) * rows * cols_pad);
         if (dst) {
-            if (hipMemcpy(tmp, t->data, sizeof(float) * rows * cols, hipMemcpyDefault) != hipSuccess) ok = false;
-            if (ch_convert_bf16(tmp, rows, cols, cols_pad, dst, s) != 0) ok = false;
+            if (hipMemcpy(tmp.as<float>(), t->data, sizeof(float) * rows * cols, hipMemcpyDefault) != hipSuccess) ok = false;
+            if (ch_convert_bf16(tmp.as<float>(), rows, cols, cols_pad, dst, s) != 0) ok = false;
             if (hipStreamSynchronize(s) != hipSuccess) ok = false;
         }
-        (void)hipFree(tmp);
         return dst;
     }
 };
