@@ -75,6 +75,77 @@ def hamming_topk(q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int = 0
     return idx, dist
 
 
+def hamming_topk_masked(q: torch.Tensor, g: torch.Tensor, mask: torch.Tensor, k: int, g_index_base: int = 0,
+                        stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """hamming_topk with dist = popcount((q ^ g) & mask).  mask: int64 [W] (one mask for all queries, e.g. `concept_mask`) or
+    [Qn, W] (one per query, e.g. `confidence_mask`).  Bits of the last word past nbit count unless the codes or the mask clear them
+    (`pack_sign` leaves them zero)."""
+    lib = _lib.load()
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    if mask.dtype != torch.int64 or mask.device != q.device or tuple(mask.shape) not in ((W,), (Qn, W)):
+        raise ValueError(f"mask must be an int64 tensor [{W}] or [{Qn}, {W}] on the queries' device, got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+    mask = mask.contiguous()
+    stride = 0 if mask.dim() == 1 else W
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
+    wsb = int(lib.ch_hamming_topk_workspace(Qn, G, W, k))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    with _dev_guard(q):
+        _lib.check(lib.ch_hamming_topk_masked(_lib.ptr(q), _lib.ptr(mask), stride, Qn, _lib.ptr(g), G, W, k, int(g_index_base),
+                                              _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)),
+                   "ch_hamming_topk_masked")
+    return idx, dist
+
+
+def subcode_dist(q: torch.Tensor, g: torch.Tensor, idx: torch.Tensor, nbit: int, nsub: int, g_index_base: int = 0,
+                 stream=None) -> torch.Tensor:
+    """Per-sub-code distances of retrieved hits: idx [Qn, k] (as returned by hamming_topk / hamming_topk_masked on the same q, g and
+    g_index_base) -> int32 [Qn, k, nsub], entry c = the distance inside bits [c nbit/nsub, (c+1) nbit/nsub); -1 rows where idx is -1.
+    Reads idx back once to check it against the gallery (a synchronisation)."""
+    lib = _lib.load()
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != Qn or idx.device != q.device:
+        raise ValueError(f"idx must be an int64 tensor [{Qn}, k] on the queries' device")
+    idx = idx.contiguous()
+    k = idx.shape[1]
+    out = torch.empty(Qn, k, int(nsub), dtype=torch.int32, device=q.device)
+    with _dev_guard(q):
+        _lib.check(lib.ch_hamming_subcode_dist(_lib.ptr(q), Qn, _lib.ptr(g), g.shape[0], W, _lib.ptr(idx), k, int(g_index_base),
+                                               int(nbit), int(nsub), _lib.ptr(out), _lib.stream_ptr(stream)), "ch_hamming_subcode_dist")
+    return out
+
+
+def concept_mask(nbit: int, ncontext: int, concepts) -> torch.Tensor:
+    """The shared mask [W] int64 (CPU) of a set of concepts: the code is concept-major, concept c owns bits
+    [c nbit/ncontext, (c+1) nbit/ncontext) (models/arch/coop.py, csrc/head.hip).  Host arithmetic only.  An empty set gives the zero
+    mask; a concept outside [0, ncontext) or named twice raises ValueError."""
+    nbit, ncontext = int(nbit), int(ncontext)
+    if nbit < 1 or ncontext < 1 or nbit % ncontext:
+        raise ValueError(f"nbit = {nbit} is not a positive multiple of ncontext = {ncontext}")
+    concepts = [int(c) for c in concepts]
+    if any(c < 0 or c >= ncontext for c in concepts):
+        raise ValueError(f"concepts {concepts} outside [0, {ncontext})")
+    if len(set(concepts)) != len(concepts):
+        raise ValueError(f"concepts {concepts} name a concept twice")
+    sb = nbit // ncontext
+    bits = 0
+    for c in concepts:
+        bits |= ((1 << sb) - 1) << (c * sb)
+    W = (nbit + 63) // 64
+    words = [(bits >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(W)]
+    return torch.tensor([w - (1 << 64) if w >= (1 << 63) else w for w in words], dtype=torch.int64)
+
+
+def confidence_mask(codes: torch.Tensor, margin: float, stream=None) -> torch.Tensor:
+    """[rows, nbit] fp32 codes -> [rows, W] int64: bit i is set iff |codes[:, i]| > margin -- the bits a query is sure of.  Two
+    ch_pack_sign launches (codes > margin, -codes > margin) and an OR; bits past nbit stay zero."""
+    return pack_sign(codes, margin, stream) | pack_sign(-codes, margin, stream)
+
+
 def topk_merge(idx_lists: torch.Tensor, dist_lists: torch.Tensor, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """[nlists, Qn, k] per-shard lists -> global [Qn, k]."""
     lib = _lib.load()

@@ -1,0 +1,168 @@
+"""Search a trained run: a `GalleryIndex` holds the packed database codes of one checkpoint and what is needed to name a hit (labels,
+file paths), and ranks the database for query codes -- by the whole code, by the sub-codes of chosen concepts, by the bits a query
+is sure of, or by both (`retrieval.hamming_topk_masked`), with the per-concept breakdown of every hit (`retrieval.subcode_dist`).
+
+The code is concept-major (models/arch/coop.py, csrc/head.hip): concept c owns bits [c nbit/ncontext, (c+1) nbit/ncontext).
+"""
+from __future__ import annotations
+
+import hashlib
+import os
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import retrieval as rt
+
+FORMAT = 1
+
+
+class StaleIndexError(RuntimeError):
+    """The index file was not encoded with this model: rebuild it."""
+
+
+def checkpoint_fingerprint(path: str) -> dict:
+    """{"file", "size", "sha256"} of a checkpoint file (`models/<best|last>.pth`)."""
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for block in iter(lambda: f.read(1 << 20), b""):
+            h.update(block)
+    return {"file": os.path.basename(path), "size": os.path.getsize(path), "sha256": h.hexdigest()}
+
+
+class GalleryIndex:
+    """codes [G, W] int64 (packed, `retrieval.pack_sign`); nbit, ncontext; labels: None, [G] int64 class ids or [G, C] uint8 indicator
+    rows; paths: None (synthetic datasets) or G paths relative to data_root; mean: None or the database mean [nbit] fp32 that was
+    subtracted before packing (`zero_mean_eval`) and is subtracted from every query; transform: {"resize", "crop", "norm"} of the
+    evaluation chain the database went through; fingerprint: `checkpoint_fingerprint` of the checkpoint that encoded it."""
+
+    def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
+                 paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
+                 transform: Optional[dict] = None, fingerprint: Optional[dict] = None):
+        nbit, ncontext = int(nbit), int(ncontext)
+        if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
+            raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
+        if ncontext < 1 or nbit % ncontext:
+            raise ValueError(f"nbit = {nbit} is not a multiple of ncontext = {ncontext}")
+        G = codes.shape[0]
+        if labels is not None and labels.shape[0] != G:
+            raise ValueError(f"{labels.shape[0]} labels for {G} codes")
+        if paths is not None and len(paths) != G:
+            raise ValueError(f"{len(paths)} paths for {G} codes")
+        if mean is not None and tuple(mean.shape) != (nbit,):
+            raise ValueError(f"mean must be [{nbit}], got {tuple(mean.shape)}")
+        self.codes, self.nbit, self.ncontext = codes.contiguous(), nbit, ncontext
+        self.labels = labels
+        self.paths = [str(p) for p in paths] if paths is not None else None
+        self.data_root = str(data_root) if data_root is not None else None
+        self.mean = mean.to(torch.float32) if mean is not None else None
+        self.transform = dict(transform or {})
+        self.fingerprint = dict(fingerprint or {})
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    def to(self, device) -> "GalleryIndex":
+        mv = lambda t: t.to(device) if t is not None else None
+        return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
+                            self.transform, self.fingerprint)
+
+    # ---- file --------------------------------------------------------------------------------------------------------------------
+    def save(self, path: str) -> None:
+        """One torch.save file of CPU tensors and plain Python values (layout: INTEGRATION.md, "Index file")."""
+        cpu = lambda t: t.detach().cpu() if t is not None else None
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        tmp = f"{path}.tmp{os.getpid()}"
+        torch.save({"format": FORMAT, "codes": cpu(self.codes), "nbit": self.nbit, "ncontext": self.ncontext, "labels": cpu(self.labels),
+                    "paths": self.paths, "data_root": self.data_root, "mean": cpu(self.mean), "transform": self.transform,
+                    "fingerprint": self.fingerprint}, tmp)
+        os.replace(tmp, path)
+
+    def check(self, fingerprint: Optional[dict] = None, nbit: Optional[int] = None, source: str = "the index") -> None:
+        """Raises StaleIndexError unless the index was encoded with the checkpoint `fingerprint` and holds `nbit`-bit codes."""
+        if nbit is not None and int(nbit) != self.nbit:
+            raise StaleIndexError(f"{source} holds {self.nbit}-bit codes but the model produces {int(nbit)}-bit codes: rebuild the index "
+                                  f"(rebuild_index=true)")
+        if fingerprint is not None:
+            mine = {k: self.fingerprint.get(k) for k in ("size", "sha256")}
+            theirs = {k: fingerprint.get(k) for k in ("size", "sha256")}
+            if mine != theirs:
+                raise StaleIndexError(f"{source} was encoded with another checkpoint (fingerprint {mine} != {theirs}): rebuild the index "
+                                      f"(rebuild_index=true)")
+
+    @classmethod
+    def load(cls, path: str, fingerprint: Optional[dict] = None, nbit: Optional[int] = None) -> "GalleryIndex":
+        """The index of `save`, on the CPU; with `fingerprint` / `nbit` given, `check`ed against them."""
+        d = torch.load(path, map_location="cpu")
+        if not isinstance(d, dict) or d.get("format") != FORMAT:
+            raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
+        index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
+                    d["fingerprint"])
+        index.check(fingerprint, nbit, source=path)
+        return index
+
+    # ---- search ------------------------------------------------------------------------------------------------------------------
+    def resolve(self, rel: Optional[str]) -> Optional[str]:
+        """A hit's path as a file name: a relative path is looked up as the list-file datasets look it up (as it stands, under
+        data_root, under the directory two levels above data_root) and taken under data_root when no such file exists."""
+        if rel is None:
+            return None
+        if os.path.isabs(rel) or self.data_root is None:
+            return rel
+        for cand in (rel, os.path.join(self.data_root, rel), os.path.join(os.path.dirname(os.path.dirname(self.data_root)), rel)):
+            if os.path.exists(cand):
+                return cand
+        return os.path.join(self.data_root, rel)
+
+    def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0) -> dict:
+        """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here).
+        Ranks the database by ascending (distance, index) and returns
+          idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
+          concept_dist [Qn, k, ncontext] int32: the UNMASKED distance inside every concept's sub-code (they sum to the whole-code
+            distance whatever the mask, so for a hit ranked by concepts 0 and 2 they still say how far the other concepts are);
+          bits [Qn] int64: the number of unmasked bits of each query;
+          labels: None or the hits' labels [Qn, k(, C)] (class id -1 / zero rows where idx is -1); paths: None or Qn lists of k paths.
+        concepts: rank by these concepts' sub-codes only (one mask shared by all queries).  margin > 0: every query ignores its own
+        bits with |code| <= margin.  Both: the per-query mask is the AND of the two.  Neither: the unmasked scan."""
+        dev = self.device
+        codes = query_codes.to(dev, torch.float32)
+        if codes.dim() != 2 or codes.shape[1] != self.nbit:
+            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
+        if self.mean is not None:
+            codes = codes - self.mean[None, :]
+        Qn, k = codes.shape[0], int(k)
+        q = rt.pack_sign(codes)
+        keep = torch.ones(self.nbit, dtype=torch.bool, device=dev)
+        mask = None
+        if concepts is not None:
+            shared = rt.concept_mask(self.nbit, self.ncontext, concepts)
+            sb = self.nbit // self.ncontext
+            keep = torch.zeros(self.nbit, dtype=torch.bool, device=dev)
+            for c in concepts:
+                keep[int(c) * sb:(int(c) + 1) * sb] = True
+            mask = shared.to(dev)
+        keep = keep[None, :].expand(Qn, self.nbit)
+        if margin > 0:
+            conf = rt.confidence_mask(codes, float(margin))
+            mask = conf if mask is None else conf & mask[None, :]
+            keep = keep & (codes.abs() > float(margin))
+        if mask is None:
+            idx, dist = rt.hamming_topk(q, self.codes, k)
+        else:
+            idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
+        out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
+                   bits=keep.sum(1), labels=None, paths=None)
+        if self.labels is not None:
+            lab = self.labels[idx.clamp_min(0)]
+            miss = idx < 0
+            out["labels"] = lab.masked_fill(miss, -1) if lab.dim() == 2 else lab.masked_fill(miss[..., None], 0)
+        if self.paths is not None:
+            rows: List[List[Optional[str]]] = []
+            for hits in idx.tolist():
+                rows.append([self.paths[i] if i >= 0 else None for i in hits])
+            out["paths"] = rows
+        return out

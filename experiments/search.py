@@ -1,0 +1,254 @@
+"""`exp=search`: image queries -> ranked database hits of a finished run, optionally by chosen concepts.
+
+    python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [concepts=[0,2]]
+        [query_margin=0.0] [index=<file>] [rebuild_index=false] [save_attention=false]
+
+The run's config and checkpoint are loaded exactly as `exp=validation` loads them.  The database split is encoded once
+(`trainer.inference_one_epoch("db", True)`) into a `concepthash_amd.search.GalleryIndex` file -- `<logdir>/index_<best|last>.pth` unless
+`index=` names another -- and later invocations load that file instead of reading the database images, as long as its checkpoint
+fingerprint and code length still match.  `query` is a split of the dataset (`test`, `db`), a directory of image files (sorted by name,
+not recursive, no labels), a list file in the dataset's own format, or one image file; queries go through the evaluation transform
+chain of the dataset config and the evaluation loader.  Output: `<search_logdir>/results.json` (schema: INTEGRATION.md, "Search
+results") and, with `save_attention=true`, `concept_attention.npy` [Nq, Q, gh, gw] fp32 -- the head mean of the last layer's
+concept-token attention over the patch grid.
+"""
+from __future__ import annotations
+
+import copy
+import json
+import math
+import os
+import time
+
+import numpy as np
+import torch
+import yaml
+
+import engine
+from concepthash_amd import retrieval as rt
+from concepthash_amd.config import DictConfig, instantiate, to_container
+from concepthash_amd.search import GalleryIndex, StaleIndexError, checkpoint_fingerprint
+
+IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".webp", ".ppm", ".tif", ".tiff", ".gif")
+SPLITS = ("test", "db")
+PRINT_QUERIES = 3
+
+
+def _label_ids(labels: torch.Tensor):
+    """[N, C] indicator rows -> [N] int64 class ids when every row names exactly one class, else uint8 indicator rows; 1-D ids pass"""
+    if labels.dim() == 1:
+        return labels.to(torch.int64)
+    hot = labels != 0
+    if bool((hot.sum(1) == 1).all()):
+        return hot.int().argmax(1).to(torch.int64)
+    return hot.to(torch.uint8)
+
+
+class SearchExperiment:
+    def __init__(self, config: DictConfig):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError("exp=search under a multi-rank process group is not built: a query tool gains nothing from sharding; "
+                                      "run it as a single process")
+        self.start_time = time.time()
+        engine.seeding(config["seed"])
+        self.config = config
+        self.timing = {}
+        logdir = config.logdir
+        modelfn = "last" if config.get("use_last") else "best"
+        self.checkpoint = f"{logdir}/models/{modelfn}.pth"
+        self.index_path = str(config.get("index") or os.path.join(logdir, f"index_{modelfn}.pth"))
+        self.search_logdir = str(config.search_logdir)
+        os.makedirs(self.search_logdir, exist_ok=True)
+        with open(os.path.join(self.search_logdir, "search_config.yaml"), "w") as f:
+            yaml.safe_dump(to_container(config), f)
+        self.query = str(config.get("query", "test"))
+        self.nbit, self.ncontext = int(config.model.nbit), int(config.model.ncontext)
+
+        # the index first: whether the database split has to be encoded decides what is loaded
+        self.fingerprint = self._phase("fingerprint", checkpoint_fingerprint, self.checkpoint)
+        self.index, self.index_note = None, "built: no index file"
+        if config.get("rebuild_index"):
+            self.index_note = "built: rebuild_index"
+        elif os.path.exists(self.index_path):
+            try:
+                self.index = self._phase("index_load", GalleryIndex.load, self.index_path, self.fingerprint, self.nbit)
+                self._check_index_settings(self.index)
+                self.index_note = "loaded"
+            except StaleIndexError as e:
+                print(f"Stale index: {e}")
+                self.index, self.index_note = None, f"built: stale index ({e})"
+
+        trainer = instantiate(config.trainer, config)
+        self._phase("datasets", trainer.load_dataset, load_db=self.index is None or self.query == "db")
+        self._phase("loaders", trainer.load_dataloader)
+        trainer.load_for_inference(logdir)
+        self._phase("model_build", trainer.load_model)
+        trainer.load_criterion()
+        self._phase("checkpoint", trainer.load_model_state, self.checkpoint)
+        self._phase("to_device", trainer.to_device)
+        self.trainer = trainer
+
+    def _phase(self, name, fn, *a, **k):
+        t0 = time.perf_counter()
+        out = fn(*a, **k)
+        self.timing[name] = round(self.timing.get(name, 0.0) + time.perf_counter() - t0, 3)
+        return out
+
+    # ---- index -------------------------------------------------------------------------------------------------------------------
+    def _transform_settings(self):
+        ds = self.config.dataset
+        return {"resize": int(ds.get("resize", 256)), "crop": int(ds.get("crop", 224)), "norm": int(ds.get("norm", 3))}
+
+    def _check_index_settings(self, index: GalleryIndex):
+        """what the fingerprint does not cover: the code layout, the evaluation transform and the zero-mean switch of THIS invocation"""
+        want_mean = bool(self.config.get("zero_mean_eval"))
+        if index.ncontext != self.ncontext or index.transform != self._transform_settings() or (index.mean is not None) != want_mean:
+            raise StaleIndexError(f"{self.index_path} was built with ncontext = {index.ncontext}, transform {index.transform}, "
+                                  f"zero_mean_eval = {index.mean is not None}; this run asks for ncontext = {self.ncontext}, "
+                                  f"{self._transform_settings()}, zero_mean_eval = {want_mean}: rebuild the index (rebuild_index=true)")
+
+    def _build_index(self) -> GalleryIndex:
+        _, out = self._phase("encode_db", self.trainer.inference_one_epoch, "db", True)
+        codes = out["codes"].to(torch.float32)
+        mean = None
+        if self.config.get("zero_mean_eval"):         # the database mean, applied to both sets (experiments/test_hashing.py)
+            mean = codes.mean(dim=0, keepdim=True)
+            codes = codes - mean
+            mean = mean[0]
+        ds = self.trainer.dataset["db"]
+        items = getattr(ds, "items", None)             # list-file datasets name their files; the synthetic ones have none
+        index = GalleryIndex(rt.pack_sign(codes.to(self.trainer.device)), self.nbit, self.ncontext, labels=_label_ids(out["labels"]),
+                             paths=[p for p, _ in items] if items is not None else None,
+                             data_root=getattr(ds, "root", None) if items is not None else None, mean=mean,
+                             transform=self._transform_settings(), fingerprint=self.fingerprint)
+        self._phase("index_save", index.save, self.index_path)
+        return index
+
+    # ---- queries -----------------------------------------------------------------------------------------------------------------
+    def _path_dataset(self, items, labelled, root=None):
+        """The test split's dataset node -- its evaluation transform list and GPU data path -- over other files"""
+        node = copy.deepcopy(self.config.dataset.test_dataset)
+        if str(node.get("_target_", "")) != "utils.datasets.HashingDataset":
+            raise ValueError(f"query='{self.query}' names image files, but dataset '{self.config.get('dataset_name', '')}' is not a list-file "
+                             f"image dataset ({node.get('_target_')}); its queries are the splits {SPLITS}")
+        if root is not None:
+            node["root"] = root
+        if not labelled:
+            node["target_transform"] = None
+        return instantiate(node, items=items)
+
+    def _query_loader(self):
+        """-> (loader, names of the queries or None, whether they carry labels)"""
+        q = self.query
+        if q in SPLITS:
+            ds = self.trainer.dataset[q]
+            items = getattr(ds, "items", None)
+            return self.trainer.dataloader[q], ([p for p, _ in items] if items is not None else None), True
+        if os.path.isdir(q):
+            files = sorted(f for f in os.listdir(q) if f.lower().endswith(IMAGE_EXTENSIONS) and os.path.isfile(os.path.join(q, f)))
+            if not files:
+                raise ValueError(f"query directory {q} holds no image file ({', '.join(IMAGE_EXTENSIONS)})")
+            names = [os.path.join(os.path.abspath(q), f) for f in files]
+            ds = self._path_dataset([(p, -1) for p in names], labelled=False)
+            labelled = False
+        elif os.path.isfile(q) and q.lower().endswith(IMAGE_EXTENSIONS):
+            names = [os.path.abspath(q)]
+            ds = self._path_dataset([(names[0], -1)], labelled=False)
+            labelled = False
+        elif os.path.isfile(q):
+            from utils.datasets import read_list
+            items = read_list(q)
+            if not items:
+                raise ValueError(f"query list file {q} is empty")
+            names = [p for p, _ in items]
+            ds = self._path_dataset(items, labelled=True)
+            labelled = True
+        else:
+            raise ValueError(f"query='{q}' is neither a split ({', '.join(SPLITS)}) nor an existing directory, list file or image file")
+        bs = self.config.batch_size
+        if getattr(ds, "gpu_decode", False) and not getattr(ds, "file_workers", 0):
+            bs = max(bs, int(self.config.get("eval_batch_min", 256) or 0))
+        return engine.dataloader(ds, bs, shuffle=False, drop_last=False), names, labelled
+
+    def _encode_queries(self, loader, want_attention):
+        tr = self.trainer
+        tr.model.eval()
+        tr.criterion.eval()
+        before = getattr(tr.model, "return_concept_attention", False)
+        if want_attention:
+            tr.model.return_concept_attention = True
+        codes, labels, attn = [], [], []
+        try:
+            for data in tr.iterate_loader(loader):
+                with torch.no_grad():
+                    (_, lab, _), out = tr.compute_features_one_batch(data)
+                codes.append(out["codes"])
+                labels.append(lab)
+                if want_attention:
+                    a = out["concept_attention"].to(torch.float32).mean(1)          # [B, heads, Q, Np] -> head mean
+                    side = math.isqrt(a.shape[-1])
+                    if side * side != a.shape[-1]:
+                        raise RuntimeError(f"concept attention over {a.shape[-1]} patches is not a square grid")
+                    attn.append(a.reshape(a.shape[0], a.shape[1], side, side))
+        finally:
+            tr.model.return_concept_attention = before
+        return torch.cat(codes), torch.cat(labels), (torch.cat(attn) if attn else None)
+
+    # ---- main --------------------------------------------------------------------------------------------------------------------
+    def main(self):
+        cfg = self.config
+        k = int(cfg.get("k", 10))
+        concepts = cfg.get("concepts")
+        concepts = [int(c) for c in concepts] if concepts is not None else None
+        margin = float(cfg.get("query_margin", 0.0) or 0.0)
+        print("Search Start")
+        index = self.index if self.index is not None else self._build_index()
+        index = index.to(self.trainer.device)
+        loader, names, labelled = self._query_loader()
+        q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
+        res = self._phase("search", index.search, q_codes, k, concepts, margin)
+        t0 = time.perf_counter()
+        q_ids = _label_ids(q_labels.cpu()) if labelled else None
+        idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
+        bits = res["bits"].tolist()
+        hit_labels = res["labels"].cpu() if res["labels"] is not None else None
+        queries = []
+        for i in range(len(idx)):
+            ql = q_ids[i] if q_ids is not None else None
+            hits = []
+            for r in range(k):
+                if idx[i][r] < 0:
+                    break
+                hl = hit_labels[i, r] if hit_labels is not None else None
+                relevant = None
+                if ql is not None and hl is not None and ql.dim() == hl.dim():
+                    relevant = bool(ql == hl) if hl.dim() == 0 else bool((ql & hl).any())
+                rel_path = res["paths"][i][r] if res["paths"] is not None else None
+                hits.append({"rank": r + 1, "index": idx[i][r], "path": index.resolve(rel_path), "distance": dist[i][r],
+                             "label": hl.tolist() if hl is not None else None, "relevant": relevant, "concept_distances": cdist[i][r]})
+            queries.append({"query": names[i] if names is not None else i, "label": ql.tolist() if ql is not None else None,
+                            "unmasked_bits": bits[i], "hits": hits})
+        self.timing["results"] = round(time.perf_counter() - t0, 3)
+        out = {"k": k, "concepts": concepts, "query_margin": margin, "nbit": index.nbit, "ncontext": index.ncontext,
+               "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
+               "checkpoint": self.fingerprint, "query": self.query, "queries": queries,
+               "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
+        with open(os.path.join(self.search_logdir, "results.json"), "w") as f:
+            json.dump(out, f)
+        if attn is not None:
+            np.save(os.path.join(self.search_logdir, "concept_attention.npy"), attn.cpu().numpy().astype(np.float32))
+        what = "the whole code" if concepts is None else f"concepts {concepts}"
+        print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}" +
+              (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + f"; index {self.index_note}")
+        for e in queries[:PRINT_QUERIES]:
+            print(f"query {e['query']}" + (f" (label {e['label']})" if e["label"] is not None and not isinstance(e["label"], list) else "") +
+                  f": {e['unmasked_bits']} bits")
+            for h in e["hits"]:
+                mark = "" if h["relevant"] is None else (" +" if h["relevant"] else " -")
+                print(f"  {h['rank']:3d}. d={h['distance']:3d} per concept {h['concept_distances']}  #{h['index']}" +
+                      (f" {h['path']}" if h["path"] else "") + mark)
+        print("Phases (s): " + ", ".join(f"{n} {v:.2f}" for n, v in self.timing.items()))
+        print(f"Done: {self.search_logdir}")
+        self.results = out
+        return out

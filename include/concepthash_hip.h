@@ -375,6 +375,24 @@ int ch_hamming_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G,
                     int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* ch_hamming_topk with a bit mask: dist = popcount((q xor g) and mask), everything else -- ranking by ascending (distance, gallery
+ * index), the -1 fill, g_index_base, 1 <= k <= 128, 1 <= W <= 4 and the workspace (ch_hamming_topk_workspace() bytes) -- as above.
+ * mask_stride == W: q_mask is [Qn,W], one mask per query (e.g. the bits a query is confident of); mask_stride == 0: q_mask is [W],
+ * shared by all queries (e.g. the sub-codes of chosen concepts).  Any other stride, or a NULL q_mask, is status 2.  Bits of the
+ * last word past nbit must be zero in the codes or in the mask. */
+int ch_hamming_topk_masked(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g, int64_t G,
+                           int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/* Per-sub-code distances of retrieved hits: idx [Qn,k] int64 as written by ch_hamming_topk(_masked) / ch_topk_merge (global index =
+ * gallery row + g_index_base, -1 = absent).  The code's first nbit bits are nsub equal sub-codes of nbit / nsub bits (sub-code c =
+ * bits [c nbit/nsub, (c+1) nbit/nsub); it may straddle a 64-bit word); out [Qn,k,nsub] int32 = popcount of q xor g inside each, -1 in
+ * all nsub slots of an absent hit.  nsub must divide nbit, nbit <= 64 W, 1 <= W <= 4.  The indices are checked on the host before
+ * any row is read (one device-to-host copy of idx and a stream synchronisation): an index outside [g_index_base, g_index_base + G)
+ * other than -1 is status 2 and nothing is launched. */
+int ch_hamming_subcode_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, const int64_t *idx, int32_t k,
+                            int64_t g_index_base, int32_t nbit, int32_t nsub, int32_t *out, void *stream);
+
 /* Merge nlists per-shard top-k lists ([nlists,Qn,k] each sorted ascending by (dist, idx); -1 entries = absent)
  * into the global top-k [Qn,k]. */
 int ch_topk_merge(const int64_t *idx_lists, const int32_t *dist_lists, int32_t nlists, int64_t Qn, int32_t k,

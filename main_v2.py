@@ -3,9 +3,11 @@
 
     python main_v2.py --config-name val.yaml logdir=<run dir> dataset=cub200 [R=-1] [PRs=[1,5,10]] [batch_size=64] ...
     python main_v2.py exp=extract model=concept_hash_final_v1_nosa_apt dataset=synthetic_cub200 ...
+    python main_v2.py --config-name search.yaml logdir=<run dir> dataset=cub200 [query=test] [k=10] [concepts=[0,2]] ...
 
 `exp` dispatch: hashing -> RetrievalExperiment (train the adapters + hashing head, frozen backbone); validation -> load
-<logdir>/config.yaml, overlay the evaluation knobs, RetrievalEvaluation; descriptor / extract -> RetrievalEvaluation on the
+<logdir>/config.yaml, overlay the evaluation knobs, RetrievalEvaluation; search -> the same run config, SearchExperiment (ranked hits of
+image queries, experiments/search.py); descriptor / extract -> RetrievalEvaluation on the
 composed config; general (the reference's train-without-eval variant) is not built.  Uses Hydra when it is installed; otherwise `concepthash_amd.config` composes the same YAML
 tree (hydra-core / omegaconf are absent from the target image).
 """
@@ -28,7 +30,26 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket")
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval")
+# exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
+SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
+               "query_margin", "index", "rebuild_index", "save_attention")
+
+
+def _run_config(config, exp, keys):
+    """<logdir>/config.yaml of a finished run with this invocation's `keys` (and the loop knobs) laid over it (reference main_v2.py:23-40)"""
+    load_config = cfglib.load(os.path.join(config.logdir, "config.yaml"))
+    for k in keys:
+        load_config[k] = config[k]
+    for k in LOOP_KEYS:
+        if k in config:
+            load_config[k] = config[k]
+    load_config["logdir"] = config.logdir if os.path.isabs(str(config.logdir)) else f"{config.work_dir}/{config.logdir}"
+    load_config["wandb"] = False
+    load_config["exp"] = exp
+    load_config["seed"] = config.get("seed", load_config.get("seed", 42))
+    load_config["device"] = config.get("device", "cuda")
+    return load_config
 
 
 def run(config):
@@ -40,20 +61,15 @@ def run(config):
         from experiments.train_helper import RetrievalExperiment
         return RetrievalExperiment(config).main()
     if config.exp == "validation":
-        load_config = cfglib.load(os.path.join(config.logdir, "config.yaml"))
-        for k in EVAL_KEYS:                      # reference main_v2.py:23-40
-            load_config[k] = config[k]
-        for k in LOOP_KEYS:
-            if k in config:
-                load_config[k] = config[k]
-        load_config["logdir"] = config.logdir if os.path.isabs(str(config.logdir)) else f"{config.work_dir}/{config.logdir}"
-        load_config["wandb"] = False
-        load_config["exp"] = "validation"
-        load_config["seed"] = config.get("seed", load_config.get("seed", 42))
-        load_config["device"] = config.get("device", "cuda")
+        load_config = _run_config(config, "validation", EVAL_KEYS)
         if load_config.get("tie_bracket"):      # the evaluator + the mAP bracket over tie orders
             from experiments.tie_bracket_eval import TieBracketEvaluation as RetrievalEvaluation
+        if load_config.get("concept_eval"):     # ... + the per-concept table (it extends the tie-bracket evaluator)
+            from experiments.concept_eval import ConceptEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
+    elif config.exp == "search":
+        from experiments.search import SearchExperiment
+        experiment = SearchExperiment(_run_config(config, "search", SEARCH_KEYS))
     elif config.exp in ("descriptor", "extract"):
         experiment = RetrievalEvaluation(config)
     else:

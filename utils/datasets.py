@@ -216,7 +216,7 @@ class HashingDataset(Dataset):
     ToTensor -> normalize on the GPU (`concepthash_amd.preprocess.GpuPreprocess`, bit-equal to the CPU chain)."""
 
     def __init__(self, root, filename="train.txt", transform=None, target_transform=None, num_classes=None, num_shots=0,
-                 separate_multiclass=False, gpu_preprocess=False, gpu_decode=False, **kwargs):
+                 separate_multiclass=False, gpu_preprocess=False, gpu_decode=False, items=None, **kwargs):
         from utils.transforms import Compose
         self.gpu_decode = bool(gpu_decode)
         self.gpu_preprocess = bool(gpu_preprocess) or self.gpu_decode
@@ -225,7 +225,8 @@ class HashingDataset(Dataset):
         elif self.gpu_preprocess:
             self.collate_fn = raw_collate
         self.root = root
-        self.items = read_list(os.path.join(root, filename))
+        # items: the (path, label) pairs themselves instead of a list file (experiments/search.py: a directory of query images)
+        self.items = [(str(p), int(lab)) for p, lab in items] if items is not None else read_list(os.path.join(root, filename))
         if num_shots:
             per, keep = {}, []
             for it in self.items:
