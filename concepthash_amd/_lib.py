@@ -100,6 +100,10 @@ SIGNATURES = {
                                 c_void_p, c_size_t, c_void_p]),
     "ch_hamming_topk_masked": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ch_weight_planes": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ch_hamming_topk_weighted_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_hamming_topk_weighted": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "ch_hamming_subcode_dist": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32,
                                         c_void_p, c_void_p]),
     "ch_topk_merge": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libconcepthash_hip.so")
-SOURCES = ["model.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_r4.hip", "attention.hip", "rowops.hip", "head.hip", "small_f32.hip", "hamming.hip",
+SOURCES = ["model.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_r4.hip", "attention.hip", "rowops.hip", "head.hip", "small_f32.hip", "hamming.hip", "hamming_weighted.hip",
            "preprocess.hip", "augment.hip", "train_kernels.hip", "attention_bwd.hip", "attention_stream.hip", "train.hip", "text_model.hip", "debug_taps.hip", "jpeg.hip", "jpeg_host.cpp", "errors.cpp"]
 # plain C++ sources (no HIP): compiled by the same driver as host code; tests/test_jpeg.py also builds them with g++ -fsanitize=address,undefined
 HOST_SOURCES = ["jpeg_host.cpp", "errors.cpp"]
@@ -18,7 +18,7 @@ HOST_SOURCES = ["jpeg_host.cpp", "errors.cpp"]
 # only into an experiments build (CH_BUILD_EXPERIMENTS=1), never into the product library
 EXPERIMENT_SOURCES = [os.path.join("experiments", f) for f in ("gemm_pq.hip", "gemm_ppp.hip", "gemm_dp.hip",
                                                                 "adapter_fused.hip", "gemm_rows.hip", "gemm_wide.hip")]
-HEADERS = ["ch_common.h", "ch_host.h", "kernels.h", "gemm_epilogue.h", "model_internal.h", "weight_builder.h", "device_owner.h", os.path.join("..", "..", "include", "concepthash_hip.h"),
+HEADERS = ["ch_common.h", "ch_host.h", "kernels.h", "gemm_epilogue.h", "model_internal.h", "weight_builder.h", "device_owner.h", "hamming_shared.h", os.path.join("..", "..", "include", "concepthash_hip.h"),
            os.path.join("..", "..", "include", "concepthash_hip_debug.h")]
 # attention post-processes every MFMA result on the VALU: keep accumulators in VGPRs (no v_accvgpr_read round trips)
 # preprocess / augment reproduce Pillow's double-precision filter coefficients (and its samplers) bit for bit: no fused multiply-adds there

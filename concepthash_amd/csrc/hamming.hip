@@ -24,6 +24,7 @@
 #include "../../include/concepthash_hip.h"
 #include "../../include/concepthash_hip_debug.h"
 #include "ch_common.h"
+#include "hamming_shared.h"
 #include "kernels.h"
 
 // test tap (include/concepthash_hip_debug.h): 1 = the mAP passes take the gallery through scalar loads instead of VMEM blocks + DPP
@@ -35,14 +36,7 @@ namespace {
 constexpr int KEY_SHIFT = 23;
 constexpr uint32_t KEY_MASK = (1u << KEY_SHIFT) - 1;
 
-// The scan is VALU-issue bound, so its inner loop is written down to the instruction:
-// v_bcnt_u32_b32 d, x, acc = popcount(x) + acc: chaining the accumulate operand keeps a distance at 2 instructions per 32-bit
-// word (left to itself the compiler re-associates into separate counts + v_add3: one more instruction per row);
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t d;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(d) : "v"(x), "v"(acc));
-    return d;
-}
+// bcnt_acc, the chained popcount of every distance below: hamming_shared.h
 // Two words of a distance against gallery words held by lane K of the lane's own row of 16 lanes: the broadcast is the DPP operand
 // of the xor (`row_newbcast:K`), so it costs no instruction.  Written as one asm block because of the DPP read hazard (a VGPR
 // written by a VALU instruction must not be read by a DPP instruction within the next two): the temporaries are distinct
@@ -98,16 +92,6 @@ __device__ __forceinline__ int hamming_masked(const uint32_t (&q)[2 * W], const 
         d = bcnt_acc((q[2 * w + 1] ^ (uint32_t)(gw >> 32)) & m[2 * w + 1], d);
     }
     return (int)d;
-}
-
-template <int W>
-__device__ __forceinline__ void load_query(uint32_t (&q)[2 * W], const uint64_t *qp, int64_t qi, int64_t Qn) {
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const uint64_t v = qi < Qn ? qp[qi * W + w] : 0ull;
-        q[2 * w] = (uint32_t)v;
-        q[2 * w + 1] = (uint32_t)(v >> 32);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -214,51 +198,7 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__res
     }
 }
 
-// one wave per query: repeatedly extract the smallest composite (dist, global row) above the previous one
-__global__ __launch_bounds__(256) void topk_merge_keys_kernel(const uint32_t *__restrict__ part, int nseg, int64_t Qn, int k,
-                                                              int seg_rows, int64_t g_index_base, int64_t *out_idx,
-                                                              int32_t *out_dist) {
-    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (qi >= Qn) return;
-    const int ncand = nseg * k;
-    unsigned long long prev = 0ull;  // composite + 1 of the last output (0 = none yet)
-    for (int r = 0; r < k; ++r) {
-        unsigned long long best = ~0ull;
-        for (int c = lane; c < ncand; c += 64) {
-            const int s = c / k, i = c - s * k;
-            const uint32_t key = part[((size_t)s * Qn + qi) * k + i];
-            if (key == 0xFFFFFFFFu) continue;
-            const unsigned long long comp =
-                ((unsigned long long)(key >> KEY_SHIFT) << 40) | ((unsigned long long)s * seg_rows + (key & KEY_MASK));
-            if (comp + 1 > prev && comp < best) best = comp;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(best, o, 64);
-            best = other < best ? other : best;
-        }
-        if (lane == 0) {
-            if (best == ~0ull) {
-                out_idx[qi * k + r] = -1;
-                out_dist[qi * k + r] = -1;
-            } else {
-                out_idx[qi * k + r] = g_index_base + (int64_t)(best & ((1ull << 40) - 1));
-                out_dist[qi * k + r] = (int32_t)(best >> 40);
-            }
-        }
-        if (best == ~0ull) {
-            // nothing left: fill the rest
-            for (int rr = r + 1; rr < k; ++rr)
-                if (lane == 0) {
-                    out_idx[qi * k + rr] = -1;
-                    out_dist[qi * k + rr] = -1;
-                }
-            return;
-        }
-        prev = best + 1;
-    }
-}
+// topk_merge_keys_kernel<KEY_SHIFT>, the merge of the per-segment key lists: hamming_shared.h
 
 // merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
 __global__ __launch_bounds__(256) void topk_merge_lists_kernel(const int64_t *__restrict__ idx_lists,
@@ -1072,22 +1012,10 @@ bool fill_limits(const int64_t *rank_limits, int nlimits, RankLimits &lims) {
 }
 
 int topk_seg_rows(int64_t Qn, int64_t G, int k) {
-    // (tile, segment) workgroups for ONE full round and never a few more: the scan kernel has no LDS, so residency is set by its
-    // registers -- 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four waves per CU), 68-74 for 32 (7), ~136 for 64 (3),
-    // the whole file for 128 (1).  ceil(2048 / tiles) segments put 2,134 workgroups on the 2,048 slots at the NABirds size
-    // (97 tiles): a second round for 86 of them doubled the launch (0.38 -> 0.2 ms).  Segments not shorter than 256 rows.
+    // the scan kernel has no LDS, so residency is set by its registers -- 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four
+    // waves per CU), 68-74 for 32 (7), ~136 for 64 (3), the whole file for 128 (1); the rest of the rule: topk_seg_rows_for
     const int per_cu = k <= 16 ? 8 : k <= 32 ? 7 : k <= 64 ? 3 : 1;
-    const int64_t slots = 256 * per_cu;
-    const int64_t tiles = ceil_div64(Qn, 256);
-    int64_t nseg = std::max<int64_t>(1, slots / tiles);
-    // ... and not more segments than needed: every segment starts with empty lists, so its first ~640 rows run the insertion
-    // network for some lane of the wave almost every row, and the merge cost grows with the segment count -- segments of >= 4,096
-    // rows as long as two workgroups per CU remain (NABirds size: 6 segments instead of 21, 0.45 -> 0.37 ms; the 1M-row scan keeps 32)
-    nseg = std::min(nseg, std::max<int64_t>(std::max<int64_t>(1, ceil_div64(512, tiles)), G / 4096));
-    int64_t rows = ceil_div64(G, nseg);
-    if (rows < 256) rows = 256;
-    if (rows > (int64_t)KEY_MASK) rows = KEY_MASK;
-    return (int)rows;
+    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)KEY_MASK);
 }
 
 template <int W, int KREG, bool MASKED>
@@ -1127,7 +1055,7 @@ int topk_run(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W,
         default: e = topk_dispatch_k<4>(q, Qn, g, G, seg_rows, k, part, qm, s); break;
     }
     if (e) return e;
-    hipLaunchKernelGGL(topk_merge_keys_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, nseg, Qn, k, seg_rows,
+    hipLaunchKernelGGL(topk_merge_keys_kernel<KEY_SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, nseg, Qn, k, seg_rows,
                        g_index_base, out_idx, out_dist);
     CH_LAUNCH_CHECK();
     return 0;

@@ -100,6 +100,61 @@ def hamming_topk_masked(q: torch.Tensor, g: torch.Tensor, mask: torch.Tensor, k:
     return idx, dist
 
 
+WEIGHT_BITS = (4, 8)
+
+
+def weight_planes(codes: torch.Tensor, bits: int = 8, mask: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The query side of the weighted (asymmetric) distance: [Qn, nbit] fp32 codes -> (planes int64 [Qn, bits, W], wsum int32 [Qn]).
+    w = floor(|code| L / max|code| + 0.5) per query, L = 2^bits - 1, evaluated in fp64; |code| counts as 0 where it is not finite or
+    the mask clears the bit (mask: int64 [W] or [Qn, W], as `hamming_topk_masked` takes); bit b of planes[i, p, w] is bit p of the
+    weight of code bit 64 w + b; wsum is the sum of a query's weights = the largest distance it can reach."""
+    lib = _lib.load()
+    if codes.dim() != 2:
+        raise ValueError("codes must be 2-D")
+    if int(bits) not in WEIGHT_BITS:
+        raise ValueError(f"weight bits must be one of {WEIGHT_BITS}, got {bits}")
+    codes = codes.to(torch.float32).contiguous()
+    Qn, nbit = codes.shape
+    W = (nbit + 63) // 64
+    stride = 0
+    if mask is not None:
+        if mask.dtype != torch.int64 or mask.device != codes.device or tuple(mask.shape) not in ((W,), (Qn, W)):
+            raise ValueError(f"mask must be an int64 tensor [{W}] or [{Qn}, {W}] on the codes' device, got {mask.dtype} "
+                             f"{tuple(mask.shape)} on {mask.device}")
+        mask = mask.contiguous()
+        stride = 0 if mask.dim() == 1 else W
+    planes = torch.empty(Qn, int(bits), W, dtype=torch.int64, device=codes.device)
+    wsum = torch.empty(Qn, dtype=torch.int32, device=codes.device)
+    with _dev_guard(codes):
+        _lib.check(lib.ch_weight_planes(_lib.ptr(codes), Qn, nbit, _lib.ptr(mask), stride, int(bits), _lib.ptr(planes), _lib.ptr(wsum),
+                                        _lib.stream_ptr(stream)), "ch_weight_planes")
+    return planes, wsum
+
+
+def hamming_topk_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int = 0,
+                          stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """hamming_topk with dist = sum_p 2^p popcount((q ^ g) & planes[:, p]): the weighted distance of `weight_planes(codes)` with
+    q = pack_sign(codes).  Lists of gallery shards merge with `topk_merge` as the unweighted ones do."""
+    lib = _lib.load()
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    if planes.dtype != torch.int64 or planes.device != q.device or planes.dim() != 3 or planes.shape[0] != Qn or planes.shape[2] != W \
+            or planes.shape[1] not in WEIGHT_BITS:
+        raise ValueError(f"planes must be an int64 tensor [{Qn}, 4 or 8, {W}] on the queries' device, got {planes.dtype} "
+                         f"{tuple(planes.shape)} on {planes.device}")
+    planes = planes.contiguous()
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
+    wsb = int(lib.ch_hamming_topk_weighted_workspace(Qn, G, W, k))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    with _dev_guard(q):
+        _lib.check(lib.ch_hamming_topk_weighted(_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W, k,
+                                                int(g_index_base), _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb,
+                                                _lib.stream_ptr(stream)), "ch_hamming_topk_weighted")
+    return idx, dist
+
+
 def subcode_dist(q: torch.Tensor, g: torch.Tensor, idx: torch.Tensor, nbit: int, nsub: int, g_index_base: int = 0,
                  stream=None) -> torch.Tensor:
     """Per-sub-code distances of retrieved hits: idx [Qn, k] (as returned by hamming_topk / hamming_topk_masked on the same q, g and

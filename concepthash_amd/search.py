@@ -15,6 +15,7 @@ import torch
 from . import retrieval as rt
 
 FORMAT = 1
+RANKS = ("hamming", "asymmetric")
 
 
 class StaleIndexError(RuntimeError):
@@ -118,7 +119,8 @@ class GalleryIndex:
                 return cand
         return os.path.join(self.data_root, rel)
 
-    def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0) -> dict:
+    def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0,
+               rank: str = "hamming", weight_bits: int = 8) -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here).
         Ranks the database by ascending (distance, index) and returns
           idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
@@ -127,7 +129,15 @@ class GalleryIndex:
           bits [Qn] int64: the number of unmasked bits of each query;
           labels: None or the hits' labels [Qn, k(, C)] (class id -1 / zero rows where idx is -1); paths: None or Qn lists of k paths.
         concepts: rank by these concepts' sub-codes only (one mask shared by all queries).  margin > 0: every query ignores its own
-        bits with |code| <= margin.  Both: the per-query mask is the AND of the two.  Neither: the unmasked scan."""
+        bits with |code| <= margin.  Both: the per-query mask is the AND of the two.  Neither: the unmasked scan.
+        rank: "hamming" (above) or "asymmetric": the same mask, but a disagreement on bit j costs the query's own |code_j|, quantised to
+        weight_bits (4 or 8) bits against the largest unmasked |code| of that query (`retrieval.weight_planes`).
+        dist is then that weighted distance, and the dict also holds rank, weight_bits and dist_max [Qn] int32, the sum of a query's
+        weights (the distance of a row that disagrees on every unmasked bit); everything else is as under "hamming"."""
+        if rank not in RANKS:
+            raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+        if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
+            raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits!r}")
         dev = self.device
         codes = query_codes.to(dev, torch.float32)
         if codes.dim() != 2 or codes.shape[1] != self.nbit:
@@ -150,12 +160,17 @@ class GalleryIndex:
             conf = rt.confidence_mask(codes, float(margin))
             mask = conf if mask is None else conf & mask[None, :]
             keep = keep & (codes.abs() > float(margin))
-        if mask is None:
+        extra = {}
+        if rank == "asymmetric":
+            planes, wsum = rt.weight_planes(codes, int(weight_bits), mask)
+            idx, dist = rt.hamming_topk_weighted(q, planes, self.codes, k)
+            extra = dict(rank=rank, weight_bits=int(weight_bits), dist_max=wsum)
+        elif mask is None:
             idx, dist = rt.hamming_topk(q, self.codes, k)
         else:
             idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
-                   bits=keep.sum(1), labels=None, paths=None)
+                   bits=keep.sum(1), labels=None, paths=None, **extra)
         if self.labels is not None:
             lab = self.labels[idx.clamp_min(0)]
             miss = idx < 0

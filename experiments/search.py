@@ -1,7 +1,7 @@
 """`exp=search`: image queries -> ranked database hits of a finished run, optionally by chosen concepts.
 
     python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [concepts=[0,2]]
-        [query_margin=0.0] [index=<file>] [rebuild_index=false] [save_attention=false]
+        [query_margin=0.0] [rank=hamming|asymmetric] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
 
 The run's config and checkpoint are loaded exactly as `exp=validation` loads them.  The database split is encoded once
 (`trainer.inference_one_epoch("db", True)`) into a `concepthash_amd.search.GalleryIndex` file -- `<logdir>/index_<best|last>.pth` unless
@@ -202,16 +202,19 @@ class SearchExperiment:
         concepts = cfg.get("concepts")
         concepts = [int(c) for c in concepts] if concepts is not None else None
         margin = float(cfg.get("query_margin", 0.0) or 0.0)
+        rank = str(cfg.get("rank", "hamming") or "hamming")
+        weight_bits = int(cfg.get("weight_bits", 8) or 8)
         print("Search Start")
         index = self.index if self.index is not None else self._build_index()
         index = index.to(self.trainer.device)
         loader, names, labelled = self._query_loader()
         q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
-        res = self._phase("search", index.search, q_codes, k, concepts, margin)
+        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits)
         t0 = time.perf_counter()
         q_ids = _label_ids(q_labels.cpu()) if labelled else None
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
         bits = res["bits"].tolist()
+        dist_max = res["dist_max"].tolist() if "dist_max" in res else bits      # the distance of a row that disagrees on every unmasked bit
         hit_labels = res["labels"].cpu() if res["labels"] is not None else None
         queries = []
         for i in range(len(idx)):
@@ -228,9 +231,9 @@ class SearchExperiment:
                 hits.append({"rank": r + 1, "index": idx[i][r], "path": index.resolve(rel_path), "distance": dist[i][r],
                              "label": hl.tolist() if hl is not None else None, "relevant": relevant, "concept_distances": cdist[i][r]})
             queries.append({"query": names[i] if names is not None else i, "label": ql.tolist() if ql is not None else None,
-                            "unmasked_bits": bits[i], "hits": hits})
+                            "unmasked_bits": bits[i], "distance_max": dist_max[i], "hits": hits})
         self.timing["results"] = round(time.perf_counter() - t0, 3)
-        out = {"k": k, "concepts": concepts, "query_margin": margin, "nbit": index.nbit, "ncontext": index.ncontext,
+        out = {"k": k, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "nbit": index.nbit, "ncontext": index.ncontext,
                "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
                "checkpoint": self.fingerprint, "query": self.query, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
@@ -239,11 +242,12 @@ class SearchExperiment:
         if attn is not None:
             np.save(os.path.join(self.search_logdir, "concept_attention.npy"), attn.cpu().numpy().astype(np.float32))
         what = "the whole code" if concepts is None else f"concepts {concepts}"
-        print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}" +
+        print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}, " +
+              ("Hamming distance" if rank == "hamming" else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
               (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + f"; index {self.index_note}")
         for e in queries[:PRINT_QUERIES]:
             print(f"query {e['query']}" + (f" (label {e['label']})" if e["label"] is not None and not isinstance(e["label"], list) else "") +
-                  f": {e['unmasked_bits']} bits")
+                  f": {e['unmasked_bits']} bits, distance <= {e['distance_max']}")
             for h in e["hits"]:
                 mark = "" if h["relevant"] is None else (" +" if h["relevant"] else " -")
                 print(f"  {h['rank']:3d}. d={h['distance']:3d} per concept {h['concept_distances']}  #{h['index']}" +

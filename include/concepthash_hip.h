@@ -384,6 +384,24 @@ int ch_hamming_topk_masked(const uint64_t *q, const uint64_t *q_mask, int32_t ma
                            int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* Weighted (asymmetric) Hamming ranking: the gallery stays binary, query i pays w_ij for a disagreement on bit j, w_ij being its own
+ * |code| quantised to P = 4 or 8 bits (L = 2^P - 1):  a_ij = |codes[i,j]|, 0 where the value is not finite or bit j is cleared in the
+ * mask; amax_i = max_j a_ij; w_ij = floor(a_ij L / amax_i + 0.5) evaluated in fp64 (all 0 when amax_i = 0; 0 for bits past nbit).
+ * out_planes [Qn,P,W] uint64 (W = ceil(nbit / 64)): bit b of planes[i,p,w] = bit p of w_{i,64w+b}; out_wsum [Qn] int32 = sum_j w_ij,
+ * the largest distance query i can reach (<= 256 * 255).  mask: NULL, [W] with mask_stride 0 or [Qn,W] with mask_stride W -- what
+ * ch_hamming_topk_masked takes.  P outside {4, 8}, nbit outside [1, 256] or another stride: status 2. */
+int ch_weight_planes(const float *codes, int64_t Qn, int32_t nbit, const uint64_t *mask, int32_t mask_stride, int32_t P,
+                     uint64_t *out_planes, int32_t *out_wsum, void *stream);
+
+/* Top-k by ascending (D, gallery index), D(i,g) = sum_p 2^p popcount((q_i xor g) and planes[i,p]) = sum_j w_ij [bit_j(q_i) != bit_j(g)]
+ * with q = ch_pack_sign of the same codes and planes from ch_weight_planes.  out_dist is D; the -1 fill, g_index_base, 1 <= k <= 128
+ * and 1 <= W <= 4 as in ch_hamming_topk; lists of several shards merge with ch_topk_merge (D < 2^16).  workspace:
+ * ch_hamming_topk_weighted_workspace() bytes (it covers both P).  A gallery of more than 65,535 segments of 65,536 rows is status 2. */
+size_t ch_hamming_topk_weighted_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
+int ch_hamming_topk_weighted(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
+                             int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Per-sub-code distances of retrieved hits: idx [Qn,k] int64 as written by ch_hamming_topk(_masked) / ch_topk_merge (global index =
  * gallery row + g_index_base, -1 = absent).  The code's first nbit bits are nsub equal sub-codes of nbit / nsub bits (sub-code c =
  * bits [c nbit/nsub, (c+1) nbit/nsub); it may straddle a 64-bit word); out [Qn,k,nsub] int32 = popcount of q xor g inside each, -1 in

@@ -33,7 +33,7 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
 LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
-               "query_margin", "index", "rebuild_index", "save_attention")
+               "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits")
 
 
 def _run_config(config, exp, keys):
