@@ -1,17 +1,14 @@
-// Packed Hamming retrieval kernels (gfx950): XOR + popcount distance, exact top-k, and the two passes of mAP.
+// Packed Hamming evaluation kernels (gfx950): the full XOR + popcount distance matrix and the two passes of mAP.  (Top-k search:
+// hamming_topk.hip.)
 //
 // Replaces the un-vendored utils.hashing.{calculate_mAP, calculate_pr_curve, get_hamm_dist} (call sites
 // experiments/test_hashing.py:106-119,153-162; trainers/orthohash.py:362; in-repo twin get_hd trainers/orthohash.py:263-264,
 // which builds a float (Qn,G) matrix with a matmul and argsorts it).  Definition: SURVEY.md section 8c / oracle/hamming_oracle.c.
 //
-// Work layout for all three scan kernels: one LANE per QUERY (its code words and its selection state live in that
-// lane's registers / LDS column), the GALLERY segment is walked sequentially and is wave-uniform, so gallery words and
-// labels arrive through the scalar data path (s_load_dwordx{4,8,16}) and every XOR uses an SGPR operand.  Nothing of
-// size Qn x G is ever written.  grid = (query tiles, gallery segments) so small galleries still fill the chip.
+// Work layout of the scan kernels (the top-k scan has the same): one LANE per QUERY (its code words and its selection state live in
+// that lane's registers / LDS column), the GALLERY segment is walked sequentially and is wave-uniform.  Nothing of size Qn x G is ever
+// written.  grid = (query tiles, gallery segments) so small galleries still fill the chip.
 //
-//  * top-k:   per-lane sorted list of the KREG smallest keys, key = dist << 23 | row-in-segment (unique, so "k smallest
-//             keys" == ascending (distance, gallery index)).  A wave-uniform branch skips the insertion network unless
-//             some lane beats its current threshold; the network itself is branch free (min/max chain).
 //  * hist:    per-lane per-distance counters in LDS, column = lane -> conflict-free ds_add; count and relevant count
 //             share one 32-bit word (16 + 16 bits, segments <= 65535 rows).
 //  * AP:      the same LDS counters, read-modify-write with return: the returned value is the row's position inside its
@@ -19,7 +16,6 @@
 //             relevant-rank; AP numerators are accumulated in 2^-32 fixed point (integer, order independent).
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/concepthash_hip.h"
 #include "../../include/concepthash_hip_debug.h"
@@ -33,10 +29,7 @@ extern "C" void ch_debug_set_hamming_scalar_loads(int32_t on) { g_scalar_loads.s
 
 namespace {
 
-constexpr int KEY_SHIFT = 23;
-constexpr uint32_t KEY_MASK = (1u << KEY_SHIFT) - 1;
-
-// bcnt_acc, the chained popcount of every distance below: hamming_shared.h
+// bcnt_acc, load_query and hamming<W>, the distance of every scan below: hamming_shared.h
 // Two words of a distance against gallery words held by lane K of the lane's own row of 16 lanes: the broadcast is the DPP operand
 // of the xor (`row_newbcast:K`), so it costs no instruction.  Written as one asm block because of the DPP read hazard (a VGPR
 // written by a VALU instruction must not be read by a DPP instruction within the next two): the temporaries are distinct
@@ -61,38 +54,6 @@ __device__ __forceinline__ uint32_t xor_row_bcast(uint32_t v, uint32_t x) {
     asm("v_xor_b32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=&v"(t) : "v"(v), "v"(x), "n"(K));
     return t;
 }
-// key = dist << KEY_SHIFT | row with the (wave-uniform) row number taken from an SGPR: one v_lshl_or_b32 (the compiler's own
-// form is a shift plus v_or3 with the row's low bits as a literal).
-__device__ __forceinline__ uint32_t make_key(uint32_t d, uint32_t row_uniform) {
-    uint32_t key;
-    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(d), "n"(KEY_SHIFT), "s"(row_uniform));
-    return key;
-}
-template <int W>
-__device__ __forceinline__ int hamming(const uint32_t (&q)[2 * W], const uint64_t *__restrict__ g) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const uint64_t gw = g[w];
-        d = bcnt_acc(q[2 * w] ^ (uint32_t)gw, d);
-        d = bcnt_acc(q[2 * w + 1] ^ (uint32_t)(gw >> 32), d);
-    }
-    return (int)d;
-}
-
-// popcount((q ^ g) & m): the mask words sit in the lane's VGPRs beside its query words, so a masked distance costs one v_and per
-// 32-bit word in front of the chained v_bcnt -- 3 instructions per word (ch_hamming_topk_masked)
-template <int W>
-__device__ __forceinline__ int hamming_masked(const uint32_t (&q)[2 * W], const uint32_t (&m)[2 * W], const uint64_t *__restrict__ g) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const uint64_t gw = g[w];
-        d = bcnt_acc((q[2 * w] ^ (uint32_t)gw) & m[2 * w], d);
-        d = bcnt_acc((q[2 * w + 1] ^ (uint32_t)(gw >> 32)) & m[2 * w + 1], d);
-    }
-    return (int)d;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // full distance matrix (small problems)
@@ -104,159 +65,6 @@ __global__ void dist_kernel(const uint64_t *q, int64_t Qn, const uint64_t *g, in
     int d = 0;
     for (int w = 0; w < W; ++w) d += __builtin_popcountll(q[i * W + w] ^ g[j * W + w]);
     out[gid] = d;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// top-k, per (query tile, gallery segment) partial lists
-// ---------------------------------------------------------------------------------------------------------------
-// MASKED (ch_hamming_topk_masked): the distance is popcount((q ^ g) & mask) with the query's own mask -- row qi of a [Qn, W] array
-// (stride W) or one mask shared by all queries (stride 0).  The unmasked instantiations carry an empty argument and no mask code.
-template <bool MASKED>
-struct TopkMask {};
-template <>
-struct TopkMask<true> {
-    const uint64_t *mask;
-    int stride;
-};
-
-template <int W, int KREG, bool MASKED>
-__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm) {
-    const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int seg = blockIdx.y;
-    const int64_t g0 = (int64_t)seg * seg_rows;
-    const int n = (int)min((int64_t)seg_rows, G - g0);
-    uint32_t qw[2 * W];
-    load_query<W>(qw, q, qi, Qn);
-    uint32_t mw[MASKED ? 2 * W : 1];
-    if constexpr (MASKED) {
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            const uint64_t v = qi < Qn ? qm.mask[qi * qm.stride + w] : 0ull;
-            mw[2 * w] = (uint32_t)v;
-            mw[2 * w + 1] = (uint32_t)(v >> 32);
-        }
-    }
-    auto dist = [&](const uint64_t *gw) -> uint32_t {
-        if constexpr (MASKED)
-            return (uint32_t)hamming_masked<W>(qw, mw, gw);
-        else
-            return (uint32_t)hamming<W>(qw, gw);
-    };
-    uint32_t list[KREG];
-#pragma unroll
-    for (int i = 0; i < KREG; ++i) list[i] = 0xFFFFFFFFu;
-    const uint64_t *gp = g + g0 * W;
-    auto insert = [&](uint32_t key) {
-        if (__builtin_amdgcn_ballot_w64(key < list[KREG - 1]) != 0ull) {
-#pragma unroll
-            for (int i = 0; i < KREG; ++i) {
-                const uint32_t lo = min(list[i], key);
-                key = max(list[i], key);
-                list[i] = lo;
-            }
-        }
-    };
-    // four gallery rows per trip: one wide scalar load (the next block is requested before this one is consumed), four
-    // XOR/popcount keys, ONE threshold test on their minimum; the insertion network runs only if some lane beats its list.
-    constexpr int UB = 4;
-    uint64_t bufA[UB * W], bufB[UB * W];
-    auto load_block = [&](uint64_t (&dst)[UB * W], int row) {
-#pragma unroll
-        for (int t = 0; t < UB * W; ++t) dst[t] = gp[(size_t)row * W + t];
-    };
-    auto scan_block = [&](const uint64_t (&blk)[UB * W], int row) {
-        uint32_t key[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) key[u] = make_key(dist(blk + u * W), (uint32_t)(row + u));
-        const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-        if (__builtin_amdgcn_ballot_w64(kmin < list[KREG - 1]) != 0ull) {
-#pragma unroll
-            for (int u = 0; u < UB; ++u) insert(key[u]);
-        }
-    };
-    // two blocks per iteration with the two SGPR buffers taking turns: no register copies between trips
-    int j = 0;
-    if (n >= UB) load_block(bufA, 0);
-    for (; j + 2 * UB <= n; j += 2 * UB) {
-        load_block(bufB, j + UB);
-        scan_block(bufA, j);
-        if (j + 3 * UB <= n) load_block(bufA, j + 2 * UB);
-        scan_block(bufB, j + UB);
-    }
-    if (j + UB <= n) {  // an odd number of whole blocks: the last one is already in bufA
-        scan_block(bufA, j);
-        j += UB;
-    }
-    for (; j < n; ++j) insert((dist(gp + (size_t)j * W) << KEY_SHIFT) | (uint32_t)j);
-    if (qi < Qn) {
-        uint32_t *o = part + ((size_t)seg * Qn + qi) * k;
-#pragma unroll
-        for (int i = 0; i < KREG; ++i)
-            if (i < k) o[i] = list[i];
-    }
-}
-
-// topk_merge_keys_kernel<KEY_SHIFT>, the merge of the per-segment key lists: hamming_shared.h
-
-// merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
-__global__ __launch_bounds__(256) void topk_merge_lists_kernel(const int64_t *__restrict__ idx_lists,
-                                                               const int32_t *__restrict__ dist_lists, int nlists, int64_t Qn,
-                                                               int k, int64_t *out_idx, int32_t *out_dist) {
-    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (qi >= Qn) return;
-    const int ncand = nlists * k;
-    unsigned long long prev = 0ull;
-    for (int r = 0; r < k; ++r) {
-        unsigned long long best = ~0ull;
-        for (int c = lane; c < ncand; c += 64) {
-            const int s = c / k, i = c - s * k;
-            const int32_t d = dist_lists[((size_t)s * Qn + qi) * k + i];
-            if (d < 0) continue;
-            const unsigned long long comp =
-                ((unsigned long long)d << 48) | (unsigned long long)idx_lists[((size_t)s * Qn + qi) * k + i];
-            if (comp + 1 > prev && comp < best) best = comp;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(best, o, 64);
-            best = other < best ? other : best;
-        }
-        if (lane == 0) {
-            out_idx[qi * k + r] = best == ~0ull ? -1 : (int64_t)(best & ((1ull << 48) - 1));
-            out_dist[qi * k + r] = best == ~0ull ? -1 : (int32_t)(best >> 48);
-        }
-        if (best != ~0ull) prev = best + 1;
-    }
-}
-
-// Per-concept breakdown of retrieved hits (ch_hamming_subcode_dist): one thread per (query, hit) gathers the hit's row and counts
-// the differing bits inside each of the nsub equal sub-codes of sb = nbit / nsub bits; a sub-code may straddle a 64-bit word.
-__global__ __launch_bounds__(256) void subcode_dist_kernel(const uint64_t *__restrict__ q, int64_t Qn, const uint64_t *__restrict__ g,
-                                                           int64_t G, int W, const int64_t *__restrict__ idx, int k,
-                                                           int64_t g_index_base, int sb, int nsub, int32_t *__restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Qn * k) return;
-    const int64_t qi = t / k;
-    const int64_t row = idx[t] - g_index_base;
-    int32_t *o = out + t * nsub;
-    if (idx[t] < 0 || row < 0 || row >= G) {   // -1 = no hit; anything else out of range was refused by the host check
-        for (int c = 0; c < nsub; ++c) o[c] = -1;
-        return;
-    }
-    const uint64_t *qp = q + qi * W, *gp = g + row * W;
-    for (int c = 0; c < nsub; ++c) {
-        const int lo = c * sb, hi = lo + sb;
-        int d = 0;
-        for (int w = lo >> 6; w <= (hi - 1) >> 6; ++w) {
-            const int a = max(lo, 64 * w) - 64 * w, nb = min(hi, 64 * w + 64) - 64 * w - a;
-            const uint64_t m = (nb == 64 ? ~0ull : ((1ull << nb) - 1ull)) << a;
-            d += __builtin_popcountll((qp[w] ^ gp[w]) & m);
-        }
-        o[c] = d;
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1011,56 +819,6 @@ bool fill_limits(const int64_t *rank_limits, int nlimits, RankLimits &lims) {
     return true;
 }
 
-int topk_seg_rows(int64_t Qn, int64_t G, int k) {
-    // the scan kernel has no LDS, so residency is set by its registers -- 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four
-    // waves per CU), 68-74 for 32 (7), ~136 for 64 (3), the whole file for 128 (1); the rest of the rule: topk_seg_rows_for
-    const int per_cu = k <= 16 ? 8 : k <= 32 ? 7 : k <= 64 ? 3 : 1;
-    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)KEY_MASK);
-}
-
-template <int W, int KREG, bool MASKED>
-int launch_topk_partial(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int seg_rows, int k, uint32_t *part,
-                        TopkMask<MASKED> qm, hipStream_t s) {
-    const int nseg = (int)ceil_div64(G, seg_rows);
-    dim3 grid((unsigned)ceil_div64(Qn, 256), (unsigned)nseg);
-    hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED>), grid, dim3(256), 0, s, q, Qn, g, G, seg_rows, k, part, qm);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int W, bool MASKED>
-int topk_dispatch_k(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int seg_rows, int k, uint32_t *part,
-                    TopkMask<MASKED> qm, hipStream_t s) {
-    if (k <= 10) return launch_topk_partial<W, 10>(q, Qn, g, G, seg_rows, k, part, qm, s);  // PRs = [1, 5, 10]: exactly k entries, so
-                                                                                             // the insertion threshold is the k-th key
-    if (k <= 16) return launch_topk_partial<W, 16>(q, Qn, g, G, seg_rows, k, part, qm, s);
-    if (k <= 32) return launch_topk_partial<W, 32>(q, Qn, g, G, seg_rows, k, part, qm, s);
-    if (k <= 64) return launch_topk_partial<W, 64>(q, Qn, g, G, seg_rows, k, part, qm, s);
-    return launch_topk_partial<W, 128>(q, Qn, g, G, seg_rows, k, part, qm, s);
-}
-
-// the body shared by ch_hamming_topk and ch_hamming_topk_masked (arguments already validated): partial lists, then the merge
-template <bool MASKED>
-int topk_run(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W, int k, int64_t g_index_base, int64_t *out_idx,
-             int32_t *out_dist, void *workspace, TopkMask<MASKED> qm, hipStream_t s) {
-    const int seg_rows = topk_seg_rows(Qn, G, k);
-    const int nseg = (int)ceil_div64(G, seg_rows);
-    CH_REQUIRE(nseg <= 65535, "hamming_topk: gallery too large for one call (shard it)");
-    uint32_t *part = (uint32_t *)workspace;
-    int e;
-    switch (W) {
-        case 1: e = topk_dispatch_k<1>(q, Qn, g, G, seg_rows, k, part, qm, s); break;
-        case 2: e = topk_dispatch_k<2>(q, Qn, g, G, seg_rows, k, part, qm, s); break;
-        case 3: e = topk_dispatch_k<3>(q, Qn, g, G, seg_rows, k, part, qm, s); break;
-        default: e = topk_dispatch_k<4>(q, Qn, g, G, seg_rows, k, part, qm, s); break;
-    }
-    if (e) return e;
-    hipLaunchKernelGGL(topk_merge_keys_kernel<KEY_SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, nseg, Qn, k, seg_rows,
-                       g_index_base, out_idx, out_dist);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int ch_hamming_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t *out,
@@ -1070,89 +828,6 @@ extern "C" int ch_hamming_dist(const uint64_t *q, int64_t Qn, const uint64_t *g,
     CH_REQUIRE(q && g && out, "hamming_dist: null pointer");
     hipLaunchKernelGGL(dist_kernel, dim3((unsigned)ceil_div64(Qn * G, 256)), dim3(256), 0, (hipStream_t)stream, q, Qn, g, G, W,
                        out);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" size_t ch_hamming_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    (void)W;
-    if (Qn <= 0 || G <= 0 || k <= 0) return 16;
-    const int seg_rows = topk_seg_rows(Qn, G, k);
-    const int64_t nseg = ceil_div64(G, seg_rows);
-    return (size_t)(nseg * Qn * k) * sizeof(uint32_t) + 16;
-}
-
-extern "C" int ch_hamming_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t k,
-                               int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
-                               size_t workspace_bytes, void *stream) {
-    CH_REQUIRE(W >= 1 && W <= 4, "hamming_topk: 1 <= W <= 4 (nbit <= 256)");
-    CH_REQUIRE(k >= 1 && k <= 128, "hamming_topk: 1 <= k <= 128");
-    CH_REQUIRE(Qn >= 0 && G >= 0, "hamming_topk: negative sizes");
-    if (Qn == 0) return 0;
-    CH_REQUIRE(q && out_idx && out_dist, "hamming_topk: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (G == 0) {
-        CH_CHECK_HIP(hipMemsetAsync(out_idx, 0xFF, sizeof(int64_t) * Qn * k, s));
-        CH_CHECK_HIP(hipMemsetAsync(out_dist, 0xFF, sizeof(int32_t) * Qn * k, s));
-        return 0;
-    }
-    CH_REQUIRE(g != nullptr, "hamming_topk: null gallery");
-    CH_REQUIRE(workspace && workspace_bytes >= ch_hamming_topk_workspace(Qn, G, W, k), "hamming_topk: workspace too small");
-    return topk_run<false>(q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, TopkMask<false>{}, s);
-}
-
-extern "C" int ch_hamming_topk_masked(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g,
-                                      int64_t G, int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
-                                      void *workspace, size_t workspace_bytes, void *stream) {
-    CH_REQUIRE(W >= 1 && W <= 4, "hamming_topk_masked: 1 <= W <= 4 (nbit <= 256)");
-    CH_REQUIRE(k >= 1 && k <= 128, "hamming_topk_masked: 1 <= k <= 128");
-    CH_REQUIRE(Qn >= 0 && G >= 0, "hamming_topk_masked: negative sizes");
-    CH_REQUIRE(mask_stride == 0 || mask_stride == W,
-               "hamming_topk_masked: mask_stride must be W (one mask per query) or 0 (one mask shared by all queries)");
-    CH_REQUIRE(q_mask != nullptr, "hamming_topk_masked: null q_mask");
-    if (Qn == 0) return 0;
-    CH_REQUIRE(q && out_idx && out_dist, "hamming_topk_masked: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    if (G == 0) {
-        CH_CHECK_HIP(hipMemsetAsync(out_idx, 0xFF, sizeof(int64_t) * Qn * k, s));
-        CH_CHECK_HIP(hipMemsetAsync(out_dist, 0xFF, sizeof(int32_t) * Qn * k, s));
-        return 0;
-    }
-    CH_REQUIRE(g != nullptr, "hamming_topk_masked: null gallery");
-    CH_REQUIRE(workspace && workspace_bytes >= ch_hamming_topk_workspace(Qn, G, W, k), "hamming_topk_masked: workspace too small");
-    return topk_run<true>(q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, TopkMask<true>{q_mask, mask_stride}, s);
-}
-
-extern "C" int ch_hamming_subcode_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, const int64_t *idx,
-                                       int32_t k, int64_t g_index_base, int32_t nbit, int32_t nsub, int32_t *out, void *stream) {
-    CH_REQUIRE(W >= 1 && W <= 4, "hamming_subcode_dist: 1 <= W <= 4 (nbit <= 256)");
-    CH_REQUIRE(nbit >= 1 && nbit <= 64 * W, "hamming_subcode_dist: nbit must be in [1, 64 W]");
-    CH_REQUIRE(nsub >= 1 && nbit % nsub == 0, "hamming_subcode_dist: nsub must divide nbit");
-    CH_REQUIRE(k >= 1 && Qn >= 0 && G >= 0, "hamming_subcode_dist: bad sizes (k >= 1, Qn >= 0, G >= 0)");
-    if (Qn == 0) return 0;
-    CH_REQUIRE(q && idx && out && (g || G == 0), "hamming_subcode_dist: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    // the hits index the gallery, so they are checked HERE, on a host copy, before any kernel reads a row through them
-    // (Qn * k indices: this is the tail of a search, not a scan)
-    std::vector<int64_t> h((size_t)(Qn * k));
-    CH_CHECK_HIP(hipMemcpyAsync(h.data(), idx, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, s));
-    CH_CHECK_HIP(hipStreamSynchronize(s));
-    for (int64_t v : h)
-        CH_REQUIRE(v == -1 || (v >= g_index_base && v - g_index_base < G),
-                   "hamming_subcode_dist: idx holds an index outside [g_index_base, g_index_base + G) that is not -1");
-    hipLaunchKernelGGL(subcode_dist_kernel, dim3((unsigned)ceil_div64(Qn * k, 256)), dim3(256), 0, s, q, Qn, g, G, (int)W, idx, (int)k,
-                       g_index_base, (int)(nbit / nsub), (int)nsub, out);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int ch_topk_merge(const int64_t *idx_lists, const int32_t *dist_lists, int32_t nlists, int64_t Qn, int32_t k,
-                             int64_t *out_idx, int32_t *out_dist, void *stream) {
-    CH_REQUIRE(nlists >= 1 && k >= 1 && Qn >= 0, "topk_merge: bad sizes");
-    if (Qn == 0) return 0;
-    CH_REQUIRE(idx_lists && dist_lists && out_idx && out_dist, "topk_merge: null pointer");
-    hipLaunchKernelGGL(topk_merge_lists_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, (hipStream_t)stream, idx_lists,
-                       dist_lists, nlists, Qn, k, out_idx, out_dist);
     CH_LAUNCH_CHECK();
     return 0;
 }

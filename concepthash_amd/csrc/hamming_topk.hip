@@ -1,0 +1,628 @@
+// Exact top-k search on packed codes (gfx950) under three distances, all integers, so any segmentation or sharding of the gallery
+// gives the same bits:
+//     plain     popcount(q ^ g)                                                    ch_hamming_topk
+//     masked    popcount((q ^ g) & mask), the query's own mask or one for all      ch_hamming_topk_masked
+//     weighted  sum_j w_ij [bit_j(q_i) != bit_j(g)] = sum_p 2^p popcount((q_i ^ g) & planes[i, p]): the gallery stays binary, the query
+//               pays w_j for a disagreement on bit j, with w_j its own |code_j| quantised to P = 4 or 8 bits and planes[i, p] = bit p of
+//               every w_ij ("weighted distance")            ch_weight_planes, ch_hamming_topk_weighted
+//
+// ONE scan (topk_scan) serves the three: one LANE per QUERY (its code words, its mask or plane words and its list live in that lane's
+// registers), the GALLERY segment is walked sequentially and is wave-uniform, so gallery words arrive through the scalar data path
+// (s_load_dwordx{4,8,16}) and every XOR uses an SGPR operand.  Nothing of size Qn x G is ever written.  grid = (query tiles, gallery
+// segments) so small galleries still fill the chip.  Per lane a sorted list of the KREG smallest keys, key = dist << SHIFT |
+// row-in-segment (unique, so "k smallest keys" == ascending (distance, gallery index)).  A wave-uniform branch skips the insertion
+// network unless some lane beats its current threshold; the network itself is branch free (min/max chain).
+//     SHIFT = 23 (plain, masked): dist <= 256, segments of < 2^23 rows.
+//     SHIFT = 16 (weighted): D <= 255 * 256 = 65,280 < 2^16 - 1, so 0xFFFFFFFF stays the empty slot; segments hold <= 65,536 rows.
+// topk_merge_keys_kernel<SHIFT> merges the per-segment lists of a call, topk_merge_lists_kernel the final lists of several shards;
+// subcode_dist_kernel breaks the distance of retrieved hits down by concept.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/concepthash_hip.h"
+#include "ch_common.h"
+#include "hamming_shared.h"
+
+namespace {
+
+constexpr int KEY_SHIFT = 23;
+constexpr int WKEY_SHIFT = 16;
+
+// ---------------------------------------------------------------------------------------------------------------
+// the three distances of one gallery row (bcnt_acc, load_query and the plain hamming<W>: hamming_shared.h)
+// ---------------------------------------------------------------------------------------------------------------
+// popcount((q ^ g) & m): the mask words sit in the lane's VGPRs beside its query words, so a masked distance costs one v_and per
+// 32-bit word in front of the chained v_bcnt -- 3 instructions per word (ch_hamming_topk_masked)
+template <int W>
+__device__ __forceinline__ int hamming_masked(const uint32_t (&q)[2 * W], const uint32_t (&m)[2 * W], const uint64_t *__restrict__ g) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const uint64_t gw = g[w];
+        d = bcnt_acc((q[2 * w] ^ (uint32_t)gw) & m[2 * w], d);
+        d = bcnt_acc((q[2 * w + 1] ^ (uint32_t)(gw >> 32)) & m[2 * w + 1], d);
+    }
+    return (int)d;
+}
+
+// sum_p 2^p a[p] as a Horner chain of P - 1 v_lshl_add_u32, in one asm block.  Written as d = (d << 1) + a[p] the chain is
+// redistributed into a sum of shifted terms a little further each time the code around it is inlined one level up, and what gets
+// selected from that follows the number of levels: 8 instructions for 8 planes while the scan was written out in each kernel, 9 to
+// 10 behind topk_scan and its distance callable.  One block, not one asm per step: between two dependent asm statements that end
+// up next to each other the compiler puts an s_nop.
+__device__ __forceinline__ uint32_t horner2(const uint32_t (&a)[4]) {
+    uint32_t d;
+    asm("v_lshl_add_u32 %0, %4, 1, %3\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %2\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %1"
+        : "=&v"(d)
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
+    return d;
+}
+__device__ __forceinline__ uint32_t horner2(const uint32_t (&a)[8]) {
+    uint32_t d;
+    asm("v_lshl_add_u32 %0, %8, 1, %7\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %6\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %5\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %4\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %3\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %2\n\t"
+        "v_lshl_add_u32 %0, %0, 1, %1"
+        : "=&v"(d)
+        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]));
+    return d;
+}
+
+// weighted D: per 32-bit word and plane one (q ^ g) & plane (a single v_bitop3_b32 with the gallery word as its SGPR operand) and one
+// chained v_bcnt into that plane's accumulator -- 2 P instructions per word -- then the Horner chain of P - 1 shift-adds
+template <int W, int P>
+__device__ __forceinline__ uint32_t weighted_dist(const uint32_t (&q)[2 * W], const uint32_t (&pl)[P][2 * W],
+                                                  const uint64_t *__restrict__ g) {
+    uint32_t acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) acc[p] = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const uint64_t gw = g[w];
+        const uint32_t lo = (uint32_t)gw, hi = (uint32_t)(gw >> 32);
+#pragma unroll
+        for (int p = 0; p < P; ++p) acc[p] = bcnt_acc((q[2 * w] ^ lo) & pl[p][2 * w], acc[p]);
+#pragma unroll
+        for (int p = 0; p < P; ++p) acc[p] = bcnt_acc((q[2 * w + 1] ^ hi) & pl[p][2 * w + 1], acc[p]);
+    }
+    return horner2(acc);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the scan: per (query tile, gallery segment) partial lists
+// ---------------------------------------------------------------------------------------------------------------
+// key = dist << SHIFT | row with the (wave-uniform) row number taken from an SGPR: one v_lshl_or_b32 (the compiler's own form is a
+// shift plus v_or3 with the row's low bits as a literal).
+template <int SHIFT>
+__device__ __forceinline__ uint32_t make_key(uint32_t d, uint32_t row_uniform) {
+    uint32_t key;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(d), "n"(SHIFT), "s"(row_uniform));
+    return key;
+}
+
+// Segment blockIdx.y of the gallery against query qi (a lane past Qn scans too -- its registers hold zeros -- and stores nothing):
+// from the empty list to the store of its k smallest keys.  dist: const uint64_t * (the W words of a gallery row) -> uint32_t.
+template <int W, int KREG, int SHIFT, class Dist>
+__device__ __forceinline__ void topk_scan(const Dist &dist, int64_t qi, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
+                                          int seg_rows, int k, uint32_t *__restrict__ part) {
+    const int seg = blockIdx.y;
+    const int64_t g0 = (int64_t)seg * seg_rows;
+    const int n = (int)min((int64_t)seg_rows, G - g0);
+    uint32_t list[KREG];
+#pragma unroll
+    for (int i = 0; i < KREG; ++i) list[i] = 0xFFFFFFFFu;
+    const uint64_t *gp = g + g0 * W;
+    auto insert = [&](uint32_t key) {
+        if (__builtin_amdgcn_ballot_w64(key < list[KREG - 1]) != 0ull) {
+#pragma unroll
+            for (int i = 0; i < KREG; ++i) {
+                const uint32_t lo = min(list[i], key);
+                key = max(list[i], key);
+                list[i] = lo;
+            }
+        }
+    };
+    // four gallery rows per trip: one wide scalar load (the next block is requested before this one is consumed), four keys, ONE
+    // threshold test on their minimum; the insertion network runs only if some lane beats its list.
+    constexpr int UB = 4;
+    uint64_t bufA[UB * W], bufB[UB * W];
+    auto load_block = [&](uint64_t (&dst)[UB * W], int row) {
+#pragma unroll
+        for (int t = 0; t < UB * W; ++t) dst[t] = gp[(size_t)row * W + t];
+    };
+    auto scan_block = [&](const uint64_t (&blk)[UB * W], int row) {
+        uint32_t key[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) key[u] = make_key<SHIFT>(dist(blk + u * W), (uint32_t)(row + u));
+        const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
+        if (__builtin_amdgcn_ballot_w64(kmin < list[KREG - 1]) != 0ull) {
+#pragma unroll
+            for (int u = 0; u < UB; ++u) insert(key[u]);
+        }
+    };
+    // two blocks per iteration with the two SGPR buffers taking turns: no register copies between trips
+    int j = 0;
+    if (n >= UB) load_block(bufA, 0);
+    for (; j + 2 * UB <= n; j += 2 * UB) {
+        load_block(bufB, j + UB);
+        scan_block(bufA, j);
+        if (j + 3 * UB <= n) load_block(bufA, j + 2 * UB);
+        scan_block(bufB, j + UB);
+    }
+    if (j + UB <= n) {  // an odd number of whole blocks: the last one is already in bufA
+        scan_block(bufA, j);
+        j += UB;
+    }
+    for (; j < n; ++j) insert((dist(gp + (size_t)j * W) << SHIFT) | (uint32_t)j);
+    if (qi < Qn) {
+        uint32_t *o = part + ((size_t)seg * Qn + qi) * k;
+#pragma unroll
+        for (int i = 0; i < KREG; ++i)
+            if (i < k) o[i] = list[i];
+    }
+}
+
+// MASKED (ch_hamming_topk_masked): the query's own mask -- row qi of a [Qn, W] array (stride W) -- or one mask shared by all queries
+// (stride 0).  The unmasked instantiations carry an empty argument and no mask code.
+template <bool MASKED>
+struct TopkMask {};
+template <>
+struct TopkMask<true> {
+    const uint64_t *mask;
+    int stride;
+};
+
+template <int W, int KREG, bool MASKED>
+__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
+                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm) {
+    const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t qw[2 * W];
+    load_query<W>(qw, q, qi, Qn);
+    if constexpr (MASKED) {
+        uint32_t mw[2 * W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint64_t v = qi < Qn ? qm.mask[qi * qm.stride + w] : 0ull;
+            mw[2 * w] = (uint32_t)v;
+            mw[2 * w + 1] = (uint32_t)(v >> 32);
+        }
+        topk_scan<W, KREG, KEY_SHIFT>([&](const uint64_t *gw) { return (uint32_t)hamming_masked<W>(qw, mw, gw); }, qi, Qn, g, G, seg_rows, k,
+                                      part);
+    } else {
+        topk_scan<W, KREG, KEY_SHIFT>([&](const uint64_t *gw) { return (uint32_t)hamming<W>(qw, gw); }, qi, Qn, g, G, seg_rows, k, part);
+    }
+}
+
+template <int W, int KREG, int P>
+__global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64_t *__restrict__ q,
+                                                                    const uint64_t *__restrict__ planes, int64_t Qn,
+                                                                    const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                                    uint32_t *__restrict__ part) {
+    const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t qw[2 * W];
+    load_query<W>(qw, q, qi, Qn);
+    uint32_t pl[P][2 * W];   // a lane past Qn holds zero planes: its distances are 0 and nothing of it is stored
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint64_t v = qi < Qn ? planes[(qi * P + p) * W + w] : 0ull;
+            pl[p][2 * w] = (uint32_t)v;
+            pl[p][2 * w + 1] = (uint32_t)(v >> 32);
+        }
+    }
+    topk_scan<W, KREG, WKEY_SHIFT>([&](const uint64_t *gw) { return weighted_dist<W, P>(qw, pl, gw); }, qi, Qn, g, G, seg_rows, k, part);
+}
+
+// The merge of per-segment key lists, key = dist << SHIFT | row-in-segment (0xFFFFFFFF = empty slot).
+// one wave per query: repeatedly extract the smallest composite (dist, global row) above the previous one
+template <int SHIFT>
+__global__ __launch_bounds__(256) void topk_merge_keys_kernel(const uint32_t *__restrict__ part, int nseg, int64_t Qn, int k,
+                                                              int seg_rows, int64_t g_index_base, int64_t *out_idx,
+                                                              int32_t *out_dist) {
+    constexpr uint32_t MASK = (1u << SHIFT) - 1;
+    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (qi >= Qn) return;
+    const int ncand = nseg * k;
+    unsigned long long prev = 0ull;  // composite + 1 of the last output (0 = none yet)
+    for (int r = 0; r < k; ++r) {
+        unsigned long long best = ~0ull;
+        for (int c = lane; c < ncand; c += 64) {
+            const int s = c / k, i = c - s * k;
+            const uint32_t key = part[((size_t)s * Qn + qi) * k + i];
+            if (key == 0xFFFFFFFFu) continue;
+            const unsigned long long comp =
+                ((unsigned long long)(key >> SHIFT) << 40) | ((unsigned long long)s * seg_rows + (key & MASK));
+            if (comp + 1 > prev && comp < best) best = comp;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        if (lane == 0) {
+            if (best == ~0ull) {
+                out_idx[qi * k + r] = -1;
+                out_dist[qi * k + r] = -1;
+            } else {
+                out_idx[qi * k + r] = g_index_base + (int64_t)(best & ((1ull << 40) - 1));
+                out_dist[qi * k + r] = (int32_t)(best >> 40);
+            }
+        }
+        if (best == ~0ull) {
+            // nothing left: fill the rest
+            for (int rr = r + 1; rr < k; ++rr)
+                if (lane == 0) {
+                    out_idx[qi * k + rr] = -1;
+                    out_dist[qi * k + rr] = -1;
+                }
+            return;
+        }
+        prev = best + 1;
+    }
+}
+
+// merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
+__global__ __launch_bounds__(256) void topk_merge_lists_kernel(const int64_t *__restrict__ idx_lists,
+                                                               const int32_t *__restrict__ dist_lists, int nlists, int64_t Qn,
+                                                               int k, int64_t *out_idx, int32_t *out_dist) {
+    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (qi >= Qn) return;
+    const int ncand = nlists * k;
+    unsigned long long prev = 0ull;
+    for (int r = 0; r < k; ++r) {
+        unsigned long long best = ~0ull;
+        for (int c = lane; c < ncand; c += 64) {
+            const int s = c / k, i = c - s * k;
+            const int32_t d = dist_lists[((size_t)s * Qn + qi) * k + i];
+            if (d < 0) continue;
+            const unsigned long long comp =
+                ((unsigned long long)d << 48) | (unsigned long long)idx_lists[((size_t)s * Qn + qi) * k + i];
+            if (comp + 1 > prev && comp < best) best = comp;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other < best ? other : best;
+        }
+        if (lane == 0) {
+            out_idx[qi * k + r] = best == ~0ull ? -1 : (int64_t)(best & ((1ull << 48) - 1));
+            out_dist[qi * k + r] = best == ~0ull ? -1 : (int32_t)(best >> 48);
+        }
+        if (best != ~0ull) prev = best + 1;
+    }
+}
+
+// Per-concept breakdown of retrieved hits (ch_hamming_subcode_dist): one thread per (query, hit) gathers the hit's row and counts
+// the differing bits inside each of the nsub equal sub-codes of sb = nbit / nsub bits; a sub-code may straddle a 64-bit word.
+__global__ __launch_bounds__(256) void subcode_dist_kernel(const uint64_t *__restrict__ q, int64_t Qn, const uint64_t *__restrict__ g,
+                                                           int64_t G, int W, const int64_t *__restrict__ idx, int k,
+                                                           int64_t g_index_base, int sb, int nsub, int32_t *__restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= Qn * k) return;
+    const int64_t qi = t / k;
+    const int64_t row = idx[t] - g_index_base;
+    int32_t *o = out + t * nsub;
+    if (idx[t] < 0 || row < 0 || row >= G) {   // -1 = no hit; anything else out of range was refused by the host check
+        for (int c = 0; c < nsub; ++c) o[c] = -1;
+        return;
+    }
+    const uint64_t *qp = q + qi * W, *gp = g + row * W;
+    for (int c = 0; c < nsub; ++c) {
+        const int lo = c * sb, hi = lo + sb;
+        int d = 0;
+        for (int w = lo >> 6; w <= (hi - 1) >> 6; ++w) {
+            const int a = max(lo, 64 * w) - 64 * w, nb = min(hi, 64 * w + 64) - 64 * w - a;
+            const uint64_t m = (nb == 64 ? ~0ull : ((1ull << nb) - 1ull)) << a;
+            d += __builtin_popcountll((qp[w] ^ gp[w]) & m);
+        }
+        o[c] = d;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// quantised weights -> bit planes
+// ---------------------------------------------------------------------------------------------------------------
+// One wave per query; lane b holds bit b of every 64-bit word (W <= 4 values).  a = |c| (0 where c is not finite, the bit is masked
+// out or past nbit); amax by wave shuffles; w = floor(a L / amax + 0.5) in fp64 on the widened fp32 values (a L is exact, the IEEE
+// quotient and the sum round as the host's do); plane p of word t is the 64-lane ballot of bit p of w.  planes [Qn, P, W]; wsum [Qn] =
+// the largest D a query can reach.
+template <int P>
+__global__ __launch_bounds__(256) void weight_planes_kernel(const float *__restrict__ codes, int64_t Qn, int nbit, int W,
+                                                            const uint64_t *__restrict__ mask, int mask_stride,
+                                                            uint64_t *__restrict__ planes, int32_t *__restrict__ wsum) {
+    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (qi >= Qn) return;  // wave-uniform
+    constexpr double L = (double)((1 << P) - 1);
+    float a[4];
+    float amax = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        a[t] = 0.f;
+        const int j = 64 * t + lane;
+        if (t < W && j < nbit) {
+            const uint32_t bits = __builtin_bit_cast(uint32_t, codes[qi * nbit + j]) & 0x7FFFFFFFu;   // |c|
+            const bool finite = bits < 0x7F800000u;
+            const bool kept = mask == nullptr || ((mask[qi * mask_stride + t] >> lane) & 1ull) != 0ull;
+            a[t] = (finite && kept) ? __builtin_bit_cast(float, bits) : 0.f;
+        }
+        amax = fmaxf(amax, a[t]);
+    }
+    amax = wave_max(amax);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        uint32_t w = 0;
+        if (amax > 0.f) w = (uint32_t)__builtin_floor((double)a[t] * L / (double)amax + 0.5);
+        sum += w;
+        if (t < W) {   // wave-uniform
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const uint64_t plane = __builtin_amdgcn_ballot_w64(((w >> p) & 1u) != 0u);
+                if (lane == 0) planes[(qi * P + p) * W + t] = plane;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == 0) wsum[qi] = (int32_t)sum;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host: segment sizing
+// ---------------------------------------------------------------------------------------------------------------
+// Gallery rows per segment of a scan whose kernel keeps `per_cu` workgroups of four waves resident per CU and whose keys hold
+// `max_rows` rows per segment.
+// (tile, segment) workgroups for ONE full round and never a few more: ceil(2048 / tiles) segments put 2,134 workgroups on the 2,048
+// slots at the NABirds size (97 tiles): a second round for 86 of them doubled the launch (0.38 -> 0.2 ms).  Segments not shorter than
+// 256 rows.
+int topk_seg_rows_for(int64_t Qn, int64_t G, int per_cu, int64_t max_rows) {
+    const int64_t slots = 256 * per_cu;
+    const int64_t tiles = ceil_div64(Qn, 256);
+    int64_t nseg = std::max<int64_t>(1, slots / tiles);
+    // ... and not more segments than needed: every segment starts with empty lists, so its first ~640 rows run the insertion
+    // network for some lane of the wave almost every row, and the merge cost grows with the segment count -- segments of >= 4,096
+    // rows as long as two workgroups per CU remain (NABirds size: 6 segments instead of 21, 0.45 -> 0.37 ms; the 1M-row scan keeps 32)
+    nseg = std::min(nseg, std::max<int64_t>(std::max<int64_t>(1, ceil_div64(512, tiles)), G / 4096));
+    int64_t rows = ceil_div64(G, nseg);
+    if (rows < 256) rows = 256;
+    if (rows > max_rows) rows = max_rows;
+    return (int)rows;
+}
+
+// The scan kernels have no LDS, so residency is set by their registers.  The two rules below are the ones each distance was tuned
+// and measured with; they are NOT the same function of the register count (the table form gives 6, not 7, workgroups for the plain
+// lists of 32 keys), so they stay apart.
+int topk_seg_rows(int64_t Qn, int64_t G, int k) {
+    // 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four waves per CU), 68-74 for 32 (7), ~136 for 64 (3), the whole file for 128 (1)
+    const int per_cu = k <= 16 ? 8 : k <= 32 ? 7 : k <= 64 ? 3 : 1;
+    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)(1 << KEY_SHIFT) - 1);
+}
+
+// VGPRs of topk_weighted_partial_kernel<W, KREG, P> from the code-object metadata of this build (profiles/search_weighted_topk.txt;
+// no instance uses scratch): a CU holds min(8, 512 / VGPRs rounded up to the allocation unit of 8) workgroups of four waves.
+constexpr int WTOPK_VGPRS[2][4][5] = {
+    // KREG 10, 16, 32, 64, 128
+    {{32, 44, 76, 140, 258}, {43, 54, 86, 150, 258}, {53, 64, 96, 160, 258}, {63, 74, 106, 170, 258}},     // P = 4, W = 1..4
+    {{47, 53, 84, 148, 258}, {67, 73, 102, 166, 258}, {85, 91, 120, 184, 258}, {103, 109, 138, 202, 266}},  // P = 8, W = 1..4
+};
+
+int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P) {
+    const int ki = k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4;
+    const int vgprs = (WTOPK_VGPRS[P == 8][W - 1][ki] + 7) / 8 * 8;
+    const int per_cu = std::max(1, std::min(8, 512 / std::max(8, vgprs)));
+    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)1 << WKEY_SHIFT);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host: one launch path.  A "scan" names one of the two kernels, holds its extra arguments and knows its key split, its
+// segmentation, its workspace and the wording of its own refusals; topk_run is the body of the three entry points.
+// ---------------------------------------------------------------------------------------------------------------
+struct TopkCall {   // what every partial launch takes
+    const uint64_t *q;
+    int64_t Qn;
+    const uint64_t *g;
+    int64_t G;
+    int seg_rows, k;
+    uint32_t *part;
+    dim3 grid;
+    hipStream_t s;
+};
+
+template <bool MASKED>
+struct HammingScan {
+    static constexpr int SHIFT = KEY_SHIFT;
+    static constexpr const char *too_many_segments = "hamming_topk: gallery too large for one call (shard it)";
+    TopkMask<MASKED> qm;
+    int check(int W) const {   // the masked entry's own refusals
+        if constexpr (MASKED) {
+            CH_REQUIRE(qm.stride == 0 || qm.stride == W,
+                       "hamming_topk_masked: mask_stride must be W (one mask per query) or 0 (one mask shared by all queries)");
+            CH_REQUIRE(qm.mask != nullptr, "hamming_topk_masked: null q_mask");
+        }
+        return 0;
+    }
+    bool operands() const { return true; }   // the mask was checked above
+    int seg_rows(int64_t Qn, int64_t G, int, int k) const { return topk_seg_rows(Qn, G, k); }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k) const { return ch_hamming_topk_workspace(Qn, G, W, k); }
+    template <int W, int KREG>
+    void launch(const TopkCall &c) const {
+        hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows, c.k, c.part,
+                           qm);
+    }
+};
+
+template <int P>
+struct WeightedScan {
+    static constexpr int SHIFT = WKEY_SHIFT;
+    static constexpr const char *too_many_segments =
+        "hamming_topk_weighted: gallery too large for one call: more than 65,535 segments (shard it)";
+    const uint64_t *planes;
+    int check(int) const { return 0; }
+    bool operands() const { return planes != nullptr; }
+    int seg_rows(int64_t Qn, int64_t G, int W, int k) const { return wtopk_seg_rows(Qn, G, W, k, P); }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k) const { return ch_hamming_topk_weighted_workspace(Qn, G, W, k); }
+    template <int W, int KREG>
+    void launch(const TopkCall &c) const {
+        hipLaunchKernelGGL((topk_weighted_partial_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G, c.seg_rows,
+                           c.k, c.part);
+    }
+};
+
+// lists of KREG = 10 / 16 / 32 / 64 / 128 keys.  k <= 10 (PRs = [1, 5, 10]): exactly k entries, so the insertion threshold is the
+// k-th key
+template <int W, class Scan>
+void topk_launch_k(const Scan &scan, const TopkCall &c) {
+    if (c.k <= 10) return scan.template launch<W, 10>(c);
+    if (c.k <= 16) return scan.template launch<W, 16>(c);
+    if (c.k <= 32) return scan.template launch<W, 32>(c);
+    if (c.k <= 64) return scan.template launch<W, 64>(c);
+    return scan.template launch<W, 128>(c);
+}
+
+template <class Scan>
+void topk_launch(const Scan &scan, int W, const TopkCall &c) {
+    switch (W) {
+        case 1: return topk_launch_k<1>(scan, c);
+        case 2: return topk_launch_k<2>(scan, c);
+        case 3: return topk_launch_k<3>(scan, c);
+        default: return topk_launch_k<4>(scan, c);
+    }
+}
+
+// The body of ch_hamming_topk / _masked / _weighted: the checks in the order the entries have always made them (`name` opens the
+// messages), partial lists, merge.
+template <class Scan>
+int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W,
+             int k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, hipStream_t s) {
+    const std::string at = std::string(name) + ": ";
+    CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
+    CH_REQUIRE(k >= 1 && k <= 128, at + "1 <= k <= 128");
+    CH_REQUIRE(Qn >= 0 && G >= 0, at + "negative sizes");
+    if (int e = scan.check(W)) return e;
+    if (Qn == 0) return 0;
+    CH_REQUIRE(q && scan.operands() && out_idx && out_dist, at + "null pointer");
+    if (G == 0) {
+        CH_CHECK_HIP(hipMemsetAsync(out_idx, 0xFF, sizeof(int64_t) * Qn * k, s));
+        CH_CHECK_HIP(hipMemsetAsync(out_dist, 0xFF, sizeof(int32_t) * Qn * k, s));
+        return 0;
+    }
+    CH_REQUIRE(g != nullptr, at + "null gallery");
+    const int seg_rows = scan.seg_rows(Qn, G, W, k);
+    const int64_t nseg = ceil_div64(G, seg_rows);
+    CH_REQUIRE(nseg <= 65535, Scan::too_many_segments);
+    CH_REQUIRE(workspace && workspace_bytes >= scan.workspace(Qn, G, W, k), at + "workspace too small");
+    uint32_t *part = (uint32_t *)workspace;
+    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s});
+    CH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(topk_merge_keys_kernel<Scan::SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, (int)nseg, Qn, k,
+                       seg_rows, g_index_base, out_idx, out_dist);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t ch_hamming_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
+    (void)W;
+    if (Qn <= 0 || G <= 0 || k <= 0) return 16;
+    return (size_t)(ceil_div64(G, topk_seg_rows(Qn, G, k)) * Qn * k) * sizeof(uint32_t) + 16;
+}
+
+extern "C" size_t ch_hamming_topk_weighted_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
+    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
+    // the call does not name P: room for the finer of the two segmentations
+    const int rows = std::min(wtopk_seg_rows(Qn, G, W, k, 4), wtopk_seg_rows(Qn, G, W, k, 8));
+    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+}
+
+extern "C" int ch_hamming_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t k,
+                               int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    return topk_run("hamming_topk", HammingScan<false>{}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
+                    workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ch_hamming_topk_masked(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g,
+                                      int64_t G, int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    return topk_run("hamming_topk_masked", HammingScan<true>{{q_mask, mask_stride}}, q, Qn, g, G, W, k, g_index_base, out_idx,
+                    out_dist, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ch_hamming_topk_weighted(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
+                                        int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
+                                        void *workspace, size_t workspace_bytes, void *stream) {
+    CH_REQUIRE(P == 4 || P == 8, "hamming_topk_weighted: P (weight bits) must be 4 or 8");
+    if (P == 4)
+        return topk_run("hamming_topk_weighted", WeightedScan<4>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx,
+                        out_dist, workspace, workspace_bytes, (hipStream_t)stream);
+    return topk_run("hamming_topk_weighted", WeightedScan<8>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist,
+                    workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int ch_weight_planes(const float *codes, int64_t Qn, int32_t nbit, const uint64_t *mask, int32_t mask_stride, int32_t P,
+                                uint64_t *out_planes, int32_t *out_wsum, void *stream) {
+    CH_REQUIRE(P == 4 || P == 8, "weight_planes: P (weight bits) must be 4 or 8");
+    CH_REQUIRE(nbit >= 1 && nbit <= 256, "weight_planes: nbit must be in [1, 256]");
+    const int W = (nbit + 63) / 64;
+    CH_REQUIRE(mask_stride == 0 || mask_stride == W,
+               "weight_planes: mask_stride must be W (one mask per query) or 0 (one mask shared by all queries, or no mask)");
+    CH_REQUIRE(Qn >= 0, "weight_planes: negative Qn");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(codes && out_planes && out_wsum, "weight_planes: null pointer");
+    const dim3 grid((unsigned)ceil_div64(Qn, 4));
+    hipStream_t s = (hipStream_t)stream;
+    if (P == 4)
+        hipLaunchKernelGGL(weight_planes_kernel<4>, grid, dim3(256), 0, s, codes, Qn, (int)nbit, W, mask, (int)mask_stride, out_planes,
+                           out_wsum);
+    else
+        hipLaunchKernelGGL(weight_planes_kernel<8>, grid, dim3(256), 0, s, codes, Qn, (int)nbit, W, mask, (int)mask_stride, out_planes,
+                           out_wsum);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ch_hamming_subcode_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, const int64_t *idx,
+                                       int32_t k, int64_t g_index_base, int32_t nbit, int32_t nsub, int32_t *out, void *stream) {
+    CH_REQUIRE(W >= 1 && W <= 4, "hamming_subcode_dist: 1 <= W <= 4 (nbit <= 256)");
+    CH_REQUIRE(nbit >= 1 && nbit <= 64 * W, "hamming_subcode_dist: nbit must be in [1, 64 W]");
+    CH_REQUIRE(nsub >= 1 && nbit % nsub == 0, "hamming_subcode_dist: nsub must divide nbit");
+    CH_REQUIRE(k >= 1 && Qn >= 0 && G >= 0, "hamming_subcode_dist: bad sizes (k >= 1, Qn >= 0, G >= 0)");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(q && idx && out && (g || G == 0), "hamming_subcode_dist: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    // the hits index the gallery, so they are checked HERE, on a host copy, before any kernel reads a row through them
+    // (Qn * k indices: this is the tail of a search, not a scan)
+    std::vector<int64_t> h((size_t)(Qn * k));
+    CH_CHECK_HIP(hipMemcpyAsync(h.data(), idx, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, s));
+    CH_CHECK_HIP(hipStreamSynchronize(s));
+    for (int64_t v : h)
+        CH_REQUIRE(v == -1 || (v >= g_index_base && v - g_index_base < G),
+                   "hamming_subcode_dist: idx holds an index outside [g_index_base, g_index_base + G) that is not -1");
+    hipLaunchKernelGGL(subcode_dist_kernel, dim3((unsigned)ceil_div64(Qn * k, 256)), dim3(256), 0, s, q, Qn, g, G, (int)W, idx, (int)k,
+                       g_index_base, (int)(nbit / nsub), (int)nsub, out);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ch_topk_merge(const int64_t *idx_lists, const int32_t *dist_lists, int32_t nlists, int64_t Qn, int32_t k,
+                             int64_t *out_idx, int32_t *out_dist, void *stream) {
+    CH_REQUIRE(nlists >= 1 && k >= 1 && Qn >= 0, "topk_merge: bad sizes");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(idx_lists && dist_lists && out_idx && out_dist, "topk_merge: null pointer");
+    hipLaunchKernelGGL(topk_merge_lists_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, (hipStream_t)stream, idx_lists,
+                       dist_lists, nlists, Qn, k, out_idx, out_dist);
+    CH_LAUNCH_CHECK();
+    return 0;
+}

@@ -3,7 +3,7 @@ gallery-sharded multi-GPU variants (one process per GPU, RCCL via ``torch.distri
 
 Replaces the reference's un-vendored ``utils.hashing`` arithmetic (call sites experiments/test_hashing.py:106-119,
 153-162).  PyTorch supplies device buffers, streams and collectives; all per-pair arithmetic runs in
-``csrc/hamming.hip``.  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
+``csrc/hamming_topk.hip`` (top-k search) and ``csrc/hamming.hip`` (distance matrix, mAP).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
 """
 from __future__ import annotations
 
@@ -59,20 +59,35 @@ def hamming_dist(q: torch.Tensor, g: torch.Tensor, stream=None) -> torch.Tensor:
     return out
 
 
-def hamming_topk(q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Top-k by ascending (distance, gallery index): (idx int64 [Qn,k], dist int32 [Qn,k]); -1 where k > G."""
+def _check_mask(mask: torch.Tensor, Qn: int, W: int, device, whose: str) -> Tuple[torch.Tensor, int]:
+    """A query mask, int64 [W] (one for all queries) or [Qn, W] (one per query) -> (contiguous mask, its row stride: 0 or W)."""
+    if mask.dtype != torch.int64 or mask.device != device or tuple(mask.shape) not in ((W,), (Qn, W)):
+        raise ValueError(f"mask must be an int64 tensor [{W}] or [{Qn}, {W}] on the {whose}' device, got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+    return mask.contiguous(), 0 if mask.dim() == 1 else W
+
+
+def _topk(entry: str, q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int, stream, operands=(),
+          workspace: str = "ch_hamming_topk_workspace") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The call of a ch_hamming_topk* entry on checked codes: allocates idx / dist / the workspace; `operands` are the entry's own
+    arguments, between q and Qn."""
     lib = _lib.load()
-    q, g = _check_packed(q, g)
     Qn, W = q.shape
     G = g.shape[0]
     idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
     dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
-    wsb = int(lib.ch_hamming_topk_workspace(Qn, G, W, k))
+    wsb = int(getattr(lib, workspace)(Qn, G, W, k))
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     with _dev_guard(q):
-        _lib.check(lib.ch_hamming_topk(_lib.ptr(q), Qn, _lib.ptr(g), G, W, k, int(g_index_base), _lib.ptr(idx),
-                                       _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), "ch_hamming_topk")
+        _lib.check(getattr(lib, entry)(_lib.ptr(q), *operands, Qn, _lib.ptr(g), G, W, k, int(g_index_base), _lib.ptr(idx), _lib.ptr(dist),
+                                       _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), entry)
     return idx, dist
+
+
+def hamming_topk(q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k by ascending (distance, gallery index): (idx int64 [Qn,k], dist int32 [Qn,k]); -1 where k > G."""
+    q, g = _check_packed(q, g)
+    return _topk("ch_hamming_topk", q, g, k, g_index_base, stream)
 
 
 def hamming_topk_masked(q: torch.Tensor, g: torch.Tensor, mask: torch.Tensor, k: int, g_index_base: int = 0,
@@ -80,24 +95,9 @@ def hamming_topk_masked(q: torch.Tensor, g: torch.Tensor, mask: torch.Tensor, k:
     """hamming_topk with dist = popcount((q ^ g) & mask).  mask: int64 [W] (one mask for all queries, e.g. `concept_mask`) or
     [Qn, W] (one per query, e.g. `confidence_mask`).  Bits of the last word past nbit count unless the codes or the mask clear them
     (`pack_sign` leaves them zero)."""
-    lib = _lib.load()
     q, g = _check_packed(q, g)
-    Qn, W = q.shape
-    G = g.shape[0]
-    if mask.dtype != torch.int64 or mask.device != q.device or tuple(mask.shape) not in ((W,), (Qn, W)):
-        raise ValueError(f"mask must be an int64 tensor [{W}] or [{Qn}, {W}] on the queries' device, got {mask.dtype} "
-                         f"{tuple(mask.shape)} on {mask.device}")
-    mask = mask.contiguous()
-    stride = 0 if mask.dim() == 1 else W
-    idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
-    dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
-    wsb = int(lib.ch_hamming_topk_workspace(Qn, G, W, k))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    with _dev_guard(q):
-        _lib.check(lib.ch_hamming_topk_masked(_lib.ptr(q), _lib.ptr(mask), stride, Qn, _lib.ptr(g), G, W, k, int(g_index_base),
-                                              _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)),
-                   "ch_hamming_topk_masked")
-    return idx, dist
+    mask, stride = _check_mask(mask, q.shape[0], q.shape[1], q.device, "queries")
+    return _topk("ch_hamming_topk_masked", q, g, k, g_index_base, stream, (_lib.ptr(mask), stride))
 
 
 WEIGHT_BITS = (4, 8)
@@ -118,11 +118,7 @@ def weight_planes(codes: torch.Tensor, bits: int = 8, mask: Optional[torch.Tenso
     W = (nbit + 63) // 64
     stride = 0
     if mask is not None:
-        if mask.dtype != torch.int64 or mask.device != codes.device or tuple(mask.shape) not in ((W,), (Qn, W)):
-            raise ValueError(f"mask must be an int64 tensor [{W}] or [{Qn}, {W}] on the codes' device, got {mask.dtype} "
-                             f"{tuple(mask.shape)} on {mask.device}")
-        mask = mask.contiguous()
-        stride = 0 if mask.dim() == 1 else W
+        mask, stride = _check_mask(mask, Qn, W, codes.device, "codes")
     planes = torch.empty(Qn, int(bits), W, dtype=torch.int64, device=codes.device)
     wsum = torch.empty(Qn, dtype=torch.int32, device=codes.device)
     with _dev_guard(codes):
@@ -135,24 +131,15 @@ def hamming_topk_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor
                           stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """hamming_topk with dist = sum_p 2^p popcount((q ^ g) & planes[:, p]): the weighted distance of `weight_planes(codes)` with
     q = pack_sign(codes).  Lists of gallery shards merge with `topk_merge` as the unweighted ones do."""
-    lib = _lib.load()
     q, g = _check_packed(q, g)
     Qn, W = q.shape
-    G = g.shape[0]
     if planes.dtype != torch.int64 or planes.device != q.device or planes.dim() != 3 or planes.shape[0] != Qn or planes.shape[2] != W \
             or planes.shape[1] not in WEIGHT_BITS:
         raise ValueError(f"planes must be an int64 tensor [{Qn}, 4 or 8, {W}] on the queries' device, got {planes.dtype} "
                          f"{tuple(planes.shape)} on {planes.device}")
     planes = planes.contiguous()
-    idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
-    dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
-    wsb = int(lib.ch_hamming_topk_weighted_workspace(Qn, G, W, k))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
-    with _dev_guard(q):
-        _lib.check(lib.ch_hamming_topk_weighted(_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W, k,
-                                                int(g_index_base), _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb,
-                                                _lib.stream_ptr(stream)), "ch_hamming_topk_weighted")
-    return idx, dist
+    return _topk("ch_hamming_topk_weighted", q, g, k, g_index_base, stream, (_lib.ptr(planes), planes.shape[1]),
+                 workspace="ch_hamming_topk_weighted_workspace")
 
 
 def subcode_dist(q: torch.Tensor, g: torch.Tensor, idx: torch.Tensor, nbit: int, nsub: int, g_index_base: int = 0,

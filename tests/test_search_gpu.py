@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import weighted_topk_ref as wref
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -150,6 +151,39 @@ def test_masked_topk_orders_heavy_ties_by_gallery_index(dev):
         assert len(np.unique(d)) in (3, 4)
         for k in (10, 40, 128):
             assert _same(rt.hamming_topk_masked(_t(q, dev), _t(g, dev), _t(mask, dev), k), _ref_topk(d, k)), k
+
+
+# ---- the scan body the three distances share ---------------------------------------------------------------------------------------
+
+SCAN_EXIT_G = tuple(base + g for base in (0, 256) for g in (1, 3, 4, 5, 8, 11, 12, 13))
+
+
+@pytest.mark.parametrize("W", [1, 3])
+def test_scan_exits_agree_for_plain_masked_and_weighted(dev, W):
+    """topk_scan's ways out of a segment, for the three distances at once: segments of 1 and 3 rows (no whole four-row block), 4 and 5
+    (one: the odd-block exit), 8 and 11 (two), 12 and 13 (three), i.e. remainders of 0, 1 and 3 rows after none, an odd and an even
+    number of whole blocks; with 256 more rows the same tails follow a full segment of 64 blocks (segments hold 256 rows at these
+    sizes) and the merge joins the two.  70 queries leave lanes past Qn in the second wave.  (distance, index) exactly."""
+    from concepthash_amd import retrieval as rt
+    nbit, Qn, k, Gmax = 64 * W, 70, 10, max(SCAN_EXIT_G)
+    rng = np.random.default_rng(700 + W)
+    c = rng.standard_normal((Qn, nbit)).astype(np.float32)
+    q, g = wref.pack_sign(c), _codes(rng, Gmax, nbit)
+    mask = _codes(rng, Qn, nbit)
+    t, gq, gg, gm = _t(c, dev), _t(q, dev), _t(g, dev), _t(mask, dev)
+    assert np.array_equal(rt.pack_sign(t).cpu().numpy().view(np.uint64), q)
+    d_plain, d_masked = _ref_dist(q, g), _ref_dist(q, g, mask)          # once, for the longest gallery: a row's distance is its own
+    weighted = {}
+    for bits in (4, 8):
+        w = wref.weights(c, bits)
+        planes, _ = rt.weight_planes(t, bits)
+        assert np.array_equal(planes.cpu().numpy().view(np.uint64), wref.planes_of(w, bits))
+        weighted[bits] = (planes, wref.dist(q, g, w))
+    for G in SCAN_EXIT_G:
+        assert _same(rt.hamming_topk(gq, gg[:G], k), _ref_topk(d_plain[:, :G], k)), ("plain", G)
+        assert _same(rt.hamming_topk_masked(gq, gg[:G], gm, k), _ref_topk(d_masked[:, :G], k)), ("masked", G)
+        for bits, (planes, D) in weighted.items():
+            assert _same(rt.hamming_topk_weighted(gq, planes, gg[:G], k), wref.topk(D[:, :G], k)), (bits, G)
 
 
 # ---- per-sub-code distances --------------------------------------------------------------------------------------------------------

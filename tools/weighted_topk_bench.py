@@ -2,7 +2,7 @@
 """Weighted (asymmetric) against plain Hamming top-k (profiles/search_weighted_topk.txt):
     python tools/weighted_topk_bench.py [--out FILE] [--asm FILE.s]
 1. Registers: VGPRs and scratch bytes of every topk_weighted_partial_kernel<W, KREG, P> instance, from the code-object metadata
-   (`amdhsa.kernels`) of csrc/hamming_weighted.hip compiled to assembly for gfx950 -- compiled here, or read from --asm.
+   (`amdhsa.kernels`) of csrc/hamming_topk.hip compiled to assembly for gfx950 -- compiled here, or read from --asm.
 2. Timing: hamming_topk, hamming_topk_weighted with 4-bit and with 8-bit weights, k = 10, at 5,794 x 5,994 x 64 bit and
    16,384 x 1M x 128 bit; one process, the three variants taking turns over --rounds rounds of --calls calls each (torch.cuda.Event
    around a round's calls, warm-ups excluded); the median round in microseconds per call and the ratios to the unweighted scan.
@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default="")
-ap.add_argument("--asm", default="", help="assembly of csrc/hamming_weighted.hip (hipcc --cuda-device-only -S); default: compile it")
+ap.add_argument("--asm", default="", help="assembly of csrc/hamming_topk.hip (hipcc --cuda-device-only -S); default: compile it")
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--calls", type=int, default=10)
 ap.add_argument("--rounds", type=int, default=3)
@@ -33,9 +33,9 @@ def register_table(asm_path):
     from concepthash_amd import build
     if not asm_path:
         tmp = tempfile.mkdtemp()
-        asm_path = os.path.join(tmp, "hamming_weighted.s")
+        asm_path = os.path.join(tmp, "hamming_topk.s")
         subprocess.run([build._hipcc()] + build.FLAGS + ["-I", build.CSRC, "--cuda-device-only", "-S", "-o", asm_path,
-                        os.path.join(build.CSRC, "hamming_weighted.hip")], check=True, capture_output=True)
+                        os.path.join(build.CSRC, "hamming_topk.hip")], check=True, capture_output=True)
     text = open(asm_path).read()
     meta = text[text.index("amdhsa.kernels:"):]
     rows = {}
