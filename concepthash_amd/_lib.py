@@ -138,6 +138,26 @@ SIGNATURES = {
     "ch_debug_wgrad": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_debug_ln_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_debug_act": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "ch_debug_hb_stats": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ch_debug_normalize_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),
+    "ch_debug_colsum": (c_int, [c_void_p, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
+    "ch_debug_reduce_partials_multi": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "ch_debug_transpose_f32_to_bf16": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "ch_debug_transpose_bf16": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "ch_debug_adapter_refresh": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "ch_debug_adapter_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int64,
+                                       c_void_p]),
+    "ch_debug_fold_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_void_p), POINTER(c_void_p),
+                                    POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    "ch_debug_embed_bwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                   c_void_p]),
+    "ch_debug_small_ln_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "ch_debug_token_rows_sum": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_concept_rows_sum": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_scatter_concept_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ch_debug_expand_head_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_gather_concept_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_hamming_hist_prefix": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,

@@ -193,7 +193,8 @@ extern "C" int ch_debug_wgrad(const void *A, int32_t lda, const void *Bm, int32_
     return e;
 }
 // row statistics of x are computed here (hb_stats on an fp32 copy is what the chain does; the tap takes bf16 x and derives the
-// partials from it through an fp32 round trip), then ln_bwd; xhat_out (optional) receives normalize(x)
+// partials from it through an fp32 round trip), then ln_bwd; xhat_out (optional) is ln_bwd's own by-product store of x_hat, as the
+// training step takes it (normalize has a tap of its own, ch_debug_normalize_bf16)
 extern "C" int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int32_t D, float eps, const float *dres_in, float *dres_out,
                                void *out_b, void *xhat_out, void *stream) {
     CH_REQUIRE(dyg && x && dres_in, "debug_ln_bwd: null argument");
@@ -208,8 +209,7 @@ extern "C" int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int
         CH_CHECK_HIP(hipMemcpy2DAsync((char *)xf + 2, 4, x, 2, 2, (size_t)rows * D, hipMemcpyDeviceToDevice, s));
     }
     e = ch_hb_stats(xf, rows, D, hb, st, s);
-    if (!e) e = ch_ln_bwd((const bf16_t *)dyg, (const bf16_t *)x, st, rows, D, eps, dres_in, dres_out, (bf16_t *)out_b, s);
-    if (!e && xhat_out) e = ch_normalize_bf16((const bf16_t *)x, st, rows, D, eps, (bf16_t *)xhat_out, s);
+    if (!e) e = ch_ln_bwd((const bf16_t *)dyg, (const bf16_t *)x, st, rows, D, eps, dres_in, dres_out, (bf16_t *)out_b, s, (bf16_t *)xhat_out);
     (void)hipStreamSynchronize(s);
     return e;
 }
@@ -218,4 +218,109 @@ extern "C" int ch_debug_act(const void *g, const void *pre, int64_t n, int32_t a
     CH_REQUIRE(pre && out, "debug_act: null argument");
     if (backward) return ch_act_bwd((const bf16_t *)g, (const bf16_t *)pre, n, act, scale_ptr, (bf16_t *)out, (hipStream_t)stream);
     return ch_act_fwd((const bf16_t *)pre, n, act, (bf16_t *)out, (hipStream_t)stream);
+}
+
+// ---- the training step's row, reduction and gradient-assembly launchers, each by itself (tests/test_train_rowkernels_gpu.py) ------
+// One launcher per tap, on caller buffers; a tap allocates only the workspace its launcher asks for and waits for the stream
+// before that workspace is released.
+extern "C" int ch_debug_hb_stats(const float *H, int64_t rows, int32_t D, void *hb, float *stats, void *stream) {
+    CH_REQUIRE(H && hb && stats && rows > 0, "debug_hb_stats: null argument");
+    return ch_hb_stats(H, rows, D, (bf16_t *)hb, stats, (hipStream_t)stream);
+}
+extern "C" int ch_debug_normalize_bf16(const void *x, const float *stats, int64_t rows, int32_t D, float eps, void *out, void *stream) {
+    CH_REQUIRE(x && stats && out && rows > 0, "debug_normalize_bf16: null argument");
+    return ch_normalize_bf16((const bf16_t *)x, stats, rows, D, eps, (bf16_t *)out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_colsum(const void *A, int32_t is_f32, int32_t lda, int64_t rows, int32_t N, float *out, void *stream) {
+    CH_REQUIRE(A && out && rows > 0 && N > 0 && lda >= N, "debug_colsum: null argument or empty problem");
+    ChDeviceTemp ws;
+    if (ws.get(sizeof(float) * ch_colsum_ws_floats(N))) return 1;
+    const int e = ch_colsum(A, is_f32, lda, rows, N, out, ws.as<float>(), (hipStream_t)stream);
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    return e;
+}
+// job j: out[j][0 .. 4 * n4[j]) = sum over c < nchunks[j] of partial[j][c][.]; the four arrays are host arrays of njobs entries
+extern "C" int ch_debug_reduce_partials_multi(int32_t njobs, const float *const *partial, float *const *out, const int32_t *nchunks,
+                                              const int32_t *n4, void *stream) {
+    CH_REQUIRE(njobs >= 1 && njobs <= 4 && partial && out && nchunks && n4, "debug_reduce_partials_multi: 1..4 jobs, no null array");
+    ChReduceJob jobs[4];
+    for (int j = 0; j < njobs; ++j) {
+        CH_REQUIRE(partial[j] && out[j] && nchunks[j] >= 1 && n4[j] >= 1, "debug_reduce_partials_multi: empty job");
+        jobs[j] = ChReduceJob{partial[j], out[j], nchunks[j], n4[j]};
+    }
+    return ch_reduce_partials_multi(jobs, njobs, (hipStream_t)stream);
+}
+extern "C" int ch_debug_transpose_f32_to_bf16(const float *src, int32_t R, int32_t C, int32_t ld_src, const float *colscale, void *dst,
+                                              int32_t ld_dst, void *stream) {
+    CH_REQUIRE(src && dst && R > 0 && C > 0 && ld_src >= C && ld_dst >= R, "debug_transpose_f32_to_bf16: null argument or short leading dimension");
+    return ch_transpose_f32_to_bf16(src, R, C, ld_src, colscale, (bf16_t *)dst, ld_dst, (hipStream_t)stream);
+}
+extern "C" int ch_debug_transpose_bf16(const void *src, int32_t R, int32_t C, int32_t ld_src, void *dst, int32_t ld_dst, void *stream) {
+    CH_REQUIRE(src && dst && R > 0 && C > 0 && ld_src >= C && ld_dst >= R, "debug_transpose_bf16: null argument or short leading dimension");
+    return ch_transpose_bf16((const bf16_t *)src, R, C, ld_src, (bf16_t *)dst, ld_dst, (hipStream_t)stream);
+}
+extern "C" int ch_debug_adapter_refresh(const float *params, int64_t stride, int32_t nad, int32_t D, int32_t b, int32_t bpad, void *down_wf,
+                                        float *fold_c, float *fold_d, void *up_w, void *up_wT, void *down_wgT, void *stream) {
+    CH_REQUIRE(params && down_wf && fold_c && fold_d && up_w && up_wT && down_wgT, "debug_adapter_refresh: null argument");
+    CH_REQUIRE(nad >= 1 && D > 0 && b > 0 && bpad >= b, "debug_adapter_refresh: empty problem or bpad < b");
+    return ch_adapter_refresh(params, stride, nad, D, b, bpad, (bf16_t *)down_wf, fold_c, fold_d, (bf16_t *)up_w, (bf16_t *)up_wT,
+                              (bf16_t *)down_wgT, (hipStream_t)stream);
+}
+extern "C" int ch_debug_adapter_grads(const float *G, const float *cu, const float *T, const float *cd, const float *params, int32_t D, int32_t b,
+                                      int32_t bpad, float *grads, int32_t nad, int64_t stride, void *stream) {
+    CH_REQUIRE(G && cu && T && cd && params && grads, "debug_adapter_grads: null argument");
+    CH_REQUIRE(nad >= 1 && D > 0 && b > 0 && bpad >= b, "debug_adapter_grads: empty problem or bpad < b");
+    ChDeviceTemp ws;
+    if (ws.get(sizeof(float) * ch_adapter_grads_ws_floats(nad))) return 1;
+    const int e = ch_adapter_grads(G, cu, T, cd, params, D, b, bpad, grads, ws.as<float>(), (hipStream_t)stream, nad, stride);
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    return e;
+}
+// W / dW / db: host arrays of nparts device pointers (the row blocks' own allocations)
+extern "C" int ch_debug_fold_grads(const float *T, const float *c, const float *gamma, const float *beta, int32_t D, int32_t nparts,
+                                   int32_t rows_each, const float *const *W, float *const *dW, float *const *db, float *dgamma, float *dbeta,
+                                   void *stream) {
+    CH_REQUIRE(T && c && gamma && beta && W && dW && db && dgamma && dbeta, "debug_fold_grads: null argument");
+    CH_REQUIRE(nparts >= 1 && nparts <= 3 && rows_each >= 1, "debug_fold_grads: 1..3 row blocks of at least one row");
+    ChFoldGradParts parts{};
+    parts.nparts = nparts;
+    parts.rows_each = rows_each;
+    for (int p = 0; p < nparts; ++p) {
+        CH_REQUIRE(W[p] && dW[p] && db[p], "debug_fold_grads: null row block");
+        parts.W[p] = W[p];
+        parts.dW[p] = dW[p];
+        parts.db[p] = db[p];
+    }
+    return ch_fold_grads(T, c, gamma, beta, D, parts, dgamma, dbeta, (hipStream_t)stream);
+}
+extern "C" int ch_debug_embed_bwd(float *X, float *dY, int32_t B, int32_t ntok, int32_t np, int32_t D, const float *cls_pos0, const float *ctx,
+                                  const float *gamma, float eps, void *dx_patch, void *stream) {
+    CH_REQUIRE(X && dY && cls_pos0 && ctx && gamma && dx_patch, "debug_embed_bwd: null argument");
+    CH_REQUIRE(B >= 1 && np >= 1 && ntok > 1 + np, "debug_embed_bwd: ntok must be 1 + np + the number of concept rows (>= 1)");
+    return ch_embed_bwd(X, dY, B, ntok, np, D, cls_pos0, ctx, gamma, eps, (bf16_t *)dx_patch, (hipStream_t)stream);
+}
+extern "C" int ch_debug_small_ln_bwd(const float *dy, const float *x, const float *gamma, int32_t rows, int32_t D, float eps, float *dx,
+                                     void *stream) {
+    CH_REQUIRE(dy && x && gamma && dx && rows >= 1 && D >= 1, "debug_small_ln_bwd: null argument or empty problem");
+    return ch_small_ln_bwd(dy, x, gamma, rows, D, eps, dx, (hipStream_t)stream);
+}
+extern "C" int ch_debug_token_rows_sum(const float *dX, int32_t B, int32_t ntok, int32_t nrows, int32_t D, float *out, void *stream) {
+    CH_REQUIRE(dX && out && B >= 1 && nrows >= 1 && nrows <= ntok && D >= 1, "debug_token_rows_sum: null argument or nrows outside 1..ntok");
+    return ch_token_rows_sum(dX, B, ntok, nrows, D, out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_concept_rows_sum(const float *dH, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *out, void *stream) {
+    CH_REQUIRE(dH && out && B >= 1 && Q >= 1 && Q <= ntok && D >= 1, "debug_concept_rows_sum: null argument or Q outside 1..ntok");
+    return ch_concept_rows_sum(dH, B, ntok, Q, D, out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_scatter_concept_rows(const float *dhf, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *dH, void *dHb, void *stream) {
+    CH_REQUIRE(dhf && dH && dHb && B >= 1 && Q >= 1 && Q <= ntok && D >= 1, "debug_scatter_concept_rows: null argument or Q outside 1..ntok");
+    return ch_scatter_concept_rows(dhf, B, ntok, Q, D, dH, (bf16_t *)dHb, (hipStream_t)stream);
+}
+extern "C" int ch_debug_expand_head_rows(const void *src, int32_t is_f32, int32_t B, int32_t ntok, int32_t Q, int32_t D, void *dst, void *stream) {
+    CH_REQUIRE(src && dst && B >= 1 && Q >= 1 && Q < ntok && D >= 1, "debug_expand_head_rows: null argument or Q outside 1..ntok-1");
+    return ch_expand_head_rows(src, is_f32, B, ntok, Q, D, dst, (hipStream_t)stream);
+}
+extern "C" int ch_debug_gather_concept_rows(const float *H, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *out, void *stream) {
+    CH_REQUIRE(H && out && B >= 1 && Q >= 1 && Q <= ntok && D >= 1, "debug_gather_concept_rows: null argument or Q outside 1..ntok");
+    return ch_gather_concept_rows(H, B, ntok, Q, D, out, (hipStream_t)stream);
 }

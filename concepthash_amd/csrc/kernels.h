@@ -267,7 +267,8 @@ int ch_transpose_bf16(const bf16_t *src, int R, int C, int ld_src, bf16_t *dst, 
 // gradients of one adapter's parameters from G = dH^T g [D, bpad], cu = colsum(dH), T = dpre^T x_hat [bpad, D], cd = colsum(dpre);
 // params / grads: one adapter's block of the arena ([ln_w D][ln_b D][down_w b*D][down_b b][up_w D*b][up_b D][scale 1])
 int ch_adapter_grads(const float *G, const float *cu, const float *T, const float *cd, const float *params, int D, int b, int bpad,
-                     float *grads, float *ws /* >= 256 floats per adapter */, hipStream_t s, int nad = 1, int64_t stride = 0);
+                     float *grads, float *ws /* ch_adapter_grads_ws_floats(nad) floats */, hipStream_t s, int nad = 1, int64_t stride = 0);
+size_t ch_adapter_grads_ws_floats(int nad);
 // nad > 1: slot arrays (G / T stride D * bpad, cu D, cd bpad, params / grads `stride`, ws 256), one launch pair for all of them
 // bf16 / LayerNorm-folded / transposed working copies of `nad` adapters from the parameter arena (slot arrays, one slot per adapter)
 int ch_adapter_refresh(const float *params, int64_t stride, int nad, int D, int b, int bpad, bf16_t *down_wf, float *fold_c, float *fold_d,

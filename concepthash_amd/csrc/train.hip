@@ -681,7 +681,7 @@ extern "C" int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *param
             t->Ts[ch] = (float *)talloc(t, sizeof(float) * nad * bpad * D, ok);
             t->cus[ch] = (float *)talloc(t, sizeof(float) * nad * D, ok);
             t->cds[ch] = (float *)talloc(t, sizeof(float) * nad * bpad, ok);
-            t->ws_ag[ch] = (float *)talloc(t, sizeof(float) * nad * 256, ok);
+            t->ws_ag[ch] = (float *)talloc(t, sizeof(float) * ch_adapter_grads_ws_floats(nad), ok);
         }
         t->G[ch] = (float *)talloc(t, sizeof(float) * (size_t)D * bpad, ok);
         t->T[ch] = (float *)talloc(t, sizeof(float) * (size_t)bpad * D, ok);

@@ -930,6 +930,7 @@ int ch_adapter_grads(const float *G, const float *cu, const float *T, const floa
     CH_LAUNCH_CHECK();
     return 0;
 }
+size_t ch_adapter_grads_ws_floats(int nad) { return (size_t)AG_BLOCKS * nad; }
 int ch_reduce_partials_multi(const ChReduceJob *jobs, int njobs, hipStream_t s) {
     CH_REQUIRE(njobs >= 1 && njobs <= 4, "reduce_partials_multi: 1..4 jobs");
     ReduceJobsArg a{};

@@ -92,6 +92,38 @@ int ch_debug_ln_bwd(const void *dyg, const void *x, int64_t rows, int32_t D, flo
 int ch_debug_act(const void *g, const void *pre, int64_t n, int32_t act, const float *scale_ptr, int32_t backward, void *out,
                  void *stream);
 
+/* The training step's row, reduction and gradient-assembly launchers of train_kernels.hip, one launch sequence each on caller buffers
+ * (tests/test_train_rowkernels_gpu.py holds every one to an fp64 restatement, tests/train_kernels_ref.py).  bf16 buffers are void *.
+ * hb_stats: hb = bf16(H), stats [rows, D/64, 2] = (sum, sum of squares) of the ROUNDED values per 64-column slice.
+ * normalize_bf16: out = bf16((x - mean) * rstd) with (mean, rstd) from `stats`.  colsum: out[n] = sum_m A[m * lda + n].
+ * reduce_partials_multi: host arrays of njobs (1..4) entries; out[j][i] = sum_c partial[j][c * 4 n4[j] + i].
+ * transposes: dst[c * ld_dst + r] = bf16(src[r * ld_src + c] * (colscale ? colscale[c] : 1)).
+ * adapter_refresh / adapter_grads: `nad` adapters `stride` floats apart in the arena ([ln_w D][ln_b D][down_w b*D][down_b b]
+ * [up_w D*b][up_b D][scale 1]); the other arrays hold one slot per adapter.  fold_grads: W / dW / db are host arrays of nparts (1..3)
+ * device pointers.  embed_bwd: X and dY are replaced in place.  The last five are the row moves and row sums of the concept tokens. */
+int ch_debug_hb_stats(const float *H, int64_t rows, int32_t D, void *hb, float *stats, void *stream);
+int ch_debug_normalize_bf16(const void *x, const float *stats, int64_t rows, int32_t D, float eps, void *out, void *stream);
+int ch_debug_colsum(const void *A, int32_t is_f32, int32_t lda, int64_t rows, int32_t N, float *out, void *stream);
+int ch_debug_reduce_partials_multi(int32_t njobs, const float *const *partial, float *const *out, const int32_t *nchunks, const int32_t *n4,
+                                   void *stream);
+int ch_debug_transpose_f32_to_bf16(const float *src, int32_t R, int32_t C, int32_t ld_src, const float *colscale, void *dst, int32_t ld_dst,
+                                   void *stream);
+int ch_debug_transpose_bf16(const void *src, int32_t R, int32_t C, int32_t ld_src, void *dst, int32_t ld_dst, void *stream);
+int ch_debug_adapter_refresh(const float *params, int64_t stride, int32_t nad, int32_t D, int32_t b, int32_t bpad, void *down_wf, float *fold_c,
+                             float *fold_d, void *up_w, void *up_wT, void *down_wgT, void *stream);
+int ch_debug_adapter_grads(const float *G, const float *cu, const float *T, const float *cd, const float *params, int32_t D, int32_t b,
+                           int32_t bpad, float *grads, int32_t nad, int64_t stride, void *stream);
+int ch_debug_fold_grads(const float *T, const float *c, const float *gamma, const float *beta, int32_t D, int32_t nparts, int32_t rows_each,
+                        const float *const *W, float *const *dW, float *const *db, float *dgamma, float *dbeta, void *stream);
+int ch_debug_embed_bwd(float *X, float *dY, int32_t B, int32_t ntok, int32_t np, int32_t D, const float *cls_pos0, const float *ctx,
+                       const float *gamma, float eps, void *dx_patch, void *stream);
+int ch_debug_small_ln_bwd(const float *dy, const float *x, const float *gamma, int32_t rows, int32_t D, float eps, float *dx, void *stream);
+int ch_debug_token_rows_sum(const float *dX, int32_t B, int32_t ntok, int32_t nrows, int32_t D, float *out, void *stream);
+int ch_debug_concept_rows_sum(const float *dH, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *out, void *stream);
+int ch_debug_scatter_concept_rows(const float *dhf, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *dH, void *dHb, void *stream);
+int ch_debug_expand_head_rows(const void *src, int32_t is_f32, int32_t B, int32_t ntok, int32_t Q, int32_t D, void *dst, void *stream);
+int ch_debug_gather_concept_rows(const float *H, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

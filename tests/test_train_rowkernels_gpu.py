@@ -1,0 +1,472 @@
+"""GPU: the training step's row, reduction and gradient-assembly kernels (train_kernels.hip), each launched alone through its tap
+(include/concepthash_hip_debug.h) and held, element by element, to the fp64 restatement and the bound DERIVED in
+tests/train_kernels_ref.py (nothing tuned to a measured error); pure row moves, fp32 copies and bf16 copies bit for bit.
+tests/test_train_kernels_ref_cpu.py shows on the CPU that the bounds are sound and that each deliberate defect breaches them.
+
+Every launch: each output lies between two guard blocks of a sentinel (a NaN bit pattern no kernel produces) that must come back
+untouched, and starts as the sentinel itself, so an element the kernel failed to write is seen; every input is followed by NaN inside
+the same allocation (none of these kernels may read past its operands: finite results show they did not); a second identical launch
+must give identical bytes (every reduction here has a fixed order).  Every test prints its worst error / bound ratio (-s).
+
+Worst error / bound ratios measured on an MI355X (1.0 is the bound; no kernel breached one, no kernel was changed):
+  hb_stats 0.436 (hb bit-exact)    normalize 1.000            ln_bwd 0.759, out_b 1.000, x_hat 1.000 (ln_bwd_kernel's own
+  by-product store, which ch_debug_ln_bwd passes through; not normalize_kernel)                           small_ln_bwd 0.081
+  embed_bwd X 0.256, dY 0.226, compact patch rows 1.000       colsum fp32 0.113, bf16 0.009               reduce_partials_multi 0.276
+  adapter_refresh c 0.013, d 0.046 (the four bf16 copies bit-exact)       token_rows_sum 0.582, concept_rows_sum 0.588
+  adapter_grads ln_w 0.090, ln_b 0.034, down_w 0.952, down_b 0 (a copy), up_w 0.956, up_b 0.943, scale 0.066
+  fold_grads dW 0.893, dgamma 0.106, dbeta 0.019 (db bit-exact)           transposes and row moves bit-exact
+A bf16 output sits at 1.000 where the fp32 value falls on a rounding tie (error = the half ulp that IS the bound); down_w, up_w, up_b
+and dW are one or two fp32 products, whose whole bound is their two or three roundings.
+Statistics path (row_mean_rstd behind hb_stats), relative error of rstd read back through ln_bwd, 37 rows:
+  benign rows:                        1.1e-7 / 1.4e-7 / 1.1e-7 at D = 128 / 384 / 1280   (derived bound 8e-7)
+  offset rows (mean +-200..206, sd 1): 1.0e-7 / 1.7e-3 / 2.2e-3                           (derived bound 6e-2, cancellation factor 9e4)
+The offset figure is the fp32 cancellation in var = sq/D - mean^2 that the bound carries; it is 20 times below what the end-to-end
+tests allow (4e-2), and a residual stream with |mean| = 200 sd does not occur in the model, so the kernels stay as they are.
+"""
+import ctypes
+
+import pytest
+import torch
+
+import train_kernels_ref as tr
+
+pytestmark = pytest.mark.gpu
+
+SENT32 = 0x7FC1BEEF                      # fp32 / bf16 NaN bit patterns no kernel produces
+SENT16 = 0x7FC1
+GUARD = 64                               # elements on either side of an output
+TAIL = 64                                # NaN elements behind an input
+_worst = {}
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def L():
+    from concepthash_amd import _lib
+    _lib.load()
+    return _lib
+
+
+class Out:
+    """an output of `shape` (fp32 or bf16) between guards, all of it the sentinel; `init` (in / out operands) replaces the payload"""
+
+    def __init__(self, dev, shape, dtype, init=None):
+        self.shape, self.dtype = tuple(shape), dtype
+        self.n = 1
+        for s in self.shape:
+            self.n *= s
+        self.it, self.sent = (torch.int32, SENT32) if dtype == torch.float32 else (torch.int16, SENT16)
+        self.buf = torch.full((self.n + 2 * GUARD,), self.sent, dtype=self.it, device=dev)
+        if init is not None:
+            self.buf[GUARD:GUARD + self.n] = init.contiguous().view(self.it).reshape(-1).to(dev)
+
+    @property
+    def ptr(self):
+        return ctypes.c_void_p(self.buf.data_ptr() + GUARD * self.buf.element_size())
+
+    def raw(self):
+        """the payload's bits on the CPU, after checking the guards"""
+        b = self.buf.cpu()
+        assert bool((b[:GUARD] == self.sent).all()) and bool((b[GUARD + self.n:] == self.sent).all()), "a guard block was written"
+        return b[GUARD:GUARD + self.n].view(self.shape)
+
+    def get(self):
+        return self.raw().view(self.dtype)
+
+    def untouched(self, mask):
+        """True when every payload element under `mask` (CPU bool tensor of the payload's shape) is still the sentinel"""
+        return bool((self.raw()[mask] == self.sent).all())
+
+
+def inp(dev, x):
+    """x on the device, followed by TAIL NaN elements in the same allocation (returns the view of x; the base stays alive through it)"""
+    buf = torch.full((x.numel() + TAIL,), float("nan"), dtype=x.dtype)
+    buf[:x.numel()] = x.reshape(-1)
+    return buf.to(dev)[:x.numel()].view(x.shape)
+
+
+def twice(launch):
+    """launch() -> list of Out, run two times on fresh outputs: returns the first run's, asserts the second's bytes are the same"""
+    a = launch()
+    torch.cuda.synchronize()
+    b = launch()
+    torch.cuda.synchronize()
+    for x, y in zip(a, b):
+        assert torch.equal(x.raw(), y.raw()), "a second identical launch gave other bytes"
+    return a
+
+
+def note(group, ratio):
+    _worst[group] = max(_worst.get(group, 0.0), ratio)
+
+
+def report(*groups):
+    for g in groups:
+        print(f"WORST {g}: {_worst.get(g, 0.0):.3f}")
+
+
+def within(group, got, ref, bound, what):
+    note(group, tr.assert_within(got, ref, bound, f"{group} {what}", quiet=True))
+
+
+# ---- row kernels ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", tr.ROW_D)
+def test_hb_stats(dev, L, D):
+    lib = L.load()
+    for rows in tr.ROW_ROWS:
+        for fam in tr.ROW_FAMILIES:
+            H = tr.row_family(fam, rows, D)
+            hb_want, ref, bound = tr.hb_stats_ref(H)
+            Hd = inp(dev, H)
+
+            def launch():
+                hb, st = Out(dev, (rows, D), torch.bfloat16), Out(dev, (rows, D // 64, 2), torch.float32)
+                L.check(lib.ch_debug_hb_stats(L.ptr(Hd), rows, D, hb.ptr, st.ptr, L.stream_ptr()), "hb_stats")
+                return [hb, st]
+
+            hb, st = twice(launch)
+            assert tr.bits_equal(hb.get(), hb_want), f"hb {fam} {rows}x{D}: not the correctly rounded bf16"
+            within("hb_stats", st.get(), ref, bound, f"{fam} {rows}x{D}")
+    report("hb_stats")
+
+
+@pytest.mark.parametrize("D", tr.ROW_D)
+def test_normalize(dev, L, D):
+    lib = L.load()
+    for rows in tr.ROW_ROWS:
+        for fam in tr.ROW_FAMILIES:
+            x = tr.row_family(fam, rows, D).to(torch.bfloat16)
+            stats = tr.hb_stats_emul(x.float())[1]
+            ref, bound, _ = tr.normalize_ref(x, stats)
+            xd, sd = inp(dev, x), inp(dev, stats)
+
+            def launch():
+                out = Out(dev, (rows, D), torch.bfloat16)
+                L.check(lib.ch_debug_normalize_bf16(L.ptr(xd), L.ptr(sd), rows, D, tr.LN_EPS, out.ptr, L.stream_ptr()), "normalize")
+                return [out]
+
+            within("normalize", twice(launch)[0].get(), ref, bound, f"{fam} {rows}x{D}")
+    report("normalize")
+
+
+@pytest.mark.parametrize("D", tr.ROW_D)
+def test_ln_bwd(dev, L, D):
+    """modes: every output; dres_out aliasing dres_in; dres_out null; out_b null"""
+    lib = L.load()
+    for rows in tr.ROW_ROWS:
+        for fam in tr.ROW_FAMILIES:
+            g = tr.gen("ln_bwd", rows, D, fam)
+            x = tr.row_family(fam, rows, D).to(torch.bfloat16)
+            dyg = torch.randn(rows, D, generator=g).to(torch.bfloat16)
+            dres = torch.randn(rows, D, generator=g)
+            d, e_d, xh, e_xh, _ = tr.ln_bwd_ref(dyg, x, dres)
+            xd, gd, rd = inp(dev, x), inp(dev, dyg), inp(dev, dres)
+            what = f"{fam} {rows}x{D}"
+            for mode in ("all", "alias", "no_dres_out", "no_out_b"):
+                def launch():
+                    o32 = Out(dev, (rows, D), torch.float32, init=dres if mode == "alias" else None)
+                    ob, oh = Out(dev, (rows, D), torch.bfloat16), Out(dev, (rows, D), torch.bfloat16)
+                    p_in = o32.ptr if mode == "alias" else L.ptr(rd)
+                    p32 = None if mode == "no_dres_out" else o32.ptr
+                    pb = None if mode == "no_out_b" else ob.ptr
+                    L.check(lib.ch_debug_ln_bwd(L.ptr(gd), L.ptr(xd), rows, D, tr.LN_EPS, p_in, p32, pb, oh.ptr, L.stream_ptr()), "ln_bwd")
+                    return [o32, ob, oh]
+
+                o32, ob, oh = twice(launch)
+                within("ln_bwd x_hat", oh.get(), xh, e_xh, what)
+                if mode == "no_dres_out":
+                    assert o32.untouched(torch.ones(rows, D, dtype=torch.bool))
+                    within("ln_bwd out_b", ob.get(), d, tr.bf16_out(d, e_d), what)
+                else:
+                    within("ln_bwd", o32.get(), d, e_d, f"{what} {mode}")
+                if mode == "no_out_b":
+                    assert ob.untouched(torch.ones(rows, D, dtype=torch.bool))
+                elif mode != "no_dres_out":
+                    assert tr.bits_equal(ob.get(), o32.get().to(torch.bfloat16)), f"{what} {mode}: out_b is not the rounded dres_out"
+    report("ln_bwd", "ln_bwd out_b", "ln_bwd x_hat")
+
+
+def test_statistics_path_rstd_on_offset_rows(dev, L):
+    """rstd of row_mean_rstd as the GPU computes it, read back through ln_bwd with a one-hot dyg and dres_in = 0:
+    d[k] = rstd (1 - 1/D - x_hat[k]^2 / D) at the hot column k.  The figure is printed next to its derived bound; the assertion is the
+    element-wise one of test_ln_bwd."""
+    lib = L.load()
+    rows = 37
+    for D in tr.ROW_D:
+        for fam in ("benign", "offset"):
+            x = tr.row_family(fam, rows, D).to(torch.bfloat16)
+            dyg = torch.zeros(rows, D, dtype=torch.bfloat16)
+            k = (torch.arange(rows) * 13 + 3) % D
+            dyg[torch.arange(rows), k] = 1.0
+            dres = torch.zeros(rows, D)
+            d, e_d, xh, _, (R, e_r, cancel) = tr.ln_bwd_ref(dyg, x, dres)
+            out = Out(dev, (rows, D), torch.float32)
+            gd, xd, rd = inp(dev, dyg), inp(dev, x), inp(dev, dres)
+            L.check(lib.ch_debug_ln_bwd(L.ptr(gd), L.ptr(xd), rows, D, tr.LN_EPS, L.ptr(rd), out.ptr, None, None, L.stream_ptr()), "ln_bwd")
+            torch.cuda.synchronize()
+            got = out.get()
+            tr.assert_within(got, d, e_d, f"one-hot {fam} D {D}", quiet=True)
+            xk = xh[torch.arange(rows), k]
+            rstd = got[torch.arange(rows), k].double() / (1 - 1.0 / D - xk * xk / D)
+            rel = ((rstd - R[:, 0]).abs() / R[:, 0])
+            print(f"RSTD {fam} D {D}: measured relative error {float(rel.max()):.2e}, derived bound {float((e_r / R).max()):.2e}, "
+                  f"cancellation factor {float(cancel.max()):.3g}")
+
+
+@pytest.mark.parametrize("np_,Q", [(4, 1), (49, 4)])
+def test_embed_bwd(dev, L, np_, Q):
+    lib = L.load()
+    B, ntok = 2, 1 + np_ + Q
+    for D in tr.ROW_D:
+        for fam in tr.ROW_FAMILIES:
+            X, dY, cls, ctx, gamma = tr.embed_inputs(B, np_, Q, D, fam)
+            yx, e_yx, d, e_d, dxp, e_dxp = tr.embed_bwd_ref(X, dY, B, ntok, np_, cls, ctx, gamma)
+            cd, xd, gd = inp(dev, cls), inp(dev, ctx), inp(dev, gamma)
+            what = f"{fam} np {np_} Q {Q} D {D}"
+
+            def launch():
+                oX, oY = Out(dev, X.shape, torch.float32, init=X), Out(dev, dY.shape, torch.float32, init=dY)
+                oP = Out(dev, (B * np_, D), torch.bfloat16)
+                L.check(lib.ch_debug_embed_bwd(oX.ptr, oY.ptr, B, ntok, np_, D, L.ptr(cd), L.ptr(xd), L.ptr(gd), tr.LN_EPS, oP.ptr, L.stream_ptr()),
+                        "embed_bwd")
+                return [oX, oY, oP]
+
+            oX, oY, oP = twice(launch)
+            within("embed_bwd X", oX.get(), yx, e_yx, what)
+            within("embed_bwd dY", oY.get(), d, e_d, what)
+            within("embed_bwd patch", oP.get(), dxp, e_dxp, what)
+            t = torch.arange(B * ntok) % ntok
+            assert tr.bits_equal(oP.get(), oY.get()[(t >= 1) & (t <= np_)].to(torch.bfloat16)), f"{what}: compact rows are not the rounded dx"
+    report("embed_bwd X", "embed_bwd dY", "embed_bwd patch")
+
+
+@pytest.mark.parametrize("rows,D", tr.SMALL_LN_SHAPES)
+def test_small_ln_bwd(dev, L, rows, D):
+    lib = L.load()
+    for fam in tr.SMALL_LN_FAMILIES:
+        dy, x, gamma = tr.small_ln_inputs(rows, D, fam)
+        d, e_d = tr.small_ln_bwd_ref(dy, x, gamma)
+        yd, xd, gd = inp(dev, dy), inp(dev, x), inp(dev, gamma)
+
+        def launch():
+            out = Out(dev, (rows, D), torch.float32)
+            L.check(lib.ch_debug_small_ln_bwd(L.ptr(yd), L.ptr(xd), L.ptr(gd), rows, D, tr.LN_EPS, out.ptr, L.stream_ptr()), "small_ln_bwd")
+            return [out]
+
+        within("small_ln_bwd", twice(launch)[0].get(), d, e_d, f"{fam} {rows}x{D}")
+    report("small_ln_bwd")
+
+
+# ---- reductions -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("is_f32", [1, 0])
+def test_colsum(dev, L, is_f32):
+    lib = L.load()
+    group = f"colsum {'f32' if is_f32 else 'bf16'}"
+    for rows, N, lda, fam in tr.colsum_cases():
+        A = tr.colsum_input(rows, N, lda, fam, is_f32)
+        ref, bound = tr.colsum_ref(A, N)
+        Ad = inp(dev, A)
+
+        def launch():
+            out = Out(dev, (N,), torch.float32)
+            L.check(lib.ch_debug_colsum(L.ptr(Ad), is_f32, lda, rows, N, out.ptr, L.stream_ptr()), "colsum")
+            return [out]
+
+        within(group, twice(launch)[0].get(), ref, bound, f"{fam} {rows}x{N} lda {lda}")
+    report(group)
+
+
+@pytest.mark.parametrize("njobs,nchunks,n4", tr.REDUCE_CASES)
+def test_reduce_partials_multi(dev, L, njobs, nchunks, n4):
+    lib = L.load()
+    parts = [tr.reduce_input(j, nchunks[j], n4[j]) for j in range(njobs)]
+    pd = [inp(dev, p) for p in parts]
+
+    def launch():
+        outs = [Out(dev, (4 * n4[j],), torch.float32) for j in range(njobs)]
+        pp = (ctypes.c_void_p * njobs)(*[p.data_ptr() for p in pd])
+        po = (ctypes.c_void_p * njobs)(*[o.ptr.value for o in outs])
+        L.check(lib.ch_debug_reduce_partials_multi(njobs, pp, po, (ctypes.c_int32 * njobs)(*nchunks), (ctypes.c_int32 * njobs)(*n4),
+                                                   L.stream_ptr()), "reduce_partials_multi")
+        return outs
+
+    for j, o in enumerate(twice(launch)):
+        ref, bound = tr.reduce_ref(parts[j])
+        within("reduce_partials_multi", o.get(), ref, bound, f"job {j} of {nchunks} {n4}")
+    report("reduce_partials_multi")
+
+
+# ---- transposes ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R,C", tr.TRANSPOSE_SHAPES)
+def test_transposes(dev, L, R, C):
+    lib = L.load()
+    for is_f32 in (1, 0):
+        for pad_src, pad_dst in ((0, 0), (8, 8), (3, 5)):
+            ld_src, ld_dst = C + pad_src, R + pad_dst
+            src, cs = tr.transpose_input(R, C, ld_src, is_f32)
+            sd, cd = inp(dev, src), inp(dev, cs)
+            for scale in ((None, cs) if is_f32 else (None,)):
+                want = tr.transpose_ref(src, C, scale)
+
+                def launch():
+                    out = Out(dev, (C, ld_dst), torch.bfloat16)
+                    if is_f32:
+                        rc = lib.ch_debug_transpose_f32_to_bf16(L.ptr(sd), R, C, ld_src, L.ptr(cd) if scale is not None else None, out.ptr, ld_dst,
+                                                                L.stream_ptr())
+                    else:
+                        rc = lib.ch_debug_transpose_bf16(L.ptr(sd), R, C, ld_src, out.ptr, ld_dst, L.stream_ptr())
+                    L.check(rc, "transpose")
+                    return [out]
+
+                out = twice(launch)[0]
+                what = f"{'f32' if is_f32 else 'bf16'} {R}x{C} ld {ld_src} {ld_dst} scale {scale is not None}"
+                assert tr.bits_equal(out.get()[:, :R].contiguous(), want), what + ": not the correctly rounded transpose"
+                mask = torch.zeros(C, ld_dst, dtype=torch.bool)
+                mask[:, R:] = True
+                assert out.untouched(mask), what + ": columns past R were written"
+
+
+# ---- adapter working copies and gradients ---------------------------------------------------------------------------------------------------
+def _adapter_cases():
+    cases = [(D, b, nad, tr.adapter_numel(D, b)) for D, b in tr.ADAPTER_SHAPES for nad in tr.ADAPTER_NAD]
+    return cases + [(128, 8, 3, tr.adapter_numel(128, 8) + 11)]
+
+
+@pytest.mark.parametrize("D,b,nad,stride", _adapter_cases())
+def test_adapter_refresh(dev, L, D, b, nad, stride):
+    lib = L.load()
+    bp = tr.bpad_of(b)
+    P = tr.adapter_arena(D, b, nad, stride)
+    ref = tr.adapter_refresh_ref(P, stride, nad, D, b)
+    Pd = inp(dev, P)
+
+    def launch():
+        o = [Out(dev, (nad, bp, D), torch.bfloat16), Out(dev, (nad, bp), torch.float32), Out(dev, (nad, bp), torch.float32),
+             Out(dev, (nad, D, bp), torch.bfloat16), Out(dev, (nad, bp, D), torch.bfloat16), Out(dev, (nad, D, bp), torch.bfloat16)]
+        L.check(lib.ch_debug_adapter_refresh(L.ptr(Pd), stride, nad, D, b, bp, o[0].ptr, o[1].ptr, o[2].ptr, o[3].ptr, o[4].ptr, o[5].ptr,
+                                             L.stream_ptr()), "adapter_refresh")
+        return o
+
+    wdf, c, d, up, upT, dwgT = twice(launch)
+    for a in range(nad):
+        r = ref[a]
+        what = f"adapter {a} of {nad}, D {D} b {b} stride {stride}"
+        assert tr.bits_equal(wdf.get()[a, :b].contiguous(), r["wdf"][:b].contiguous()), what + ": down_wf is not bf16(W * gamma)"
+        assert not bool(wdf.get()[a, b:].float().any()), what + ": down_wf rows past b must be zero (0 * gamma: either sign of zero)"
+        assert tr.bits_equal(up.get()[a], r["up"]), what + ": up_w (columns past b must be zero)"
+        within("adapter_refresh c", c.get()[a], r["c"], r["e_c"], what)
+        within("adapter_refresh d", d.get()[a], r["d"], r["e_d"], what)
+        assert not bool(c.get()[a, b:].any()) and not bool(d.get()[a, b:].any()), what + ": fold_c / fold_d past b must be zero"
+        assert tr.bits_equal(upT.get()[a, :b].contiguous(), r["upT"]), what + ": up_wT"
+        assert tr.bits_equal(dwgT.get()[a, :, :b].contiguous(), r["dwgT"]), what + ": down_wgT"
+    m = torch.zeros(nad, bp, D, dtype=torch.bool)
+    m[:, b:] = True
+    assert upT.untouched(m), "up_wT: rows past b are left alone"
+    m = torch.zeros(nad, D, bp, dtype=torch.bool)
+    m[:, :, b:] = True
+    assert dwgT.untouched(m), "down_wgT: columns past b are left alone"
+    report("adapter_refresh c", "adapter_refresh d")
+
+
+@pytest.mark.parametrize("D,b,nad,stride", _adapter_cases())
+def test_adapter_grads(dev, L, D, b, nad, stride):
+    lib = L.load()
+    bp, n = tr.bpad_of(b), tr.adapter_numel(D, b)
+    P = tr.adapter_arena(D, b, nad, stride)
+    G, cu, T, cd = tr.adapter_grad_operands(P, stride, nad, D, b)
+    ref, bound = tr.adapter_grads_ref(G, cu, T, cd, P, stride, nad, D, b)
+    Gd, cud, Td, cdd, Pd = (inp(dev, v) for v in (G, cu, T, cd, P))
+    total = (nad - 1) * stride + n
+
+    def launch():
+        gr = Out(dev, (total,), torch.float32)
+        L.check(lib.ch_debug_adapter_grads(L.ptr(Gd), L.ptr(cud), L.ptr(Td), L.ptr(cdd), L.ptr(Pd), D, b, bp, gr.ptr, nad, stride, L.stream_ptr()),
+                "adapter_grads")
+        return [gr]
+
+    gr = twice(launch)[0]
+    got = gr.get()
+    gap = torch.ones(total, dtype=torch.bool)
+    names = ("ln_w", "ln_b", "down_w", "down_b", "up_w", "up_b", "scale")
+    for a in range(nad):
+        gap[a * stride:a * stride + n] = False
+        blk = got[a * stride:a * stride + n]
+        for name, g_, r_, e_ in zip(names, tr.adapter_fields(blk, D, b), tr.adapter_fields(ref[a], D, b), tr.adapter_fields(bound[a], D, b)):
+            within(f"adapter_grads {name}", g_, r_, e_, f"adapter {a} of {nad}, D {D} b {b} stride {stride}")
+        assert tr.bits_equal(tr.adapter_fields(blk, D, b)[3], cd[a, :b].contiguous()), "db_down is a copy of cd"
+    assert gr.untouched(gap), "floats between the adapters' blocks were written"
+    report(*[f"adapter_grads {nm}" for nm in names])
+
+
+@pytest.mark.parametrize("D,nparts,rows_each", tr.FOLD_SHAPES)
+def test_fold_grads(dev, L, D, nparts, rows_each):
+    lib = L.load()
+    T, c, gamma, beta, W = tr.fold_inputs(D, nparts, rows_each)
+    dW, e_dW, db, dg, e_dg, dbt, e_dbt = tr.fold_grads_ref(T, c, gamma, beta, W)
+    Td, cd, gd, bd = (inp(dev, v) for v in (T, c, gamma, beta))
+    Wd = [inp(dev, w) for w in W]                       # every row block in an allocation of its own
+
+    def launch():
+        odW = [Out(dev, (rows_each, D), torch.float32) for _ in range(nparts)]
+        odb = [Out(dev, (rows_each,), torch.float32) for _ in range(nparts)]
+        og, ob = Out(dev, (D,), torch.float32), Out(dev, (D,), torch.float32)
+        arr = lambda ps: (ctypes.c_void_p * nparts)(*ps)
+        L.check(lib.ch_debug_fold_grads(L.ptr(Td), L.ptr(cd), L.ptr(gd), L.ptr(bd), D, nparts, rows_each, arr([w.data_ptr() for w in Wd]),
+                                        arr([o.ptr.value for o in odW]), arr([o.ptr.value for o in odb]), og.ptr, ob.ptr, L.stream_ptr()),
+                "fold_grads")
+        return odW + odb + [og, ob]
+
+    outs = twice(launch)
+    what = f"D {D} {nparts}x{rows_each}"
+    for p in range(nparts):
+        rs = slice(p * rows_each, (p + 1) * rows_each)
+        within("fold_grads dW", outs[p].get(), dW[rs], e_dW[rs], f"{what} part {p}")
+        assert torch.equal(outs[nparts + p].get().double(), db[rs]), f"{what} part {p}: db is a copy of c"
+    within("fold_grads dgamma", outs[-2].get(), dg, e_dg, what)
+    within("fold_grads dbeta", outs[-1].get(), dbt, e_dbt, what)
+    report("fold_grads dW", "fold_grads dgamma", "fold_grads dbeta")
+
+
+# ---- row moves and row sums of the concept tokens -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,ntok,Q,D", tr.MOVE_SHAPES)
+def test_row_moves_and_row_sums(dev, L, B, ntok, Q, D):
+    lib = L.load()
+    g = tr.gen("moves", Q, D)
+    dH = torch.randn(B * ntok, D, generator=g)
+    dhf = torch.randn(B * Q, D, generator=g)
+    head = torch.randn(B * (1 + Q), D, generator=g)
+    dHd, dhfd, headd, headbd = inp(dev, dH), inp(dev, dhf), inp(dev, head), inp(dev, head.to(torch.bfloat16))
+    nrows = ntok - Q
+    s = L.stream_ptr
+
+    def sums():
+        oc, ot = Out(dev, (Q, D), torch.float32), Out(dev, (nrows, D), torch.float32)
+        L.check(lib.ch_debug_concept_rows_sum(L.ptr(dHd), B, ntok, Q, D, oc.ptr, s()), "concept_rows_sum")
+        L.check(lib.ch_debug_token_rows_sum(L.ptr(dHd), B, ntok, nrows, D, ot.ptr, s()), "token_rows_sum")
+        return [oc, ot]
+
+    oc, ot = twice(sums)
+    within("concept_rows_sum", oc.get(), *tr.concept_rows_sum_ref(dH, B, ntok, Q), f"Q {Q} D {D}")
+    within("token_rows_sum", ot.get(), *tr.token_rows_sum_ref(dH, B, ntok, nrows), f"Q {Q} D {D}")
+
+    def moves():
+        o = [Out(dev, (B * ntok, D), torch.float32), Out(dev, (B * ntok, D), torch.bfloat16), Out(dev, (B * ntok, D), torch.float32),
+             Out(dev, (B * ntok, D), torch.bfloat16), Out(dev, (B * Q, D), torch.float32)]
+        L.check(lib.ch_debug_scatter_concept_rows(L.ptr(dhfd), B, ntok, Q, D, o[0].ptr, o[1].ptr, s()), "scatter_concept_rows")
+        L.check(lib.ch_debug_expand_head_rows(L.ptr(headd), 1, B, ntok, Q, D, o[2].ptr, s()), "expand_head_rows f32")
+        L.check(lib.ch_debug_expand_head_rows(L.ptr(headbd), 0, B, ntok, Q, D, o[3].ptr, s()), "expand_head_rows bf16")
+        L.check(lib.ch_debug_gather_concept_rows(L.ptr(dHd), B, ntok, Q, D, o[4].ptr, s()), "gather_concept_rows")
+        return o
+
+    sc32, sc16, ex32, ex16, ga = twice(moves)
+    want32, want16 = tr.scatter_concept_rows_ref(dhf, B, ntok, Q)
+    assert tr.bits_equal(sc32.get(), want32) and tr.bits_equal(sc16.get(), want16), "scatter_concept_rows"
+    assert tr.bits_equal(ex32.get(), tr.expand_head_rows_ref(head, B, ntok, Q)), "expand_head_rows fp32"
+    assert tr.bits_equal(ex16.get(), tr.expand_head_rows_ref(head.to(torch.bfloat16), B, ntok, Q)), "expand_head_rows bf16"
+    assert tr.bits_equal(ga.get(), tr.gather_concept_rows_ref(dH, B, ntok, Q)), "gather_concept_rows"
+    report("concept_rows_sum", "token_rows_sum")
