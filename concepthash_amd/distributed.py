@@ -323,12 +323,16 @@ class ShardedRetrieval:
     # ---- mAP / P@k / R@k -----------------------------------------------------------------------------------------
     def evaluate(self, q_all: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Sequence[int] = (1, 5, 10),
                  remove_first: bool = False, seg_rows: Optional[int] = None, skip_queries_without_relevant: bool = False,
-                 tie_bracket: bool = False) -> dict:
+                 tie_bracket: bool = False, radii: Optional[Sequence[int]] = None) -> dict:
         """Same statistics as ``retrieval.evaluate`` (R an int or a list; `skip_queries_without_relevant` as there), gallery sharded by rows: per-shard histograms are
         all-gathered, every rank builds the same global bases, ONE local AP pass accumulates every rank limit (each R and each
         k), and the integer sums are all-reduced -- bit-identical to the single-GPU result for any shard count.
         tie_bracket: as ``retrieval.evaluate``: the whole-gallery bucket counts are the sum over ranks of the per-shard totals that were
-        all-gathered anyway, and every rank runs the bracket kernel on the same integers (replicated; no further collective)."""
+        all-gathered anyway, and every rank runs the bracket kernel on the same integers (replicated; no further collective).
+        radii (hash lookup, ``retrieval.hash_lookup_stats``): not built for the sharded evaluator."""
+        if radii is not None:
+            raise NotImplementedError("ShardedRetrieval.evaluate(radii=...): hash lookup is not built for a sharded gallery (it would take "
+                                      "one all-reduce of the [Qn, nb, 2] bucket counts); evaluate on one GPU with retrieval.evaluate")
         if self.labels is None:
             raise ValueError("gallery labels are required for evaluate()")
         ops = self.ops

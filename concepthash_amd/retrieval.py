@@ -551,6 +551,215 @@ def hamming_ap_rec(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Tenso
     return S, nrel
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# ranked lists of any depth and hash lookup (csrc/hamming_rank.hip)
+# ---------------------------------------------------------------------------------------------------------------
+RANK_BUDGET_BYTES = 1 << 30    # hist + base of one chunk of queries (the budget `record_cap` spends on its lists)
+
+
+def _u32(t: torch.Tensor) -> torch.Tensor:
+    """non-negative integers < 2^32 -> int32 holding their uint32 bit patterns"""
+    t = t.to(torch.int64)
+    return torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32)
+
+
+def bucket_counts(q: torch.Tensor, g: torch.Tensor, seg_rows: Optional[int] = None, stream=None):
+    """The histogram pass without labels -> (hist [nseg, Qn, 64W+1, 2], base (same shape: `hist_prefix`), counts int64 [Qn, 64W+1]):
+    counts[i, d] = gallery rows at distance d of query i.  The pass takes labels; it is handed zeros (every row "relevant"), and
+    column 0 of its pairs is the row count.  seg_rows: default `map_seg_rows`."""
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    seg = int(seg_rows) if seg_rows else map_seg_rows(Qn, G, W)
+    zq = torch.zeros(Qn, dtype=torch.int32, device=q.device)
+    zg = torch.zeros(G, dtype=torch.int32, device=q.device)
+    hist = hamming_hist(q, g, zq, zg, 0, seg, stream=stream)
+    base, _ = hist_prefix(hist, stream=stream)
+    return hist, base, hist[..., 0].sum(0, dtype=torch.int64)
+
+
+def rank_scatter(q, g, seg_rows: int, base: torch.Tensor, out_start: torch.Tensor, out_limit: torch.Tensor, out_idx: torch.Tensor,
+                 out_dist: torch.Tensor, g_index_base: int = 0, stream=None, check: bool = True) -> None:
+    """ch_hamming_rank_scatter: row j of query i, of 0-based rank r in ascending (distance, index), goes to slot out_start[i] + r of the
+    flat out_idx (int64) / out_dist (int32) when r < out_limit[i].  base: `bucket_counts(q, g, seg_rows)[1]`.  The limits must fit the
+    buffers: out_start[i] + out_limit[i] <= out_idx.numel() (checked here, a host read; `check=False` is for callers whose limits fit by
+    construction)."""
+    lib = _lib.load()
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    nseg = max(1, -(-G // seg_rows))
+    if tuple(base.shape) != (nseg, Qn, 64 * W + 1, 2) or base.dtype != torch.int32 or not base.is_contiguous():
+        raise ValueError(f"base must be a contiguous int32 tensor [{nseg}, {Qn}, {64 * W + 1}, 2], got {base.dtype} {tuple(base.shape)}")
+    if out_idx.dtype != torch.int64 or out_dist.dtype != torch.int32 or not out_idx.is_contiguous() or not out_dist.is_contiguous() \
+            or out_idx.numel() != out_dist.numel():
+        raise ValueError("out_idx (int64) and out_dist (int32) must be contiguous and of one size")
+    start = out_start.to(torch.int64).contiguous()
+    limit = out_limit.to(torch.int64)
+    if start.shape != (Qn,) or limit.shape != (Qn,):
+        raise ValueError(f"out_start and out_limit must be [{Qn}]")
+    if check and Qn and (bool((start < 0).any()) or bool((limit < 0).any()) or int((start + limit).max()) > out_idx.numel()):
+        raise ValueError("out_start / out_limit reach outside the output buffers")
+    if out_idx.numel() == 0 or Qn == 0 or G == 0:
+        return                               # no slot to fill (every limit is 0): nothing to launch, and an empty tensor has no address
+    limit = _u32(limit).contiguous()
+    with _dev_guard(q):
+        _lib.check(lib.ch_hamming_rank_scatter(_lib.ptr(q), Qn, _lib.ptr(g), G, W, int(seg_rows), _lib.ptr(base), _lib.ptr(start),
+                                               _lib.ptr(limit), int(g_index_base), _lib.ptr(out_idx), _lib.ptr(out_dist),
+                                               _lib.stream_ptr(stream)), "ch_hamming_rank_scatter")
+
+
+def _ranked_inputs(q, g, mask, radius):
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    if mask is not None:
+        if mask.dim() == 2:
+            raise ValueError("a per-query mask [Qn, W] is not built for ranked lists / radius search (both passes would need the mask); "
+                             "pass one shared int64 [W] mask, or rank with hamming_topk_masked (k <= 128)")
+        mask, _ = _check_mask(mask, Qn, W, q.device, "queries")
+        q, g = q & mask[None, :], g & mask[None, :]          # popcount((q ^ g) & m) = popcount((q & m) ^ (g & m))
+    if radius is not None and not 0 <= int(radius) <= 64 * W:
+        raise ValueError(f"radius must be in [0, {64 * W}], got {radius}")
+    return q, g
+
+
+def _query_chunks(Qn: int, G: int, W: int, seg_rows: Optional[int]):
+    """(c0, c1, seg_rows) blocks of queries whose hist + base stay under RANK_BUDGET_BYTES"""
+    c0 = 0
+    while c0 < Qn:
+        n = Qn - c0
+        while True:
+            seg = int(seg_rows) if seg_rows else map_seg_rows(n, G, W)
+            per_query = 2 * max(1, -(-G // seg)) * (64 * W + 1) * 8
+            fit = max(1, RANK_BUDGET_BYTES // per_query)
+            if n <= fit:
+                break
+            n = fit
+        yield c0, c0 + n, seg
+        c0 += n
+
+
+def hamming_ranked(q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int = 0, radius: Optional[int] = None,
+                   mask: Optional[torch.Tensor] = None, seg_rows: Optional[int] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The first k rows of every query's ranking by ascending (distance, gallery index), for ANY k >= 1 (hamming_topk stops at 128):
+    (idx int64 [Qn, k], dist int32 [Qn, k]), -1 past min(k, G) -- with `radius`, -1 past the rows with dist <= radius.  Histogram pass,
+    prefix, then the pass that writes every row out at its rank (csrc/hamming_rank.hip).  mask: one shared int64 [W] mask
+    (dist = popcount((q ^ g) & mask)); a per-query mask is a ValueError.  Queries go in chunks that keep hist + base under 1 GiB."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be >= 1, got {k}")
+    q, g = _ranked_inputs(q, g, mask, radius)
+    Qn, W = q.shape
+    G = g.shape[0]
+    idx = torch.full((Qn, k), -1, dtype=torch.int64, device=q.device)
+    dist = torch.full((Qn, k), -1, dtype=torch.int32, device=q.device)
+    if Qn == 0 or G == 0:
+        return idx, dist
+    for c0, c1, seg in _query_chunks(Qn, G, W, seg_rows):
+        qc = q[c0:c1]
+        _, base, counts = bucket_counts(qc, g, seg, stream=stream)
+        if radius is None:
+            limit = torch.full((c1 - c0,), min(k, G), dtype=torch.int64, device=q.device)
+        else:
+            limit = counts[:, :int(radius) + 1].sum(1).clamp_max(k)
+        start = torch.arange(c0, c1, dtype=torch.int64, device=q.device) * k
+        rank_scatter(qc, g, seg, base, start, limit, idx.view(-1), dist.view(-1), g_index_base, stream=stream,
+                     check=False)         # slots i k .. i k + limit_i - 1, limit_i <= k
+    return idx, dist
+
+
+def hamming_radius(q: torch.Tensor, g: torch.Tensor, radius: int, g_index_base: int = 0, mask: Optional[torch.Tensor] = None,
+                   max_hits: Optional[int] = None, seg_rows: Optional[int] = None, stream=None):
+    """Hash lookup: every gallery row within `radius` bits of each query, as CSR -> (offsets int64 [Qn + 1], idx int64 [total],
+    dist int32 [total]); query i's rows are offsets[i]:offsets[i + 1], ascending (distance, gallery index), at most `max_hits` of them
+    when given.  radius outside [0, 64 W]: ValueError.  mask as in `hamming_ranked`.  Reads the list lengths back (a synchronisation)."""
+    if radius is None:
+        raise ValueError("hamming_radius needs a radius")
+    if max_hits is not None and int(max_hits) < 0:
+        raise ValueError(f"max_hits must be >= 0, got {max_hits}")
+    q, g = _ranked_inputs(q, g, mask, radius)
+    Qn, W = q.shape
+    G = g.shape[0]
+    dev = q.device
+    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=dev)
+    idxs, dists = [], []
+    if Qn and G:
+        done = 0
+        for c0, c1, seg in _query_chunks(Qn, G, W, seg_rows):
+            qc = q[c0:c1]
+            _, base, counts = bucket_counts(qc, g, seg, stream=stream)
+            limit = counts[:, :int(radius) + 1].sum(1)
+            if max_hits is not None:
+                limit = limit.clamp_max(int(max_hits))
+            ends = limit.cumsum(0)
+            total = int(ends[-1])
+            idx = torch.full((total,), -1, dtype=torch.int64, device=dev)
+            dist = torch.full((total,), -1, dtype=torch.int32, device=dev)
+            rank_scatter(qc, g, seg, base, ends - limit, limit, idx, dist, g_index_base, stream=stream,
+                         check=False)     # the lists tile [0, total)
+            offsets[c0 + 1:c1 + 1] = ends + done
+            done += total
+            idxs.append(idx)
+            dists.append(dist)
+    if len(idxs) == 1:
+        return offsets, idxs[0], dists[0]
+    if not idxs:
+        return offsets, torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    return offsets, torch.cat(idxs), torch.cat(dists)
+
+
+LOOKUP_KEYS = ("precisions_radius", "recalls_radius", "retrieved_radius", "empty_radius", "lookup_retrieved", "lookup_hits")
+
+
+def lowest_bucket(counts2: torch.Tensor) -> torch.Tensor:
+    """[Qn, nb, 2] -> [Qn] int64: every query's lowest non-empty distance bucket (0 for a query with no row at all)"""
+    return (counts2[..., 0] != 0).to(torch.int8).argmax(1)
+
+
+def hash_lookup_stats(counts2: torch.Tensor, radii: Sequence[int], first=None) -> dict:
+    """Hash lookup within a Hamming radius ("P@H<=r") from the whole-gallery bucket counts [Qn, nb, 2] (rows /
+    relevant rows per (query, distance): the histogram of the mAP passes summed over its segments).  Pure torch, CPU or GPU.  Per
+    radius r and query: retrieved = sum_{d<=r} rows, hits = sum_{d<=r} relevant rows, P = hits / retrieved (0 where nothing is
+    retrieved), R = hits / total relevant (0 where the query has no relevant row).
+    first = (d0 [Qn], first_rel [Qn]): remove_first_retrieved -- the dropped rank-1 row lies in the query's lowest non-empty bucket d0
+    (`lowest_bucket`) and is relevant where first_rel is 1: retrieved and hits lose it for every r >= d0, and the recall denominator
+    loses a dropped relevant row, as R@k's does.
+    -> lookup_retrieved, lookup_hits int64 [Qn, len(radii)]; precisions_radius, recalls_radius, retrieved_radius (mean rows retrieved)
+    and empty_radius (share of queries that retrieve nothing): lists of floats, one per radius."""
+    if counts2.dim() != 3 or counts2.shape[2] != 2:
+        raise TypeError("counts2 must be an integer tensor [Qn, nb, 2]")
+    Qn, nb, _ = counts2.shape
+    radii = [int(r) for r in radii]
+    if any(r < 0 or r >= nb for r in radii):
+        raise ValueError(f"radii must be in [0, {nb - 1}], got {radii}")
+    c = counts2.to(torch.int64)
+    if counts2.dtype == torch.int32:
+        c = c & 0xFFFFFFFF                                  # uint32 bit patterns
+    dev = c.device
+    rad = torch.tensor(radii, dtype=torch.int64, device=dev)
+    cn, cr = c[..., 0].cumsum(1), c[..., 1].cumsum(1)
+    retrieved, hits = cn[:, rad], cr[:, rad]
+    total = cr[:, -1] if nb else torch.zeros(Qn, dtype=torch.int64, device=dev)
+    if first is not None:
+        d0, first_rel = first
+        d0, first_rel = d0.to(dev, torch.int64), first_rel.to(dev, torch.int64)
+        dropped = ((d0[:, None] <= rad[None, :]) & (cn[:, -1] > 0)[:, None]).to(torch.int64)
+        retrieved = retrieved - dropped
+        hits = hits - first_rel[:, None] * dropped
+        total = total - first_rel * (cn[:, -1] > 0).to(torch.int64)
+    out = dict(lookup_retrieved=retrieved, lookup_hits=hits)
+    if not Qn or not radii:
+        z = [0.0] * len(radii)
+        out.update(precisions_radius=z, recalls_radius=list(z), retrieved_radius=list(z), empty_radius=list(z))
+        return out
+    zero = torch.zeros(retrieved.shape, dtype=torch.float64, device=dev)
+    P = torch.where(retrieved > 0, hits.double() / retrieved.clamp_min(1).double(), zero)
+    R = torch.where(total[:, None] > 0, hits.double() / total.clamp_min(1).double()[:, None], zero)
+    vals = torch.stack([P.mean(0), R.mean(0), retrieved.double().mean(0), (retrieved == 0).double().mean(0)]).tolist()
+    out.update(precisions_radius=vals[0], recalls_radius=vals[1], retrieved_radius=vals[2], empty_radius=vals[3])
+    return out
+
+
 def ap_from_fixed(S: torch.Tensor, nrel: torch.Tensor) -> torch.Tensor:
     """AP[q] = S / (nrel * 2^32) in float64 (0 where nrel == 0); S holds uint64 bit patterns."""
     Sf = S.to(torch.float64)
@@ -596,7 +805,7 @@ def summarize(S, nrel, total, idx_of, Rs: Sequence[int], ks: Sequence[int], skip
 def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
              ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, seg_rows: Optional[int] = None,
              records: Optional[bool] = None, rec_cap: Optional[int] = None, skip_queries_without_relevant: bool = False,
-             tie_bracket: bool = False) -> dict:
+             tie_bracket: bool = False, radii: Optional[Sequence[int]] = None) -> dict:
     """Single-GPU mAP@R + P@k + R@k on packed codes: histogram pass, prefix, ONE AP pass whose rank limits are R (an int or
     a list) and every k -- the number of relevant rows inside limit k is exactly hits@k, for any k.  Returns python
     floats/lists plus the raw integer statistics (S, nrel, hits, total) that the parity tests compare bit-for-bit with the
@@ -608,7 +817,9 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
     skip_queries_without_relevant: which queries the mean of AP runs over (`summarize`); the integers S / nrel do not depend on it.
     tie_bracket: also report, for every statistic, the smallest and the largest value any order of equal-distance rows can give
     (TIE_KEYS: mAP_low / mAP_high ... hits_low / hits_high) -- one more small kernel on the histogram this
-    call holds anyway.  Off: exactly the keys, integers and launches of before."""
+    call holds anyway.  Off: exactly the keys, integers and launches of before.
+    radii: a list of Hamming radii adds the hash-lookup statistics of `hash_lookup_stats` (LOOKUP_KEYS) from the same histogram -- a few
+    elementwise launches; None adds nothing and costs nothing."""
     q, g = _check_packed(q, g)
     Qn, W = q.shape
     G = g.shape[0]
@@ -632,6 +843,8 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
                 out.update({"mAP_" + side: out["mAP"], "ap_" + side: out["ap"], "S_" + side: out["S"], "nrel_" + side: out["nrel"],
                             "precisions_" + side: list(out["precisions"]), "recalls_" + side: list(out["recalls"]),
                             "hits_" + side: out["hits"]})
+        if radii is not None:
+            out.update(hash_lookup_stats(torch.zeros(Qn, 64 * W + 1, 2, dtype=torch.int32, device=dev), radii))
         return out
     first_rel = None
     if remove_first:   # relevance of every query's rank-1 row (the self-match when the test set is the database)
@@ -661,6 +874,9 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
                    ap=sm["aps"])
     else:
         out.update(mAP=sm["mAPs"][0], S=S[idx_of[0]], nrel=nrel[idx_of[0]], ap=sm["aps"][0])
+    counts2 = hist.sum(0, dtype=hist.dtype) if tie_bracket or radii is not None else None
     if tie_bracket:
-        out.update(tie_results(hist.sum(0, dtype=hist.dtype), Rs, ks, remove_first, many, skip_queries_without_relevant))
+        out.update(tie_results(counts2, Rs, ks, remove_first, many, skip_queries_without_relevant))
+    if radii is not None:
+        out.update(hash_lookup_stats(counts2, radii, (lowest_bucket(counts2), first_rel) if remove_first else None))
     return out

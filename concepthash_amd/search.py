@@ -16,6 +16,7 @@ from . import retrieval as rt
 
 FORMAT = 1
 RANKS = ("hamming", "asymmetric")
+TOPK_MAX = 128    # the deepest list of the top-k scan (csrc/hamming_topk.hip); deeper ones: retrieval.hamming_ranked
 
 
 class StaleIndexError(RuntimeError):
@@ -120,7 +121,7 @@ class GalleryIndex:
         return os.path.join(self.data_root, rel)
 
     def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0,
-               rank: str = "hamming", weight_bits: int = 8) -> dict:
+               rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None) -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here).
         Ranks the database by ascending (distance, index) and returns
           idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
@@ -133,18 +134,35 @@ class GalleryIndex:
         rank: "hamming" (above) or "asymmetric": the same mask, but a disagreement on bit j costs the query's own |code_j|, quantised to
         weight_bits (4 or 8) bits against the largest unmasked |code| of that query (`retrieval.weight_planes`).
         dist is then that weighted distance, and the dict also holds rank, weight_bits and dist_max [Qn] int32, the sum of a query's
-        weights (the distance of a row that disagrees on every unmasked bit); everything else is as under "hamming"."""
+        weights (the distance of a row that disagrees on every unmasked bit); everything else is as under "hamming".
+        k > 128: the list comes from `retrieval.hamming_ranked` (any depth); built for rank="hamming" without a margin (the whole code
+        or `concepts`); the other combinations raise ValueError.
+        radius: hash lookup -- only rows whose ranking distance (the masked one under `concepts` / `margin`) is <= radius stay; idx and
+        dist are -1 behind them, as past the end of the database.  Not defined for rank="asymmetric" (ValueError)."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
         if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
             raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits!r}")
+        k = int(k)
+        deep = k > TOPK_MAX
+        if radius is not None:
+            if rank == "asymmetric":
+                raise ValueError("radius with rank='asymmetric' is not built: a radius is a number of bits, the asymmetric distance is not")
+            radius = int(radius)
+            if not 0 <= radius <= 64 * self.codes.shape[1]:
+                raise ValueError(f"radius must be in [0, {64 * self.codes.shape[1]}], got {radius}")
+        if deep and rank != "hamming":
+            raise ValueError(f"k = {k} > {TOPK_MAX} with rank='{rank}' is not built: lists deeper than {TOPK_MAX} rank by the Hamming distance")
+        if deep and margin > 0:
+            raise ValueError(f"k = {k} > {TOPK_MAX} with margin > 0 is not built: lists deeper than {TOPK_MAX} take one mask shared by all "
+                             f"queries (concepts), not a mask per query")
         dev = self.device
         codes = query_codes.to(dev, torch.float32)
         if codes.dim() != 2 or codes.shape[1] != self.nbit:
             raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
         if self.mean is not None:
             codes = codes - self.mean[None, :]
-        Qn, k = codes.shape[0], int(k)
+        Qn = codes.shape[0]
         q = rt.pack_sign(codes)
         keep = torch.ones(self.nbit, dtype=torch.bool, device=dev)
         mask = None
@@ -165,10 +183,15 @@ class GalleryIndex:
             planes, wsum = rt.weight_planes(codes, int(weight_bits), mask)
             idx, dist = rt.hamming_topk_weighted(q, planes, self.codes, k)
             extra = dict(rank=rank, weight_bits=int(weight_bits), dist_max=wsum)
+        elif deep:
+            idx, dist = rt.hamming_ranked(q, self.codes, k, radius=radius, mask=mask)
         elif mask is None:
             idx, dist = rt.hamming_topk(q, self.codes, k)
         else:
             idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
+        if radius is not None and not deep:
+            far = dist > radius
+            idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
                    bits=keep.sum(1), labels=None, paths=None, **extra)
         if self.labels is not None:

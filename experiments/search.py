@@ -1,6 +1,6 @@
 """`exp=search`: image queries -> ranked database hits of a finished run, optionally by chosen concepts.
 
-    python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [concepts=[0,2]]
+    python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [radius=2] [concepts=[0,2]]
         [query_margin=0.0] [rank=hamming|asymmetric] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
 
 The run's config and checkpoint are loaded exactly as `exp=validation` loads them.  The database split is encoded once
@@ -204,12 +204,14 @@ class SearchExperiment:
         margin = float(cfg.get("query_margin", 0.0) or 0.0)
         rank = str(cfg.get("rank", "hamming") or "hamming")
         weight_bits = int(cfg.get("weight_bits", 8) or 8)
+        radius = cfg.get("radius")
+        radius = int(radius) if radius is not None else None
         print("Search Start")
         index = self.index if self.index is not None else self._build_index()
         index = index.to(self.trainer.device)
         loader, names, labelled = self._query_loader()
         q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
-        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits)
+        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius)
         t0 = time.perf_counter()
         q_ids = _label_ids(q_labels.cpu()) if labelled else None
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
@@ -233,7 +235,7 @@ class SearchExperiment:
             queries.append({"query": names[i] if names is not None else i, "label": ql.tolist() if ql is not None else None,
                             "unmasked_bits": bits[i], "distance_max": dist_max[i], "hits": hits})
         self.timing["results"] = round(time.perf_counter() - t0, 3)
-        out = {"k": k, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "nbit": index.nbit, "ncontext": index.ncontext,
+        out = {"k": k, "radius": radius, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "nbit": index.nbit, "ncontext": index.ncontext,
                "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
                "checkpoint": self.fingerprint, "query": self.query, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
@@ -244,7 +246,7 @@ class SearchExperiment:
         what = "the whole code" if concepts is None else f"concepts {concepts}"
         print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}, " +
               ("Hamming distance" if rank == "hamming" else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
-              (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + f"; index {self.index_note}")
+              (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + (f", within {radius} bits" if radius is not None else "") + f"; index {self.index_note}")
         for e in queries[:PRINT_QUERIES]:
             print(f"query {e['query']}" + (f" (label {e['label']})" if e["label"] is not None and not isinstance(e["label"], list) else "") +
                   f": {e['unmasked_bits']} bits, distance <= {e['distance_max']}")

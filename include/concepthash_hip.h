@@ -468,6 +468,19 @@ int ch_hamming_ap_rec(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t 
 int ch_hamming_hist_prefix(const uint32_t *hist, int32_t nseg, int64_t Qn, int32_t nb, uint32_t *out_base,
                            uint32_t *out_totals, void *stream);
 
+/* Ranked lists of any depth: writes the gallery rows out AT THEIR RANK.  Replaces what a caller of the un-vendored utils.hashing
+ * takes from a full argsort of the distance matrix: the first K hits for any K (ch_hamming_topk stops at 128) and hash lookup, every
+ * row within a Hamming radius.  base [nseg, Qn, nb, 2] as ch_hamming_hist_prefix builds it from ch_hamming_hist with the SAME seg_rows
+ * (only [..,0], the row counts, is read; the histogram pass may run with labels of zeros).  Gallery row j of query i has the 0-based
+ * rank of ascending (distance, gallery index); where rank < out_limit[i] the pass writes
+ *     out_idx[out_start[i] + rank] = g_index_base + j,   out_dist[out_start[i] + rank] = popcount(q_i xor g_j).
+ * out_start int64 [Qn], out_limit uint32 [Qn]: device arrays; the caller sizes out_idx / out_dist so that slots
+ * out_start[i] .. out_start[i] + out_limit[i] - 1 exist, and pre-fills what it wants in the slots no row reaches (limit > G).
+ * All integers: the result does not depend on seg_rows.  1 <= W <= 4, 1 <= seg_rows <= 65535, G < 2^32. */
+int ch_hamming_rank_scatter(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t seg_rows,
+                            const uint32_t *base, const int64_t *out_start, const uint32_t *out_limit, int64_t g_index_base,
+                            int64_t *out_idx, int32_t *out_dist, void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

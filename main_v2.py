@@ -3,7 +3,7 @@
 
     python main_v2.py --config-name val.yaml logdir=<run dir> dataset=cub200 [R=-1] [PRs=[1,5,10]] [batch_size=64] ...
     python main_v2.py exp=extract model=concept_hash_final_v1_nosa_apt dataset=synthetic_cub200 ...
-    python main_v2.py --config-name search.yaml logdir=<run dir> dataset=cub200 [query=test] [k=10] [concepts=[0,2]] ...
+    python main_v2.py --config-name search.yaml logdir=<run dir> dataset=cub200 [query=test] [k=10] [radius=2] [concepts=[0,2]] ...
 
 `exp` dispatch: hashing -> RetrievalExperiment (train the adapters + hashing head, frozen backbone); validation -> load
 <logdir>/config.yaml, overlay the evaluation knobs, RetrievalEvaluation; search -> the same run config, SearchExperiment (ranked hits of
@@ -30,10 +30,10 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval")
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
-               "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits")
+               "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits", "radius")
 
 
 def _run_config(config, exp, keys):
@@ -66,6 +66,8 @@ def run(config):
             from experiments.tie_bracket_eval import TieBracketEvaluation as RetrievalEvaluation
         if load_config.get("concept_eval"):     # ... + the per-concept table (it extends the tie-bracket evaluator)
             from experiments.concept_eval import ConceptEvaluation as RetrievalEvaluation
+        if load_config.get("hash_lookup_radii") is not None:   # ... + hash lookup within Hamming radii (it extends both)
+            from experiments.hash_lookup_eval import HashLookupEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp == "search":
         from experiments.search import SearchExperiment

@@ -47,10 +47,14 @@ def _sharded():
 # The tie bracket of the last calculate_mAP(..., tie_bracket=True) call: {"mAP_low", "mAP_high", "precisions_low", "precisions_high",
 # "recalls_low", "recalls_high"} (the return arity of calculate_mAP is the reference's and cannot grow); None after any other call.
 last_tie_bracket = None
+# Hash lookup of the last calculate_mAP(..., radii=[...]) call, the same pattern: {"radii", "precisions_radius", "recalls_radius",
+# "retrieved_radius", "empty_radius"} (lists, one entry per radius); None after any other call.
+last_hash_lookup = None
 
 
-def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False):
+def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False, radii=None):
     dev = _device()
+    look = {} if radii is None else {"radii": radii}    # the sharded evaluator refuses it (NotImplementedError)
     from concepthash_amd.distributed import RowShard
     if isinstance(db_codes, RowShard) or isinstance(test_codes, RowShard):
         # multi-rank evaluation on the outputs of BaseTrainer.inference_one_epoch: every rank's block of the DATABASE stays on the
@@ -71,7 +75,7 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
             ql, _ = _all_gather_ragged(tl.contiguous(), sr.group)
         else:
             ql = _labels(test_labels, dev)
-        return sr.evaluate(q, ql, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip, tie_bracket=tie)
+        return sr.evaluate(q, ql, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip, tie_bracket=tie, **look)
     q = rt.pack_sign(torch.as_tensor(test_codes).to(dev, torch.float32))
     if _sharded():
         # replicated inputs under an initialised process group (a caller that gathered its codes): every rank takes its block
@@ -82,15 +86,15 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
         g = rt.pack_sign(torch.as_tensor(db_codes[lo:hi]).to(dev, torch.float32))
         sr = ShardedRetrieval(g, _labels(db_labels[lo:hi], dev))
         return sr.evaluate(q, _labels(test_labels, dev), R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip,
-                           tie_bracket=tie)
+                           tie_bracket=tie, **look)
     g = rt.pack_sign(torch.as_tensor(db_codes).to(dev, torch.float32))
     return rt.evaluate(q, g, _labels(test_labels, dev), _labels(db_labels, dev), R=R, ks=ks, remove_first=remove_first,
-                       skip_queries_without_relevant=skip, tie_bracket=tie)
+                       skip_queries_without_relevant=skip, tie_bracket=tie, **look)
 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False, tie_bracket=False):
+                  skip_queries_without_relevant=False, tie_bracket=False, radii=None):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
@@ -101,9 +105,13 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     tie_bracket (not a reference argument): also compute the smallest / largest value of every statistic over all orders of the
     database rows that share a Hamming distance -- the one thing another implementation's sort may do
     differently.  The triple returned is unchanged; the bracket is left in the module attribute `last_tie_bracket` (a dict with
-    mAP_low, mAP_high, precisions_low/high, recalls_low/high; lists where the triple has lists), which is None after a call without it."""
-    global last_tie_bracket
+    mAP_low, mAP_high, precisions_low/high, recalls_low/high; lists where the triple has lists), which is None after a call without it.
+    radii (not a reference argument): a list of Hamming radii -- also compute hash lookup within each ("P@H<=r": precision, recall, rows
+    retrieved and the share of queries retrieving nothing) from the histogram the call holds anyway; left in the
+    module attribute `last_hash_lookup` in the same way.  Single-process evaluation only."""
+    global last_tie_bracket, last_hash_lookup
     last_tie_bracket = None
+    last_hash_lookup = None
     _check(dist_metric, threshold, landmark_gt)
     ks = [int(k) for k in (PRs or [])]
     many = isinstance(R, (list, tuple)) or (hasattr(R, "__iter__") and not isinstance(R, (int, float)))
@@ -111,7 +119,10 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     if many and not Rs:
         return [], [], []
     res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
-                    bool(tie_bracket))
+                    bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
+    if radii is not None:
+        last_hash_lookup = dict({k: res[k] for k in ("precisions_radius", "recalls_radius", "retrieved_radius", "empty_radius")},
+                                radii=[int(r) for r in radii])
     if tie_bracket:
         last_tie_bracket = {k: res[k] for k in ("mAP_low", "mAP_high", "precisions_low", "precisions_high", "recalls_low", "recalls_high")}
     return res["mAP"], res["recalls"], res["precisions"]
