@@ -161,7 +161,7 @@ __global__ __launch_bounds__(BLK) void map_scan_kernel(const uint64_t *__restric
     const uint32_t wg_index = blockIdx.y * gridDim.x + blockIdx.x;
     if (MODE == 1 && ra.wg_flags != nullptr && ra.wg_flags[wg_index] == 0u) return;   // fallback launch: only the workgroups whose
                                                                                        // record lists overflowed (wave-uniform)
-    constexpr int NB = 64 * W + 1;
+    constexpr int NB = scan_buckets(W);
     constexpr int UB = 4;
     const int tid = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * BLK;
@@ -260,6 +260,19 @@ __global__ __launch_bounds__(BLK) void map_scan_kernel(const uint64_t *__restric
         po0 = old[0]; po1 = old[1]; po2 = old[2]; po3 = old[3];
         prev_m = (uint32_t)rel[0] | ((uint32_t)rel[1] << 1) | ((uint32_t)rel[2] << 2) | ((uint32_t)rel[3] << 3);
     };
+    auto trip = [&](const uint32_t (&d)[UB], const bool (&rel)[UB]) {   // the UB rows of a trip, distances and relevance known
+        uint32_t old[UB];
+        if (MODE != 0) park_trip();     // the previous trip's rows; its counters came back long ago
+#pragma unroll
+        for (int u = 0; u < UB; ++u) {  // in row order: two rows of a trip may share a bucket
+            const uint32_t inc = 1u | ((uint32_t)rel[u] << 16);
+            if (MODE == 0)
+                atomicAdd(col + d[u] * BLK, inc);
+            else
+                old[u] = atomicAdd(col + d[u] * BLK, inc);
+        }
+        if (MODE != 0) keep_trip(d, old, rel);
+    };
     auto row = [&](const uint64_t *gw, bool rel) {   // single-row form (segment tail, multi-hot labels)
         const uint32_t d = (uint32_t)hamming<W>(qw, gw);
         const uint32_t inc = 1u | ((uint32_t)rel << 16);
@@ -328,7 +341,7 @@ __global__ __launch_bounds__(BLK) void map_scan_kernel(const uint64_t *__restric
         // rows 4 G .. 4 G + 3 of a block: one "trip" of the parking logic
         auto group = [&](const VBlk &b, auto gc) {
             constexpr int G = decltype(gc)::value;
-            uint32_t d[UB], old[UB];
+            uint32_t d[UB];
             bool rel[UB];
             auto one = [&](auto uc) {
                 constexpr int U = decltype(uc)::value, K = 4 * G + U;
@@ -345,16 +358,7 @@ __global__ __launch_bounds__(BLK) void map_scan_kernel(const uint64_t *__restric
             one(std::integral_constant<int, 1>{});
             one(std::integral_constant<int, 2>{});
             one(std::integral_constant<int, 3>{});
-            if (MODE != 0) park_trip();     // the previous trip's rows; its counters came back long ago
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {  // in row order: two rows of a trip may share a bucket
-                const uint32_t inc = 1u | ((uint32_t)rel[u] << 16);
-                if (MODE == 0)
-                    atomicAdd(col + d[u] * BLK, inc);
-                else
-                    old[u] = atomicAdd(col + d[u] * BLK, inc);
-            }
-            if (MODE != 0) keep_trip(d, old, rel);
+            trip(d, rel);
         };
         auto scan_vblk = [&](const VBlk &b) {
             group(b, std::integral_constant<int, 0>{});
@@ -403,23 +407,14 @@ __global__ __launch_bounds__(BLK) void map_scan_kernel(const uint64_t *__restric
             for (int u = 0; u < UB; ++u) lab[u] = gl32[r0 + u];
         };
         auto scan_block = [&](const uint64_t (&blk)[UB * W], const int32_t (&lab)[UB]) {
-            uint32_t d[UB], old[UB];
+            uint32_t d[UB];
             bool rel[UB];
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 d[u] = (uint32_t)hamming<W>(qw, blk + u * W);
                 rel[u] = valid && (lab[u] == qlab);
             }
-            if (MODE != 0) park_trip();     // the previous trip's rows; its counters came back long ago
-#pragma unroll
-            for (int u = 0; u < UB; ++u) {  // in row order: two rows of a trip may share a bucket
-                const uint32_t inc = 1u | ((uint32_t)rel[u] << 16);
-                if (MODE == 0)
-                    atomicAdd(col + d[u] * BLK, inc);
-                else
-                    old[u] = atomicAdd(col + d[u] * BLK, inc);
-            }
-            if (MODE != 0) keep_trip(d, old, rel);
+            trip(d, rel);
         };
         if (n >= UB) load_block(bufA, labA, 0);
         for (; j + 2 * UB <= n; j += 2 * UB) {
@@ -763,7 +758,7 @@ struct ScanArgs {   // everything a map_scan_kernel launch takes
 template <int W, int BLK, int MODE, int NR, bool VM>
 int launch_scan_vm(const ScanArgs &a, hipStream_t s) {
     const int nseg = (int)ceil_div64(a.G, a.seg_rows);
-    const size_t lds = sizeof(uint32_t) * (64 * W + 1) * BLK;
+    const size_t lds = sizeof(uint32_t) * scan_buckets(W) * BLK;
     dim3 grid((unsigned)ceil_div64(a.Qn, BLK), (unsigned)nseg);
     static ch_once_per_device lds_once;
     if (int e = ch_func_max_lds((const void *)map_scan_kernel<W, BLK, MODE, NR, VM>, (int)lds, lds_once)) return e;
@@ -782,16 +777,15 @@ int launch_scan_nr(const ScanArgs &a, hipStream_t s) {
     return launch_scan_vm<W, BLK, MODE, NR, false>(a, s);
 }
 
-// mode 0: histogram, 1: AP pass (all workgroups, or only the flagged ones when a.ra.wg_flags is set), 2: histogram + records
-template <int W, int BLK>
-int launch_scan(int mode, const ScanArgs &a, hipStream_t s) {
-    if (mode == 0) return launch_scan_nr<W, BLK, 0, 1>(a, s);
-    if (mode == 2) return launch_scan_nr<W, BLK, 2, 1>(a, s);
-    if (a.nlim == 1) return launch_scan_nr<W, BLK, 1, 1>(a, s);
-    if (a.nlim <= 4) return launch_scan_nr<W, BLK, 1, 4>(a, s);
-    return launch_scan_nr<W, BLK, 1, MAX_LIMITS>(a, s);
+// f(std::integral_constant<int, NR>) for the instance that accumulates nlim rank limits: NR = 1 / 4 / 16
+template <class F>
+int dispatch_nr(int nlim, F &&f) {
+    if (nlim == 1) return f(std::integral_constant<int, 1>{});
+    if (nlim <= 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, MAX_LIMITS>{});
 }
 
+// mode 0: histogram, 1: AP pass (all workgroups, or only the flagged ones when a.ra.wg_flags is set), 2: histogram + records
 // lims: nlim ascending rank limits, padded to MAX_LIMITS with copies of the last one (the kernel instance accumulates
 // NR = 1 / 4 / 16 of them and stores rows [0, nlim) of out_S / out_nrel)
 int scan_dispatch(int mode, const ScanArgs &a, int W, hipStream_t s) {
@@ -802,21 +796,24 @@ int scan_dispatch(int mode, const ScanArgs &a, int W, hipStream_t s) {
     if (a.Qn == 0 || a.G == 0) return 0;
     CH_REQUIRE(a.q && a.g && a.ql && a.gl, "hamming: null pointer");
     CH_REQUIRE(ceil_div64(a.G, a.seg_rows) <= 65535, "hamming: too many gallery segments (raise seg_rows)");
-    switch (W) {
-        case 1: return launch_scan<1, 256>(mode, a, s);
-        case 2: return launch_scan<2, 256>(mode, a, s);
-        case 3: return launch_scan<3, 128>(mode, a, s);
-        default: return launch_scan<4, 128>(mode, a, s);
-    }
+    return dispatch_w(W, [&](auto w) {
+        constexpr int Wc = decltype(w)::value, BLK = scan_lanes(Wc);
+        if (mode == 0) return launch_scan_nr<Wc, BLK, 0, 1>(a, s);
+        if (mode == 2) return launch_scan_nr<Wc, BLK, 2, 1>(a, s);
+        return dispatch_nr(a.nlim, [&](auto nr) { return launch_scan_nr<Wc, BLK, 1, decltype(nr)::value>(a, s); });
+    });
 }
 
-bool fill_limits(const int64_t *rank_limits, int nlimits, RankLimits &lims) {
+// The two checks of an entry that takes rank limits (`who`: its name in the messages): their number, in front of the entry's other
+// checks, and -- behind them -- their order, which fills lims.
+#define CH_REQUIRE_NLIMITS(who) CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, who ": 1 <= nlimits <= 16")
+int fill_limits(const char *who, const int64_t *rank_limits, int nlimits, RankLimits &lims) {
     for (int i = 0; i < MAX_LIMITS; ++i) {
         const int64_t r = rank_limits[i < nlimits ? i : nlimits - 1];
         lims.lim[i] = (r <= 0 || r >= 0xFFFFFFFFll) ? 0xFFFFFFFFu : (uint32_t)r;
-        if (i > 0 && lims.lim[i] < lims.lim[i - 1]) return false;
+        CH_REQUIRE(i == 0 || lims.lim[i] >= lims.lim[i - 1], std::string(who) + ": rank limits must ascend (<= 0 = unlimited, last)");
     }
-    return true;
+    return 0;
 }
 
 }  // namespace
@@ -843,10 +840,10 @@ extern "C" int ch_hamming_ap_multi(const uint64_t *q, int64_t Qn, const uint64_t
                                    const void *g_labels, int32_t LW, int32_t seg_rows, const uint32_t *base,
                                    const int64_t *rank_limits, int32_t nlimits, const int32_t *first_rel,
                                    unsigned long long *out_S, uint32_t *out_nrel, void *stream) {
-    CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, "hamming_ap_multi: 1 <= nlimits <= 16");
+    CH_REQUIRE_NLIMITS("hamming_ap_multi");
     CH_REQUIRE(Qn == 0 || G == 0 || (base && out_S && out_nrel), "hamming_ap_multi: null pointer");
     RankLimits lims;
-    CH_REQUIRE(fill_limits(rank_limits, nlimits, lims), "hamming_ap_multi: rank limits must ascend (<= 0 = unlimited, last)");
+    if (int e = fill_limits("hamming_ap_multi", rank_limits, nlimits, lims)) return e;
     ScanArgs a{q, Qn, g, G, q_labels, g_labels, LW, seg_rows, nullptr, base, lims, nlimits, first_rel, out_S, out_nrel, RecordArgs{}};
     return scan_dispatch(1, a, W, (hipStream_t)stream);
 }
@@ -861,9 +858,9 @@ extern "C" int ch_hamming_ap(const uint64_t *q, int64_t Qn, const uint64_t *g, i
 // ---- record form: ONE distance scan (csrc/hamming.hip, MODE 2) --------------------------------------------------------------
 extern "C" size_t ch_hamming_rec_workgroups(int64_t Qn, int64_t G, int32_t W, int32_t seg_rows) {
     if (Qn <= 0 || G <= 0 || seg_rows <= 0) return 0;
-    return (size_t)(ceil_div64(Qn, W <= 2 ? 256 : 128) * ceil_div64(G, seg_rows));
+    return (size_t)(ceil_div64(Qn, scan_lanes(W)) * ceil_div64(G, seg_rows));
 }
-extern "C" int32_t ch_hamming_rec_block(int32_t W) { return W <= 2 ? 256 : 128; }
+extern "C" int32_t ch_hamming_rec_block(int32_t W) { return scan_lanes(W); }
 
 extern "C" int ch_hamming_hist_rec(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, const void *q_labels,
                                    const void *g_labels, int32_t LW, int32_t seg_rows, uint32_t *out_hist, void *rec,
@@ -880,23 +877,22 @@ extern "C" int ch_hamming_ap_rec(const uint64_t *q, int64_t Qn, const uint64_t *
                                  int32_t rec_cap, const uint32_t *rec_cnt, const uint32_t *wg_flags, const int64_t *rank_limits,
                                  int32_t nlimits, const int32_t *first_rel, unsigned long long *out_S, uint32_t *out_nrel,
                                  void *stream) {
-    CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, "hamming_ap_rec: 1 <= nlimits <= 16");
+    CH_REQUIRE_NLIMITS("hamming_ap_rec");
     CH_REQUIRE(W >= 1 && W <= 4, "hamming_ap_rec: 1 <= W <= 4");
     CH_REQUIRE(seg_rows >= 1 && seg_rows <= 65535 && rec_cap >= 1, "hamming_ap_rec: bad seg_rows / rec_cap");
     if (Qn <= 0 || G <= 0) return 0;
     CH_REQUIRE(base && rec && rec_cnt && wg_flags && out_S && out_nrel, "hamming_ap_rec: null pointer");
     RankLimits lims;
-    CH_REQUIRE(fill_limits(rank_limits, nlimits, lims), "hamming_ap_rec: rank limits must ascend (<= 0 = unlimited, last)");
+    if (int e = fill_limits("hamming_ap_rec", rank_limits, nlimits, lims)) return e;
     hipStream_t s = (hipStream_t)stream;
-    const int BLK = W <= 2 ? 256 : 128, NB = 64 * W + 1;
+    const int BLK = scan_lanes(W);
     dim3 grid((unsigned)ceil_div64(Qn, BLK), (unsigned)ceil_div64(G, seg_rows));
     RecordArgs ra{(uint2 *)rec, (uint32_t *)rec_cnt, (uint32_t *)wg_flags, rec_cap};
-    if (nlimits == 1)
-        hipLaunchKernelGGL(ap_records_kernel<1>, grid, dim3(BLK), 0, s, Qn, NB, ra, base, lims, nlimits, first_rel, out_S, out_nrel);
-    else if (nlimits <= 4)
-        hipLaunchKernelGGL(ap_records_kernel<4>, grid, dim3(BLK), 0, s, Qn, NB, ra, base, lims, nlimits, first_rel, out_S, out_nrel);
-    else
-        hipLaunchKernelGGL(ap_records_kernel<MAX_LIMITS>, grid, dim3(BLK), 0, s, Qn, NB, ra, base, lims, nlimits, first_rel, out_S, out_nrel);
+    dispatch_nr(nlimits, [&](auto nr) {
+        hipLaunchKernelGGL(ap_records_kernel<decltype(nr)::value>, grid, dim3(BLK), 0, s, Qn, scan_buckets(W), ra, base, lims, nlimits,
+                           first_rel, out_S, out_nrel);
+        return 0;
+    });
     CH_LAUNCH_CHECK();
     // the workgroups whose lists overflowed: the two-scan form, which skips every unflagged workgroup at its first instruction
     ScanArgs a{q, Qn, g, G, q_labels, g_labels, LW, seg_rows, nullptr, base, lims, nlimits, first_rel, out_S, out_nrel, ra};
@@ -918,14 +914,14 @@ extern "C" int ch_hamming_hist_prefix(const uint32_t *hist, int32_t nseg, int64_
 extern "C" int ch_hamming_tie_bracket(const uint32_t *bucket_counts, int64_t Qn, int32_t nb, const int64_t *rank_limits,
                                       int32_t nlimits, int32_t remove_first, unsigned long long *out_S_low, uint32_t *out_nrel_low,
                                       unsigned long long *out_S_high, uint32_t *out_nrel_high, void *stream) {
-    CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, "hamming_tie_bracket: 1 <= nlimits <= 16");
+    CH_REQUIRE_NLIMITS("hamming_tie_bracket");
     CH_REQUIRE(Qn >= 0 && nb >= 1 && nb <= 257, "hamming_tie_bracket: bad sizes (nb = 64 W + 1, W <= 4)");
     if (Qn == 0) return 0;
     CH_REQUIRE(bucket_counts && out_S_low && out_nrel_low && out_S_high && out_nrel_high, "hamming_tie_bracket: null pointer");
     CH_REQUIRE((((uintptr_t)bucket_counts | (uintptr_t)out_S_low | (uintptr_t)out_S_high) & 7u) == 0,
                "hamming_tie_bracket: bucket_counts (read as pairs), out_S_low and out_S_high must be 8-byte aligned");
     RankLimits lims;
-    CH_REQUIRE(fill_limits(rank_limits, nlimits, lims), "hamming_tie_bracket: rank limits must ascend (<= 0 = unlimited, last)");
+    if (int e = fill_limits("hamming_tie_bracket", rank_limits, nlimits, lims)) return e;
     TieOut o{out_S_low, out_S_high, out_nrel_low, out_nrel_high};
     hipLaunchKernelGGL(tie_bracket_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, (hipStream_t)stream, bucket_counts, Qn,
                        (int)nb, lims, (int)nlimits, (int)remove_first, o);

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(BLK) void rank_scatter_kernel(const uint64_t *__res
                                                            const uint32_t *__restrict__ out_limit, int64_t g_index_base,
                                                            int64_t *__restrict__ out_idx, int32_t *__restrict__ out_dist) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cnt[];  // [NB][BLK]
-    constexpr int NB = 64 * W + 1;
+    constexpr int NB = scan_buckets(W);
     constexpr int UB = W <= 2 ? 8 : 4;
     const int tid = threadIdx.x;
     const int64_t q0 = (int64_t)blockIdx.x * BLK;
@@ -108,20 +108,6 @@ __global__ __launch_bounds__(BLK) void rank_scatter_kernel(const uint64_t *__res
     for (; j < n; ++j) place((uint32_t)hamming<W>(qw, gp + (size_t)j * W), j);
 }
 
-template <int W, int BLK>
-int launch_rank(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int seg_rows, const uint32_t *base,
-                const int64_t *out_start, const uint32_t *out_limit, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
-                hipStream_t s) {
-    const size_t lds = sizeof(uint32_t) * (64 * W + 1) * BLK;
-    dim3 grid((unsigned)ceil_div64(Qn, BLK), (unsigned)ceil_div64(G, seg_rows));
-    static ch_once_per_device lds_once;
-    if (int e = ch_func_max_lds((const void *)rank_scatter_kernel<W, BLK>, (int)lds, lds_once)) return e;
-    hipLaunchKernelGGL((rank_scatter_kernel<W, BLK>), grid, dim3(BLK), lds, s, q, Qn, g, G, seg_rows, base, out_start, out_limit,
-                       g_index_base, out_idx, out_dist);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int ch_hamming_rank_scatter(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t seg_rows,
@@ -134,11 +120,15 @@ extern "C" int ch_hamming_rank_scatter(const uint64_t *q, int64_t Qn, const uint
     CH_REQUIRE(q && g && base && out_start && out_limit && out_idx && out_dist, "hamming_rank_scatter: null pointer");
     CH_REQUIRE(G <= 0xFFFFFFFFll, "hamming_rank_scatter: ranks are 32-bit (G < 2^32)");
     CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "hamming_rank_scatter: too many gallery segments (raise seg_rows)");
-    hipStream_t s = (hipStream_t)stream;
-    switch (W) {
-        case 1: return launch_rank<1, 256>(q, Qn, g, G, seg_rows, base, out_start, out_limit, g_index_base, out_idx, out_dist, s);
-        case 2: return launch_rank<2, 256>(q, Qn, g, G, seg_rows, base, out_start, out_limit, g_index_base, out_idx, out_dist, s);
-        case 3: return launch_rank<3, 128>(q, Qn, g, G, seg_rows, base, out_start, out_limit, g_index_base, out_idx, out_dist, s);
-        default: return launch_rank<4, 128>(q, Qn, g, G, seg_rows, base, out_start, out_limit, g_index_base, out_idx, out_dist, s);
-    }
+    return dispatch_w(W, [&](auto w) {
+        constexpr int Wc = decltype(w)::value, BLK = scan_lanes(Wc);
+        const size_t lds = sizeof(uint32_t) * scan_buckets(Wc) * BLK;
+        dim3 grid((unsigned)ceil_div64(Qn, BLK), (unsigned)ceil_div64(G, seg_rows));
+        static ch_once_per_device lds_once;   // one per instance of this body, i.e. per kernel
+        if (int e = ch_func_max_lds((const void *)rank_scatter_kernel<Wc, BLK>, (int)lds, lds_once)) return e;
+        hipLaunchKernelGGL((rank_scatter_kernel<Wc, BLK>), grid, dim3(BLK), lds, (hipStream_t)stream, q, Qn, g, G, seg_rows, base, out_start,
+                           out_limit, g_index_base, out_idx, out_dist);
+        CH_LAUNCH_CHECK();
+        return 0;
+    });
 }

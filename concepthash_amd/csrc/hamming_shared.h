@@ -1,7 +1,9 @@
-// What the top-k scan (hamming_topk.hip) and the mAP passes (hamming.hip) share: the chained popcount, the query load and the plain
-// Hamming distance built on them.  Everything here has internal linkage.
+// What the top-k scan (hamming_topk.hip), the mAP passes (hamming.hip) and the rank pass (hamming_rank.hip) share: the chained popcount,
+// the query load and the plain Hamming distance built on them; for the latter two, which keep a tile's per-distance counters in LDS, the
+// shape of a workgroup and the W -> instance dispatch.  Everything here has internal linkage.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
@@ -35,6 +37,21 @@ __device__ __forceinline__ int hamming(const uint32_t (&q)[2 * W], const uint64_
         d = bcnt_acc(q[2 * w + 1] ^ (uint32_t)(gw >> 32), d);
     }
     return (int)d;
+}
+
+// A scan with counters in LDS, [buckets][lanes] x 4 B, one lane per query: lanes per workgroup and distance buckets of W-word codes
+constexpr int scan_lanes(int W) { return W <= 2 ? 256 : 128; }
+constexpr int scan_buckets(int W) { return 64 * W + 1; }
+
+// f(std::integral_constant<int, W>) for a W the caller has checked to be in [1, 4]
+template <class F>
+int dispatch_w(int W, F &&f) {
+    switch (W) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
 }
 
 }  // namespace

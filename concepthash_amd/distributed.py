@@ -24,6 +24,8 @@ from typing import Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from . import retrieval
+
 
 def shard_bounds(total_rows: int, world: int):
     """Contiguous row blocks: rank r owns [bounds[r], bounds[r+1])."""
@@ -273,33 +275,33 @@ def gather_outputs(outputs: dict, dst=0):
     return {k: (v.gather(dst) if isinstance(v, RowShard) else v) for k, v in outputs.items()}
 
 
-class ShardedRetrieval:
+class ShardedRetrieval(retrieval.WholeGallery):
     """Rank-local view of a row-sharded gallery.
 
     gallery:  packed codes of THIS rank's rows, int64 [G_local, W]
     labels:   labels of this rank's rows (1-D class ids or 2-D indicator matrix), optional
-    ops:      module/object providing hamming_topk, topk_merge, prepare_labels, hamming_hist, hist_prefix,
-              hamming_ap_multi, normalize_limits, summarize, map_seg_rows  (default: concepthash_amd.retrieval)
+    ops:      module/object providing hamming_topk, topk_merge, prepare_labels, labels_single, hamming_hist, hist_prefix,
+              hamming_ap_multi, normalize_limits, summarize, map_seg_rows -- and, for the one-scan form, hamming_hist_rec /
+              hamming_ap_rec  (default: concepthash_amd.retrieval)
+
+    A `retrieval.WholeGallery` whose cross-rank steps are collectives: `evaluate` runs `retrieval.evaluate_gallery` on it.
     """
 
     def __init__(self, gallery: torch.Tensor, labels: Optional[torch.Tensor] = None, group=None, ops=None):
         if not dist.is_initialized():
             raise RuntimeError("ShardedRetrieval needs an initialised torch.distributed process group")
-        if ops is None:
-            from . import retrieval as ops
-        self.ops = ops
+        super().__init__(gallery.contiguous(), labels, retrieval if ops is None else ops)
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)
-        self.gallery = gallery.contiguous()
-        self.labels = labels
         dev = gallery.device
         n = torch.tensor([gallery.shape[0]], dtype=torch.int64, device=dev)
         counts = [torch.zeros_like(n) for _ in range(self.world)]
         dist.all_gather(counts, n, group=group)
         self.counts = [int(c.item()) for c in counts]
         self.base = sum(self.counts[: self.rank])       # global index of this shard's first row
-        self.total = sum(self.counts)
+        self.total = self.rows = sum(self.counts)
+        self.scan_rows = max(max(self.counts), 1)       # one segment size for all ranks, chosen for the largest shard
         # CH_FORCE_COLLECTIVES=1: run every collective also in a one-rank group (they are then identities) -- lets a single GPU
         # exercise the RCCL backend with this module's dtypes and shapes (tests/test_parity_r3_gpu.py)
         self.coll = self.world > 1 or os.environ.get("CH_FORCE_COLLECTIVES") == "1"
@@ -335,79 +337,38 @@ class ShardedRetrieval:
                                       "one all-reduce of the [Qn, nb, 2] bucket counts); evaluate on one GPU with retrieval.evaluate")
         if self.labels is None:
             raise ValueError("gallery labels are required for evaluate()")
-        ops = self.ops
-        dev = q_all.device
-        Qn, W = q_all.shape
         # one-hot rows -> class ids only if EVERY shard's rows (and the queries) are single-label: the ranks must agree on the form
         single = None
-        ql, gl = q_labels.to(dev), self.labels.to(dev)
-        if self.coll and ql.dim() == 2 and gl.dim() == 2 and hasattr(ops, "labels_single"):
-            flag = torch.tensor([1 if ops.labels_single(ql, gl) else 0], dtype=torch.int32, device=dev)
+        if self.coll and q_labels.dim() == 2 and self.labels.dim() == 2:
+            dev = q_all.device
+            flag = torch.tensor([1 if self.ops.labels_single(q_labels.to(dev), self.labels.to(dev)) else 0], dtype=torch.int32, device=dev)
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
             single = bool(flag.item())
-        q_lab, g_lab, LW = ops.prepare_labels(ql, gl, single) if single is not None else ops.prepare_labels(ql, gl)
-        ks = [int(k) for k in ks]
-        if any(k <= 0 for k in ks):
-            raise ValueError("P@k / R@k need k >= 1")
-        many = isinstance(R, (list, tuple))
-        Rs = [int(r) for r in R] if many else [int(R)]
-        first_rel = None
-        if remove_first:      # relevance of the global rank-1 row of every query
-            idx, _ = self.topk(q_all, 1)
-            g_lab_all, _ = _all_gather_ragged(g_lab, self.group) if self.coll else (g_lab, None)
-            safe = idx.clamp_min(0)
-            if LW == 0:
-                rel = (g_lab_all[safe] == q_lab[:, None]) & (idx >= 0)
-            else:
-                rel = (g_lab_all[safe] & q_lab[:, None, :]).ne(0).any(-1) & (idx >= 0)
-            first_rel = rel[:, 0].to(torch.int32)
-        # one segment size for all ranks (chosen for the largest shard)
-        gmax = max(self.counts) if self.counts else 0
-        seg = seg_rows or ops.map_seg_rows(Qn, max(gmax, 1), W)
-        # one-scan form where the ops provide it (concepthash_amd.retrieval does): the histogram pass also records this shard's
-        # relevant rows, and the AP terms come from the records once the GLOBAL bases exist (CH_HAMMING_RECORDS=0 = two scans)
-        use_rec = (hasattr(ops, "hamming_hist_rec") and os.environ.get("CH_HAMMING_RECORDS", "1") != "0"
-                   and ops.records_fit(Qn, max(gmax, 1), W, seg))
-        if use_rec and LW == 0 and hasattr(ops, "predicted_overflow") and Qn * max(gmax, 1) >= ops.OVERFLOW_MIN_PAIRS:
-            # a local choice (each rank for its own shard): only speed depends on it
-            use_rec = ops.predicted_overflow(q_lab, g_lab, W, seg, ops.record_cap(Qn, max(gmax, 1), W, seg)) <= ops.OVERFLOW_SWITCH
-        if use_rec:
-            hist, recs = ops.hamming_hist_rec(q_all, self.gallery, q_lab, g_lab, LW, seg)
-        else:
-            hist = ops.hamming_hist(q_all, self.gallery, q_lab, g_lab, LW, seg)        # [nseg_local, Qn, nb, 2]
-        if self.coll:
-            # "ranked before" bases of THIS shard's segments need, per (query, bucket), the rows of all lower buckets anywhere plus
-            # the same bucket's rows in earlier shards and earlier local segments: only per-SHARD totals travel ([Qn, nb, 2] per
-            # rank -- 17 MB at 16,384 queries x 128 bit -- instead of every segment's histogram, 16x that at the 1M-row size), and
-            # the prefix runs over [all earlier shards | local segments | all later shards]
-            tot = hist.sum(0, dtype=hist.dtype)
-            tot_all = _all_gather_rows(tot.unsqueeze(0), self.group)                        # [world, Qn, nb, 2], rank-major
-            before = tot_all[: self.rank].sum(0, dtype=hist.dtype)
-            after = tot_all[self.rank + 1:].sum(0, dtype=hist.dtype)
-            base_s, totals = ops.hist_prefix(torch.cat([before.unsqueeze(0), hist, after.unsqueeze(0)], dim=0))
-            base = base_s[1:1 + hist.shape[0]].contiguous()
-            counts = tot_all.sum(0, dtype=hist.dtype) if tie_bracket else None
-        else:
-            base, totals = ops.hist_prefix(hist)
-            counts = hist.sum(0, dtype=hist.dtype) if tie_bracket else None
-        limits, idx_of = ops.normalize_limits(Rs + ks)
-        if use_rec:
-            S, nrel = ops.hamming_ap_rec(q_all, self.gallery, q_lab, g_lab, LW, seg, base, recs, limits, first_rel=first_rel)
-        else:
-            S, nrel = ops.hamming_ap_multi(q_all, self.gallery, q_lab, g_lab, LW, seg, base, limits, first_rel=first_rel)
+        return retrieval.evaluate_gallery(self, q_all, q_labels, R, ks, remove_first, seg_rows, None, None, skip_queries_without_relevant,
+                                          tie_bracket, None, single)
+
+    # ---- the steps of `retrieval.evaluate_gallery` that cross ranks ------------------------------------------------
+    def first_relevant(self, q_all, q_lab, g_lab, LW):
+        """relevance of the global rank-1 row of every query"""
+        idx, _ = self.topk(q_all, 1)
+        g_lab_all, _ = _all_gather_ragged(g_lab, self.group) if self.coll else (g_lab, None)
+        return retrieval._relevance_of(idx, q_lab, g_lab_all, LW)[:, 0].to(torch.int32)
+
+    def bases(self, hist, want_counts):
+        if not self.coll:
+            return super().bases(hist, want_counts)
+        # "ranked before" bases of THIS shard's segments need, per (query, bucket), the rows of all lower buckets anywhere plus
+        # the same bucket's rows in earlier shards and earlier local segments: only per-SHARD totals travel ([Qn, nb, 2] per
+        # rank -- 17 MB at 16,384 queries x 128 bit -- instead of every segment's histogram, 16x that at the 1M-row size), and
+        # the prefix runs over [all earlier shards | local segments | all later shards]
+        tot = hist.sum(0, dtype=hist.dtype)
+        tot_all = _all_gather_rows(tot.unsqueeze(0), self.group)                        # [world, Qn, nb, 2], rank-major
+        before = tot_all[: self.rank].sum(0, dtype=hist.dtype)
+        after = tot_all[self.rank + 1:].sum(0, dtype=hist.dtype)
+        base_s, totals = self.ops.hist_prefix(torch.cat([before.unsqueeze(0), hist, after.unsqueeze(0)], dim=0))
+        return base_s[1:1 + hist.shape[0]].contiguous(), totals, tot_all.sum(0, dtype=hist.dtype) if want_counts else None
+
+    def reduce(self, S, nrel):
         if self.coll:
             dist.all_reduce(S, op=dist.ReduceOp.SUM, group=self.group)       # int64 wrap-around sum == uint64 sum
             dist.all_reduce(nrel, op=dist.ReduceOp.SUM, group=self.group)
-        total = totals[:, 1].clone()
-        if remove_first:
-            total = total - first_rel
-        sm = ops.summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-        out = dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total)
-        if many:
-            out.update(mAP=sm["mAPs"], S=[S[idx_of[i]] for i in range(len(Rs))], nrel=[nrel[idx_of[i]] for i in range(len(Rs))],
-                       ap=sm["aps"])
-        else:
-            out.update(mAP=sm["mAPs"][0], S=S[idx_of[0]], nrel=nrel[idx_of[0]], ap=sm["aps"][0])
-        if tie_bracket:
-            out.update(ops.tie_results(counts, Rs, ks, remove_first, many, skip_queries_without_relevant))
-        return out

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import sys
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -259,18 +260,23 @@ def map_seg_rows(Qn: int, G: int, W: int) -> int:
     return int(min(65535, max(256, rows)))
 
 
-def hamming_hist(q, g, q_lab, g_lab, LW: int, seg_rows: int, stream=None) -> torch.Tensor:
-    """mAP pass 1: [nseg, Qn, 64W+1, 2] int32 (uint32 bit patterns)."""
-    lib = _lib.load()
+def _hist_pass(q, g, seg_rows: int):
+    """What both forms of mAP pass 1 start from: checked codes and the histogram [nseg, Qn, 64W+1, 2] int32 they fill."""
     q, g = _check_packed(q, g)
     Qn, W = q.shape
     G = g.shape[0]
     nseg = max(1, -(-G // seg_rows))
     # the pass writes every counter of every (segment, query); an empty gallery launches nothing
-    hist = (torch.empty if G > 0 else torch.zeros)(nseg, Qn, 64 * W + 1, 2, dtype=torch.int32, device=q.device)
+    return q, g, (torch.empty if G > 0 else torch.zeros)(nseg, Qn, 64 * W + 1, 2, dtype=torch.int32, device=q.device)
+
+
+def hamming_hist(q, g, q_lab, g_lab, LW: int, seg_rows: int, stream=None) -> torch.Tensor:
+    """mAP pass 1: [nseg, Qn, 64W+1, 2] int32 (uint32 bit patterns)."""
+    lib = _lib.load()
+    q, g, hist = _hist_pass(q, g, seg_rows)
     with _dev_guard(q):
-        _lib.check(lib.ch_hamming_hist(_lib.ptr(q), Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
-                                       _lib.ptr(hist), _lib.stream_ptr(stream)), "ch_hamming_hist")
+        _lib.check(lib.ch_hamming_hist(_lib.ptr(q), q.shape[0], _lib.ptr(g), g.shape[0], q.shape[1], _lib.ptr(q_lab), _lib.ptr(g_lab), LW,
+                                       seg_rows, _lib.ptr(hist), _lib.stream_ptr(stream)), "ch_hamming_hist")
     return hist
 
 
@@ -286,22 +292,48 @@ def hist_prefix(hist: torch.Tensor, stream=None) -> Tuple[torch.Tensor, torch.Te
     return base, totals
 
 
-def hamming_ap(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Tensor, rank_limit: int = -1,
-               first_rel: Optional[torch.Tensor] = None, out_S: Optional[torch.Tensor] = None,
-               out_nrel: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """mAP pass 2 -> (S int64 [Qn] fixed-point numerators, nrel int32 [Qn])."""
+MAX_LIMITS = 16   # rank limits one AP pass accumulates (csrc/hamming.hip)
+
+
+def _limit_chunks(limits: Sequence[int]):
+    """(rows, C array, count) per launch of an entry that takes rank limits: MAX_LIMITS of them at a time; `rows` slices the [n, Qn]
+    outputs."""
+    lim = [int(r) for r in limits]
+    for c0 in range(0, len(lim), MAX_LIMITS):
+        chunk = lim[c0:c0 + MAX_LIMITS]
+        yield slice(c0, c0 + len(chunk)), (ctypes.c_int64 * len(chunk))(*chunk), len(chunk)
+
+
+def _ap(entry: str, q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Tensor, rank_limits: Sequence[int], first_rel, stream,
+        operands=(), out=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The calls of a ch_hamming_ap* entry on checked codes, one per MAX_LIMITS limits: S int64 / nrel int32 [n, Qn], zeroed here
+    unless the caller hands them in as `out` (the entries accumulate); `operands` are the entry's own arguments, between base and the
+    limits."""
     lib = _lib.load()
     q, g = _check_packed(q, g)
     Qn, W = q.shape
-    G = g.shape[0]
-    S = out_S if out_S is not None else torch.zeros(Qn, dtype=torch.int64, device=q.device)
-    nrel = out_nrel if out_nrel is not None else torch.zeros(Qn, dtype=torch.int32, device=q.device)
+    n = len(rank_limits)
+    S, nrel = out or (torch.zeros(n, Qn, dtype=torch.int64, device=q.device), torch.zeros(n, Qn, dtype=torch.int32, device=q.device))
     if first_rel is not None:
         first_rel = first_rel.to(torch.int32).contiguous()
+    base = base.contiguous()
     with _dev_guard(q):
-        _lib.check(lib.ch_hamming_ap(_lib.ptr(q), Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
-                                     _lib.ptr(base.contiguous()), int(rank_limit), _lib.ptr(first_rel), _lib.ptr(S),
-                                     _lib.ptr(nrel), _lib.stream_ptr(stream)), "ch_hamming_ap")
+        for rows, arr, cnt in _limit_chunks(rank_limits):
+            _lib.check(getattr(lib, entry)(_lib.ptr(q), Qn, _lib.ptr(g), g.shape[0], W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
+                                           _lib.ptr(base), *operands, arr, cnt, _lib.ptr(first_rel), _lib.ptr(S[rows]), _lib.ptr(nrel[rows]),
+                                           _lib.stream_ptr(stream)), entry)
+    return S, nrel
+
+
+def hamming_ap(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Tensor, rank_limit: int = -1,
+               first_rel: Optional[torch.Tensor] = None, out_S: Optional[torch.Tensor] = None,
+               out_nrel: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """mAP pass 2 -> (S int64 [Qn] fixed-point numerators, nrel int32 [Qn]): `hamming_ap_multi` for one limit; out_S / out_nrel, where
+    given, are accumulated into."""
+    Qn = q.shape[0]
+    S = out_S if out_S is not None else torch.zeros(Qn, dtype=torch.int64, device=q.device)
+    nrel = out_nrel if out_nrel is not None else torch.zeros(Qn, dtype=torch.int32, device=q.device)
+    _ap("ch_hamming_ap_multi", q, g, q_lab, g_lab, LW, seg_rows, base, [rank_limit], first_rel, stream, out=(S[None], nrel[None]))
     return S, nrel
 
 
@@ -313,9 +345,6 @@ def _relevance_of(idx: torch.Tensor, q_lab: torch.Tensor, g_lab_all: torch.Tenso
     else:
         rel = (g_lab_all[safe] & q_lab[:, None, :]).ne(0).any(-1)
     return rel & (idx >= 0)
-
-
-MAX_LIMITS = 16   # rank limits one AP pass accumulates (csrc/hamming.hip)
 
 
 def normalize_limits(limits: Sequence[int]):
@@ -330,25 +359,7 @@ def hamming_ap_multi(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Ten
                      first_rel: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """mAP pass 2 for a list of ascending rank limits (<= 0 = unlimited, last) in ONE gallery scan per 16 limits
     -> (S int64 [n, Qn], nrel int32 [n, Qn]); nrel[i] = number of relevant rows inside limit i."""
-    lib = _lib.load()
-    q, g = _check_packed(q, g)
-    Qn, W = q.shape
-    G = g.shape[0]
-    lim = [int(r) for r in rank_limits]
-    n = len(lim)
-    S = torch.zeros(n, Qn, dtype=torch.int64, device=q.device)
-    nrel = torch.zeros(n, Qn, dtype=torch.int32, device=q.device)
-    if first_rel is not None:
-        first_rel = first_rel.to(torch.int32).contiguous()
-    base = base.contiguous()
-    with _dev_guard(q):
-        for c0 in range(0, n, MAX_LIMITS):
-            chunk = lim[c0:c0 + MAX_LIMITS]
-            arr = (ctypes.c_int64 * len(chunk))(*chunk)
-            _lib.check(lib.ch_hamming_ap_multi(_lib.ptr(q), Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
-                                               _lib.ptr(base), arr, len(chunk), _lib.ptr(first_rel), _lib.ptr(S[c0:c0 + len(chunk)]),
-                                               _lib.ptr(nrel[c0:c0 + len(chunk)]), _lib.stream_ptr(stream)), "ch_hamming_ap_multi")
-    return S, nrel
+    return _ap("ch_hamming_ap_multi", q, g, q_lab, g_lab, LW, seg_rows, base, rank_limits, first_rel, stream)
 
 
 def tie_bracket(bucket_counts: torch.Tensor, limits: Sequence[int], remove_first: bool = False, stream=None):
@@ -361,19 +372,13 @@ def tie_bracket(bucket_counts: torch.Tensor, limits: Sequence[int], remove_first
         raise TypeError("bucket_counts must be an int32 tensor [Qn, nb, 2]")
     bc = bucket_counts.contiguous()
     Qn, nb, _ = bc.shape
-    lim = [int(r) for r in limits]
-    n = len(lim)
-    S_lo = torch.zeros(n, Qn, dtype=torch.int64, device=bc.device)
-    S_hi = torch.zeros(n, Qn, dtype=torch.int64, device=bc.device)
-    n_lo = torch.zeros(n, Qn, dtype=torch.int32, device=bc.device)
-    n_hi = torch.zeros(n, Qn, dtype=torch.int32, device=bc.device)
+    n = len(limits)
+    S_lo, S_hi = (torch.zeros(n, Qn, dtype=torch.int64, device=bc.device) for _ in range(2))
+    n_lo, n_hi = (torch.zeros(n, Qn, dtype=torch.int32, device=bc.device) for _ in range(2))
     with _dev_guard(bc):
-        for c0 in range(0, n, MAX_LIMITS):
-            chunk = lim[c0:c0 + MAX_LIMITS]
-            arr = (ctypes.c_int64 * len(chunk))(*chunk)
-            c1 = c0 + len(chunk)
-            _lib.check(lib.ch_hamming_tie_bracket(_lib.ptr(bc), Qn, nb, arr, len(chunk), int(bool(remove_first)), _lib.ptr(S_lo[c0:c1]),
-                                                  _lib.ptr(n_lo[c0:c1]), _lib.ptr(S_hi[c0:c1]), _lib.ptr(n_hi[c0:c1]),
+        for rows, arr, cnt in _limit_chunks(limits):
+            _lib.check(lib.ch_hamming_tie_bracket(_lib.ptr(bc), Qn, nb, arr, cnt, int(bool(remove_first)), _lib.ptr(S_lo[rows]),
+                                                  _lib.ptr(n_lo[rows]), _lib.ptr(S_hi[rows]), _lib.ptr(n_hi[rows]),
                                                   _lib.stream_ptr(stream)), "ch_hamming_tie_bracket")
     return S_lo, n_lo, S_hi, n_hi
 
@@ -507,16 +512,14 @@ def hamming_hist_rec(q, g, q_lab, g_lab, LW: int, seg_rows: int, rec_cap: Option
     """mAP pass 1 of the one-scan form: the histogram of hamming_hist plus the per-lane record lists of the relevant rows
     -> (hist, records) where records = (rec, rec_cap, rec_cnt, wg_flags) is what hamming_ap_rec takes."""
     lib = _lib.load()
-    q, g = _check_packed(q, g)
+    q, g, hist = _hist_pass(q, g, seg_rows)
     Qn, W = q.shape
     G = g.shape[0]
-    nseg = max(1, -(-G // seg_rows))
     cap = int(rec_cap) if rec_cap else record_cap(Qn, G, W, seg_rows)
     wgs = int(lib.ch_hamming_rec_workgroups(Qn, G, W, seg_rows))
     blk = int(lib.ch_hamming_rec_block(W))
-    hist = (torch.empty if G > 0 else torch.zeros)(nseg, Qn, 64 * W + 1, 2, dtype=torch.int32, device=q.device)
     rec = torch.empty(max(1, wgs) * cap * blk, 2, dtype=torch.int32, device=q.device)
-    rec_cnt = torch.empty(nseg, Qn, dtype=torch.int32, device=q.device)
+    rec_cnt = torch.empty(hist.shape[0], Qn, dtype=torch.int32, device=q.device)
     wg_flags = torch.zeros(max(1, wgs), dtype=torch.int32, device=q.device)
     with _dev_guard(q):
         _lib.check(lib.ch_hamming_hist_rec(_lib.ptr(q), Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
@@ -528,27 +531,9 @@ def hamming_hist_rec(q, g, q_lab, g_lab, LW: int, seg_rows: int, rec_cap: Option
 def hamming_ap_rec(q, g, q_lab, g_lab, LW: int, seg_rows: int, base: torch.Tensor, records, rank_limits: Sequence[int],
                    first_rel: Optional[torch.Tensor] = None, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """hamming_ap_multi from the records of hamming_hist_rec (no second distance scan except for overflowed workgroups)."""
-    lib = _lib.load()
-    q, g = _check_packed(q, g)
-    Qn, W = q.shape
-    G = g.shape[0]
     rec, cap, rec_cnt, wg_flags = records
-    lim = [int(r) for r in rank_limits]
-    n = len(lim)
-    S = torch.zeros(n, Qn, dtype=torch.int64, device=q.device)
-    nrel = torch.zeros(n, Qn, dtype=torch.int32, device=q.device)
-    if first_rel is not None:
-        first_rel = first_rel.to(torch.int32).contiguous()
-    base = base.contiguous()
-    with _dev_guard(q):
-        for c0 in range(0, n, MAX_LIMITS):
-            chunk = lim[c0:c0 + MAX_LIMITS]
-            arr = (ctypes.c_int64 * len(chunk))(*chunk)
-            _lib.check(lib.ch_hamming_ap_rec(_lib.ptr(q), Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, seg_rows,
-                                             _lib.ptr(base), _lib.ptr(rec), cap, _lib.ptr(rec_cnt), _lib.ptr(wg_flags), arr,
-                                             len(chunk), _lib.ptr(first_rel), _lib.ptr(S[c0:c0 + len(chunk)]),
-                                             _lib.ptr(nrel[c0:c0 + len(chunk)]), _lib.stream_ptr(stream)), "ch_hamming_ap_rec")
-    return S, nrel
+    return _ap("ch_hamming_ap_rec", q, g, q_lab, g_lab, LW, seg_rows, base, rank_limits, first_rel, stream,
+               (_lib.ptr(rec), cap, _lib.ptr(rec_cnt), _lib.ptr(wg_flags)))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -802,6 +787,111 @@ def summarize(S, nrel, total, idx_of, Rs: Sequence[int], ks: Sequence[int], skip
     return dict(mAPs=vals[:nR], aps=aps, hits=hits, precisions=vals[nR:nR + len(ks)], recalls=vals[nR + len(ks):])
 
 
+def use_records(ops, Qn: int, rows: int, W: int, LW: int, seg_rows: int, q_lab, g_lab, records: Optional[bool] = None,
+                rec_cap: Optional[int] = None) -> bool:
+    """Whether an evaluation whose scan walks `rows` gallery rows takes the record (one-scan) form.  An explicit `records` wins;
+    `ops` without `hamming_hist_rec` have the two-scan form only; otherwise CH_HAMMING_RECORDS=0 turns it off, and it needs lists
+    that fit (`records_fit`, or the caller's `rec_cap`).  The label layout then decides which form is faster (never the result): left
+    to the default capacity, a large single-label problem whose lists would overflow almost everywhere runs two scans."""
+    if records is not None:
+        return bool(records)
+    if not hasattr(ops, "hamming_hist_rec") or os.environ.get("CH_HAMMING_RECORDS", "1") == "0" \
+            or (rec_cap is None and not records_fit(Qn, rows, W, seg_rows)):
+        return False
+    if rec_cap is None and LW == 0 and Qn * rows >= OVERFLOW_MIN_PAIRS:
+        return predicted_overflow(q_lab, g_lab, W, seg_rows, record_cap(Qn, rows, W, seg_rows)) <= OVERFLOW_SWITCH
+    return True
+
+
+def empty_result(Qn: int, W: int, dev, Rs: Sequence[int], ks: Sequence[int], many: bool, tie_bracket: bool, radii) -> dict:
+    """What the evaluation returns without a query or without a gallery row: zeros in every key's type and shape."""
+    z64 = torch.zeros(Qn, dtype=torch.int64, device=dev)
+    z32 = torch.zeros(Qn, dtype=torch.int32, device=dev)
+    out = dict(mAP=0.0, precisions=[0.0] * len(ks), recalls=[0.0] * len(ks), S=z64, nrel=z32,
+               hits=torch.zeros(Qn, len(ks), dtype=torch.int32, device=dev), total=z32, ap=z64.double())
+    if many:
+        out.update(mAP=[0.0] * len(Rs), S=[z64] * len(Rs), nrel=[z32] * len(Rs), ap=[z64.double()] * len(Rs))
+    if tie_bracket:
+        for side in ("low", "high"):
+            out.update({"mAP_" + side: out["mAP"], "ap_" + side: out["ap"], "S_" + side: out["S"], "nrel_" + side: out["nrel"],
+                        "precisions_" + side: list(out["precisions"]), "recalls_" + side: list(out["recalls"]),
+                        "hits_" + side: out["hits"]})
+    if radii is not None:
+        out.update(hash_lookup_stats(torch.zeros(Qn, 64 * W + 1, 2, dtype=torch.int32, device=dev), radii))
+    return out
+
+
+class WholeGallery:
+    """The gallery side of `evaluate_gallery` for a gallery this process holds whole: nothing is exchanged.
+    (`distributed.ShardedRetrieval` is the row-sharded one.)  gallery / labels: the rows this process scans; rows: the WHOLE gallery's
+    row count; scan_rows: the longest scan of any process, which sizes the segments and the record lists."""
+
+    def __init__(self, gallery: torch.Tensor, labels: torch.Tensor, ops):
+        self.gallery, self.labels, self.ops = gallery, labels, ops
+        self.rows = self.scan_rows = gallery.shape[0]
+
+    def first_relevant(self, q, q_lab, g_lab, LW: int) -> torch.Tensor:
+        """int32 [Qn]: is every query's rank-1 row relevant"""
+        idx, _ = self.ops.hamming_topk(q, self.gallery, 1)
+        return _relevance_of(idx, q_lab, g_lab, LW)[:, 0].to(torch.int32)
+
+    def bases(self, hist: torch.Tensor, want_counts: bool):
+        """this process's histogram -> ("ranked before" bases of its segments, whole-gallery totals [Qn, 2], whole-gallery bucket
+        counts [Qn, nb, 2] or None)"""
+        base, totals = self.ops.hist_prefix(hist)
+        return base, totals, hist.sum(0, dtype=hist.dtype) if want_counts else None
+
+    def reduce(self, S: torch.Tensor, nrel: torch.Tensor) -> None:
+        """this process's AP integers -> the whole gallery's, in place"""
+
+
+def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Sequence[int] = (1, 5, 10), remove_first: bool = False,
+                     seg_rows: Optional[int] = None, records: Optional[bool] = None, rec_cap: Optional[int] = None,
+                     skip_queries_without_relevant: bool = False, tie_bracket: bool = False,
+                     radii: Optional[Sequence[int]] = None, single: Optional[bool] = None) -> dict:
+    """The evaluation behind `evaluate` and `ShardedRetrieval.evaluate`: labels, rank-1 relevance, histogram pass (with records or
+    without), prefix, ONE AP pass over every R and k, the statistics.  `gal` (`WholeGallery` or a `ShardedRetrieval`) holds the rows
+    this process scans, the `ops` that scan them and the steps that cross ranks; every process of a sharded evaluation gets here with
+    the same q and takes the same path through this body.  single: `prepare_labels`' decision, where the caller has made it."""
+    ops, g = gal.ops, gal.gallery
+    dev = q.device
+    Qn, W = q.shape
+    ql, gl = q_labels.to(dev), gal.labels.to(dev)
+    q_lab, g_lab, LW = ops.prepare_labels(ql, gl, single)
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    many = isinstance(R, (list, tuple))
+    Rs = [int(r) for r in R] if many else [int(R)]
+    if Qn == 0 or gal.rows == 0:
+        return empty_result(Qn, W, dev, Rs, ks, many, tie_bracket, radii)
+    # relevance of every query's rank-1 row (the self-match when the test set is the database)
+    first_rel = gal.first_relevant(q, q_lab, g_lab, LW) if remove_first else None
+    seg = seg_rows or ops.map_seg_rows(Qn, gal.scan_rows, W)
+    limits, idx_of = ops.normalize_limits(Rs + ks)
+    # one distance scan (histogram + records of the relevant rows, prefix, the AP terms from the records) or two
+    rec = use_records(ops, Qn, gal.scan_rows, W, LW, seg, q_lab, g_lab, records, rec_cap)
+    hist, recs = ops.hamming_hist_rec(q, g, q_lab, g_lab, LW, seg, rec_cap=rec_cap) if rec else (ops.hamming_hist(q, g, q_lab, g_lab, LW, seg), None)
+    base, totals, counts2 = gal.bases(hist, tie_bracket or radii is not None)
+    if rec:
+        S, nrel = ops.hamming_ap_rec(q, g, q_lab, g_lab, LW, seg, base, recs, limits, first_rel=first_rel)
+    else:
+        S, nrel = ops.hamming_ap_multi(q, g, q_lab, g_lab, LW, seg, base, limits, first_rel=first_rel)
+    gal.reduce(S, nrel)
+    total = totals[:, 1].clone()
+    if remove_first:
+        total = total - first_rel
+    sm = ops.summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
+    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    out = dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
+               mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+    if tie_bracket:
+        out.update(ops.tie_results(counts2, Rs, ks, remove_first, many, skip_queries_without_relevant))
+    if radii is not None:
+        out.update(hash_lookup_stats(counts2, radii, (lowest_bucket(counts2), first_rel) if remove_first else None))
+    return out
+
+
 def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
              ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, seg_rows: Optional[int] = None,
              records: Optional[bool] = None, rec_cap: Optional[int] = None, skip_queries_without_relevant: bool = False,
@@ -821,62 +911,5 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
     radii: a list of Hamming radii adds the hash-lookup statistics of `hash_lookup_stats` (LOOKUP_KEYS) from the same histogram -- a few
     elementwise launches; None adds nothing and costs nothing."""
     q, g = _check_packed(q, g)
-    Qn, W = q.shape
-    G = g.shape[0]
-    q_lab, g_lab, LW = prepare_labels(q_labels.to(q.device), g_labels.to(q.device))
-    seg = seg_rows or map_seg_rows(Qn, G, W)
-    ks = [int(k) for k in ks]
-    if any(k <= 0 for k in ks):
-        raise ValueError("P@k / R@k need k >= 1")
-    many = isinstance(R, (list, tuple))
-    Rs = [int(r) for r in R] if many else [int(R)]
-    dev = q.device
-    if Qn == 0 or G == 0:
-        z64 = torch.zeros(Qn, dtype=torch.int64, device=dev)
-        z32 = torch.zeros(Qn, dtype=torch.int32, device=dev)
-        out = dict(mAP=0.0, precisions=[0.0] * len(ks), recalls=[0.0] * len(ks), S=z64, nrel=z32,
-                   hits=torch.zeros(Qn, len(ks), dtype=torch.int32, device=dev), total=z32, ap=z64.double())
-        if many:
-            out.update(mAP=[0.0] * len(Rs), S=[z64] * len(Rs), nrel=[z32] * len(Rs), ap=[z64.double()] * len(Rs))
-        if tie_bracket:
-            for side in ("low", "high"):
-                out.update({"mAP_" + side: out["mAP"], "ap_" + side: out["ap"], "S_" + side: out["S"], "nrel_" + side: out["nrel"],
-                            "precisions_" + side: list(out["precisions"]), "recalls_" + side: list(out["recalls"]),
-                            "hits_" + side: out["hits"]})
-        if radii is not None:
-            out.update(hash_lookup_stats(torch.zeros(Qn, 64 * W + 1, 2, dtype=torch.int32, device=dev), radii))
-        return out
-    first_rel = None
-    if remove_first:   # relevance of every query's rank-1 row (the self-match when the test set is the database)
-        idx, _ = hamming_topk(q, g, 1)
-        first_rel = _relevance_of(idx, q_lab, g_lab, LW)[:, 0].to(torch.int32)
-    limits, idx_of = normalize_limits(Rs + ks)
-    if records is None:
-        records = os.environ.get("CH_HAMMING_RECORDS", "1") != "0" and (rec_cap is not None or records_fit(Qn, G, W, seg))
-        if records and rec_cap is None and LW == 0 and Qn * G >= OVERFLOW_MIN_PAIRS:
-            # the label layout decides which form is faster (never the result): lists that would overflow almost everywhere -> two scans
-            records = predicted_overflow(q_lab, g_lab, W, seg, record_cap(Qn, G, W, seg)) <= OVERFLOW_SWITCH
-    if records:   # one distance scan: histogram + records of the relevant rows, prefix, then the AP terms from the records
-        hist, recs = hamming_hist_rec(q, g, q_lab, g_lab, LW, seg, rec_cap=rec_cap)
-        base, totals = hist_prefix(hist)
-        S, nrel = hamming_ap_rec(q, g, q_lab, g_lab, LW, seg, base, recs, limits, first_rel=first_rel)
-    else:         # two scans (the round-1 / early round-2 form; also what the sharded evaluator runs)
-        hist = hamming_hist(q, g, q_lab, g_lab, LW, seg)
-        base, totals = hist_prefix(hist)
-        S, nrel = hamming_ap_multi(q, g, q_lab, g_lab, LW, seg, base, limits, first_rel=first_rel)
-    total = totals[:, 1].clone()
-    if remove_first:
-        total = total - first_rel
-    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-    out = dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total)
-    if many:
-        out.update(mAP=sm["mAPs"], S=[S[idx_of[i]] for i in range(len(Rs))], nrel=[nrel[idx_of[i]] for i in range(len(Rs))],
-                   ap=sm["aps"])
-    else:
-        out.update(mAP=sm["mAPs"][0], S=S[idx_of[0]], nrel=nrel[idx_of[0]], ap=sm["aps"][0])
-    counts2 = hist.sum(0, dtype=hist.dtype) if tie_bracket or radii is not None else None
-    if tie_bracket:
-        out.update(tie_results(counts2, Rs, ks, remove_first, many, skip_queries_without_relevant))
-    if radii is not None:
-        out.update(hash_lookup_stats(counts2, radii, (lowest_bucket(counts2), first_rel) if remove_first else None))
-    return out
+    return evaluate_gallery(WholeGallery(g, g_labels, sys.modules[__name__]), q, q_labels, R, ks, remove_first, seg_rows, records, rec_cap,
+                            skip_queries_without_relevant, tie_bracket, radii)

@@ -77,6 +77,48 @@ def test_two_rank_sharded_retrieval_matches_oracle(tmp_path, bounds, remove_firs
         assert np.allclose(z["P"], ref["precisions"]) and np.allclose(z["Rc"], ref["recalls"])
 
 
+@pytest.mark.parametrize("remove_first", [False, True])
+@pytest.mark.parametrize("R", [-1, [5, 100, -1]])
+def test_whole_gallery_pipeline_matches_oracle_in_one_process(remove_first, R):
+    """The evaluation body both entry points run (retrieval.evaluate_gallery), with the whole-gallery object `retrieval.evaluate` hands
+    it and the CPU stand-in as ops: the single-GPU host logic without a GPU and without a process group, bit-equal to the oracle."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import cpu_ops
+    from concepthash_amd import retrieval as rt
+    from oracle import hamming_oracle as ho
+    q, ql = ho.synthetic_codes(61, 64, seed=5, nclass=6)
+    g, gl = ho.synthetic_codes(333, 64, seed=6, nclass=6)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64) if a.dtype == np.uint64 else a)
+    ev = rt.evaluate_gallery(rt.WholeGallery(tt(g), tt(gl), cpu_ops), tt(q), tt(ql), R=R, ks=(1, 5, 10), remove_first=remove_first, seg_rows=97)
+    many = isinstance(R, list)
+    for i, r_ in enumerate(R if many else [R]):
+        ref = ho.mean_ap(q, g, ql, gl, R=r_, ks=(1, 5, 10), remove_first=remove_first)
+        S, nrel = (ev["S"][i], ev["nrel"][i]) if many else (ev["S"], ev["nrel"])
+        assert np.array_equal(S.numpy().view(np.uint64), ref["S"]) and np.array_equal(nrel.numpy().astype(np.uint32), ref["nrel"])
+        assert abs(float(ev["mAP"][i] if many else ev["mAP"]) - ref["mAP"]) < 1e-12
+        assert np.array_equal(ev["hits"].numpy().astype(np.uint32), ref["hits"])
+        assert np.array_equal(ev["total"].numpy().astype(np.uint32), ref["total"])
+    # no gallery row: the zeros of every key, in the types and shapes of a real result
+    empty = rt.evaluate_gallery(rt.WholeGallery(tt(g[:0]), tt(gl[:0]), cpu_ops), tt(q), tt(ql), R=R, ks=(1, 5, 10), remove_first=remove_first,
+                                seg_rows=97, tie_bracket=True, radii=[0, 3])
+    assert set(empty) == set(ev) | set(rt.TIE_KEYS) | set(rt.LOOKUP_KEYS)
+    def same_form_all_zero(got, val):
+        if isinstance(val, list):
+            assert isinstance(got, list) and len(got) == len(val)
+            for a, b in zip(got, val):
+                same_form_all_zero(a, b)
+        elif torch.is_tensor(val):
+            assert got.dtype == val.dtype and got.shape == val.shape and not got.any()
+        else:
+            assert type(got) is type(val) and got == 0.0
+
+    for key, val in ev.items():
+        for name in [key] if key == "total" else [key, key + "_low", key + "_high"]:
+            same_form_all_zero(empty[name], val)
+    assert empty["lookup_retrieved"].shape == (61, 2) and empty["precisions_radius"] == [0.0, 0.0]
+
+
 def test_shard_bounds():
     from concepthash_amd.distributed import shard_bounds
     assert shard_bounds(10, 3) == [0, 4, 7, 10]

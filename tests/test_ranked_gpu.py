@@ -72,6 +72,36 @@ def test_ranked_lists_equal_the_stable_argsort_on_the_shape_grid(dev, W):
                     assert _same(rt.hamming_ranked(tq, tg, k, seg_rows=seg), want), (W, Qn, G, k, seg)
 
 
+@pytest.mark.parametrize("W", [1, 3])
+def test_every_exit_of_the_scalar_block_walk_in_both_of_its_users(dev, W):
+    """The scalar double-buffered walk over a segment -- load a block, scan the previous one, the odd-block case, the row tail -- is
+    written in the two-scan mAP passes (blocks of 4 rows; taken under the scalar-load tap) and in the rank pass (blocks of 8 rows at
+    W <= 2, of 4 above).  Segments of 3 / 4 / 8 / 9 / 16 / 25 rows are shorter than a block, exactly one block, two blocks, and odd
+    whole blocks plus a tail for one block size or the other; the gallery's last segment is ragged.  evaluate(records=False) in the
+    VMEM form and the scalar form against the oracle, hamming_ranked for a short and a past-the-gallery k against the stable argsort."""
+    from concepthash_amd import _lib, retrieval as rt
+    from oracle import hamming_oracle as ho
+    lib = _lib.load()
+    Qn, G = 70, 130 if W == 3 else 100
+    q, ql = ho.synthetic_codes(Qn, 64 * W, seed=71, nclass=5, flip=0.15)
+    g, gl = ho.synthetic_codes(G, 64 * W, seed=72, nclass=5, flip=0.15)
+    ref = ho.mean_ap(q, g, ql, gl, R=-1, ks=(1, 5, 10), remove_first=False)
+    order, ds, _ = rr.ranking(q, g)
+    tq, tg, tql, tgl = _t(q, dev), _t(g, dev), _t(ql, dev), _t(gl, dev)
+    for seg in (3, 4, 8, 9, 16, 25):
+        for scalar in (0, 1):
+            lib.ch_debug_set_hamming_scalar_loads(scalar)
+            try:
+                got = rt.evaluate(tq, tg, tql, tgl, R=-1, ks=(1, 5, 10), seg_rows=seg, records=False)
+            finally:
+                lib.ch_debug_set_hamming_scalar_loads(0)
+            assert np.array_equal(got["S"].cpu().numpy().view(np.uint64), ref["S"]), (seg, scalar)
+            for key in ("nrel", "hits", "total"):
+                assert np.array_equal(got[key].cpu().numpy().astype(np.uint32), ref[key]), (seg, scalar, key)
+        for k in (7, G + 3):
+            assert _same(rt.hamming_ranked(tq, tg, k, seg_rows=seg), _slice(order, ds, k)), (seg, k)
+
+
 def test_ranked_lists_with_the_default_segments(dev):
     from concepthash_amd import retrieval as rt
     q, g, order, ds = _case(1, 700, 9001)
