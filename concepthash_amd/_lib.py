@@ -158,6 +158,20 @@ SIGNATURES = {
     "ch_debug_scatter_concept_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "ch_debug_expand_head_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ch_debug_gather_concept_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_im2col": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_assemble_preln": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_float, c_void_p, c_void_p]),
+    "ch_debug_layernorm_f32": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "ch_debug_layernorm_bf16": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
+    "ch_debug_gather_head_rows": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_head": (c_int, [c_void_p] + [c_int32] * 7 + [c_void_p] * 11 + [c_float] + [c_void_p] * 8),
+    "ch_debug_small_linear": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_small_layernorm": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    "ch_debug_small_add": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ch_debug_small_mha": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_small_l2norm": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ch_debug_convert_bf16": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_debug_bn_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "ch_debug_fold_ln": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_hamming_hist_prefix": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "ch_hamming_rank_scatter": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_void_p, c_void_p, c_void_p]),

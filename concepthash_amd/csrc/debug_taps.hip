@@ -324,3 +324,99 @@ extern "C" int ch_debug_gather_concept_rows(const float *H, int32_t B, int32_t n
     CH_REQUIRE(H && out && B >= 1 && Q >= 1 && Q <= ntok && D >= 1, "debug_gather_concept_rows: null argument or Q outside 1..ntok");
     return ch_gather_concept_rows(H, B, ntok, Q, D, out, (hipStream_t)stream);
 }
+
+// ---- the forward row kernels (rowops.hip), the hashing head (head.hip) and the load-time folds (small_f32.hip), each launcher by
+// itself on caller buffers (tests/test_forward_kernels_gpu.py)
+extern "C" int ch_debug_im2col(const void *images, int32_t image_dtype, int32_t B, int32_t image, int32_t patch, int32_t Kp, void *out,
+                               void *stream) {
+    CH_REQUIRE(images && out && (image_dtype == 0 || image_dtype == 1), "debug_im2col: null argument or image_dtype not 0 (fp32) / 1 (bf16)");
+    CH_REQUIRE(B >= 1 && patch >= 1 && image >= patch && image % patch == 0, "debug_im2col: the image must be a whole number of patches");
+    return ch_im2col(images, image_dtype, B, image, patch, Kp, (bf16_t *)out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_assemble_preln(float *H, int32_t B, int32_t ntok, int32_t np, int32_t D, const float *cls_pos0, const float *ctx,
+                                       const float *pre_w, const float *pre_b, const float *ln_w, const float *ln_b, float eps, void *xn,
+                                       void *stream) {
+    CH_REQUIRE(H && cls_pos0 && ctx && pre_w && pre_b && ln_w && ln_b && xn, "debug_assemble_preln: null argument");
+    CH_REQUIRE(B >= 1 && np >= 1 && ntok > 1 + np, "debug_assemble_preln: ntok must be 1 + np + the number of concept rows (>= 1)");
+    return ch_assemble_preln(H, B, ntok, np, D, cls_pos0, ctx, pre_w, pre_b, ln_w, ln_b, eps, (bf16_t *)xn, (hipStream_t)stream);
+}
+extern "C" int ch_debug_layernorm_f32(const float *x, int64_t rows, int32_t D, const float *w, const float *b, float eps, void *out,
+                                      void *stream) {
+    CH_REQUIRE(x && w && b && out && rows > 0, "debug_layernorm_f32: null argument");
+    return ch_layernorm_f32(x, rows, D, w, b, eps, (bf16_t *)out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_layernorm_bf16(const void *x, int64_t rows, int32_t D, const float *w, const float *b, float eps, void *out,
+                                       int32_t kernel, void *stream) {
+    CH_REQUIRE(x && w && b && out && rows > 0, "debug_layernorm_bf16: null argument");
+    return ch_layernorm_bf16((const bf16_t *)x, rows, D, w, b, eps, (bf16_t *)out, (hipStream_t)stream, kernel);
+}
+extern "C" int ch_debug_gather_head_rows(const float *H, int32_t B, int32_t ntok, int32_t ncon, int32_t D, float *out, void *stream) {
+    CH_REQUIRE(H && out && D >= 4, "debug_gather_head_rows: null argument");
+    return ch_gather_head_rows(H, B, ntok, ncon, D, out, (hipStream_t)stream);
+}
+// Every HeadParams pointer goes through as given, nulls included: an optional output is asked for by passing its buffer.  The operands
+// that an output reads must come with it (the kernel would read them), and the two workspaces are allocated here.
+extern "C" int ch_debug_head(const float *H, int32_t B, int32_t ntok, int32_t D, int32_t Q, int32_t nbit, int32_t C, int32_t P,
+                             const float *hash_pe, const float *hash_fc, const float *bn_scale, const float *bn_shift,
+                             const float *center_l2, const float *center_bin, const float *concept_pe, const float *concept_cent_l2,
+                             const float *post_w, const float *post_b, const float *vis_proj, float ln_eps, float *out_codes,
+                             void *out_packed, float *out_logits_cont, float *out_logits_bin, float *out_logits_concept,
+                             float *out_hash_features, float *out_image_features, void *stream) {
+    CH_REQUIRE(H && hash_pe && hash_fc && bn_scale && bn_shift && out_codes, "debug_head: null argument");
+    CH_REQUIRE(B >= 1 && D >= 1 && Q >= 1 && nbit >= 1 && ntok > Q, "debug_head: empty problem or ntok <= Q");
+    CH_REQUIRE(!(out_logits_cont || out_logits_bin) || (center_l2 && center_bin && C >= 1), "debug_head: the code logits need both centre arrays");
+    CH_REQUIRE(!out_logits_concept || (concept_pe && concept_cent_l2 && C >= 1), "debug_head: the concept logits need concept_pe and the centroids");
+    CH_REQUIRE(!out_image_features || (post_w && post_b && vis_proj && P >= 1), "debug_head: the image features need post_w, post_b and vis_proj");
+    hipStream_t s = (hipStream_t)stream;
+    ChDeviceTemp txn, tcls;
+    if (out_logits_concept && txn.get(sizeof(float) * (size_t)B * Q * D)) return 1;
+    if (out_image_features && tcls.get(sizeof(float) * (size_t)B * D)) return 1;
+    HeadParams p{};
+    p.H = H; p.B = B; p.ntok = ntok; p.D = D; p.Q = Q; p.nbit = nbit; p.C = C; p.P = P;
+    p.hash_pe = hash_pe; p.hash_fc = hash_fc; p.bn_scale = bn_scale; p.bn_shift = bn_shift;
+    p.center_l2 = center_l2; p.center_bin = center_bin; p.concept_pe = concept_pe; p.concept_cent_l2 = concept_cent_l2;
+    p.post_w = post_w; p.post_b = post_b; p.vis_proj = vis_proj; p.ln_eps = ln_eps;
+    p.out_codes = out_codes; p.out_packed = (uint64_t *)out_packed; p.out_logits_cont = out_logits_cont; p.out_logits_bin = out_logits_bin;
+    p.out_logits_concept = out_logits_concept; p.out_hash_features = out_hash_features; p.out_image_features = out_image_features;
+    p.ws_xn = txn.as<float>(); p.ws_cls = tcls.as<float>();
+    const int e = ch_head(p, s);
+    (void)hipStreamSynchronize(s);
+    return e;
+}
+extern "C" int ch_debug_small_linear(const float *x, int32_t rows, int32_t in_f, const float *W, const float *b, int32_t out_f, int32_t act,
+                                     float *y, void *stream) {
+    CH_REQUIRE(x && W && y && rows >= 1 && in_f >= 1 && out_f >= 1, "debug_small_linear: null argument or empty problem");
+    return ch_small_linear(x, rows, in_f, W, b, out_f, act, y, (hipStream_t)stream);
+}
+extern "C" int ch_debug_small_layernorm(const float *x, int32_t rows, int32_t D, const float *w, const float *b, float eps, float *y,
+                                        void *stream) {
+    CH_REQUIRE(x && w && b && y && rows >= 1 && D >= 1, "debug_small_layernorm: null argument or empty problem");
+    return ch_small_layernorm(x, rows, D, w, b, eps, y, (hipStream_t)stream);
+}
+extern "C" int ch_debug_small_add(const float *a, const float *b, int64_t n, float *y, void *stream) {
+    CH_REQUIRE(a && b && y && n >= 1, "debug_small_add: null argument or empty problem");
+    return ch_small_add(a, b, n, y, (hipStream_t)stream);
+}
+extern "C" int ch_debug_small_mha(const float *qkv, int32_t T, int32_t P, int32_t heads, float *out, void *stream) {
+    CH_REQUIRE(qkv && out && T >= 1 && heads >= 1 && P >= heads, "debug_small_mha: null argument or empty problem");
+    return ch_small_mha(qkv, T, P, heads, out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_small_l2norm(const float *x, int32_t rows, int32_t cols, float *out_l2, float *out_bin, void *stream) {
+    CH_REQUIRE(x && out_l2 && rows >= 1 && cols >= 1, "debug_small_l2norm: null argument or empty problem");
+    return ch_small_l2norm(x, rows, cols, out_l2, out_bin, (hipStream_t)stream);
+}
+extern "C" int ch_debug_convert_bf16(const float *x, int64_t rows, int32_t cols, int32_t cols_pad, void *out, void *stream) {
+    CH_REQUIRE(x && out && rows >= 1 && cols >= 1 && cols_pad >= cols, "debug_convert_bf16: null argument or cols_pad < cols");
+    return ch_convert_bf16(x, rows, cols, cols_pad, (bf16_t *)out, (hipStream_t)stream);
+}
+extern "C" int ch_debug_bn_fold(const float *w, const float *b, const float *mean, const float *var, int32_t n, float eps, float *scale,
+                                float *shift, void *stream) {
+    CH_REQUIRE(w && b && mean && var && scale && shift && n >= 1, "debug_bn_fold: null argument or empty problem");
+    return ch_bn_fold(w, b, mean, var, n, eps, scale, shift, (hipStream_t)stream);
+}
+extern "C" int ch_debug_fold_ln(const float *Wd, const float *bd, const float *gamma, const float *beta, int32_t b, int32_t bpad, int32_t D,
+                                void *Wdf, float *c, float *d, void *stream) {
+    CH_REQUIRE(Wd && bd && gamma && beta && Wdf && c && d, "debug_fold_ln: null argument");
+    CH_REQUIRE(b >= 1 && bpad >= b && D >= 1, "debug_fold_ln: empty problem or bpad < b");
+    return ch_fold_ln(Wd, bd, gamma, beta, b, bpad, D, (bf16_t *)Wdf, c, d, (hipStream_t)stream);
+}

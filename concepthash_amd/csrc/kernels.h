@@ -156,8 +156,9 @@ int ch_assemble_preln(float *H, int B, int ntok, int np, int D, const float *cls
 int ch_layernorm_f32(const float *x, int64_t rows, int D, const float *w, const float *b, float eps, bf16_t *out,
                      hipStream_t s);
 // LayerNorm over D of bf16 rows -> bf16
+// kernel: 0 = by width (up to 1024 features the 16-byte kernel, wider rows the generic one), 1 = 16-byte, 2 = generic (test taps)
 int ch_layernorm_bf16(const bf16_t *x, int64_t rows, int D, const float *w, const float *b, float eps, bf16_t *out,
-                      hipStream_t s);
+                      hipStream_t s, int kernel = 0);
 
 // compact copy of the residual rows the hashing head reads: out[b*(1+ncon) + j] = H[b*ntok + (j == 0 ? 0 : ntok-ncon+j-1)]
 int ch_gather_head_rows(const float *H, int B, int ntok, int ncon, int D, float *out, hipStream_t s);

@@ -258,10 +258,12 @@ int ch_layernorm_f32(const float *x, int64_t rows, int D, const float *w, const 
 }
 
 int ch_layernorm_bf16(const bf16_t *x, int64_t rows, int D, const float *w, const float *b, float eps, bf16_t *out,
-                      hipStream_t s) {
+                      hipStream_t s, int kernel) {
     CH_REQUIRE(D % 128 == 0 && D <= 128 * MAXP, "layernorm: D must be a multiple of 128 and <= 1280");
+    CH_REQUIRE(kernel >= 0 && kernel <= 2, "layernorm: kernel must be 0 (by width), 1 (wide) or 2 (generic)");
+    CH_REQUIRE(kernel != 1 || D <= 1024, "layernorm: the wide kernel holds rows of at most 1024 features");
     if (rows == 0) return 0;
-    if (D <= 1024) {
+    if (kernel == 1 || (kernel == 0 && D <= 1024)) {
         hipLaunchKernelGGL(layernorm_bf16_wide_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, s, x, rows, D, w, b,
                            eps, out);
         CH_LAUNCH_CHECK();

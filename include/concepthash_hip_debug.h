@@ -124,6 +124,43 @@ int ch_debug_scatter_concept_rows(const float *dhf, int32_t B, int32_t ntok, int
 int ch_debug_expand_head_rows(const void *src, int32_t is_f32, int32_t B, int32_t ntok, int32_t Q, int32_t D, void *dst, void *stream);
 int ch_debug_gather_concept_rows(const float *H, int32_t B, int32_t ntok, int32_t Q, int32_t D, float *out, void *stream);
 
+/* The forward row kernels (rowops.hip), the hashing head (head.hip) and the load-time folds (small_f32.hip), one launcher each on caller
+ * buffers (tests/test_forward_kernels_gpu.py holds every one to an fp64 restatement, tests/forward_kernels_ref.py).
+ * im2col: images [B, 3, image, image] fp32 (image_dtype 0) or bf16 (1) -> out [B * (image / patch)^2, Kp] bf16, column
+ * c * patch^2 + ky * patch + kx, zeros from 3 * patch^2 up to Kp.  assemble_preln: H [B * ntok, D] is replaced in place (row 0 of an image
+ * from cls_pos0, rows past np from ctx, pre-LayerNorm) and xn = bf16(LayerNorm(H)).  layernorm_bf16: kernel 0 = the launcher's rule
+ * (up to 1024 features the 16-byte kernel, wider rows the generic one), 1 = 16-byte kernel, 2 = generic kernel.
+ * gather_head_rows: out [B * (1 + ncon), D] = the CLS row and the last ncon rows of every image.
+ * head: the arguments are the fields of HeadParams (csrc/kernels.h) in order; every output but out_codes may be null and is then not
+ * computed; out_packed [B, ceil(nbit / 64)] uint64, out_logits_concept [Q, B, C]; the two workspaces are allocated by the tap.
+ * small_*: y = act(x W^T + b) (act 1 = relu, b may be null); LayerNorm of fp32 rows; y = a + b; attention on packed qkv [T, 3P];
+ * l2-normalised rows and (out_bin, optional) their signs / sqrt(cols).  convert_bf16: [rows, cols] -> [rows, cols_pad], zero padded.
+ * bn_fold: scale = w / sqrt(var + eps), shift = b - mean * scale.  fold_ln: Wdf [bpad, D] = bf16(Wd * gamma), c = its row sums,
+ * d = Wd beta + bd; rows b .. bpad - 1 are zero. */
+int ch_debug_im2col(const void *images, int32_t image_dtype, int32_t B, int32_t image, int32_t patch, int32_t Kp, void *out, void *stream);
+int ch_debug_assemble_preln(float *H, int32_t B, int32_t ntok, int32_t np, int32_t D, const float *cls_pos0, const float *ctx,
+                            const float *pre_w, const float *pre_b, const float *ln_w, const float *ln_b, float eps, void *xn, void *stream);
+int ch_debug_layernorm_f32(const float *x, int64_t rows, int32_t D, const float *w, const float *b, float eps, void *out, void *stream);
+int ch_debug_layernorm_bf16(const void *x, int64_t rows, int32_t D, const float *w, const float *b, float eps, void *out, int32_t kernel,
+                            void *stream);
+int ch_debug_gather_head_rows(const float *H, int32_t B, int32_t ntok, int32_t ncon, int32_t D, float *out, void *stream);
+int ch_debug_head(const float *H, int32_t B, int32_t ntok, int32_t D, int32_t Q, int32_t nbit, int32_t C, int32_t P, const float *hash_pe,
+                  const float *hash_fc, const float *bn_scale, const float *bn_shift, const float *center_l2, const float *center_bin,
+                  const float *concept_pe, const float *concept_cent_l2, const float *post_w, const float *post_b, const float *vis_proj,
+                  float ln_eps, float *out_codes, void *out_packed, float *out_logits_cont, float *out_logits_bin, float *out_logits_concept,
+                  float *out_hash_features, float *out_image_features, void *stream);
+int ch_debug_small_linear(const float *x, int32_t rows, int32_t in_f, const float *W, const float *b, int32_t out_f, int32_t act, float *y,
+                          void *stream);
+int ch_debug_small_layernorm(const float *x, int32_t rows, int32_t D, const float *w, const float *b, float eps, float *y, void *stream);
+int ch_debug_small_add(const float *a, const float *b, int64_t n, float *y, void *stream);
+int ch_debug_small_mha(const float *qkv, int32_t T, int32_t P, int32_t heads, float *out, void *stream);
+int ch_debug_small_l2norm(const float *x, int32_t rows, int32_t cols, float *out_l2, float *out_bin, void *stream);
+int ch_debug_convert_bf16(const float *x, int64_t rows, int32_t cols, int32_t cols_pad, void *out, void *stream);
+int ch_debug_bn_fold(const float *w, const float *b, const float *mean, const float *var, int32_t n, float eps, float *scale, float *shift,
+                     void *stream);
+int ch_debug_fold_ln(const float *Wd, const float *bd, const float *gamma, const float *beta, int32_t b, int32_t bpad, int32_t D, void *Wdf,
+                     float *c, float *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
