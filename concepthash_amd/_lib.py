@@ -175,6 +175,12 @@ SIGNATURES = {
     "ch_hamming_hist_prefix": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "ch_hamming_rank_scatter": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
                                         c_void_p, c_void_p, c_void_p]),
+    "ch_hamming_rank_collect": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32,
+                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ch_hamming_rank_count": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p,
+                                      c_void_p, c_int32, c_void_p, c_void_p]),
+    "ch_hamming_rank_ap": (c_int, [c_int64, c_void_p, c_void_p, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

@@ -76,33 +76,7 @@ __device__ __forceinline__ bool relevant_multi(const uint64_t *qm, const uint64_
     return r;
 }
 
-// floor(a * 2^32 / b) for 1 <= a <= b < 2^32, exact: double estimate (hardware reciprocal + one Newton step, relative error
-// ~2^-51, i.e. < 2^-18 absolute on a quotient <= 2^32) + integer correction.  No IEEE division sequence.
-__device__ __forceinline__ unsigned long long fixdiv32(uint32_t a, uint32_t b) {
-    const unsigned long long num = (unsigned long long)a << 32;
-    const double bd = (double)b;
-    double r = __builtin_amdgcn_rcp(bd);
-    r = __builtin_fma(r, __builtin_fma(-bd, r, 1.0), r);
-    unsigned long long qq = (unsigned long long)((double)a * 4294967296.0 * r);
-    long long rem = (long long)(num - qq * (unsigned long long)b);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        if (rem < 0) {
-            qq -= 1;
-            rem += b;
-        }
-        if (rem >= (long long)b) {
-            qq += 1;
-            rem -= b;
-        }
-    }
-    return qq;
-}
-
-constexpr int MAX_LIMITS = 16;
-struct RankLimits {
-    uint32_t lim[MAX_LIMITS];  // mAP@R cut-offs of one AP pass; 0xFFFFFFFF = the whole ranking
-};
+// fixdiv32 (the exact fixed-point quotient of an AP term), MAX_LIMITS and RankLimits: hamming_shared.h
 
 // one relevant row: exact global rank / relevant-rank from (base, position in bucket), AP term into every limit it is inside
 template <int NR>
@@ -804,17 +778,7 @@ int scan_dispatch(int mode, const ScanArgs &a, int W, hipStream_t s) {
     });
 }
 
-// The two checks of an entry that takes rank limits (`who`: its name in the messages): their number, in front of the entry's other
-// checks, and -- behind them -- their order, which fills lims.
-#define CH_REQUIRE_NLIMITS(who) CH_REQUIRE(nlimits >= 1 && nlimits <= MAX_LIMITS && rank_limits != nullptr, who ": 1 <= nlimits <= 16")
-int fill_limits(const char *who, const int64_t *rank_limits, int nlimits, RankLimits &lims) {
-    for (int i = 0; i < MAX_LIMITS; ++i) {
-        const int64_t r = rank_limits[i < nlimits ? i : nlimits - 1];
-        lims.lim[i] = (r <= 0 || r >= 0xFFFFFFFFll) ? 0xFFFFFFFFu : (uint32_t)r;
-        CH_REQUIRE(i == 0 || lims.lim[i] >= lims.lim[i - 1], std::string(who) + ": rank limits must ascend (<= 0 = unlimited, last)");
-    }
-    return 0;
-}
+// CH_REQUIRE_NLIMITS and fill_limits, the two checks of an entry that takes rank limits: hamming_shared.h
 
 }  // namespace
 

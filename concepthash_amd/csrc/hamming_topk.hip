@@ -46,34 +46,7 @@ __device__ __forceinline__ int hamming_masked(const uint32_t (&q)[2 * W], const 
     return (int)d;
 }
 
-// sum_p 2^p a[p] as a Horner chain of P - 1 v_lshl_add_u32, in one asm block.  Written as d = (d << 1) + a[p] the chain is
-// redistributed into a sum of shifted terms a little further each time the code around it is inlined one level up, and what gets
-// selected from that follows the number of levels: 8 instructions for 8 planes while the scan was written out in each kernel, 9 to
-// 10 behind topk_scan and its distance callable.  One block, not one asm per step: between two dependent asm statements that end
-// up next to each other the compiler puts an s_nop.
-__device__ __forceinline__ uint32_t horner2(const uint32_t (&a)[4]) {
-    uint32_t d;
-    asm("v_lshl_add_u32 %0, %4, 1, %3\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %2\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %1"
-        : "=&v"(d)
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
-    return d;
-}
-__device__ __forceinline__ uint32_t horner2(const uint32_t (&a)[8]) {
-    uint32_t d;
-    asm("v_lshl_add_u32 %0, %8, 1, %7\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %6\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %5\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %4\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %3\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %2\n\t"
-        "v_lshl_add_u32 %0, %0, 1, %1"
-        : "=&v"(d)
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7]));
-    return d;
-}
-
+// horner2, sum_p 2^p a[p] as one block of P - 1 v_lshl_add_u32: hamming_shared.h
 // weighted D: per 32-bit word and plane one (q ^ g) & plane (a single v_bitop3_b32 with the gallery word as its SGPR operand) and one
 // chained v_bcnt into that plane's accumulator -- 2 P instructions per word -- then the Horner chain of P - 1 shift-adds
 template <int W, int P>

@@ -3,7 +3,7 @@ gallery-sharded multi-GPU variants (one process per GPU, RCCL via ``torch.distri
 
 Replaces the reference's un-vendored ``utils.hashing`` arithmetic (call sites experiments/test_hashing.py:106-119,
 153-162).  PyTorch supplies device buffers, streams and collectives; all per-pair arithmetic runs in
-``csrc/hamming_topk.hip`` (top-k search) and ``csrc/hamming.hip`` (distance matrix, mAP).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
+``csrc/hamming_topk.hip`` (top-k search), ``csrc/hamming.hip`` (distance matrix, mAP) and ``csrc/hamming_rankcount.hip`` (mAP under the weighted distance).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
 """
 from __future__ import annotations
 
@@ -913,3 +913,159 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
     q, g = _check_packed(q, g)
     return evaluate_gallery(WholeGallery(g, g_labels, sys.modules[__name__]), q, q_labels, R, ks, remove_first, seg_rows, records, rec_cap,
                             skip_queries_without_relevant, tie_bracket, radii)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# evaluation under the weighted (asymmetric) distance, by rank counting (csrc/hamming_rankcount.hip)
+# ---------------------------------------------------------------------------------------------------------------
+RANK_LIST_MAX = 8192   # longest list of relevant keys a workgroup of the rank-count scan holds in LDS (csrc/hamming_rankcount.hip)
+
+
+def rank_seg_rows(Qn: int, G: int) -> int:
+    """Gallery rows per segment of the rank-count scan (grid = queries x segments): about 2,048 workgroups, segments of at least 256
+    rows, at most 65,535 of them."""
+    want = max(1, -(-2048 // max(1, Qn)))
+    return int(max(256, -(-G // want), -(-G // 65535)))
+
+
+def _check_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor):
+    q, g = _check_packed(q, g)
+    Qn, W = q.shape
+    if planes.dtype != torch.int64 or planes.device != q.device or planes.dim() != 3 or planes.shape[0] != Qn or planes.shape[2] != W \
+            or planes.shape[1] not in WEIGHT_BITS:
+        raise ValueError(f"planes must be an int64 tensor [{Qn}, 4 or 8, {W}] on the queries' device, got {planes.dtype} "
+                         f"{tuple(planes.shape)} on {planes.device}")
+    return q, planes.contiguous(), g
+
+
+def rank_collect(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,
+                 g_index_base: int = 0, stream=None):
+    """The keys D << 32 | global index of every query's relevant rows, as CSR -> (offsets int64 [Qn + 1], keys int64 [total], UNSORTED
+    inside a slice, longest slice).  Two ch_hamming_rank_collect launches (count, then write) around the prefix; reads the total and the
+    longest slice back (one synchronisation).  q_lab / g_lab / LW: `prepare_labels`."""
+    lib = _lib.load()
+    q, planes, g = _check_weighted(q, planes, g)
+    Qn, W = q.shape
+    G, P = g.shape[0], planes.shape[1]
+    count = torch.zeros(Qn, dtype=torch.int32, device=q.device)
+    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q.device)
+    if Qn == 0 or G == 0:
+        return offsets, torch.empty(0, dtype=torch.int64, device=q.device), 0
+
+    def call(off, keys):
+        _lib.check(lib.ch_hamming_rank_collect(_lib.ptr(q), _lib.ptr(planes), P, Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab),
+                                               LW, int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
+                                               _lib.stream_ptr(stream)), "ch_hamming_rank_collect")
+
+    with _dev_guard(q):
+        call(None, None)
+        offsets[1:] = count.cumsum(0, dtype=torch.int64)
+        total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
+        keys = torch.empty(total, dtype=torch.int64, device=q.device)
+        if total:
+            count.zero_()
+            call(offsets, keys)
+    return offsets, keys, int(longest)
+
+
+def sort_slices(offsets: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """Every CSR slice of `keys` ascending.  The keys are below 2^48 (D < 2^16, a 32-bit index), so their order as int64 is their order
+    as uint64, and up to 32,767 slices the slice number fits above them: ONE sort of slice << 48 | key.  More slices: a sort of the flat
+    buffer, then a stable sort by slice."""
+    if keys.numel() == 0:
+        return keys
+    n = offsets[1:] - offsets[:-1]
+    owner = torch.repeat_interleave(torch.arange(n.numel(), device=keys.device), n, output_size=keys.numel())
+    if n.numel() <= 0x7FFF:
+        return (torch.sort(keys | (owner << 48))[0] & ((1 << 48) - 1)).contiguous()
+    keys, order = torch.sort(keys)
+    return keys[torch.sort(owner[order], stable=True)[1]].contiguous()
+
+
+def rank_count(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int,
+               seg_rows: Optional[int] = None, g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """The Qn x G scan -> bins int32 [total] (uint32 bit patterns): bins[offsets[i] + pos] = gallery rows with exactly pos of query i's
+    relevant keys below their own key (rows above the largest relevant key are not counted).  keys: `sort_slices(rank_collect(...))`.
+    `bins`, where given, is added into (gallery shards)."""
+    lib = _lib.load()
+    q, planes, g = _check_weighted(q, planes, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    if bins is None:
+        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q.device)
+    if Qn == 0 or G == 0 or keys.numel() == 0:
+        return bins
+    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
+    with _dev_guard(q):
+        _lib.check(lib.ch_hamming_rank_count(_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W, int(g_index_base), seg,
+                                             _lib.ptr(offsets), _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)),
+                   "ch_hamming_rank_count")
+    return bins
+
+
+def rank_ap(offsets: torch.Tensor, bins: torch.Tensor, rank_limits: Sequence[int], remove_first: bool = False, stream=None):
+    """AP integers from the bins, one launch per MAX_LIMITS limits -> (S int64 [n, Qn], nrel int32 [n, Qn], total int32 [Qn]) in the
+    layout of `hamming_ap_multi`; total = a query's relevant rows (less a dropped relevant rank-1 row)."""
+    lib = _lib.load()
+    Qn = offsets.numel() - 1
+    n = len(rank_limits)
+    dev = offsets.device
+    S = torch.zeros(n, Qn, dtype=torch.int64, device=dev)
+    nrel = torch.zeros(n, Qn, dtype=torch.int32, device=dev)
+    total = torch.zeros(Qn, dtype=torch.int32, device=dev)
+    if Qn == 0:
+        return S, nrel, total
+    with _dev_guard(offsets):
+        for rows, arr, cnt in _limit_chunks(rank_limits):
+            _lib.check(lib.ch_hamming_rank_ap(Qn, _lib.ptr(offsets), _lib.ptr(bins) if bins.numel() else _lib.ptr(None), arr, cnt,
+                                              int(bool(remove_first)), _lib.ptr(S[rows]), _lib.ptr(nrel[rows]), _lib.ptr(total),
+                                              _lib.stream_ptr(stream)), "ch_hamming_rank_ap")
+    return S, nrel, total
+
+
+def evaluate_weighted(codes: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, bits: int = 8,
+                      mask: Optional[torch.Tensor] = None, R=-1, ks: Sequence[int] = (1, 5, 10), remove_first: bool = False,
+                      skip_queries_without_relevant: bool = False, seg_rows: Optional[int] = None,
+                      list_cap: Optional[int] = None) -> dict:
+    """`evaluate` under the weighted (asymmetric) ranking that `hamming_topk_weighted` serves: ascending
+    (D, gallery index), D = sum_j w_ij [bit_j(q_i) != bit_j(g)] with the query's own |code| quantised to `bits` (4 or 8) bits as its
+    weights.  codes: [Qn, nbit] fp32, the real-valued query codes (the queries are pack_sign(codes) and weight_planes(codes, bits,
+    mask)); g: the packed gallery; mask as `weight_planes` takes it.  Returns the keys of `evaluate` -- mAP, precisions, recalls, hits,
+    total, S, nrel, ap, lists under a list R -- with the same integers' meaning, exact for any R and k.
+    The keys of each query's relevant rows are collected and sorted, one Qn x G scan counts how many gallery rows fall between
+    consecutive ones (`rank_count`), and one lane per query turns the counts into ranks and AP terms; more than 16 limits repeat that
+    last launch only.  seg_rows / list_cap (tests): the scan's segmentation and the list length up to which a list is searched in LDS
+    -- neither changes a result."""
+    if codes.dim() != 2:
+        raise ValueError("codes must be 2-D [Qn, nbit] real-valued query codes")
+    if g.dtype != torch.int64 or g.dim() != 2:
+        raise TypeError("the gallery must be a 2-D int64 tensor of packed codes")
+    Qn, nbit = codes.shape
+    W = (nbit + 63) // 64
+    if g.shape[1] != W:
+        raise ValueError(f"query codes of {nbit} bits take {W} words per code, the gallery has {g.shape[1]}")
+    if int(bits) not in WEIGHT_BITS:
+        raise ValueError(f"weight bits must be one of {WEIGHT_BITS}, got {bits}")
+    dev = g.device
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    many = isinstance(R, (list, tuple))
+    Rs = [int(r) for r in R] if many else [int(R)]
+    G = g.shape[0]
+    if Qn == 0 or G == 0:
+        return empty_result(Qn, W, dev, Rs, ks, many, False, None)
+    codes = codes.to(dev, torch.float32).contiguous()
+    q = pack_sign(codes)
+    planes, _ = weight_planes(codes, bits, mask)
+    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
+    limits, idx_of = normalize_limits(Rs + ks)
+    offsets, keys, longest = rank_collect(q, planes, g, q_lab, g_lab, LW)
+    keys = sort_slices(offsets, keys)
+    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
+    bins = rank_count(q, planes, g, offsets, keys, cap, seg_rows)
+    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
+    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
+    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
+                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])

@@ -481,6 +481,41 @@ int ch_hamming_rank_scatter(const uint64_t *q, int64_t Qn, const uint64_t *g, in
                             const uint32_t *base, const int64_t *out_start, const uint32_t *out_limit, int64_t g_index_base,
                             int64_t *out_idx, int32_t *out_dist, void *stream);
 
+/* Evaluation under the weighted distance (mAP@R, P@k, R@k of the ranking ch_hamming_topk_weighted serves), by rank counting.
+ * For one query: key(g) = D(q, g) << 32 | global index of g (uint64, unique; ascending keys = ascending (D, gallery index)), D and
+ * planes as in ch_hamming_topk_weighted, global index = g_index_base + gallery row, g_index_base >= 0 and g_index_base + G <= 2^32.
+ * r_0 < r_1 < ... < r_{n-1}: the sorted keys of the query's relevant rows.  Every gallery row adds one to bins[pos], pos = #{j : r_j <
+ * key(row)}; then rank(r_j) = sum_{b <= j} bins[b] (1-based) and its rank among the relevant rows is j + 1.  A row whose key exceeds
+ * r_{n-1} would fall into bin n, which is never read and does not exist.  The lists of all queries share CSR buffers: offsets int64
+ * [Qn + 1] (device), keys uint64 [total], bins uint32 [total], total = offsets[Qn].  Labels as for the mAP passes (LW == 0: int32 ids,
+ * LW > 0: uint64 [rows, LW] bitmasks).  P in {4, 8}, 1 <= W <= 4, otherwise status 2.  Nothing of size Qn x G is written.
+ *
+ * ch_hamming_rank_collect, offsets == NULL: count[i] += the number of relevant rows of query i (count uint32 [Qn], zeroed by the caller;
+ * q, planes and keys are not read).  With offsets (the exclusive prefix of those counts; count zeroed again): writes the keys of query
+ * i's relevant rows into keys[offsets[i] .. offsets[i + 1]), in no particular order -- the caller sorts every slice ascending -- and
+ * leaves the slice's fill in count[i]. */
+int ch_hamming_rank_collect(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G, int32_t W,
+                            const void *q_labels, const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets,
+                            uint32_t *count, uint64_t *keys, void *stream);
+
+/* The Qn x G scan: bins[offsets[i] + pos] += 1 for every gallery row with key <= r_{n-1} (atomic adds: zero bins first; calls on
+ * gallery segments or shards with their own g_index_base add into the same bins, in any order, with the same result).  keys: every
+ * slice sorted ascending.  The gallery is cut into segments of seg_rows rows (at most 65,535 of them), one workgroup per (query,
+ * segment); a query with an empty slice does no work.  A list of at most list_cap keys (1 <= list_cap <= 8192) is searched in LDS
+ * (12 list_cap bytes per workgroup: pass the longest list, capped), a longer one in global memory -- the result does not depend on
+ * list_cap or seg_rows. */
+int ch_hamming_rank_count(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G, int32_t W,
+                          int64_t g_index_base, int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap,
+                          uint32_t *bins, void *stream);
+
+/* AP from the bins: out_S [nlimits, Qn] uint64 and out_nrel [nlimits, Qn] uint32 as ch_hamming_ap_multi defines them (S = sum over the
+ * relevant rows inside the limit of floor(relrank 2^32 / rank); rank_limits: host array, ascending, <= 0 = no limit, last, at most
+ * 16), WRITTEN, not accumulated; out_total [Qn] int32 (may be NULL) = the query's relevant rows.  remove_first != 0: rank 1 is dropped
+ * before ranking, as first_rel does for ch_hamming_ap: it is relevant iff rank(r_0) == 1 (frel); a relevant row at rank 1 is skipped,
+ * every other row counts with rank - 1 and relrank - frel, and out_total loses frel.  A query with an empty slice gets zeros. */
+int ch_hamming_rank_ap(int64_t Qn, const int64_t *offsets, const uint32_t *bins, const int64_t *rank_limits, int32_t nlimits,
+                       int32_t remove_first, unsigned long long *out_S, uint32_t *out_nrel, int32_t *out_total, void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

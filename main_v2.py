@@ -30,7 +30,7 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii")
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
                "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits", "radius")
@@ -68,6 +68,8 @@ def run(config):
             from experiments.concept_eval import ConceptEvaluation as RetrievalEvaluation
         if load_config.get("hash_lookup_radii") is not None:   # ... + hash lookup within Hamming radii (it extends both)
             from experiments.hash_lookup_eval import HashLookupEvaluation as RetrievalEvaluation
+        if load_config.get("asymmetric_eval"):  # ... + every score once more under the asymmetric ranking (it extends all three)
+            from experiments.asymmetric_eval import AsymmetricEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp == "search":
         from experiments.search import SearchExperiment

@@ -92,9 +92,24 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
                        skip_queries_without_relevant=skip, tie_bracket=tie, **look)
 
 
+RANKS = ("hamming", "asymmetric")
+
+
+def _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits):
+    """rank="asymmetric": the queries keep their real values (`retrieval.evaluate_weighted`), the database is sign-packed as ever."""
+    from concepthash_amd.distributed import RowShard
+    if any(isinstance(x, RowShard) for x in (db_codes, db_labels, test_codes, test_labels)) or _sharded():
+        raise NotImplementedError("rank='asymmetric' is evaluated by one process on a whole database; the sharded form is not built "
+                                  "(its bins are additive over gallery shards)")
+    dev = _device()
+    g = rt.pack_sign(torch.as_tensor(db_codes).to(dev, torch.float32))
+    return rt.evaluate_weighted(torch.as_tensor(test_codes).to(dev, torch.float32), g, _labels(test_labels, dev), _labels(db_labels, dev),
+                                bits=weight_bits, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
+
+
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False, tie_bracket=False, radii=None):
+                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
@@ -108,8 +123,19 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     mAP_low, mAP_high, precisions_low/high, recalls_low/high; lists where the triple has lists), which is None after a call without it.
     radii (not a reference argument): a list of Hamming radii -- also compute hash lookup within each ("P@H<=r": precision, recall, rows
     retrieved and the share of queries retrieving nothing) from the histogram the call holds anyway; left in the
-    module attribute `last_hash_lookup` in the same way.  Single-process evaluation only."""
+    module attribute `last_hash_lookup` in the same way.  Single-process evaluation only.
+    rank (not a reference argument): "hamming" (default) or "asymmetric" -- the ranking `exp=search rank=asymmetric` serves (DESIGN.md
+    section 2.0): `test_codes` stay real-valued and every query pays its own |code|, quantised to `weight_bits` (4 or 8) bits, for a
+    disagreeing bit of the sign-packed database.  Same triple, same limits; no tie bracket and no radii under it (ValueError), and
+    single-process evaluation only (NotImplementedError for RowShards or a process group of more than one rank)."""
     global last_tie_bracket, last_hash_lookup
+    if rank not in RANKS:
+        raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+    if rank == "asymmetric":
+        if tie_bracket or radii is not None:
+            raise ValueError("rank='asymmetric' has no tie bracket and no radius lookup: both are defined on Hamming distances")
+        if int(weight_bits) not in rt.WEIGHT_BITS:
+            raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits}")
     last_tie_bracket = None
     last_hash_lookup = None
     _check(dist_metric, threshold, landmark_gt)
@@ -118,6 +144,10 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     Rs = [int(r) for r in R] if many else int(R)
     if many and not Rs:
         return [], [], []
+    if rank == "asymmetric":
+        res = _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
+                                   bool(skip_queries_without_relevant), int(weight_bits))
+        return res["mAP"], res["recalls"], res["precisions"]
     res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
                     bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
     if radii is not None:
