@@ -172,6 +172,16 @@ extern "C" int ch_debug_copy_buffer(ch_model *m, int32_t which, void *out, int64
     return 0;
 }
 
+// test tap: the centre arrays of a handle (`center` as ingested, and what ch_model_create folded from it)
+extern "C" int ch_debug_model_centers(ch_model *m, int32_t which, float *out, void *stream) {
+    CH_REQUIRE(m != nullptr && out != nullptr, "debug_model_centers: null pointer");
+    CH_REQUIRE(which >= 0 && which <= 2, "debug_model_centers: which must be 0 (center), 1 (center_l2) or 2 (center_bin)");
+    const float *src = which == 0 ? m->center : which == 1 ? m->center_l2 : m->center_bin;
+    const size_t cols = which == 0 ? m->cfg.center_dim : m->cfg.nbit;
+    CH_CHECK_HIP(hipMemcpyAsync(out, src, sizeof(float) * (size_t)m->cfg.nclass * cols, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
 // ---- kernel taps of the training step ----------------------------------------------------------------------------------------
 extern "C" int ch_debug_attention_bwd(const void *qkv, const void *dO, int32_t B, int32_t ntok, int32_t heads, void *dqkv, const float *dpext,
                                       int32_t ncon, void *stream) {

@@ -48,6 +48,24 @@ struct Builder : ChWeightBuilder {
     }
 };
 
+// text_projection on n rows of [center_dim] -> out [n, nbit]: the load-time fold of the centres and ch_model_project_text are this one
+// launch sequence.  Every output is one wave's dot product over its own row, so a row's result does not depend on n or on the chunk it
+// falls into; the two-layer form goes through the handle's tp_hidden in chunks of at most tp_rows rows, in stream order.
+int project_rows(const ch_model *m, const float *rows, int64_t n, float *out, hipStream_t s) {
+    const int cd = m->cfg.center_dim, nbit = m->cfg.nbit;
+    const int64_t chunk = m->tp_w0 ? m->tp_rows : (int64_t)1 << 16;   // one Linear needs no buffer: chunks only bound the grid
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int nr = (int)std::min<int64_t>(chunk, n - r0);
+        const float *x = rows + (size_t)r0 * cd;
+        if (m->tp_w0) {
+            if (int e = ch_small_linear(x, nr, cd, m->tp_w0, m->tp_b0, cd, 1, m->tp_hidden, s)) return e;
+            x = m->tp_hidden;
+        }
+        if (int e = ch_small_linear(x, nr, cd, m->tp_w1, m->tp_b1, nbit, 0, out + (size_t)r0 * nbit, s)) return e;
+    }
+    return 0;
+}
+
 int build_model(ch_model *m, const ch_tensor *tensors, int ntensors) {
     const ch_model_config &c = m->cfg;
     Builder B(m->own);
@@ -195,19 +213,27 @@ int build_model(ch_model *m, const ch_tensor *tensors, int ntensors) {
     {
         const int cd = c.center_dim;
         const float *cen = B.f32("center", (int64_t)C * cd);
-        float *proj = (float *)B.alloc(sizeof(float) * C * c.nbit);
+        const float *proj = cen;   // no text_projection and centres of code width (LGHWithoutText.get_center): the centres as they are
+        m->center = cen;
         if (B.has("text_projection.0.weight")) {
-            const float *w0 = B.f32("text_projection.0.weight", (int64_t)cd * cd), *b0 = B.f32("text_projection.0.bias", cd);
-            const float *w2 = B.f32("text_projection.2.weight", (int64_t)c.nbit * cd),
-                        *b2 = B.f32("text_projection.2.bias", c.nbit);
-            float *t = (float *)B.alloc(sizeof(float) * C * cd);
+            m->tp_w0 = B.f32("text_projection.0.weight", (int64_t)cd * cd);
+            m->tp_b0 = B.f32("text_projection.0.bias", cd);
+            m->tp_w1 = B.f32("text_projection.2.weight", (int64_t)c.nbit * cd);
+            m->tp_b1 = B.f32("text_projection.2.bias", c.nbit);
+        } else if (B.has("text_projection.weight") || cd != c.nbit) {
+            m->tp_w1 = B.f32("text_projection.weight", (int64_t)c.nbit * cd);
+            m->tp_b1 = B.f32("text_projection.bias", c.nbit);
+        }
+        if (!B.ok) return 4;
+        if (m->tp_w1) {
+            // the hidden rows of the centres' own fold; ch_model_project_text goes through them C rows at a time: no allocation per
+            // call, whatever its N
+            m->tp_rows = C;
+            if (m->tp_w0) m->tp_hidden = (float *)B.alloc(sizeof(float) * (size_t)m->tp_rows * cd);
+            float *p = (float *)B.alloc(sizeof(float) * C * c.nbit);
             if (!B.ok) return 4;
-            if (ch_small_linear(cen, C, cd, w0, b0, cd, 1, t, s)) return 4;
-            if (ch_small_linear(t, C, cd, w2, b2, c.nbit, 0, proj, s)) return 4;
-        } else {
-            const float *w = B.f32("text_projection.weight", (int64_t)c.nbit * cd), *bb = B.f32("text_projection.bias", c.nbit);
-            if (!B.ok) return 4;
-            if (ch_small_linear(cen, C, cd, w, bb, c.nbit, 0, proj, s)) return 4;
+            if (project_rows(m, cen, C, p, s)) return 4;
+            proj = p;
         }
         float *l2 = (float *)B.alloc(sizeof(float) * C * c.nbit), *bin = (float *)B.alloc(sizeof(float) * C * c.nbit);
         if (!B.ok) return 4;
@@ -782,6 +808,14 @@ extern "C" int ch_encode_hidden(ch_model *m, const void *images, int32_t image_d
     CH_CHECK_HIP(hipMemcpyAsync(out_hidden, m->H, sizeof(float) * (size_t)B * m->ntok * m->cfg.dim,
                                 hipMemcpyDeviceToDevice, s));
     return 0;
+}
+
+extern "C" int ch_model_project_text(ch_model *m, const float *feats, int64_t N, float *out_codes, void *stream) {
+    CH_REQUIRE(m != nullptr, "project_text: null model");
+    CH_REQUIRE(feats != nullptr && out_codes != nullptr, "project_text: null feats / out_codes");
+    CH_REQUIRE(N >= 1, "project_text: N must be >= 1");
+    CH_REQUIRE(m->tp_w1 != nullptr, "project_text: the model was created without text_projection");
+    return project_rows(m, feats, N, out_codes, (hipStream_t)stream);
 }
 
 extern "C" int ch_pack_sign(const float *codes, int64_t rows, int32_t nbit, float threshold, uint64_t *out_packed,

@@ -67,6 +67,12 @@ struct ch_model {
     const float *hash_pe = nullptr, *hash_fc = nullptr, *bn_scale = nullptr, *bn_shift = nullptr;
     const float *center_l2 = nullptr, *center_bin = nullptr, *concept_pe = nullptr, *concept_cent_l2 = nullptr;
     const float *post_w = nullptr, *post_b = nullptr, *vis_proj = nullptr;
+    // the centre head (get_center, coop.py:624-625): `center` [C, center_dim] and text_projection, kept so that ch_model_project_text
+    // applies to caller rows the launches that folded center_l2 / center_bin.  Linear: tp_w1 / tp_b1 only; Sequential(Linear, ReLU,
+    // Linear): tp_w0 / tp_b0, then tp_w1 / tp_b1 through tp_hidden [tp_rows, center_dim].  No text_projection: all null.
+    const float *center = nullptr, *tp_w0 = nullptr, *tp_b0 = nullptr, *tp_w1 = nullptr, *tp_b1 = nullptr;
+    float *tp_hidden = nullptr;
+    int tp_rows = 0;
     // launch profiler (bench.py): one hipEvent before every launch + one after the last; elapsed(e[j], e[j+1]) is
     // attributed to launch j's category
     // adapter_fused.hip is correct (parity-tested) but measured slower than the three-launch chain on MI355X (200 vs 179 us

@@ -271,6 +271,19 @@ class ConceptHashEncoder:
                 out["concept_attn"] = out["concept_attn_layers"][-1]
         return out
 
+    def project_text(self, feats: torch.Tensor, stream=None) -> torch.Tensor:
+        """`ch_model_project_text`: rows [N, center_dim] in the layout of the `center` buffer -> text_projection(rows) [N, nbit] fp32, by
+        the launches that folded the model's own centres when the handle was built (any N >= 1)."""
+        cd = self.cfg["center_dim"]
+        if feats.dim() != 2 or feats.shape[1] != cd or feats.shape[0] < 1:
+            raise ValueError(f"text features must be [N >= 1, {cd}] (the width of the model's `center` buffer), got {tuple(feats.shape)}")
+        feats = feats.to(self.device, torch.float32).contiguous()
+        out = torch.empty(feats.shape[0], self.nbit, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ch_model_project_text(self._h, _lib.ptr(feats), feats.shape[0], _lib.ptr(out), _lib.stream_ptr(stream)),
+                       "ch_model_project_text")
+        return out
+
     def hidden_states(self, images: torch.Tensor, layer: int, stream=None) -> torch.Tensor:
         """Parity tap: fp32 residual stream [B, N, D] after `layer` encoder layers (0 = after pre-LN)."""
         self._check_images(images)

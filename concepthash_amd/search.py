@@ -121,8 +121,9 @@ class GalleryIndex:
         return os.path.join(self.data_root, rel)
 
     def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0,
-               rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None) -> dict:
-        """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here).
+               rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None, mean_shift: bool = True) -> dict:
+        """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here;
+        mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0).
         Ranks the database by ascending (distance, index) and returns
           idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
           concept_dist [Qn, k, ncontext] int32: the UNMASKED distance inside every concept's sub-code (they sum to the whole-code
@@ -160,7 +161,7 @@ class GalleryIndex:
         codes = query_codes.to(dev, torch.float32)
         if codes.dim() != 2 or codes.shape[1] != self.nbit:
             raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
-        if self.mean is not None:
+        if self.mean is not None and mean_shift:
             codes = codes - self.mean[None, :]
         Qn = codes.shape[0]
         q = rt.pack_sign(codes)

@@ -239,3 +239,106 @@ class TextEncoder:
             hidden.append(h)
         pooled = torch.cat(pooled, dim=0)
         return (pooled, torch.cat(hidden, dim=0)) if want_hidden else pooled
+
+
+DEFAULT_PREFIX = "a photo of a "          # configs/model/*.yaml `model.fixed_center.prompt_prefix`, as the reference's codebook builder has it
+
+
+def _cfg(node, *path, default=None):
+    for key in path:
+        if node is None or not hasattr(node, "get"):
+            return default
+        node = node.get(key)
+    return default if node is None else node
+
+
+def text_query_settings(config, text_model=None, prefix=None):
+    """(text model directory, prompt prefix) of a run for text queries, from its config alone -- no model is built and no GPU touched.
+    `text_model` / `prefix` override `model.backbone.name` / `model.fixed_center.prompt_prefix` ("" = no prefix).  One ValueError names
+    everything that is missing: a local HF CLIP directory with text weights and tokeniser files, a model with `text_projection`."""
+    source = text_model if text_model is not None else _cfg(config, "model", "backbone", "name")
+    missing = []
+    if not local_text_files(source):
+        missing.append(f"'{source}' ({'text_model' if text_model is not None else 'model.backbone.name'}) is not a local HF CLIP directory "
+                       "with config.json, model.safetensors / pytorch_model.bin, vocab.json and merges.txt")
+    target = str(_cfg(config, "model", "_target_", default=""))
+    if not target.endswith("LGHWithFixedPrompt"):
+        missing.append(f"the model ({target or 'no model._target_'}) has no text_projection: only LGHWithFixedPrompt maps text features "
+                       "onto the code space")
+    if missing:
+        raise ValueError("text queries are not possible for this run: " + "; ".join(missing))
+    if prefix is None:
+        prefix = _cfg(config, "model", "fixed_center", "prompt_prefix", default=DEFAULT_PREFIX)
+    return str(source), str(prefix)
+
+
+class TextQueryEncoder:
+    """Prompt strings -> query codes of a run ("text query"): tokenise `prefix + prompt`, `pooler_output` of the
+    text tower, the centre row the "L" codebook makes of it (`trainers.orthohash.centre_rows`), and the model's own `text_projection`
+    through `ch_model_project_text`.  Owns the tower's handle: `close()` (or the `with` block) releases it."""
+
+    def __init__(self, model, text_model, prefix: str = DEFAULT_PREFIX, max_batch: int = TEXT_BATCH, device=None):
+        missing = []
+        if not local_text_files(text_model):
+            missing.append(f"'{text_model}' is not a local HF CLIP directory with config.json, model.safetensors / pytorch_model.bin, "
+                           "vocab.json and merges.txt")
+        if getattr(model, "text_projection", None) is None or not hasattr(model, "project_text"):
+            missing.append(f"the model ({type(model).__name__}) has no text_projection")
+        if missing:
+            raise ValueError("text queries are not possible: " + "; ".join(missing))
+        self.model, self.text_model, self.prefix = model, str(text_model), str(prefix)
+        self.tokenizer = ClipBpeTokenizer.from_directory(self.text_model)
+        self.tower = TextEncoder(self.text_model, max_batch=max_batch, device=device if device is not None else model.center.device)
+        cd = int(model.center.shape[1])
+        if self.tower.dim != cd:
+            self.close()
+            raise ValueError(f"the text tower of '{text_model}' is {self.tower.dim} wide, the model's centres are {cd} wide: not the text "
+                             "model this run's centres were built with")
+
+    def close(self):
+        tower, self.tower = getattr(self, "tower", None), None
+        if tower is not None:
+            tower.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def prompts(self, prompts, prefix: Optional[str] = None) -> List[str]:
+        prompts = [prompts] if isinstance(prompts, str) else [str(p) for p in prompts]
+        if not prompts:
+            raise ValueError("no prompt given")
+        prefix = self.prefix if prefix is None else str(prefix)
+        return [prefix + p for p in prompts]
+
+    def features(self, ids) -> torch.Tensor:
+        """ids [N, T] -> pooler_output [N, Dt] on the device, in the tower's batches of at most `max_batch` prompts"""
+        return self.tower.encode(ids)
+
+    def project(self, features: torch.Tensor) -> torch.Tensor:
+        from trainers.orthohash import centre_rows
+        return self.model.project_text(centre_rows(features))
+
+    def text_codes(self, prompts, prefix: Optional[str] = None) -> torch.Tensor:
+        """-> [N, nbit] fp32 on the device: real-valued query codes, used exactly as an image's pre-sign codes"""
+        return self.project(self.features(self.tokenizer(self.prompts(prompts, prefix))))
+
+    def center_agreement(self, class_name_path: str, prefix: Optional[str] = None) -> float:
+        """Share of equal entries between the centres this tower rebuilds from `class_name_path` and the model's `center` buffer: 1.0
+        when the tower, the tokeniser and the prefix are the ones the run's centres came from.  A class count other than the model's is
+        refused; anything else is reported (a warning below 1), never judged."""
+        import logging
+        from trainers.orthohash import centre_rows, class_prompts
+        prompts = class_prompts(class_name_path, self.prefix if prefix is None else str(prefix))
+        center = self.model.center.detach()
+        if len(prompts) != center.shape[0]:
+            raise ValueError(f"{class_name_path} names {len(prompts)} classes, the model's centres have {center.shape[0]} rows")
+        rebuilt = centre_rows(self.features(self.tokenizer(prompts)))
+        share = float((rebuilt == center.to(rebuilt.device)).float().mean())
+        if share < 1.0:
+            logging.warning("text queries: %.4f of the centre entries rebuilt from %s by the text tower of %s equal the checkpoint's `center` "
+                            "buffer; the run's centres were built with another text model, tokeniser or prompt prefix", share,
+                            class_name_path, self.text_model)
+        return share

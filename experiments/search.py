@@ -1,7 +1,11 @@
-"""`exp=search`: image queries -> ranked database hits of a finished run, optionally by chosen concepts.
+"""`exp=search`: image or text queries -> ranked database hits of a finished run, optionally by chosen concepts.
 
     python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [radius=2] [concepts=[0,2]]
         [query_margin=0.0] [rank=hamming|asymmetric] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
+        [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
+
+Text queries ("text query") become codes through the CLIP text tower and the run's own `text_projection`
+(`concepthash_amd.text.TextQueryEncoder`) and go through the same `GalleryIndex.search` call as image codes, never shifted by an index's mean.
 
 The run's config and checkpoint are loaded exactly as `exp=validation` loads them.  The database split is encoded once
 (`trainer.inference_one_epoch("db", True)`) into a `concepthash_amd.search.GalleryIndex` file -- `<logdir>/index_<best|last>.pth` unless
@@ -44,6 +48,50 @@ def _label_ids(labels: torch.Tensor):
     return hot.to(torch.uint8)
 
 
+def class_name_file(config) -> str:
+    """`class_names.txt` of the dataset folder this invocation names"""
+    return os.path.join(str(config.data_dir), str(config.dataset.data_folder), "class_names.txt")
+
+
+def text_request(config):
+    """The text queries of an invocation, from its config alone (no model, no GPU): None when it asks for image queries, else a dict
+    with `prompts` (the strings the tokeniser gets, prefix included), `labels` (class ids for `query=classes`, else None), `prefix`, `run_prefix`
+    (the run's own, for the tower check) and `text_model`.  `query_text` (one string or a list) / `query_text_file` (one prompt per line) are appended to the prefix;
+    `query=classes` is `trainers.orthohash.class_prompts` of the dataset's class_names.txt under that prefix."""
+    from concepthash_amd.text import text_query_settings
+    from trainers.orthohash import class_prompts
+    query = str(config.get("query", "test") or "test")
+    given = [k for k in ("query_text", "query_text_file") if config.get(k) is not None]
+    if not given and query != "classes":
+        return None
+    if len(given) > 1 or (given and query != "test"):
+        raise ValueError(f"text queries come from ONE of query_text, query_text_file and query=classes; got {given} with query='{query}'")
+    if config.get("save_attention"):
+        raise ValueError("save_attention=true needs image queries: a text query has no image whose patches the concept tokens attend to")
+    source, prefix = text_query_settings(config, config.get("text_model"), config.get("prompt_prefix"))
+    labels = None
+    if query == "classes":
+        path = class_name_file(config)
+        if not os.path.isfile(path):
+            raise ValueError(f"query=classes reads one class name per line from {path}, which does not exist")
+        prompts = class_prompts(path, prefix)
+        labels = list(range(len(prompts)))
+    elif given[0] == "query_text":
+        qt = config.query_text
+        prompts = [prefix + str(p) for p in ([qt] if isinstance(qt, str) else list(qt))]
+    else:
+        path = str(config.query_text_file)
+        if not os.path.isfile(path):
+            raise ValueError(f"query_text_file={path} does not exist")
+        with open(path, encoding="utf-8") as f:
+            prompts = [prefix + line.strip() for line in f if line.strip()]
+    if not prompts:
+        raise ValueError(f"{'query=classes' if query == 'classes' else given[0]} gives no prompt")
+    # the tower check (center_agreement) rebuilds the run's centres: under the run's own prefix, whatever the queries use
+    run_prefix = text_query_settings(config, config.get("text_model"))[1]
+    return {"prompts": prompts, "labels": labels, "prefix": prefix, "run_prefix": run_prefix, "text_model": source}
+
+
 class SearchExperiment:
     def __init__(self, config: DictConfig):
         import torch.distributed as dist
@@ -51,8 +99,10 @@ class SearchExperiment:
             raise NotImplementedError("exp=search under a multi-rank process group is not built: a query tool gains nothing from sharding; "
                                       "run it as a single process")
         self.start_time = time.time()
-        engine.seeding(config["seed"])
         self.config = config
+        self.query = str(config.get("query", "test") or "test")
+        self.text = text_request(config)              # None: image queries.  Argument errors surface here, before anything is loaded
+        engine.seeding(config["seed"])
         self.timing = {}
         logdir = config.logdir
         modelfn = "last" if config.get("use_last") else "best"
@@ -62,7 +112,6 @@ class SearchExperiment:
         os.makedirs(self.search_logdir, exist_ok=True)
         with open(os.path.join(self.search_logdir, "search_config.yaml"), "w") as f:
             yaml.safe_dump(to_container(config), f)
-        self.query = str(config.get("query", "test"))
         self.nbit, self.ncontext = int(config.model.nbit), int(config.model.ncontext)
 
         # the index first: whether the database split has to be encoded decides what is loaded
@@ -80,8 +129,9 @@ class SearchExperiment:
                 self.index, self.index_note = None, f"built: stale index ({e})"
 
         trainer = instantiate(config.trainer, config)
-        self._phase("datasets", trainer.load_dataset, load_db=self.index is None or self.query == "db")
-        self._phase("loaders", trainer.load_dataloader)
+        if self.text is None or self.index is None:   # text queries over a valid index read no image: no dataset is loaded at all
+            self._phase("datasets", trainer.load_dataset, load_db=self.index is None or self.query == "db")
+            self._phase("loaders", trainer.load_dataloader)
         trainer.load_for_inference(logdir)
         self._phase("model_build", trainer.load_model)
         trainer.load_criterion()
@@ -195,6 +245,18 @@ class SearchExperiment:
             tr.model.return_concept_attention = before
         return torch.cat(codes), torch.cat(labels), (torch.cat(attn) if attn else None)
 
+    def _encode_text(self):
+        """-> (query codes [N, nbit] of the prompts, share of the run's centre entries the same tower rebuilds from class_names.txt or
+        None without that file)"""
+        from concepthash_amd.text import TextQueryEncoder
+        model = self.trainer.model
+        model.eval()
+        names = class_name_file(self.config)
+        with TextQueryEncoder(model, self.text["text_model"], prefix="") as enc, torch.no_grad():   # the prompts carry their prefix
+            codes = enc.text_codes(self.text["prompts"])
+            agreement = enc.center_agreement(names, self.text["run_prefix"]) if os.path.isfile(names) else None
+        return codes, agreement
+
     # ---- main --------------------------------------------------------------------------------------------------------------------
     def main(self):
         cfg = self.config
@@ -209,9 +271,15 @@ class SearchExperiment:
         print("Search Start")
         index = self.index if self.index is not None else self._build_index()
         index = index.to(self.trainer.device)
-        loader, names, labelled = self._query_loader()
-        q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
-        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius)
+        agreement = None
+        if self.text is not None:
+            names, labelled, attn = self.text["prompts"], self.text["labels"] is not None, None
+            q_codes, agreement = self._phase("encode_query", self._encode_text)
+            q_labels = torch.tensor(self.text["labels"] if labelled else [], dtype=torch.int64)
+        else:
+            loader, names, labelled = self._query_loader()
+            q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
+        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius, mean_shift=self.text is None)
         t0 = time.perf_counter()
         q_ids = _label_ids(q_labels.cpu()) if labelled else None
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
@@ -237,7 +305,10 @@ class SearchExperiment:
         self.timing["results"] = round(time.perf_counter() - t0, 3)
         out = {"k": k, "radius": radius, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "nbit": index.nbit, "ncontext": index.ncontext,
                "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
-               "checkpoint": self.fingerprint, "query": self.query, "queries": queries,
+               "checkpoint": self.fingerprint, "query_kind": "image" if self.text is None else "text",
+               "query": self.query if self.text is None else list(self.text["prompts"]),
+               "prefix": None if self.text is None else self.text["prefix"], "text_model": None if self.text is None else self.text["text_model"],
+               "center_agreement": agreement, "mean_shift": self.text is None and index.mean is not None, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
         with open(os.path.join(self.search_logdir, "results.json"), "w") as f:
             json.dump(out, f)

@@ -76,7 +76,8 @@ const char *ch_last_error(void);
  * operands -> bf16, everything else fp32), and folds the input-independent parts of the forward once, on the GPU:
  * forward_hash_query (models/arch/coop.py:413-427) -> concept tokens; get_center (coop.py:624-625) -> projected,
  * l2-normalised centres; BatchNorm1d eval (coop.py:559) -> per-bit affine.  Unknown/missing names are an error;
- * aliases (`adapter_params.*`, `trainable_params.*`) are ignored. */
+ * aliases (`adapter_params.*`, `trainable_params.*`) are ignored.  `text_projection.*` may be absent when `center` is already nbit wide
+ * (LGHWithoutText.get_center: the centres as they are); ch_model_project_text then refuses the handle. */
 int ch_model_create(const ch_model_config *cfg, const ch_tensor *tensors, int32_t ntensors, ch_model **out);
 void ch_model_destroy(ch_model *m);
 /* bytes of device memory held by the model (weights + workspace) */
@@ -138,6 +139,17 @@ int ch_encode(ch_model *m, const void *images, int32_t image_dtype, int32_t B, f
  * (models/arch/coop.py:474-486). */
 int ch_encode_hidden(ch_model *m, const void *images, int32_t image_dtype, int32_t B, int32_t layer,
                      float *out_hidden, void *stream);
+
+/* Replaces: LGHWithFixedPrompt.get_center (models/arch/coop.py:624-625) on rows other than the model's own `center` buffer -- the
+ * step from CLIP text features to the code space that a text query needs (the rows are
+ * `sign(pooler_output)` of ch_text_encode, as trainers/orthohash.py:94-145 builds the centres).
+ *   feats      [N, center_dim] fp32 device
+ *   out_codes  [N, nbit] fp32 device: text_projection(feats), Linear or Sequential(Linear, ReLU, Linear) as the model was created
+ * Runs the launches that folded the model's own centres at ch_model_create, so the model's `center` rows give bit for bit the
+ * projected centres behind out_logits_cont / out_logits_bin.  Any N >= 1: the hidden rows of the two-layer form go through a buffer
+ * of the handle in chunks, nothing is allocated per call (so one handle serves one stream at a time here, as it does in ch_encode).
+ * A model created without text_projection is an error. */
+int ch_model_project_text(ch_model *m, const float *feats, int64_t N, float *out_codes, void *stream);
 
 /* ---- Training step of the adapters -----------------------------------------------------------
  * Replaces, for everything that touches the [B*N, *] activations: the forward and `loss.backward()` of

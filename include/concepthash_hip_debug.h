@@ -161,6 +161,11 @@ int ch_debug_bn_fold(const float *w, const float *b, const float *mean, const fl
 int ch_debug_fold_ln(const float *Wd, const float *bd, const float *gamma, const float *beta, int32_t b, int32_t bpad, int32_t D, void *Wdf,
                      float *c, float *d, void *stream);
 
+/* Copy one of the centre arrays a model holds since ch_model_create to `out` (device): which = 0 `center` [C, center_dim] as ingested |
+ * 1 center_l2 [C, nbit] (projected, l2-normalised) | 2 center_bin [C, nbit] (its signs / sqrt(nbit)).  tests/test_text_query_gpu.py
+ * holds ch_model_project_text + the normalisation launch against 1 and 2, bit for bit. */
+int ch_debug_model_centers(ch_model *m, int32_t which, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

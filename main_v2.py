@@ -7,7 +7,7 @@
 
 `exp` dispatch: hashing -> RetrievalExperiment (train the adapters + hashing head, frozen backbone); validation -> load
 <logdir>/config.yaml, overlay the evaluation knobs, RetrievalEvaluation; search -> the same run config, SearchExperiment (ranked hits of
-image queries, experiments/search.py); descriptor / extract -> RetrievalEvaluation on the
+image or text queries, experiments/search.py); descriptor / extract -> RetrievalEvaluation on the
 composed config; general (the reference's train-without-eval variant) is not built.  Uses Hydra when it is installed; otherwise `concepthash_amd.config` composes the same YAML
 tree (hydra-core / omegaconf are absent from the target image).
 """
@@ -30,10 +30,12 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits")
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits", "text_eval",
+             "prompt_prefix", "text_model")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
-               "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits", "radius")
+               "query_margin", "index", "rebuild_index", "save_attention", "rank", "weight_bits", "radius", "query_text", "query_text_file",
+               "prompt_prefix", "text_model")
 
 
 def _run_config(config, exp, keys):
@@ -70,6 +72,8 @@ def run(config):
             from experiments.hash_lookup_eval import HashLookupEvaluation as RetrievalEvaluation
         if load_config.get("asymmetric_eval"):  # ... + every score once more under the asymmetric ranking (it extends all three)
             from experiments.asymmetric_eval import AsymmetricEvaluation as RetrievalEvaluation
+        if load_config.get("text_eval"):        # ... + the class prompts as text queries against the database codes (it extends all four)
+            from experiments.text_eval import TextEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp == "search":
         from experiments.search import SearchExperiment

@@ -326,3 +326,14 @@ class LGHWithFixedPrompt(LGHWithoutText):
         parameters' device for callers that ask for it (the encode path folds it inside ch_model_create; the training forward
         differentiates through it)."""
         return self.text_projection(self.center)
+
+    def project_text(self, feats):
+        """Rows in the layout of `center` (C', center_dim) -> text_projection(rows) (C', nbit), in the HIP library
+        (`ch_model_project_text`): the launches that fold this model's own centres on the encode path, so `project_text(self.center)`
+        is bit for bit what `logits_cont` / `logits_bin` are computed against.  Evaluation only (no autograd)."""
+        dev = self.center.device
+        if dev.type != "cuda":
+            raise RuntimeError("LGHWithFixedPrompt.project_text needs the model on a GPU; there is no CPU fallback")
+        # the engine of the resolution the model last encoded at, when its weights are still these; else one at the pretrain resolution
+        size = self._engine_key[1] if self._engine_key is not None else None
+        return self._ensure_engine(dev, size).project_text(feats)

@@ -26,7 +26,13 @@ def get_codebook(codebook_method, nclass, nbit, **kwargs):
         return torch.randn(nclass, nbit).sign()
     if codebook_method == "B":
         return torch.bernoulli(torch.full((nclass, nbit), 0.5)).mul(2.0).sub(1.0).sign()
-    return language_guided_codebook(nbit=nbit, **kwargs).sign()
+    return centre_rows(language_guided_codebook(nbit=nbit, **kwargs))
+
+
+def centre_rows(features):
+    """The last step of the "L" codebook: text features (`pooler_output`) -> centre rows, their sign (+-1; an exact zero stays 0).  A
+    text query (concepthash_amd.text.TextQueryEncoder) turns its own features into a centre row through this function."""
+    return features.sign()
 
 
 def class_prompts(class_name_path, prompt_prefix="a photo of a ", prompt_postfix=""):
