@@ -14,6 +14,7 @@
 thread_local ch_prof_pair g_ch_prof_pair;   // (the last-error string lives in errors.cpp)
 extern "C" int ch_abi_version(void) { return CH_ABI_VERSION; }
 
+#include "layer_forward.h"
 #include "model_internal.h"
 #include "weight_builder.h"
 
@@ -308,6 +309,55 @@ inline void mark(ch_model *m, int pi, int cat, double flops, hipStream_t s) {
     P.n++;
 }
 
+// ch_encode's launcher of one chain (layer_forward.h): the profiler mark in front of every launch, the serpentine direction flipped in
+// call order, and the per-model options a GEMM of the chain honours
+struct EncodeLaunch {
+    ch_model *mm;
+    int pi, B, Btot;      // chain (profiler, split-K slabs); its images; the images of all concurrent chains of this call
+    int64_t rows_alloc;   // rows behind every activation buffer of the chain's view
+    hipStream_t s;
+    int dir = 0;          // serpentine: flipped before every row-streaming launch of the chain
+    int next_dir() { return mm->serpentine ? (dir ^= 1) : 0; }
+    static int pruned_cat(int cat) {   // profiler category of the same launch on the compact head rows (final layer)
+        switch (cat) {
+            case CH_CAT_GEMM_OUT: return (int)CH_CAT_GEMM_OUT_PRUNED;
+            case CH_CAT_GEMM_DOWN: return (int)CH_CAT_GEMM_DOWN_PRUNED;
+            case CH_CAT_GEMM_UP: return (int)CH_CAT_GEMM_UP_PRUNED;
+            case CH_CAT_GEMM_FC1: return (int)CH_CAT_GEMM_FC1_PRUNED;
+            case CH_CAT_GEMM_FC2: return (int)CH_CAT_GEMM_FC2_PRUNED;
+        }
+        return cat;
+    }
+    GemmParams params(int rows, const ChGemmCall &g) {
+        const int D = mm->cfg.dim;
+        GemmParams p{};
+        p.tag = g.cat == CH_CAT_GEMM_FC2 ? 1 : 0;   // fc2 runs out_proj's kernel instance: second symbol name for per-kernel profiles
+        p.splitk_ws = mm->splitk_ws[pi]; p.splitk_cnt = mm->splitk_cnt[pi]; p.pp_min_k = mm->pp_min_k; p.pp_sched = mm->pp_sched; p.small_kernel = mm->small_kernel; p.rev = next_dir();
+        p.nt_resid_opt = mm->resid_nt; p.nt_out_opt = mm->nt_out; p.group_n_opt = mm->group_n; p.splitk_opt = mm->splitk; p.rows_opt = mm->gemm_rows; p.wide_opt = mm->wide_kernel;
+        p.footprint_rows = (int64_t)rows * Btot / B;   // all concurrent chains of this call: what the cache-policy choice is sized on
+        p.stats_in = g.stats_in; p.fold_c = g.fold_c; p.ln_eps = g.eps; p.stats_out = g.stats_out; p.hb_out = g.hb_out; p.ld_hb = g.ld_hb ? g.ld_hb : D;
+        p.addend = g.addend; p.ld_addend = D;
+        p.X = g.X; p.W = g.W; p.M = rows; p.N = g.N; p.K = g.K; p.X_rows_alloc = rows_alloc; p.bias = g.bias;
+        p.out_bf16 = g.out; p.ldo = g.ldo; p.resid = g.resid; p.ldr = D; p.scale_ptr = g.scale;
+        return p;
+    }
+    int gemm(int rows, const ChGemmCall &g) {
+        const int cat = rows != B * mm->ntok ? pruned_cat(g.cat) : g.cat;
+        mark(mm, pi, cat, 2.0 * rows * (double)(g.n_true ? g.n_true : g.N) * (g.k_true ? g.k_true : g.K), s);
+        return ch_gemm_bf16(params(rows, g), g.epi, s);
+    }
+    int attention(const bf16_t *qkv, bf16_t *out, float *cattn, bool compact) {
+        const ch_model_config &c = mm->cfg;
+        const int ntok = mm->ntok;
+        mark(mm, pi, compact ? CH_CAT_ATTENTION_PRUNED : CH_CAT_ATTENTION, 4.0 * B * (double)(compact ? 1 + c.ncontext : ntok) * ntok * c.dim, s);
+        return ch_attention(qkv, B, ntok, c.heads, out, s, cattn, c.ncontext, compact, next_dir() != 0, mm->attn_stream ? 2 : 0);
+    }
+    int gather_head_rows(const float *H, float *Hc) {
+        mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
+        return ch_gather_head_rows(H, B, mm->ntok, mm->cfg.ncontext, mm->cfg.dim, Hc, s);
+    }
+};
+
 // one launch chain: images [img0, img0 + B) through `nlayers` layers on stream s; rows of every activation buffer are
 // independent, so a micro-batch simply works on its own row range of the shared workspace
 // prune: (ch_encode) in the final layer only the rows the hashing head reads -- CLS and the Q concept tokens of every image --
@@ -317,7 +367,6 @@ int run_chain(ch_model *mm, int pi, const void *images_all, int image_dtype, int
     const ch_model_config &c = mm->cfg;
     const int D = c.dim, M = c.ffn, ntok = mm->ntok, np = mm->np;
     const int rows = B * ntok;
-    const int act_epi = c.act == 0 ? EPI_BIAS_QUICKGELU : EPI_BIAS_GELU;
     const size_t row0 = (size_t)img0 * ntok, prow0 = (size_t)img0 * np;
     // view of the workspace for this micro-batch
     struct View {
@@ -348,58 +397,17 @@ int run_chain(ch_model *mm, int pi, const void *images_all, int image_dtype, int
                                   c.ln_eps, m->Xn, s))
         return e;
 
-    // cat / n_true / k_true: profiler category and the un-padded (algorithmic) GEMM extents
-    // LayerNorm-fold plumbing of one GEMM: statistics it consumes (fold_c != nullptr) and/or produces (stats_out != nullptr)
-    struct Fold {
-        const float *stats_in = nullptr, *fold_c = nullptr;
-        float eps = 0.f;
-        float *stats_out = nullptr;
-        bf16_t *hb_out = nullptr;
-    };
-    const bool fold = mm->ln_fold && c.adapter_dim > 0 && !mm->use_fused_adapter;
-    int dir = 0;              // serpentine: flipped before every row-streaming launch of the chain
-    auto next_dir = [&]() { return mm->serpentine ? (dir ^= 1) : 0; };
-    int cur_rows = rows;      // rows the GEMMs work on: all token rows, or the compact head rows in the pruned final layer
-    float *cur_H = m->H;      // ... and their residual stream
-    auto pruned_cat = [](int cat) {   // profiler category of the same launch on the compact head rows (final layer)
-        switch (cat) {
-            case CH_CAT_GEMM_OUT: return (int)CH_CAT_GEMM_OUT_PRUNED;
-            case CH_CAT_GEMM_DOWN: return (int)CH_CAT_GEMM_DOWN_PRUNED;
-            case CH_CAT_GEMM_UP: return (int)CH_CAT_GEMM_UP_PRUNED;
-            case CH_CAT_GEMM_FC1: return (int)CH_CAT_GEMM_FC1_PRUNED;
-            case CH_CAT_GEMM_FC2: return (int)CH_CAT_GEMM_FC2_PRUNED;
-        }
-        return cat;
-    };
-    auto gemm = [&](int cat, int n_true, int k_true, const bf16_t *X, const bf16_t *W, int N, int K, const float *bias,
-                    int epi, bf16_t *out, int ldo, const float *scale, const bf16_t *addend = nullptr, const Fold &f = Fold()) {
-        mark(mm, pi, cur_rows != rows ? pruned_cat(cat) : cat, 2.0 * cur_rows * (double)n_true * k_true, s);
-        GemmParams p{};
-        p.tag = cat == CH_CAT_GEMM_FC2 ? 1 : 0;   // fc2 runs out_proj's kernel instance: second symbol name for per-kernel profiles
-        p.splitk_ws = mm->splitk_ws[pi]; p.splitk_cnt = mm->splitk_cnt[pi]; p.pp_min_k = mm->pp_min_k; p.pp_sched = mm->pp_sched; p.small_kernel = mm->small_kernel; p.rev = next_dir();
-        p.nt_resid_opt = mm->resid_nt; p.nt_out_opt = mm->nt_out; p.group_n_opt = mm->group_n; p.splitk_opt = mm->splitk; p.rows_opt = mm->gemm_rows; p.wide_opt = mm->wide_kernel;
-        p.footprint_rows = (int64_t)cur_rows * Btot / B;   // all concurrent chains of this call: what the cache-policy choice is sized on
-        p.stats_in = f.stats_in; p.fold_c = f.fold_c; p.ln_eps = f.eps; p.stats_out = f.stats_out; p.hb_out = f.hb_out; p.ld_hb = D;
-        p.addend = addend; p.ld_addend = D;
-        p.X = X; p.W = W; p.M = cur_rows; p.N = N; p.K = K; p.X_rows_alloc = m->rows_alloc; p.bias = bias;
-        p.out_bf16 = out; p.ldo = ldo; p.resid = cur_H; p.ldr = D; p.scale_ptr = scale;
-        return ch_gemm_bf16(p, epi, s);
-    };
-    // emit_h: (LN-fold chain) the up-projection also writes bf16(H) to Xn + its row statistics for the next folded GEMM
-    auto adapter = [&](const AdapterW &aw, bool emit_h) -> int {
+    EncodeLaunch run{mm, pi, B, Btot, m->rows_alloc, s};
+    ChChain st{B, ntok, c.ncontext, D, M, mm->bpad, c.adapter_dim, c.act, c.ln_eps, rows, m->H};
+    // LN-fold chain (layer_forward.h): every layer works in the same buffers; Xn / statsH carry bf16(H) and its row statistics from the
+    // up-projection that writes them to the folded GEMM that reads them, A / statsA the sub-block output of out_proj, then of fc2
+    const bool fold = ch_encode_folds(mm);
+    ChLayerBufs fb{};
+    fb.Xn1 = fb.Xn2 = fb.Xn_next = m->Xn; fb.st1 = fb.st2 = fb.st_next = m->statsH;
+    fb.QKV = m->QKV; fb.AO = m->AO; fb.A = fb.A2 = m->A; fb.stA = fb.stA2 = m->statsA; fb.AD[0] = fb.AD[1] = m->AD; fb.F1 = m->F1;
+    // plain chain: Adapter (models/layers/adapter.py:46-60) on the bf16 copy of the sub-block output held in m->A
+    auto plain_adapter = [&](const AdapterW &aw) -> int {
         if (!aw.down_w) return 0;
-        if (fold) {
-            // adapter LayerNorm folded into the down projection, which reads the sub-block output `a` (m->A) directly
-            Fold fd;
-            fd.stats_in = m->statsA; fd.fold_c = aw.fold_c; fd.eps = 1e-5f;
-            if (int e = gemm(CH_CAT_GEMM_DOWN, c.adapter_dim, D, m->A, aw.down_wf, mm->bpad, D, aw.fold_d, EPI_FOLD_GELU, m->AD,
-                             mm->bpad, nullptr, nullptr, fd))
-                return e;
-            Fold fu;
-            if (emit_h) { fu.stats_out = m->statsH; fu.hb_out = m->Xn; }
-            return gemm(CH_CAT_GEMM_UP, D, c.adapter_dim, m->AD, aw.up_w, D, mm->bpad, aw.up_b,
-                        emit_h ? EPI_SCALE_RESID_STATS : EPI_SCALE_RESID, nullptr, 0, aw.scale, m->A, fu);
-        }
         if (aw.down_wf && mm->use_fused_adapter && ch_adapter_fused_supported(D, mm->bpad)) {
             // LN + down + GELU + up + residual in one launch (adapter_fused.hip); a = m->A (bf16), H updated in place
             mark(mm, pi, CH_CAT_ADAPTER, 4.0 * rows * (double)D * c.adapter_dim, s);
@@ -408,69 +416,55 @@ int run_chain(ch_model *mm, int pi, const void *images_all, int image_dtype, int
             ap.d = aw.fold_d; ap.Wu = aw.up_w; ap.bu = aw.up_b; ap.scale = aw.scale; ap.eps = 1e-5f;
             return ch_adapter_fused(ap, s);
         }
-        // Adapter (models/layers/adapter.py:46-60) on the bf16 copy of the sub-block output held in m->A
         mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
         if (int e = ch_layernorm_bf16(m->A, rows, D, aw.ln_w, aw.ln_b, 1e-5f, m->Xn, s)) return e;
-        if (int e = gemm(CH_CAT_GEMM_DOWN, c.adapter_dim, D, m->Xn, aw.down_w, mm->bpad, D, aw.down_b, EPI_BIAS_GELU, m->AD,
-                         mm->bpad, nullptr))
-            return e;
+        ChGemmCall g{mm->bpad, D, m->Xn, aw.down_w, aw.down_b, EPI_BIAS_GELU};
+        g.cat = CH_CAT_GEMM_DOWN; g.n_true = c.adapter_dim; g.out = m->AD; g.ldo = mm->bpad;
+        if (int e = run.gemm(rows, g)) return e;
         // one fp32 read-modify-write of the residual per sub-block: H += a + scale * (up(...) + bias), `a` read back as bf16
-        return gemm(CH_CAT_GEMM_UP, D, c.adapter_dim, m->AD, aw.up_w, D, mm->bpad, aw.up_b, EPI_SCALE_RESID, nullptr, 0,
-                    aw.scale, m->A);
+        g = ChGemmCall{D, mm->bpad, m->AD, aw.up_w, aw.up_b, EPI_SCALE_RESID};
+        g.cat = CH_CAT_GEMM_UP; g.k_true = c.adapter_dim; g.resid = m->H; g.scale = aw.scale; g.addend = m->A;
+        return run.gemm(rows, g);
     };
-
-    Fold stats_a;  // out_proj / fc2 of the LN-fold chain: row statistics of `a` for the adapter's folded LayerNorm
-    if (fold) stats_a.stats_out = m->statsA;
     for (int i = 0; i < nlayers; ++i) {
         const LayerW &w = mm->layers[i];
-        if (i > 0 && fold) {
-            // layer_norm1 folded: Xn holds bf16(H) and statsH its row statistics (previous layer's second up-projection)
-            Fold fq;
-            fq.stats_in = m->statsH; fq.fold_c = w.qkv_c; fq.eps = c.ln_eps;
-            if (int e = gemm(CH_CAT_GEMM_QKV, 3 * D, D, m->Xn, w.qkv_wf, 3 * D, D, w.qkv_d, EPI_FOLD_BIAS, m->QKV, 3 * D, nullptr,
-                             nullptr, fq))
-                return e;
-        } else {
-            if (i > 0) {
-                mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
-                if (int e = ch_layernorm_f32(m->H, rows, D, w.ln1_w, w.ln1_b, c.ln_eps, m->Xn, s)) return e;
-            }
-            if (int e = gemm(CH_CAT_GEMM_QKV, 3 * D, D, m->Xn, w.qkv_w, 3 * D, D, w.qkv_b, EPI_BIAS, m->QKV, 3 * D, nullptr)) return e;
-        }
-        const bool pruned = prune && fold && mm->prune_last && i == nlayers - 1 && nlayers == c.layers;
-        const int nq = 1 + c.ncontext;
-        mark(mm, pi, pruned ? CH_CAT_ATTENTION_PRUNED : CH_CAT_ATTENTION, 4.0 * B * (double)(pruned ? nq : ntok) * ntok * D, s);
+        const bool last = i == nlayers - 1;
         // concept-token attention tap: the last layer's rows, or (the call's concept_attn_all_layers) every layer's, [L, Btot, heads, Q, Np]
         float *cattn = !concept_attn ? nullptr
                        : attn_all_layers ? concept_attn + (size_t)i * Btot * c.heads * c.ncontext * np
-                       : i == nlayers - 1 ? concept_attn : nullptr;
-        if (int e = ch_attention(m->QKV, B, ntok, c.heads, m->AO, s, cattn, c.ncontext, pruned, next_dir() != 0, mm->attn_stream ? 2 : 0))
-            return e;
-        if (pruned) {
-            // from here on every buffer holds B * (1 + Q) compact rows (image-major: CLS, then the concept tokens)
-            cur_rows = B * nq;
-            cur_H = mm->Hc + (size_t)img0 * nq * D;
-            mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
-            if (int e = ch_gather_head_rows(m->H, B, ntok, c.ncontext, D, cur_H, s)) return e;
-        }
-        // h = r + a  (+ adapter_1(a) below);  a kept as bf16 in m->A for the adapter branch
-        // with adapters the residual add of `a` is deferred to the adapter's up-projection epilogue (see adapter())
-        const int sub_epi = fold ? EPI_BIAS_STATS : (w.ad[0].down_w ? EPI_BIAS : EPI_BIAS_RESID);
-        if (int e = gemm(CH_CAT_GEMM_OUT, D, D, m->AO, w.out_w, D, D, w.out_b, sub_epi, m->A, D, nullptr, nullptr, stats_a)) return e;
-        if (int e = adapter(w.ad[0], true)) return e;
+                       : last ? concept_attn : nullptr;
         if (fold) {
-            Fold f1;
-            f1.stats_in = m->statsH; f1.fold_c = w.fc1_c; f1.eps = c.ln_eps;
-            if (int e = gemm(CH_CAT_GEMM_FC1, M, D, m->Xn, w.fc1_wf, M, D, w.fc1_d,
-                             c.act == 0 ? EPI_FOLD_QUICKGELU : EPI_FOLD_GELU, m->F1, M, nullptr, nullptr, f1))
-                return e;
-        } else {
-            mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
-            if (int e = ch_layernorm_f32(m->H, rows, D, w.ln2_w, w.ln2_b, c.ln_eps, m->Xn, s)) return e;
-            if (int e = gemm(CH_CAT_GEMM_FC1, M, D, m->Xn, w.fc1_w, M, D, w.fc1_b, act_epi, m->F1, M, nullptr)) return e;
+            fb.qkv_folded = i > 0;   // layer 0 reads the rows ch_assemble_preln has normalised with its layer_norm1
+            if (last) fb.Xn_next = nullptr, fb.st_next = nullptr;
+            const bool prunes = prune && mm->prune_last && last && nlayers == c.layers;
+            if (int e = ch_layer_forward(run, st, w, fb, cattn, prunes ? mm->Hc + (size_t)img0 * (1 + c.ncontext) * D : nullptr)) return e;
+            continue;
         }
-        if (int e = gemm(CH_CAT_GEMM_FC2, D, M, m->F1, w.fc2_w, D, M, w.fc2_b, sub_epi, m->A, D, nullptr, nullptr, stats_a)) return e;
-        if (int e = adapter(w.ad[1], i + 1 < nlayers)) return e;
+        // ---- plain chain (option ln_fold off, a model without adapters, fused_adapter): LayerNorm launches of their own
+        if (i > 0) {
+            mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
+            if (int e = ch_layernorm_f32(m->H, rows, D, w.ln1_w, w.ln1_b, c.ln_eps, m->Xn, s)) return e;
+        }
+        ChGemmCall g{3 * D, D, m->Xn, w.qkv_w, w.qkv_b, EPI_BIAS};
+        g.cat = CH_CAT_GEMM_QKV; g.out = m->QKV; g.ldo = 3 * D;
+        if (int e = run.gemm(rows, g)) return e;
+        if (int e = run.attention(m->QKV, m->AO, cattn, false)) return e;
+        // h = r + a  (+ adapter_1(a));  a kept as bf16 in m->A for the adapter branch
+        // with adapters the residual add of `a` is deferred to the adapter's up-projection epilogue (see plain_adapter)
+        const int sub_epi = w.ad[0].down_w ? EPI_BIAS : EPI_BIAS_RESID;
+        g = ChGemmCall{D, D, m->AO, w.out_w, w.out_b, sub_epi};
+        g.cat = CH_CAT_GEMM_OUT; g.out = m->A; g.ldo = D; g.resid = m->H;
+        if (int e = run.gemm(rows, g)) return e;
+        if (int e = plain_adapter(w.ad[0])) return e;
+        mark(mm, pi, CH_CAT_ROWOPS, 0.0, s);
+        if (int e = ch_layernorm_f32(m->H, rows, D, w.ln2_w, w.ln2_b, c.ln_eps, m->Xn, s)) return e;
+        g = ChGemmCall{M, D, m->Xn, w.fc1_w, w.fc1_b, c.act == 0 ? EPI_BIAS_QUICKGELU : EPI_BIAS_GELU};
+        g.cat = CH_CAT_GEMM_FC1; g.out = m->F1; g.ldo = M;
+        if (int e = run.gemm(rows, g)) return e;
+        g = ChGemmCall{D, M, m->F1, w.fc2_w, w.fc2_b, sub_epi};
+        g.cat = CH_CAT_GEMM_FC2; g.out = m->A; g.ldo = D; g.resid = m->H;
+        if (int e = run.gemm(rows, g)) return e;
+        if (int e = plain_adapter(w.ad[1])) return e;
     }
     return 0;
 }
@@ -681,7 +675,7 @@ extern "C" double ch_model_flops_per_image(const ch_model *m) {
     const double patch = 2.0 * m->np * D * 3.0 * c.patch * c.patch;
     const double layer = 8.0 * N * D * D + 4.0 * N * D * M + 4.0 * N * N * D + 8.0 * N * D * b;
     double total = patch + L * layer + 2.0 * D * c.nbit;
-    if (m->prune_last && m->ln_fold && c.adapter_dim > 0 && !m->use_fused_adapter) {
+    if (ch_encode_prunes_last(m)) {
         // final layer: qkv on all rows, everything after it on the 1 + Q rows the head reads
         const double nq = 1 + c.ncontext;
         total += -layer + 6.0 * N * D * D + 4.0 * nq * N * D + 2.0 * nq * D * D + 4.0 * nq * D * M + 8.0 * nq * D * b;
@@ -697,7 +691,7 @@ int encode_impl(ch_model *m, const void *images, int image_dtype, int B, float *
                 float *out_concept_attn, bool all_layers, hipStream_t s) {
     if (int e = run_encoder(m, images, image_dtype, B, m->cfg.layers, s, out_concept_attn, all_layers, true)) return e;
     const ch_model_config &c = m->cfg;
-    const bool pruned = m->prune_last && m->ln_fold && c.adapter_dim > 0 && !m->use_fused_adapter;  // as run_chain decides
+    const bool pruned = ch_encode_prunes_last(m);
     HeadParams p{};
     p.H = pruned ? m->Hc : m->H; p.B = B; p.ntok = pruned ? 1 + c.ncontext : m->ntok; p.D = c.dim; p.Q = c.ncontext; p.nbit = c.nbit; p.C = c.nclass; p.P = c.proj_dim;
     p.hash_pe = m->hash_pe; p.hash_fc = m->hash_fc; p.bn_scale = m->bn_scale; p.bn_shift = m->bn_shift;

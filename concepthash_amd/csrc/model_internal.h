@@ -10,24 +10,9 @@
 #include "ch_common.h"
 #include "device_owner.h"
 #include "kernels.h"
+#include "layer_types.h"
 
 constexpr int CH_MAX_STREAMS = 4;  // micro-batch chains that may run concurrently (option "streams")
-
-struct AdapterW {
-    const float *ln_w = nullptr, *ln_b = nullptr, *down_b = nullptr, *up_b = nullptr, *scale = nullptr;
-    const bf16_t *down_w = nullptr, *up_w = nullptr;
-    // adapter LayerNorm folded into the down projection (LN-fold chain and adapter_fused.hip)
-    const bf16_t *down_wf = nullptr;
-    const float *fold_c = nullptr, *fold_d = nullptr;
-};
-struct LayerW {
-    const float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *qkv_b, *out_b, *fc1_b, *fc2_b;
-    const bf16_t *qkv_w, *out_w, *fc1_w, *fc2_w;
-    // layer_norm1 / layer_norm2 folded into qkv / fc1: W' = bf16(W * gamma), c = row sums of W', d = bias + W beta
-    const bf16_t *qkv_wf = nullptr, *fc1_wf = nullptr;
-    const float *qkv_c = nullptr, *qkv_d = nullptr, *fc1_c = nullptr, *fc1_d = nullptr;
-    AdapterW ad[2];
-};
 
 // Fork / join of micro-batch chains (ch_encode: model.hip run_encoder; the training step: train.hip): chain 0 runs on the caller's
 // stream s, chain i > 0 on aux stream i.  The streams and events belong to the handle's owner.
@@ -147,4 +132,8 @@ struct ch_model {
     float *statsA = nullptr, *statsH = nullptr;  // [rows, D/64, 2] partial (sum, sumsq) of the rows of A / of bf16(H) in Xn
     bf16_t *Xn = nullptr, *QKV = nullptr, *AO = nullptr, *A = nullptr, *AD = nullptr, *F1 = nullptr, *PATCH = nullptr;
 };
+
+// ch_encode runs the LN-fold chain (layer_forward.h) / carries only the head's rows past the last layer's attention
+inline bool ch_encode_folds(const ch_model *m) { return m->ln_fold && m->cfg.adapter_dim > 0 && !m->use_fused_adapter; }
+inline bool ch_encode_prunes_last(const ch_model *m) { return m->prune_last && ch_encode_folds(m); }
 

@@ -9,11 +9,12 @@
 // generator (4 tokens), the hashing head on [B, Q, D] and the loss are a few MFLOP; they stay on the host framework's autograd
 // (concepthash_amd/training.py), which hands `concept_tokens` in and d(hash_features) back, and receives d(concept_tokens).
 //
-// Forward = the LN-fold chain of model.hip, one chain, with every layer's operands kept: bf16(H) + row statistics (the
-// LayerNorm inputs), qkv, attention output, a / m (sub-block outputs) + statistics, adapter pre-activations and activations,
-// fc1 pre-activation.  Pre-activations are saved instead of activations, so the activations are applied by a separate
-// epilogue mode in training: the GEMM writes the pre-activation AND its activation (EPI_FOLD_ACT2_*); backward multiplies by the
-// activation's derivative in the dgrad GEMM's epilogue (EPI_BIAS_DACT_*).
+// Forward = the LN-fold layer of ch_encode -- ONE definition, ch_layer_forward in layer_forward.h, issued by both -- with every
+// layer's operands kept in buffers of its own: bf16(H) + row statistics (the LayerNorm inputs), qkv, attention output, a / m
+// (sub-block outputs) + statistics, adapter pre-activations and activations, fc1 pre-activation.  Pre-activations are saved
+// instead of activations: handing the layer a pre-activation buffer selects the epilogue that writes the pre-activation AND its
+// activation; backward multiplies by the activation's derivative in the dgrad GEMM's epilogue (EPI_BIAS_DACT_*).  Layer 0's
+// LayerNorm input comes from ch_hb_stats (ch_encode's layer 0 reads rows already normalised instead).
 // Backward per layer, dH = gradient of the residual stream (fp32, bf16 copy dHb as the GEMM operand):
 //   adapter:  G = dHb^T g, cu = colsum(dH)                                [weight-gradient products, up]
 //             dpre = s (dHb W_up) o gelu'(pre)                            [dgrad GEMM + act_bwd]
@@ -28,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "layer_forward.h"
 #include "model_internal.h"
 
 namespace {
@@ -177,24 +179,8 @@ AdPtr ad_ptrs(float *base, const ch_model_config &c) {
     return p;
 }
 
-struct GemmCall {
-    int N, K;
-    const bf16_t *X, *W;
-    const float *bias;
-    int epi;
-    bf16_t *out = nullptr;
-    int ldo = 0;
-    float *resid = nullptr;
-    const float *scale = nullptr;
-    const bf16_t *addend = nullptr;
-    const float *stats_in = nullptr, *fold_c = nullptr;
-    float eps = 0.f;
-    float *stats_out = nullptr;
-    bf16_t *hb_out = nullptr;
-    int ld_hb = 0;              // 0 = D
-    const bf16_t *aux = nullptr;
-};
-int gemm(ch_trainer *t, int chain, int rows, const GemmCall &g, hipStream_t s, int64_t x_rows_alloc = 0) {
+// a ChGemmCall (layer_forward.h) as GemmParams, with the per-model options the training step honours
+int gemm(ch_trainer *t, int chain, int rows, const ChGemmCall &g, hipStream_t s, int64_t x_rows_alloc = 0) {
     const int D = t->m->cfg.dim;
     GemmParams p{};
     p.X = g.X; p.W = g.W; p.M = rows; p.N = g.N; p.K = g.K; p.X_rows_alloc = x_rows_alloc ? x_rows_alloc : t->region_rows[chain];
@@ -218,6 +204,19 @@ struct Rows {
     template <typename T>
     T *b(T *p) const { return p + r0 * bpad; }
     float *st(float *p) const { return p + r0 * (D / 64) * 2; }
+};
+
+// the training step's launcher of one chain's forward layers (layer_forward.h)
+struct TrainLaunch {
+    ch_trainer *t;
+    int ch, B;
+    hipStream_t s;
+    int gemm(int rows, const ChGemmCall &g) { return ::gemm(t, ch, rows, g, s); }
+    int attention(const bf16_t *qkv, bf16_t *out, float *cattn, bool compact) {
+        const ch_model *m = t->m;
+        return ch_attention(qkv, B, m->ntok, m->cfg.heads, out, s, cattn, m->cfg.ncontext, compact, false, m->attn_stream ? 2 : 0);
+    }
+    int gather_head_rows(const float *H, float *Hc) { return ch_gather_head_rows(H, B, t->m->ntok, t->m->cfg.ncontext, t->m->cfg.dim, Hc, s); }
 };
 
 int forward_chain(ch_trainer *t, int ch, const void *images_all, int image_dtype, int img0, int B, float *out_hf_all, float *out_cls_all,
@@ -246,59 +245,28 @@ int forward_chain(ch_trainer *t, int ch, const void *images_all, int image_dtype
     if (int e = ch_hb_stats(H, rows, D, R.d(t->sv[0].Xn1), R.st(t->sv[0].st1), s)) return e;
     const int nq = 1 + Q;
     float *Hc = t->Hc + (size_t)ch * t->hc_rows * D;
-    int cur = rows;          // rows carried: all tokens, or B * (1 + Q) past the last layer's attention
+    TrainLaunch run{t, ch, B, s};
+    ChChain st{B, ntok, Q, D, M, bpad, c.adapter_dim, c.act, c.ln_eps, rows, H};
     for (int l = 0; l < L; ++l) {
-        const LayerW &w = t->lw[l];
-        Saved &v = t->sv[l];
-        GemmCall g;
-        // attention block
-        g = GemmCall{3 * D, D, R.d(v.Xn1), w.qkv_wf, w.qkv_d, EPI_FOLD_BIAS};
-        g.out = R.d3(v.QKV); g.ldo = 3 * D; g.stats_in = R.st(v.st1); g.fold_c = w.qkv_c; g.eps = c.ln_eps;
-        if (int e = gemm(t, ch, rows, g, s)) return e;
-        const bool pruned = t->prune_last && l == L - 1;
+        const Saved &v = t->sv[l];
+        const bool last = l == L - 1;
+        // every operand is kept per layer for backward, pre-activations included; only fc1's activation is scratch, and the bf16(H)
+        // that nothing follows goes to the dummies
+        ChLayerBufs b{};
+        b.Xn1 = R.d(v.Xn1); b.st1 = R.st(v.st1); b.qkv_folded = true;
+        b.QKV = R.d3(v.QKV); b.AO = R.d(v.AO); b.A = R.d(v.A); b.stA = R.st(v.stA); b.A2 = R.d(v.A2); b.stA2 = R.st(v.stA2);
+        b.AD[0] = R.b(v.G1); b.ADpre[0] = R.b(v.P1); b.AD[1] = R.b(v.G2); b.ADpre[1] = R.b(v.P2);
+        b.Xn2 = R.d(v.Xn2); b.st2 = R.st(v.st2); b.F1 = R.m(t->F1act); b.F1pre = R.m(v.F1pre);
+        b.Xn_next = R.d(last ? t->XnDummy : t->sv[l + 1].Xn1); b.st_next = R.st(last ? t->stDummy : t->sv[l + 1].st1);
         // last layer: optionally tap the concept tokens' attention rows over the patch tokens (attn_cache[-1][:, :, -Q:, 1:-Q])
         // (concept_attn_all_layers of the call: every layer's rows, [L, B, heads, Q, Np])
         float *cattn = !out_cattn_all ? nullptr
                        : t->attn_all_layers ? out_cattn_all + ((size_t)l * t->B + img0) * c.heads * Q * np
-                       : l == L - 1 ? out_cattn_all + (size_t)img0 * c.heads * Q * np : nullptr;
-        if (int e = ch_attention(R.d3(v.QKV), B, ntok, c.heads, R.d(v.AO), s, cattn, Q, pruned, false, m->attn_stream ? 2 : 0)) return e;
-        if (pruned) {      // from here on every buffer of this layer holds B * (1 + Q) compact rows (CLS, then the concept tokens)
-            cur = B * nq;
-            if (int e = ch_gather_head_rows(H, B, ntok, Q, D, Hc, s)) return e;
-            H = Hc;
-        }
-        g = GemmCall{D, D, R.d(v.AO), w.out_w, w.out_b, EPI_BIAS_STATS};
-        g.out = R.d(v.A); g.ldo = D; g.stats_out = R.st(v.stA);
-        if (int e = gemm(t, ch, cur, g, s)) return e;
-        for (int a = 0; a < 2; ++a) {
-            const AdWork &aw = t->ad[l * 2 + a];
-            const AdPtr ap = ad_ptrs(t->params + (int64_t)(l * 2 + a) * t->ad_numel, c);
-            const bf16_t *in = R.d(a == 0 ? v.A : v.A2);
-            const float *stin = R.st(a == 0 ? v.stA : v.stA2);
-            bf16_t *P = R.b(a == 0 ? v.P1 : v.P2), *G = R.b(a == 0 ? v.G1 : v.G2);
-            // pre-activation kept for backward, nn.GELU() (models/layers/adapter.py:36) of it as the second output
-            g = GemmCall{bpad, D, in, aw.down_wf, aw.fold_d, EPI_FOLD_ACT2_GELU};
-            g.out = P; g.ldo = bpad; g.stats_in = stin; g.fold_c = aw.fold_c; g.eps = 1e-5f; g.hb_out = G; g.ld_hb = bpad;
-            if (int e = gemm(t, ch, cur, g, s)) return e;
-            g = GemmCall{D, bpad, G, aw.up_w, ap.up_b, EPI_SCALE_RESID_STATS};
-            g.resid = H; g.scale = ap.scale; g.addend = in;
-            if (a == 0) {
-                g.stats_out = R.st(v.st2); g.hb_out = R.d(v.Xn2);
-            } else {
-                g.stats_out = R.st(l + 1 < L ? t->sv[l + 1].st1 : t->stDummy);
-                g.hb_out = R.d(l + 1 < L ? t->sv[l + 1].Xn1 : t->XnDummy);
-            }
-            if (int e = gemm(t, ch, cur, g, s)) return e;
-            if (a == 0) {  // MLP
-                g = GemmCall{M, D, R.d(v.Xn2), w.fc1_wf, w.fc1_d, c.act == 0 ? EPI_FOLD_ACT2_QUICK : EPI_FOLD_ACT2_GELU};
-                g.out = R.m(v.F1pre); g.ldo = M; g.stats_in = R.st(v.st2); g.fold_c = w.fc1_c; g.eps = c.ln_eps; g.hb_out = R.m(t->F1act); g.ld_hb = M;
-                if (int e = gemm(t, ch, cur, g, s)) return e;
-                g = GemmCall{D, M, R.m(t->F1act), w.fc2_w, w.fc2_b, EPI_BIAS_STATS};
-                g.out = R.d(v.A2); g.ldo = D; g.stats_out = R.st(v.stA2);
-                if (int e = gemm(t, ch, cur, g, s)) return e;
-            }
-        }
+                       : last ? out_cattn_all + (size_t)img0 * c.heads * Q * np : nullptr;
+        if (int e = ch_layer_forward(run, st, t->lw[l], b, cattn, t->prune_last && last ? Hc : nullptr)) return e;
     }
+    H = st.H;   // the compact copy past a pruned last layer
+    const int cur = st.cur;
     const int tok_out = cur == rows ? ntok : nq;   // row layout of the final residual: all tokens, or (CLS, concept tokens) per image
     if (int e = ch_gather_concept_rows(H, B, tok_out, Q, D, out_hf_all + (size_t)img0 * Q * D, s)) return e;
     if (out_cls_all) {  // CLS rows of the final residual (the pooled branch, models/arch/coop.py:484-499, is not part of the loss)
@@ -350,12 +318,12 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
         if (int e = ch_wgrad_tn(dHb, D, G, bpad, cur, dalloc, D, bpad, t->G[ch], t->ws_wgrad[ch], s, bg ? &nchunk[0] : nullptr)) return e;
         // of the fp32 gradient: a bias gradient is a sum over rows that largely cancels, the bf16 copy costs 1e-1 relative there
         if (int e = ch_colsum(dH, 1, D, cur, D, t->cu[ch], t->ws_colsum[ch], s, bg ? &nchunk[1] : nullptr)) return e;
-        GemmCall g{bpad, D, dHb, aw.up_wT, zero, EPI_BIAS_DACT_GELU};   // dpre = s (dH W_up) o gelu'(pre), in the epilogue
+        ChGemmCall g{bpad, D, dHb, aw.up_wT, zero, EPI_BIAS_DACT_GELU};   // dpre = s (dH W_up) o gelu'(pre), in the epilogue
         g.out = tB; g.ldo = bpad; g.aux = P; g.scale = ap.scale;
         if (int e = gemm(t, ch, cur, g, s, dalloc)) return e;
         // down projection + adapter LayerNorm: the input-gradient GEMM and the LayerNorm backward first -- the latter emits the
         // normalised adapter input x_hat (bf16) on the way, which the weight-gradient product then consumes
-        g = GemmCall{D, bpad, tB, aw.down_wgT, zero, EPI_BIAS};
+        g = ChGemmCall{D, bpad, tB, aw.down_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
         if (int e = ch_ln_bwd(tD, in, stin, cur, D, 1e-5f, dH, dMf, dMb, s, tD2)) return e;
@@ -397,10 +365,10 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
             if (int e = ch_act_fwd(R.m(v.F1pre), (int64_t)cur * M, c.act == 0 ? 0 : 1, R.m(t->F1act), s)) return e;
             if (int e = plain_grads(dMb, dMf, R.m(t->F1act), D, M, ralloc, bg.fc2_w, bg.fc2_b)) return e;
         }
-        GemmCall g{M, D, dMb, x.fc2_wT, zero, c.act == 0 ? EPI_BIAS_DACT_QUICK : EPI_BIAS_DACT_GELU};
+        ChGemmCall g{M, D, dMb, x.fc2_wT, zero, c.act == 0 ? EPI_BIAS_DACT_QUICK : EPI_BIAS_DACT_GELU};
         g.out = tM; g.ldo = M; g.aux = R.m(v.F1pre);
         if (int e = gemm(t, ch, cur, g, s)) return e;
-        g = GemmCall{D, M, tM, x.fc1_wgT, zero, EPI_BIAS};
+        g = ChGemmCall{D, M, tM, x.fc1_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
         if (int e = ch_ln_bwd(tD, R.d(v.Xn2), R.st(v.st2), cur, D, c.ln_eps, dH, dH, dHb, s, bb ? tD2 : nullptr)) return e;
@@ -412,7 +380,7 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
         if (int e = adapter_bwd(l, 0)) return e;
         if (bb)     // out_proj: dA^T ctx (the saved attention output; compact rows inside the pruned last layer, as dA is)
             if (int e = plain_grads(dMb, dMf, R.d(v.AO), D, D, ralloc, bg.out_w, bg.out_b)) return e;
-        g = GemmCall{D, D, dMb, x.out_wT, zero, EPI_BIAS};
+        g = ChGemmCall{D, D, dMb, x.out_wT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
         const bf16_t *dctx = tD;
@@ -430,7 +398,7 @@ int backward_chain(ch_trainer *t, int ch, const float *dhf_all, const float *dca
                              : t->attn_all_layers ? dcattn_all + ((size_t)l * t->B + img0) * c.heads * Q * (ntok - Q - 1)
                              : l == L - 1 ? dcattn_all + (size_t)img0 * c.heads * Q * (ntok - Q - 1) : nullptr;
         if (int e = ch_attention_bwd(R.d3(v.QKV), dctx, B, ntok, c.heads, tQKV, s, dpext, Q, m->attn_stream ? 2 : 0)) return e;
-        g = GemmCall{D, 3 * D, tQKV, x.qkv_wgT, zero, EPI_BIAS};
+        g = ChGemmCall{D, 3 * D, tQKV, x.qkv_wgT, zero, EPI_BIAS};
         g.out = tD; g.ldo = D;
         if (int e = gemm(t, ch, cur, g, s)) return e;
         if (int e = ch_ln_bwd(tD, R.d(v.Xn1), R.st(v.st1), cur, D, c.ln_eps, dH, dH, dHb, s, bb ? tD2 : nullptr)) return e;
@@ -634,6 +602,10 @@ extern "C" int ch_trainer_create_ex(ch_model *m, int32_t max_batch, float *param
             AdWork &w = t->ad[i];
             w.down_wf = dwf + i * mat; w.up_w = uw + i * mat; w.up_wT = uwT + i * mat; w.down_wgT = dwT + i * mat;
             w.fold_c = fc + i * bpad; w.fold_d = fd + i * bpad;
+            // what the forward reads (layer_forward.h): these working copies; bias and scale straight from the parameter arena
+            AdapterW &fw = t->lw[i / 2].ad[i % 2];
+            const AdPtr ap = ad_ptrs(t->params + (int64_t)i * t->ad_numel, c);
+            fw.down_wf = w.down_wf; fw.fold_c = w.fold_c; fw.fold_d = w.fold_d; fw.up_w = w.up_w; fw.up_b = ap.up_b; fw.scale = ap.scale;
         }
     }
     hipStream_t s = nullptr;
