@@ -183,6 +183,15 @@ SIGNATURES = {
                                       c_void_p, c_int32, c_void_p, c_void_p]),
     "ch_hamming_rank_ap": (c_int, [c_int64, c_void_p, c_void_p, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "ch_pack_ternary": (c_int, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),
+    "ch_ternary_dist": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_ternary_topk_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_ternary_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
+    "ch_ternary_rank_collect": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ch_ternary_rank_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                      c_int32, c_void_p, c_void_p]),
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

@@ -10,6 +10,8 @@
 //     AP          one lane per query walks its bins: prefix, remove_first, the fixed-point AP terms under up to 16 rank limits.
 // bins are integer sums over gallery rows: gallery segments (blockIdx.y) add up in any order and give the same bits.
 // Nothing of size Qn x G is written.
+// The collect and the count kernel are templates on the distance (hamming_shared.h); this file holds the weighted distance's two forms
+// for them, the AP pass and the entries.  hamming_ternary.hip instantiates the same two templates under the ternary distance.
 #include <algorithm>
 #include <string>
 
@@ -19,15 +21,8 @@
 
 namespace {
 
-constexpr int RC_BLK = 256;          // lanes of a workgroup of the two scans
-constexpr int RC_MAX_LIST = 8192;    // longest list held in LDS: 8 B per key + 4 B per bin = 96 KB
-constexpr int RC_TQ = 16;            // queries per workgroup of the collect pass
-constexpr int RC_QUEUE = 8192;       // ... and the (query, row) pairs its LDS queue holds: two trips' worth at the most (32 KB)
-constexpr int RC_ROW_BITS = 27;      // a queue entry = query in tile << 27 | row in segment: segments of at most 2^27 rows
-static_assert(RC_QUEUE >= 2 * RC_BLK * RC_TQ && RC_TQ <= (1 << (32 - RC_ROW_BITS)), "queue entry layout");
-
 // ---------------------------------------------------------------------------------------------------------------
-// collect: the keys of the relevant rows
+// collect: the keys of the relevant rows (rank_collect_kernel, hamming_shared.h, under the distance below)
 // ---------------------------------------------------------------------------------------------------------------
 // D of one (query, row) pair with everything read from memory: the collect pass pays it for relevant rows only (G / C of G).
 __device__ __forceinline__ uint32_t weighted_dist_row(const uint64_t *__restrict__ q, const uint64_t *__restrict__ pl, int P, int W,
@@ -40,100 +35,13 @@ __device__ __forceinline__ uint32_t weighted_dist_row(const uint64_t *__restrict
     return d;
 }
 
-__device__ __forceinline__ bool masks_meet(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, int LW) {
-    bool r = false;
-    for (int w = 0; w < LW; ++w) r |= (a[w] & b[w]) != 0ull;
-    return r;
-}
-
-// One workgroup per (tile of RC_TQ queries, gallery segment); lanes stride over the segment's rows, and a row's label is loaded once for
-// the whole tile (the queries of a tile are walked by a workgroup-uniform loop: their labels arrive through the scalar data path).
-// WRITE = false (the entry's offsets == NULL): count[q] += relevant rows.  WRITE = true: count[q] is the fill of the query's slice
-// keys[offsets[q] .. offsets[q + 1]): every relevant row reserves a slot with an atomic add and leaves its key there (any order inside
-// a slice).  A slot past the slice is never written.
-template <bool WRITE>
-__global__ __launch_bounds__(RC_BLK) void rank_collect_kernel(const uint64_t *__restrict__ q, const uint64_t *__restrict__ planes, int P,
-                                                              int64_t Qn, const uint64_t *__restrict__ g, int64_t G, int W,
-                                                              const void *q_labels, const void *g_labels, int LW, int seg_rows,
-                                                              int64_t g_index_base, const int64_t *__restrict__ offsets,
-                                                              uint32_t *__restrict__ count, uint64_t *__restrict__ keys) {
-    const int64_t q0 = (int64_t)blockIdx.x * RC_TQ;
-    const int nq = (int)min((int64_t)RC_TQ, Qn - q0);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t g0 = (int64_t)blockIdx.y * seg_rows;
-    const int n = (int)min((int64_t)seg_rows, G - g0);
-    const int32_t *gl32 = (const int32_t *)g_labels, *ql32 = (const int32_t *)q_labels;
-    const uint64_t *glm = (const uint64_t *)g_labels, *qlm = (const uint64_t *)q_labels;
-    if constexpr (!WRITE) {
-        int32_t qlab[RC_TQ];
-        uint32_t mine[RC_TQ];
-#pragma unroll
-        for (int t = 0; t < RC_TQ; ++t) {
-            qlab[t] = (LW == 0 && t < nq) ? ql32[q0 + t] : 0;
-            mine[t] = 0u;
-        }
-        for (int r = tid; r < n; r += RC_BLK) {
-            const int64_t j = g0 + r;
-            const int32_t glab = LW == 0 ? gl32[j] : 0;
-#pragma unroll
-            for (int t = 0; t < RC_TQ; ++t) {
-                bool rel = false;
-                if (t < nq) rel = LW == 0 ? glab == qlab[t] : masks_meet(qlm + (q0 + t) * LW, glm + j * LW, LW);
-                mine[t] += rel ? 1u : 0u;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < RC_TQ; ++t) {
-            uint32_t c = mine[t];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-            if (lane == 0 && c != 0u && t < nq) atomicAdd(count + q0 + t, c);
-        }
-    } else {
-        // Relevant (query, row) pairs are rare and scattered over the lanes, and a key costs a slot reservation (an atomic that returns) and
-        // a distance: done where the pair is found, one or two lanes of a wave would pay that latency pair after pair.  Instead a lane that
-        // finds a pair leaves (query in tile, row in segment) in an LDS queue, and the workgroup empties the queue with every lane busy --
-        // whenever the next trip might not fit (a trip adds at most RC_BLK * RC_TQ pairs), and at the end.
-        __shared__ uint32_t queue[RC_QUEUE];
-        __shared__ uint32_t queued;
-        if (tid == 0) queued = 0u;
-        __syncthreads();
-        auto drain = [&](uint32_t cnt) {   // called by the whole workgroup with the count every lane read between two barriers
-            for (uint32_t e = tid; e < cnt; e += RC_BLK) {
-                const uint32_t entry = queue[e];
-                const int64_t qi = q0 + (entry >> RC_ROW_BITS), j = g0 + (entry & ((1u << RC_ROW_BITS) - 1u));
-                const int64_t off = offsets[qi];
-                const uint32_t room = (uint32_t)(offsets[qi + 1] - off);
-                const uint32_t slot = atomicAdd(count + qi, 1u);
-                if (slot < room)
-                    keys[off + slot] = ((uint64_t)weighted_dist_row(q + qi * W, planes + qi * P * W, P, W, g + j * W) << 32) |
-                                       (uint64_t)(g_index_base + j);
-            }
-            __syncthreads();
-            if (tid == 0) queued = 0u;
-            __syncthreads();
-        };
-        for (int r0 = 0; r0 < n; r0 += RC_BLK) {   // the same trips for every lane: the barriers below are a workgroup's
-            const int r = r0 + tid;
-            if (r < n) {
-                const int64_t j = g0 + r;
-                const int32_t glab = LW == 0 ? gl32[j] : 0;
-                for (int t = 0; t < nq; ++t) {
-                    const int64_t qi = q0 + t;
-                    if (LW == 0 ? glab == ql32[qi] : masks_meet(qlm + qi * LW, glm + j * LW, LW))
-                        queue[atomicAdd(&queued, 1u)] = ((uint32_t)t << RC_ROW_BITS) | (uint32_t)r;
-                }
-            }
-            __syncthreads();
-            const uint32_t cnt = queued;   // the same value in every lane: nobody adds to the queue before the next barrier
-            if (cnt > (uint32_t)(RC_QUEUE - RC_BLK * RC_TQ))
-                drain(cnt);
-            else
-                __syncthreads();
-        }
-        drain(queued);
+struct WeightedRow {
+    const uint64_t *q, *planes;
+    int P;
+    __device__ __forceinline__ uint32_t row(int64_t qi, int W, const uint64_t *__restrict__ g, int64_t j) const {
+        return weighted_dist_row(q + qi * W, planes + qi * P * W, P, W, g + j * W);
     }
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // rank count: the Qn x G scan
@@ -160,94 +68,33 @@ __device__ __forceinline__ uint32_t weighted_dist_uniform(const uint32_t (&qs)[2
     return horner2(acc);
 }
 
-// #{j < n : list[j] < key}
-__device__ __forceinline__ uint32_t keys_below(const uint64_t *list, uint32_t n, uint64_t key) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (list[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// The rows [0, nrows) of a segment against one query, two rows per lane and trip (both rows' loads are out before the first distance).
-// list / bins: the query's sorted keys and its bins, in LDS or in global memory.  A key above `last` = list[n - 1] is done after the
-// compare; any other has keys_below <= n - 1, so bins[n] does not exist.
+// what rank_count_kernel (hamming_shared.h) takes as its distance: the query's words and planes, read once into wave-uniform registers
 template <int W, int P>
-__device__ __forceinline__ void rank_count_rows(const uint32_t (&qs)[2 * W], const uint32_t (&ps)[P][2 * W],
-                                                const uint64_t *__restrict__ gp, int nrows, uint64_t row0, const uint64_t *list,
-                                                uint32_t n, uint64_t last, uint32_t *bins) {
-    for (int r = threadIdx.x; r < nrows; r += 2 * RC_BLK) {
-        const bool two = r + RC_BLK < nrows;
-        const int r1 = two ? r + RC_BLK : r;
-        uint64_t ga[W], gb[W];
-#pragma unroll
-        for (int w = 0; w < W; ++w) ga[w] = gp[(size_t)r * W + w];
-#pragma unroll
-        for (int w = 0; w < W; ++w) gb[w] = gp[(size_t)r1 * W + w];
-        const uint64_t ka = ((uint64_t)weighted_dist_uniform<W, P>(qs, ps, ga) << 32) | (row0 + (uint64_t)r);
-        const uint64_t kb1 = ((uint64_t)weighted_dist_uniform<W, P>(qs, ps, gb) << 32) | (row0 + (uint64_t)r1);
-        const uint64_t kb = two ? kb1 : ~0ull;   // no second row: above every key
-        if (ka <= last) atomicAdd(bins + keys_below(list, n, ka), 1u);
-        if (kb <= last) atomicAdd(bins + keys_below(list, n, kb), 1u);
-    }
-}
-
-// One workgroup per (query, gallery segment).  A query without a relevant row ends at its first branch.  A list of at most list_cap
-// keys lives in LDS with its bins, which leave through global atomic adds at the end (segments add up); a longer one is searched where
-// it lies, in global memory, and its bins are added to directly.
-template <int W, int P>
-__global__ __launch_bounds__(RC_BLK) void rank_count_kernel(const uint64_t *__restrict__ q, const uint64_t *__restrict__ planes,
-                                                            const uint64_t *__restrict__ g, int64_t G, int seg_rows,
-                                                            int64_t g_index_base, const int64_t *__restrict__ offsets,
-                                                            const uint64_t *__restrict__ keys, int list_cap,
-                                                            uint32_t *__restrict__ bins) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];   // [list_cap] keys, then [list_cap] uint32 bins
-    const int64_t qi = blockIdx.x;
-    const int64_t off = offsets[qi];
-    const int64_t n64 = offsets[qi + 1] - off;
-    if (n64 <= 0) return;   // workgroup-uniform
-    const uint32_t n = (uint32_t)n64;
-    const int tid = threadIdx.x;
-    const int64_t g0 = (int64_t)blockIdx.y * seg_rows;
-    const int nrows = (int)min((int64_t)seg_rows, G - g0);
-    uint32_t qs[2 * W], ps[P][2 * W];
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const uint64_t v = q[qi * W + w];
-        qs[2 * w] = __builtin_amdgcn_readfirstlane((uint32_t)v);
-        qs[2 * w + 1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    }
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
+struct WeightedUniform {
+    static constexpr int ROW = W;
+    struct Regs {
+        uint32_t qs[2 * W], ps[P][2 * W];
+    };
+    const uint64_t *q, *planes;
+    __device__ __forceinline__ void load(Regs &r, int64_t qi) const {
 #pragma unroll
         for (int w = 0; w < W; ++w) {
-            const uint64_t v = planes[(qi * P + p) * W + w];
-            ps[p][2 * w] = __builtin_amdgcn_readfirstlane((uint32_t)v);
-            ps[p][2 * w + 1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+            const uint64_t v = q[qi * W + w];
+            r.qs[2 * w] = __builtin_amdgcn_readfirstlane((uint32_t)v);
+            r.qs[2 * w + 1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const uint64_t v = planes[(qi * P + p) * W + w];
+                r.ps[p][2 * w] = __builtin_amdgcn_readfirstlane((uint32_t)v);
+                r.ps[p][2 * w + 1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+            }
         }
     }
-    const uint64_t *list = keys + off;
-    const uint64_t last = list[n - 1];
-    const uint64_t *gp = g + g0 * W;
-    const uint64_t row0 = (uint64_t)(g_index_base + g0);
-    if (n <= (uint32_t)list_cap) {
-        uint32_t *lds_bins = (uint32_t *)(lds_keys + list_cap);
-        for (uint32_t i = tid; i < n; i += RC_BLK) {
-            lds_keys[i] = list[i];
-            lds_bins[i] = 0u;
-        }
-        __syncthreads();
-        rank_count_rows<W, P>(qs, ps, gp, nrows, row0, lds_keys, n, last, lds_bins);
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += RC_BLK) {
-            const uint32_t c = lds_bins[i];
-            if (c != 0u) atomicAdd(bins + off + i, c);
-        }
-    } else {
-        rank_count_rows<W, P>(qs, ps, gp, nrows, row0, list, n, last, bins + off);
-    }
-}
+    __device__ __forceinline__ static uint32_t at(const Regs &r, const uint64_t (&g)[W]) { return weighted_dist_uniform<W, P>(r.qs, r.ps, g); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // AP from the bins
@@ -308,13 +155,8 @@ int dispatch_p(int P, F &&f) {
 
 // what the collect and count entries check alike
 int check_scan_sizes(const char *who, int P, int64_t Qn, int64_t G, int W, int64_t g_index_base) {
-    const std::string at = std::string(who) + ": ";
-    CH_REQUIRE(P == 4 || P == 8, at + "P (weight bits) must be 4 or 8");
-    CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
-    CH_REQUIRE(Qn >= 0 && G >= 0, at + "negative sizes");
-    CH_REQUIRE(Qn <= 0x7FFFFFFFll, at + "one workgroup column per query (Qn < 2^31)");
-    CH_REQUIRE(g_index_base >= 0 && g_index_base + G <= 0x100000000ll, at + "keys hold 32-bit global indices (g_index_base + G <= 2^32)");
-    return 0;
+    CH_REQUIRE(P == 4 || P == 8, std::string(who) + ": P (weight bits) must be 4 or 8");
+    return check_rank_sizes(who, Qn, G, W, g_index_base);
 }
 
 }  // namespace
@@ -327,20 +169,8 @@ extern "C" int ch_hamming_rank_collect(const uint64_t *q, const uint64_t *planes
     if (Qn == 0 || G == 0) return 0;
     CH_REQUIRE(g && q_labels && g_labels && count, "hamming_rank_collect: null pointer");
     CH_REQUIRE(offsets == nullptr || (q && planes && keys), "hamming_rank_collect: null pointer (q, planes and keys go with offsets)");
-    // segments so that a small query set still fills the chip; a workgroup walks at least 1,024 labels
-    const int64_t tiles = ceil_div64(Qn, RC_TQ);
-    const int64_t nseg = std::max<int64_t>(ceil_div64(G, (int64_t)1 << RC_ROW_BITS),
-                                           std::min<int64_t>(std::min<int64_t>(65535, ceil_div64(G, 1024)), ceil_div64(4096, tiles)));
-    const int64_t rows = ceil_div64(G, nseg);   // at most 2^27: a queue entry of the write pass holds the row in its segment
-    const dim3 grid((unsigned)tiles, (unsigned)ceil_div64(G, rows));
-    if (offsets == nullptr)
-        hipLaunchKernelGGL(rank_collect_kernel<false>, grid, dim3(RC_BLK), 0, (hipStream_t)stream, q, planes, (int)P, Qn, g, G, (int)W,
-                           q_labels, g_labels, (int)LW, (int)rows, g_index_base, offsets, count, keys);
-    else
-        hipLaunchKernelGGL(rank_collect_kernel<true>, grid, dim3(RC_BLK), 0, (hipStream_t)stream, q, planes, (int)P, Qn, g, G, (int)W,
-                           q_labels, g_labels, (int)LW, (int)rows, g_index_base, offsets, count, keys);
-    CH_LAUNCH_CHECK();
-    return 0;
+    return rank_collect_launch(WeightedRow{q, planes, (int)P}, Qn, g, G, (int)W, q_labels, g_labels, (int)LW, g_index_base, offsets, count,
+                               keys, (hipStream_t)stream);
 }
 
 extern "C" int ch_hamming_rank_count(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
@@ -352,17 +182,10 @@ extern "C" int ch_hamming_rank_count(const uint64_t *q, const uint64_t *planes, 
     if (Qn == 0 || G == 0) return 0;
     CH_REQUIRE(q && planes && g && offsets && keys && bins, "hamming_rank_count: null pointer");
     CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "hamming_rank_count: too many gallery segments (raise seg_rows)");
-    const dim3 grid((unsigned)Qn, (unsigned)ceil_div64(G, seg_rows));
-    const size_t lds = (size_t)list_cap * (sizeof(uint64_t) + sizeof(uint32_t));
     return dispatch_w(W, [&](auto w) {
         return dispatch_p(P, [&](auto p) {
-            constexpr int Wc = decltype(w)::value, Pc = decltype(p)::value;
-            static ch_once_per_device lds_once;   // one per instance of this body, i.e. per kernel
-            if (int e = ch_func_max_lds((const void *)rank_count_kernel<Wc, Pc>, RC_MAX_LIST * 12, lds_once)) return e;
-            hipLaunchKernelGGL((rank_count_kernel<Wc, Pc>), grid, dim3(RC_BLK), lds, (hipStream_t)stream, q, planes, g, G, (int)seg_rows,
-                               g_index_base, offsets, keys, (int)list_cap, bins);
-            CH_LAUNCH_CHECK();
-            return 0;
+            return rank_count_launch(WeightedUniform<decltype(w)::value, decltype(p)::value>{q, planes}, Qn, g, G, g_index_base, (int)seg_rows,
+                                     offsets, keys, (int)list_cap, bins, (hipStream_t)stream);
         });
     });
 }

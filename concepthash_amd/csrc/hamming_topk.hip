@@ -6,7 +6,7 @@
 //               pays w_j for a disagreement on bit j, with w_j its own |code_j| quantised to P = 4 or 8 bits and planes[i, p] = bit p of
 //               every w_ij ("weighted distance")            ch_weight_planes, ch_hamming_topk_weighted
 //
-// ONE scan (topk_scan) serves the three: one LANE per QUERY (its code words, its mask or plane words and its list live in that lane's
+// ONE scan (topk_scan, hamming_shared.h, which the ternary distance of hamming_ternary.hip takes too) serves the three: one LANE per QUERY (its code words, its mask or plane words and its list live in that lane's
 // registers), the GALLERY segment is walked sequentially and is wave-uniform, so gallery words arrive through the scalar data path
 // (s_load_dwordx{4,8,16}) and every XOR uses an SGPR operand.  Nothing of size Qn x G is ever written.  grid = (query tiles, gallery
 // segments) so small galleries still fill the chip.  Per lane a sorted list of the KREG smallest keys, key = dist << SHIFT |
@@ -67,80 +67,6 @@ __device__ __forceinline__ uint32_t weighted_dist(const uint32_t (&q)[2 * W], co
     return horner2(acc);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// the scan: per (query tile, gallery segment) partial lists
-// ---------------------------------------------------------------------------------------------------------------
-// key = dist << SHIFT | row with the (wave-uniform) row number taken from an SGPR: one v_lshl_or_b32 (the compiler's own form is a
-// shift plus v_or3 with the row's low bits as a literal).
-template <int SHIFT>
-__device__ __forceinline__ uint32_t make_key(uint32_t d, uint32_t row_uniform) {
-    uint32_t key;
-    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(key) : "v"(d), "n"(SHIFT), "s"(row_uniform));
-    return key;
-}
-
-// Segment blockIdx.y of the gallery against query qi (a lane past Qn scans too -- its registers hold zeros -- and stores nothing):
-// from the empty list to the store of its k smallest keys.  dist: const uint64_t * (the W words of a gallery row) -> uint32_t.
-template <int W, int KREG, int SHIFT, class Dist>
-__device__ __forceinline__ void topk_scan(const Dist &dist, int64_t qi, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
-                                          int seg_rows, int k, uint32_t *__restrict__ part) {
-    const int seg = blockIdx.y;
-    const int64_t g0 = (int64_t)seg * seg_rows;
-    const int n = (int)min((int64_t)seg_rows, G - g0);
-    uint32_t list[KREG];
-#pragma unroll
-    for (int i = 0; i < KREG; ++i) list[i] = 0xFFFFFFFFu;
-    const uint64_t *gp = g + g0 * W;
-    auto insert = [&](uint32_t key) {
-        if (__builtin_amdgcn_ballot_w64(key < list[KREG - 1]) != 0ull) {
-#pragma unroll
-            for (int i = 0; i < KREG; ++i) {
-                const uint32_t lo = min(list[i], key);
-                key = max(list[i], key);
-                list[i] = lo;
-            }
-        }
-    };
-    // four gallery rows per trip: one wide scalar load (the next block is requested before this one is consumed), four keys, ONE
-    // threshold test on their minimum; the insertion network runs only if some lane beats its list.
-    constexpr int UB = 4;
-    uint64_t bufA[UB * W], bufB[UB * W];
-    auto load_block = [&](uint64_t (&dst)[UB * W], int row) {
-#pragma unroll
-        for (int t = 0; t < UB * W; ++t) dst[t] = gp[(size_t)row * W + t];
-    };
-    auto scan_block = [&](const uint64_t (&blk)[UB * W], int row) {
-        uint32_t key[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) key[u] = make_key<SHIFT>(dist(blk + u * W), (uint32_t)(row + u));
-        const uint32_t kmin = min(min(key[0], key[1]), min(key[2], key[3]));
-        if (__builtin_amdgcn_ballot_w64(kmin < list[KREG - 1]) != 0ull) {
-#pragma unroll
-            for (int u = 0; u < UB; ++u) insert(key[u]);
-        }
-    };
-    // two blocks per iteration with the two SGPR buffers taking turns: no register copies between trips
-    int j = 0;
-    if (n >= UB) load_block(bufA, 0);
-    for (; j + 2 * UB <= n; j += 2 * UB) {
-        load_block(bufB, j + UB);
-        scan_block(bufA, j);
-        if (j + 3 * UB <= n) load_block(bufA, j + 2 * UB);
-        scan_block(bufB, j + UB);
-    }
-    if (j + UB <= n) {  // an odd number of whole blocks: the last one is already in bufA
-        scan_block(bufA, j);
-        j += UB;
-    }
-    for (; j < n; ++j) insert((dist(gp + (size_t)j * W) << SHIFT) | (uint32_t)j);
-    if (qi < Qn) {
-        uint32_t *o = part + ((size_t)seg * Qn + qi) * k;
-#pragma unroll
-        for (int i = 0; i < KREG; ++i)
-            if (i < k) o[i] = list[i];
-    }
-}
-
 // MASKED (ch_hamming_topk_masked): the query's own mask -- row qi of a [Qn, W] array (stride W) -- or one mask shared by all queries
 // (stride 0).  The unmasked instantiations carry an empty argument and no mask code.
 template <bool MASKED>
@@ -192,55 +118,6 @@ __global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64
         }
     }
     topk_scan<W, KREG, WKEY_SHIFT>([&](const uint64_t *gw) { return weighted_dist<W, P>(qw, pl, gw); }, qi, Qn, g, G, seg_rows, k, part);
-}
-
-// The merge of per-segment key lists, key = dist << SHIFT | row-in-segment (0xFFFFFFFF = empty slot).
-// one wave per query: repeatedly extract the smallest composite (dist, global row) above the previous one
-template <int SHIFT>
-__global__ __launch_bounds__(256) void topk_merge_keys_kernel(const uint32_t *__restrict__ part, int nseg, int64_t Qn, int k,
-                                                              int seg_rows, int64_t g_index_base, int64_t *out_idx,
-                                                              int32_t *out_dist) {
-    constexpr uint32_t MASK = (1u << SHIFT) - 1;
-    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (qi >= Qn) return;
-    const int ncand = nseg * k;
-    unsigned long long prev = 0ull;  // composite + 1 of the last output (0 = none yet)
-    for (int r = 0; r < k; ++r) {
-        unsigned long long best = ~0ull;
-        for (int c = lane; c < ncand; c += 64) {
-            const int s = c / k, i = c - s * k;
-            const uint32_t key = part[((size_t)s * Qn + qi) * k + i];
-            if (key == 0xFFFFFFFFu) continue;
-            const unsigned long long comp =
-                ((unsigned long long)(key >> SHIFT) << 40) | ((unsigned long long)s * seg_rows + (key & MASK));
-            if (comp + 1 > prev && comp < best) best = comp;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(best, o, 64);
-            best = other < best ? other : best;
-        }
-        if (lane == 0) {
-            if (best == ~0ull) {
-                out_idx[qi * k + r] = -1;
-                out_dist[qi * k + r] = -1;
-            } else {
-                out_idx[qi * k + r] = g_index_base + (int64_t)(best & ((1ull << 40) - 1));
-                out_dist[qi * k + r] = (int32_t)(best >> 40);
-            }
-        }
-        if (best == ~0ull) {
-            // nothing left: fill the rest
-            for (int rr = r + 1; rr < k; ++rr)
-                if (lane == 0) {
-                    out_idx[qi * k + rr] = -1;
-                    out_dist[qi * k + rr] = -1;
-                }
-            return;
-        }
-        prev = best + 1;
-    }
 }
 
 // merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
@@ -352,27 +229,8 @@ __global__ __launch_bounds__(256) void weight_planes_kernel(const float *__restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host: segment sizing
+// host: segment sizing (topk_seg_rows_for: hamming_shared.h)
 // ---------------------------------------------------------------------------------------------------------------
-// Gallery rows per segment of a scan whose kernel keeps `per_cu` workgroups of four waves resident per CU and whose keys hold
-// `max_rows` rows per segment.
-// (tile, segment) workgroups for ONE full round and never a few more: ceil(2048 / tiles) segments put 2,134 workgroups on the 2,048
-// slots at the NABirds size (97 tiles): a second round for 86 of them doubled the launch (0.38 -> 0.2 ms).  Segments not shorter than
-// 256 rows.
-int topk_seg_rows_for(int64_t Qn, int64_t G, int per_cu, int64_t max_rows) {
-    const int64_t slots = 256 * per_cu;
-    const int64_t tiles = ceil_div64(Qn, 256);
-    int64_t nseg = std::max<int64_t>(1, slots / tiles);
-    // ... and not more segments than needed: every segment starts with empty lists, so its first ~640 rows run the insertion
-    // network for some lane of the wave almost every row, and the merge cost grows with the segment count -- segments of >= 4,096
-    // rows as long as two workgroups per CU remain (NABirds size: 6 segments instead of 21, 0.45 -> 0.37 ms; the 1M-row scan keeps 32)
-    nseg = std::min(nseg, std::max<int64_t>(std::max<int64_t>(1, ceil_div64(512, tiles)), G / 4096));
-    int64_t rows = ceil_div64(G, nseg);
-    if (rows < 256) rows = 256;
-    if (rows > max_rows) rows = max_rows;
-    return (int)rows;
-}
-
 // The scan kernels have no LDS, so residency is set by their registers.  The two rules below are the ones each distance was tuned
 // and measured with; they are NOT the same function of the register count (the table form gives 6, not 7, workgroups for the plain
 // lists of 32 keys), so they stay apart.
@@ -398,20 +256,9 @@ int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host: one launch path.  A "scan" names one of the two kernels, holds its extra arguments and knows its key split, its
-// segmentation, its workspace and the wording of its own refusals; topk_run is the body of the three entry points.
+// host: the "scans" of the one launch path (TopkCall, topk_run: hamming_shared.h).  A scan names one of the two kernels, holds its
+// extra arguments and knows its key split, its segmentation, its workspace and the wording of its own refusals.
 // ---------------------------------------------------------------------------------------------------------------
-struct TopkCall {   // what every partial launch takes
-    const uint64_t *q;
-    int64_t Qn;
-    const uint64_t *g;
-    int64_t G;
-    int seg_rows, k;
-    uint32_t *part;
-    dim3 grid;
-    hipStream_t s;
-};
-
 template <bool MASKED>
 struct HammingScan {
     static constexpr int SHIFT = KEY_SHIFT;
@@ -451,58 +298,6 @@ struct WeightedScan {
                            c.k, c.part);
     }
 };
-
-// lists of KREG = 10 / 16 / 32 / 64 / 128 keys.  k <= 10 (PRs = [1, 5, 10]): exactly k entries, so the insertion threshold is the
-// k-th key
-template <int W, class Scan>
-void topk_launch_k(const Scan &scan, const TopkCall &c) {
-    if (c.k <= 10) return scan.template launch<W, 10>(c);
-    if (c.k <= 16) return scan.template launch<W, 16>(c);
-    if (c.k <= 32) return scan.template launch<W, 32>(c);
-    if (c.k <= 64) return scan.template launch<W, 64>(c);
-    return scan.template launch<W, 128>(c);
-}
-
-template <class Scan>
-void topk_launch(const Scan &scan, int W, const TopkCall &c) {
-    switch (W) {
-        case 1: return topk_launch_k<1>(scan, c);
-        case 2: return topk_launch_k<2>(scan, c);
-        case 3: return topk_launch_k<3>(scan, c);
-        default: return topk_launch_k<4>(scan, c);
-    }
-}
-
-// The body of ch_hamming_topk / _masked / _weighted: the checks in the order the entries have always made them (`name` opens the
-// messages), partial lists, merge.
-template <class Scan>
-int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W,
-             int k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, hipStream_t s) {
-    const std::string at = std::string(name) + ": ";
-    CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
-    CH_REQUIRE(k >= 1 && k <= 128, at + "1 <= k <= 128");
-    CH_REQUIRE(Qn >= 0 && G >= 0, at + "negative sizes");
-    if (int e = scan.check(W)) return e;
-    if (Qn == 0) return 0;
-    CH_REQUIRE(q && scan.operands() && out_idx && out_dist, at + "null pointer");
-    if (G == 0) {
-        CH_CHECK_HIP(hipMemsetAsync(out_idx, 0xFF, sizeof(int64_t) * Qn * k, s));
-        CH_CHECK_HIP(hipMemsetAsync(out_dist, 0xFF, sizeof(int32_t) * Qn * k, s));
-        return 0;
-    }
-    CH_REQUIRE(g != nullptr, at + "null gallery");
-    const int seg_rows = scan.seg_rows(Qn, G, W, k);
-    const int64_t nseg = ceil_div64(G, seg_rows);
-    CH_REQUIRE(nseg <= 65535, Scan::too_many_segments);
-    CH_REQUIRE(workspace && workspace_bytes >= scan.workspace(Qn, G, W, k), at + "workspace too small");
-    uint32_t *part = (uint32_t *)workspace;
-    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s});
-    CH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(topk_merge_keys_kernel<Scan::SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, (int)nseg, Qn, k,
-                       seg_rows, g_index_base, out_idx, out_dist);
-    CH_LAUNCH_CHECK();
-    return 0;
-}
 
 }  // namespace
 

@@ -3,7 +3,7 @@ gallery-sharded multi-GPU variants (one process per GPU, RCCL via ``torch.distri
 
 Replaces the reference's un-vendored ``utils.hashing`` arithmetic (call sites experiments/test_hashing.py:106-119,
 153-162).  PyTorch supplies device buffers, streams and collectives; all per-pair arithmetic runs in
-``csrc/hamming_topk.hip`` (top-k search), ``csrc/hamming.hip`` (distance matrix, mAP) and ``csrc/hamming_rankcount.hip`` (mAP under the weighted distance).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
+``csrc/hamming_topk.hip`` (top-k search), ``csrc/hamming.hip`` (distance matrix, mAP) and ``csrc/hamming_rankcount.hip`` (mAP under the weighted distance) and ``csrc/hamming_ternary.hip`` (ternary codes: two bit planes per row, [rows, 2, W]).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
 """
 from __future__ import annotations
 
@@ -1064,6 +1064,156 @@ def evaluate_weighted(codes: torch.Tensor, g: torch.Tensor, q_labels: torch.Tens
     keys = sort_slices(offsets, keys)
     cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
     bins = rank_count(q, planes, g, offsets, keys, cap, seg_rows)
+    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
+    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
+    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
+                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ternary codes (csrc/hamming_ternary.hip; DESIGN.md section 2.0, "ternary codes")
+# ---------------------------------------------------------------------------------------------------------------
+def check_margin(margin, what: str = "margin") -> float:
+    """A ternary margin: a finite number >= 0 (ValueError otherwise; None included -- there is no default, the scale of the codes
+    belongs to the run)."""
+    if margin is None:
+        raise ValueError(f"{what} is required: ternary codes have no default margin (the scale of the codes belongs to the run)")
+    m = float(margin)
+    if not (m >= 0.0) or m == float("inf"):
+        raise ValueError(f"{what} must be finite and >= 0, got {margin}")
+    return m
+
+
+def pack_ternary(codes: torch.Tensor, margin: float, stream=None) -> torch.Tensor:
+    """[rows, nbit] fp32 -> [rows, 2, W] int64, the two adjacent bit planes of the ternary code t_j = sign(x_j) where |x_j| > margin,
+    0 otherwise (NaN gives 0): plane 0 (sign) = pack_sign(codes) & mask, plane 1 (mask) = confidence_mask(codes, margin); bits past
+    nbit are zero in both.  One launch.  The margin is compared as fp32."""
+    lib = _lib.load()
+    if codes.dim() != 2:
+        raise ValueError("codes must be 2-D")
+    margin = check_margin(margin)
+    codes = codes.to(torch.float32).contiguous()
+    rows, nbit = codes.shape
+    out = torch.empty(rows, 2, (nbit + 63) // 64, dtype=torch.int64, device=codes.device)
+    with _dev_guard(codes):
+        _lib.check(lib.ch_pack_ternary(_lib.ptr(codes), rows, nbit, margin, _lib.ptr(out), _lib.stream_ptr(stream)), "ch_pack_ternary")
+    return out
+
+
+def _check_ternary(q3: torch.Tensor, g3: torch.Tensor, nbit: int):
+    if q3.dtype != torch.int64 or g3.dtype != torch.int64 or q3.dim() != 3 or g3.dim() != 3 or q3.shape[1] != 2 or g3.shape[1] != 2:
+        raise TypeError("ternary codes must be int64 tensors [rows, 2, W] (pack_ternary)")
+    if q3.shape[2] != g3.shape[2]:
+        raise ValueError(f"query has {q3.shape[2]} words per plane, gallery {g3.shape[2]}")
+    if q3.device != g3.device:
+        raise ValueError("query and gallery codes must be on the same device")
+    W = q3.shape[2]
+    if not 1 <= int(nbit) <= 64 * W:
+        raise ValueError(f"nbit must be in [1, {64 * W}] for planes of {W} words, got {nbit}")
+    return q3.contiguous(), g3.contiguous()
+
+
+def ternary_dist(q3: torch.Tensor, g3: torch.Tensor, nbit: int, stream=None) -> torch.Tensor:
+    """Full [Qn, G] int32 matrix of K = nbit - sum_j t_q,j t_g,j (small problems), in half bits: K / 2 is the distance in bits."""
+    lib = _lib.load()
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    out = torch.empty(q3.shape[0], g3.shape[0], dtype=torch.int32, device=q3.device)
+    with _dev_guard(q3):
+        _lib.check(lib.ch_ternary_dist(_lib.ptr(q3), q3.shape[0], _lib.ptr(g3), g3.shape[0], q3.shape[2], int(nbit), _lib.ptr(out),
+                                       _lib.stream_ptr(stream)), "ch_ternary_dist")
+    return out
+
+
+def ternary_topk(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k by ascending (K, gallery index) on `pack_ternary` codes: (idx int64 [Qn,k], dist int32 [Qn,k] = K); -1 where k > G.  Lists of
+    gallery shards merge with `topk_merge`."""
+    lib = _lib.load()
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    Qn, _, W = q3.shape
+    G = g3.shape[0]
+    k = int(k)
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=q3.device)
+    dist = torch.empty(Qn, k, dtype=torch.int32, device=q3.device)
+    wsb = int(lib.ch_ternary_topk_workspace(Qn, G, W, k))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q3.device)
+    with _dev_guard(q3):
+        _lib.check(lib.ch_ternary_topk(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), k, int(g_index_base), _lib.ptr(idx), _lib.ptr(dist),
+                                       _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), "ch_ternary_topk")
+    return idx, dist
+
+
+def ternary_rank_collect(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,
+                         g_index_base: int = 0, stream=None):
+    """`rank_collect` under K: the keys K << 32 | global index of every query's relevant rows -> (offsets, keys, longest slice)."""
+    lib = _lib.load()
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    Qn, _, W = q3.shape
+    G = g3.shape[0]
+    count = torch.zeros(Qn, dtype=torch.int32, device=q3.device)
+    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q3.device)
+    if Qn == 0 or G == 0:
+        return offsets, torch.empty(0, dtype=torch.int64, device=q3.device), 0
+
+    def call(off, keys):
+        _lib.check(lib.ch_ternary_rank_collect(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), _lib.ptr(q_lab), _lib.ptr(g_lab), LW,
+                                               int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
+                                               _lib.stream_ptr(stream)), "ch_ternary_rank_collect")
+
+    with _dev_guard(q3):
+        call(None, None)
+        offsets[1:] = count.cumsum(0, dtype=torch.int64)
+        total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
+        keys = torch.empty(total, dtype=torch.int64, device=q3.device)
+        if total:
+            count.zero_()
+            call(offsets, keys)
+    return offsets, keys, int(longest)
+
+
+def ternary_rank_count(q3: torch.Tensor, g3: torch.Tensor, nbit: int, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int,
+                       seg_rows: Optional[int] = None, g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """`rank_count` under K -> bins int32 [total]; keys: `sort_slices(ternary_rank_collect(...))`."""
+    lib = _lib.load()
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    Qn, _, W = q3.shape
+    G = g3.shape[0]
+    if bins is None:
+        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q3.device)
+    if Qn == 0 or G == 0 or keys.numel() == 0:
+        return bins
+    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
+    with _dev_guard(q3):
+        _lib.check(lib.ch_ternary_rank_count(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), int(g_index_base), seg, _lib.ptr(offsets),
+                                             _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)),
+                   "ch_ternary_rank_count")
+    return bins
+
+
+def evaluate_ternary(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
+                     ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, skip_queries_without_relevant: bool = False,
+                     seg_rows: Optional[int] = None, list_cap: Optional[int] = None) -> dict:
+    """`evaluate` under the ternary ranking that `ternary_topk` serves: ascending (K, gallery index) on
+    `pack_ternary` codes of both sides.  Returns the keys of `evaluate_weighted` -- mAP, precisions, recalls, hits, total, S, nrel, ap,
+    lists under a list R -- exact for any R and k, by the same rank counting: collect and sort the keys of each query's relevant rows,
+    one Qn x G scan for the bins, one lane per query for the AP terms.  seg_rows / list_cap (tests) change no result."""
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    Qn, _, W = q3.shape
+    G = g3.shape[0]
+    dev = g3.device
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    many = isinstance(R, (list, tuple))
+    Rs = [int(r) for r in R] if many else [int(R)]
+    if Qn == 0 or G == 0:
+        return empty_result(Qn, W, dev, Rs, ks, many, False, None)
+    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
+    limits, idx_of = normalize_limits(Rs + ks)
+    offsets, keys, longest = ternary_rank_collect(q3, g3, nbit, q_lab, g_lab, LW)
+    keys = sort_slices(offsets, keys)
+    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
+    bins = ternary_rank_count(q3, g3, nbit, offsets, keys, cap, seg_rows)
     S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
     sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
     pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])

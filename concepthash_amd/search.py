@@ -15,7 +15,7 @@ import torch
 from . import retrieval as rt
 
 FORMAT = 1
-RANKS = ("hamming", "asymmetric")
+RANKS = ("hamming", "asymmetric", "ternary")
 TOPK_MAX = 128    # the deepest list of the top-k scan (csrc/hamming_topk.hip); deeper ones: retrieval.hamming_ranked
 
 
@@ -36,11 +36,15 @@ class GalleryIndex:
     """codes [G, W] int64 (packed, `retrieval.pack_sign`); nbit, ncontext; labels: None, [G] int64 class ids or [G, C] uint8 indicator
     rows; paths: None (synthetic datasets) or G paths relative to data_root; mean: None or the database mean [nbit] fp32 that was
     subtracted before packing (`zero_mean_eval`) and is subtracted from every query; transform: {"resize", "crop", "norm"} of the
-    evaluation chain the database went through; fingerprint: `checkpoint_fingerprint` of the checkpoint that encoded it."""
+    evaluation chain the database went through; fingerprint: `checkpoint_fingerprint` of the checkpoint that encoded it.
+    mask: None, or the plane [G, W] int64 of the bits every database row is sure of, `retrieval.confidence_mask(codes, margin)` of the
+    real codes that were packed, with `margin` the number it was built with -- what rank="ternary" needs; an index
+    without it serves every other ranking as before."""
 
     def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
                  paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
-                 transform: Optional[dict] = None, fingerprint: Optional[dict] = None):
+                 transform: Optional[dict] = None, fingerprint: Optional[dict] = None, mask: Optional[torch.Tensor] = None,
+                 margin: Optional[float] = None):
         nbit, ncontext = int(nbit), int(ncontext)
         if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
             raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
@@ -53,7 +57,15 @@ class GalleryIndex:
             raise ValueError(f"{len(paths)} paths for {G} codes")
         if mean is not None and tuple(mean.shape) != (nbit,):
             raise ValueError(f"mean must be [{nbit}], got {tuple(mean.shape)}")
+        if mask is not None:
+            if mask.dtype != torch.int64 or tuple(mask.shape) != tuple(codes.shape) or mask.device != codes.device:
+                raise ValueError(f"mask must be an int64 plane {tuple(codes.shape)} on the codes' device, got {mask.dtype} {tuple(mask.shape)} "
+                                 f"on {mask.device}")
+            margin = rt.check_margin(margin, "the mask plane's margin")
+        elif margin is not None:
+            raise ValueError("a margin without a mask plane")
         self.codes, self.nbit, self.ncontext = codes.contiguous(), nbit, ncontext
+        self.mask, self.margin = (mask.contiguous() if mask is not None else None), margin
         self.labels = labels
         self.paths = [str(p) for p in paths] if paths is not None else None
         self.data_root = str(data_root) if data_root is not None else None
@@ -71,7 +83,7 @@ class GalleryIndex:
     def to(self, device) -> "GalleryIndex":
         mv = lambda t: t.to(device) if t is not None else None
         return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
-                            self.transform, self.fingerprint)
+                            self.transform, self.fingerprint, mv(self.mask), self.margin)
 
     # ---- file --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -79,9 +91,12 @@ class GalleryIndex:
         cpu = lambda t: t.detach().cpu() if t is not None else None
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         tmp = f"{path}.tmp{os.getpid()}"
-        torch.save({"format": FORMAT, "codes": cpu(self.codes), "nbit": self.nbit, "ncontext": self.ncontext, "labels": cpu(self.labels),
-                    "paths": self.paths, "data_root": self.data_root, "mean": cpu(self.mean), "transform": self.transform,
-                    "fingerprint": self.fingerprint}, tmp)
+        d = {"format": FORMAT, "codes": cpu(self.codes), "nbit": self.nbit, "ncontext": self.ncontext, "labels": cpu(self.labels),
+             "paths": self.paths, "data_root": self.data_root, "mean": cpu(self.mean), "transform": self.transform,
+             "fingerprint": self.fingerprint}
+        if self.mask is not None:           # an index without the plane is the file it has always been
+            d.update(mask=cpu(self.mask), margin=self.margin)
+        torch.save(d, tmp)
         os.replace(tmp, path)
 
     def check(self, fingerprint: Optional[dict] = None, nbit: Optional[int] = None, source: str = "the index") -> None:
@@ -103,7 +118,7 @@ class GalleryIndex:
         if not isinstance(d, dict) or d.get("format") != FORMAT:
             raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
         index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
-                    d["fingerprint"])
+                    d["fingerprint"], d.get("mask"), d.get("margin"))
         index.check(fingerprint, nbit, source=path)
         return index
 
@@ -139,7 +154,12 @@ class GalleryIndex:
         k > 128: the list comes from `retrieval.hamming_ranked` (any depth); built for rank="hamming" without a margin (the whole code
         or `concepts`); the other combinations raise ValueError.
         radius: hash lookup -- only rows whose ranking distance (the masked one under `concepts` / `margin`) is <= radius stay; idx and
-        dist are -1 behind them, as past the end of the database.  Not defined for rank="asymmetric" (ValueError)."""
+        dist are -1 behind them, as past the end of the database.  Not defined for rank="asymmetric" (ValueError).
+        rank="ternary": both sides are ternary codes -- the database rows under the index's own margin (its mask plane; an index without
+        one raises ValueError), the queries under `margin` -- and dist is K = nbit - t_q . t_g in HALF bits (a bit either side is unsure of
+        costs 1, a disagreement both are sure of 2); dist_bits = K / 2.  `concepts` clears the query's mask outside the chosen sub-codes and
+        nbit becomes the number of bits in play, so K stays the distance on those bits; radius keeps K <= 2 radius; bits counts the
+        query's sure bits in play and dist_max = bits in play + bits; k <= 128.  The dict also holds rank and index_margin."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
         if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
@@ -152,6 +172,11 @@ class GalleryIndex:
             radius = int(radius)
             if not 0 <= radius <= 64 * self.codes.shape[1]:
                 raise ValueError(f"radius must be in [0, {64 * self.codes.shape[1]}], got {radius}")
+        if rank == "ternary" and self.mask is None:
+            raise ValueError("rank='ternary' needs the index's mask plane, which this index was built without: build it with index_margin=<m> "
+                             "(exp=search rank=ternary index_margin=<m> rebuild_index=true)")
+        if rank == "ternary":
+            margin = rt.check_margin(margin, "rank='ternary': the query margin")
         if deep and rank != "hamming":
             raise ValueError(f"k = {k} > {TOPK_MAX} with rank='{rank}' is not built: lists deeper than {TOPK_MAX} rank by the Hamming distance")
         if deep and margin > 0:
@@ -175,7 +200,14 @@ class GalleryIndex:
                 keep[int(c) * sb:(int(c) + 1) * sb] = True
             mask = shared.to(dev)
         keep = keep[None, :].expand(Qn, self.nbit)
-        if margin > 0:
+        if rank == "ternary":
+            q3 = rt.pack_ternary(codes, margin)
+            keep = keep & (codes.abs() > margin)
+            nbit_play = self.nbit
+            if mask is not None:            # the chosen concepts: the query is unsure of every other bit, and only theirs are in play
+                q3 = q3 & mask[None, None, :]
+                nbit_play = len(concepts) * (self.nbit // self.ncontext)
+        elif margin > 0:
             conf = rt.confidence_mask(codes, float(margin))
             mask = conf if mask is None else conf & mask[None, :]
             keep = keep & (codes.abs() > float(margin))
@@ -184,13 +216,24 @@ class GalleryIndex:
             planes, wsum = rt.weight_planes(codes, int(weight_bits), mask)
             idx, dist = rt.hamming_topk_weighted(q, planes, self.codes, k)
             extra = dict(rank=rank, weight_bits=int(weight_bits), dist_max=wsum)
+        elif rank == "ternary":
+            g3 = torch.stack([self.codes & self.mask, self.mask], dim=1)
+            if nbit_play == 0:
+                raise ValueError("rank='ternary' with an empty set of concepts leaves no bit in play")
+            idx, dist = rt.ternary_topk(q3, g3, nbit_play, k)
+            if radius is not None:
+                far = dist > 2 * radius
+                idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
+            bits_sure = keep.sum(1)
+            extra = dict(rank=rank, index_margin=self.margin, dist_bits=torch.where(dist < 0, -torch.ones_like(dist, dtype=torch.float64), dist.double() / 2),
+                         dist_max=(bits_sure + nbit_play).to(torch.int32))
         elif deep:
             idx, dist = rt.hamming_ranked(q, self.codes, k, radius=radius, mask=mask)
         elif mask is None:
             idx, dist = rt.hamming_topk(q, self.codes, k)
         else:
             idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
-        if radius is not None and not deep:
+        if radius is not None and not deep and rank != "ternary":
             far = dist > radius
             idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),

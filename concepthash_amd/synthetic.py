@@ -111,3 +111,14 @@ def synthetic_codes(rows: int, nbit: int, seed: int = 1234, nclass: int = 0, fli
         bits = np.concatenate([bits, np.zeros((rows, pad), np.uint8)], axis=1)
     out = np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8").reshape(rows, W)
     return out, labels
+
+
+def synthetic_real_codes(rows: int, nbit: int, seed: int = 1234, nclass: int = 200, noise: float = 0.78, device="cpu"):
+    """Real-valued clustered codes, what a trained head emits before the sign: the class centres of `synthetic_codes` (same
+    (nclass, nbit) -> same centres) as +-1, plus N(0, noise^2) -- about 10 % of the signs differ from the centre's at 0.78.
+    Returns (codes fp32 [rows, nbit] on `device`, labels int64 [rows] there)."""
+    centres = np.random.default_rng(1000003 * nclass + nbit).integers(0, 2, size=(nclass, nbit), dtype=np.uint8)
+    g = torch.Generator(device=device).manual_seed(seed)
+    labels = torch.randint(0, nclass, (rows,), device=device, generator=g)
+    c = torch.from_numpy(centres.astype(np.float32) * 2.0 - 1.0).to(device)
+    return c[labels] + noise * torch.randn(rows, nbit, device=device, generator=g), labels

@@ -113,6 +113,9 @@ class SearchExperiment:
         with open(os.path.join(self.search_logdir, "search_config.yaml"), "w") as f:
             yaml.safe_dump(to_container(config), f)
         self.nbit, self.ncontext = int(config.model.nbit), int(config.model.ncontext)
+        # rank=ternary ranks against the database's own ternary codes: the index then carries the mask plane of index_margin
+        self.ternary = str(config.get("rank", "hamming") or "hamming") == "ternary"
+        self.index_margin = rt.check_margin(config.get("index_margin", 0.0) or 0.0, "index_margin") if self.ternary else None
 
         # the index first: whether the database split has to be encoded decides what is loaded
         self.fingerprint = self._phase("fingerprint", checkpoint_fingerprint, self.checkpoint)
@@ -157,6 +160,10 @@ class SearchExperiment:
             raise StaleIndexError(f"{self.index_path} was built with ncontext = {index.ncontext}, transform {index.transform}, "
                                   f"zero_mean_eval = {index.mean is not None}; this run asks for ncontext = {self.ncontext}, "
                                   f"{self._transform_settings()}, zero_mean_eval = {want_mean}: rebuild the index (rebuild_index=true)")
+        if self.ternary and (index.mask is None or index.margin != self.index_margin):
+            have = "no mask plane" if index.mask is None else f"the mask plane of index_margin = {index.margin}"
+            raise StaleIndexError(f"{self.index_path} holds {have}; rank=ternary index_margin={self.index_margin} needs its own: rebuild the "
+                                  f"index (rebuild_index=true)")
 
     def _build_index(self) -> GalleryIndex:
         _, out = self._phase("encode_db", self.trainer.inference_one_epoch, "db", True)
@@ -168,10 +175,12 @@ class SearchExperiment:
             mean = mean[0]
         ds = self.trainer.dataset["db"]
         items = getattr(ds, "items", None)             # list-file datasets name their files; the synthetic ones have none
-        index = GalleryIndex(rt.pack_sign(codes.to(self.trainer.device)), self.nbit, self.ncontext, labels=_label_ids(out["labels"]),
+        codes = codes.to(self.trainer.device)
+        mask = rt.confidence_mask(codes, self.index_margin) if self.ternary else None
+        index = GalleryIndex(rt.pack_sign(codes), self.nbit, self.ncontext, labels=_label_ids(out["labels"]),
                              paths=[p for p, _ in items] if items is not None else None,
                              data_root=getattr(ds, "root", None) if items is not None else None, mean=mean,
-                             transform=self._transform_settings(), fingerprint=self.fingerprint)
+                             transform=self._transform_settings(), fingerprint=self.fingerprint, mask=mask, margin=self.index_margin)
         self._phase("index_save", index.save, self.index_path)
         return index
 
@@ -285,6 +294,7 @@ class SearchExperiment:
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
         bits = res["bits"].tolist()
         dist_max = res["dist_max"].tolist() if "dist_max" in res else bits      # the distance of a row that disagrees on every unmasked bit
+        dist_bits = res["dist_bits"].tolist() if "dist_bits" in res else None   # rank=ternary: the distance is in half bits
         hit_labels = res["labels"].cpu() if res["labels"] is not None else None
         queries = []
         for i in range(len(idx)):
@@ -300,10 +310,12 @@ class SearchExperiment:
                 rel_path = res["paths"][i][r] if res["paths"] is not None else None
                 hits.append({"rank": r + 1, "index": idx[i][r], "path": index.resolve(rel_path), "distance": dist[i][r],
                              "label": hl.tolist() if hl is not None else None, "relevant": relevant, "concept_distances": cdist[i][r]})
+                if dist_bits is not None:
+                    hits[-1]["distance_bits"] = dist_bits[i][r]
             queries.append({"query": names[i] if names is not None else i, "label": ql.tolist() if ql is not None else None,
                             "unmasked_bits": bits[i], "distance_max": dist_max[i], "hits": hits})
         self.timing["results"] = round(time.perf_counter() - t0, 3)
-        out = {"k": k, "radius": radius, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "nbit": index.nbit, "ncontext": index.ncontext,
+        out = {"k": k, "radius": radius, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "index_margin": index.margin, "nbit": index.nbit, "ncontext": index.ncontext,
                "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
                "checkpoint": self.fingerprint, "query_kind": "image" if self.text is None else "text",
                "query": self.query if self.text is None else list(self.text["prompts"]),
@@ -316,7 +328,8 @@ class SearchExperiment:
             np.save(os.path.join(self.search_logdir, "concept_attention.npy"), attn.cpu().numpy().astype(np.float32))
         what = "the whole code" if concepts is None else f"concepts {concepts}"
         print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}, " +
-              ("Hamming distance" if rank == "hamming" else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
+              ("Hamming distance" if rank == "hamming" else f"ternary distance in half bits (database margin {index.margin})" if rank == "ternary"
+               else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
               (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + (f", within {radius} bits" if radius is not None else "") + f"; index {self.index_note}")
         for e in queries[:PRINT_QUERIES]:
             print(f"query {e['query']}" + (f" (label {e['label']})" if e["label"] is not None and not isinstance(e["label"], list) else "") +

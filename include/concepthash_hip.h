@@ -528,6 +528,39 @@ int ch_hamming_rank_count(const uint64_t *q, const uint64_t *planes, int32_t P, 
 int ch_hamming_rank_ap(int64_t Qn, const int64_t *offsets, const uint32_t *bins, const int64_t *rank_limits, int32_t nlimits,
                        int32_t remove_first, unsigned long long *out_S, uint32_t *out_nrel, int32_t *out_total, void *stream);
 
+/* Ternary codes (the reference's `ternary_threshold`, configs/val.yaml): t_j = sign(x_j) where |x_j| > margin,
+ * 0 otherwise (NaN gives 0), on BOTH sides.  Packed as two adjacent bit planes per row, [rows, 2, W] uint64, W = ceil(nbit / 64):
+ * plane 0 (sign): bit j = t_j > 0; plane 1 (mask): bit j = t_j != 0; bits past nbit are zero in both.  The distance is
+ *     K(q, g) = nbit - sum_j t_q,j t_g,j = nbit - popcount(mq & mg) + 2 popcount((sq ^ sg) & mq & mg),   an int32 in [0, 2 nbit]:
+ * twice the matmul form 0.5 (nbit - q g^T) on ternary codes -- "half bits": a disagreement both sides are sure of costs
+ * 2, a bit either side is unsure of 1, an agreement 0.  Every ranking below is ascending (K, gallery index); all integers, so no
+ * result depends on how a gallery is segmented or sharded.  1 <= W <= 4 and 1 <= nbit <= 64 W everywhere, otherwise status 2.
+ *
+ * ch_pack_ternary: codes [rows,nbit] fp32 -> out_planes [rows,2,W], ONE launch for both planes.  nbit outside [1, 256], or a margin
+ * that is negative or not finite: status 2. */
+int ch_pack_ternary(const float *codes, int64_t rows, int32_t nbit, float margin, uint64_t *out_planes, void *stream);
+
+/* Full matrix of K (small problems): q [Qn,2,W], g [G,2,W] -> out [Qn,G] int32. */
+int ch_ternary_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t *out, void *stream);
+
+/* Top-k by ascending (K, gallery index) over a two-plane gallery; out_dist is K.  The -1 fill, g_index_base, 1 <= k <= 128 and
+ * 1 <= W <= 4 as in ch_hamming_topk; lists of several shards merge with ch_topk_merge.  workspace: ch_ternary_topk_workspace() bytes.
+ * Keys are K << 22 | row in segment (K takes 10 bits), so a segment holds at most 2^22 rows; a gallery of more than 65,535 segments
+ * is status 2. */
+size_t ch_ternary_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
+int ch_ternary_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t k,
+                    int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Evaluation under K by rank counting: ch_hamming_rank_collect and ch_hamming_rank_count with key(g) = K(q, g) << 32 | global index
+ * of g over two-plane codes -- the same CSR buffers (offsets, count, keys, bins), the same offsets == NULL counting call, the same
+ * list_cap and seg_rows guarantees, the same labels.  Their bins go to ch_hamming_rank_ap as they are. */
+int ch_ternary_rank_collect(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, const void *q_labels,
+                            const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count,
+                            uint64_t *keys, void *stream);
+int ch_ternary_rank_count(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int64_t g_index_base,
+                          int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins,
+                          void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

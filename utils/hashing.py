@@ -29,7 +29,8 @@ def _check(dist_metric, threshold, landmark_gt):
     if dist_metric != "hamming":
         raise NotImplementedError(f"dist_metric='{dist_metric}': only 'hamming' is built (the shipped configs use it)")
     if threshold not in (0, 0.0):
-        raise NotImplementedError("ternary_threshold != 0 (ternary codes) is not built; every reference call site uses 0")
+        raise NotImplementedError("threshold != 0 is not built: what the reference's un-vendored package does with it cannot be read; "
+                                  "ternary codes are ranked with rank=\"ternary\", margin=<m> (every reference call site passes 0)")
     if landmark_gt is not None:
         raise NotImplementedError("landmark ground-truth evaluation is outside the ConceptHash path")
 
@@ -92,7 +93,7 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
                        skip_queries_without_relevant=skip, tie_bracket=tie, **look)
 
 
-RANKS = ("hamming", "asymmetric")
+RANKS = ("hamming", "asymmetric", "ternary")
 
 
 def _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits):
@@ -107,9 +108,23 @@ def _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, R, ks, re
                                 bits=weight_bits, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
 
 
+def _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, margin):
+    """rank="ternary": both code sets become ternary codes under one margin (`retrieval.pack_ternary`), ranked by K."""
+    from concepthash_amd.distributed import RowShard
+    if any(isinstance(x, RowShard) for x in (db_codes, db_labels, test_codes, test_labels)) or _sharded():
+        raise NotImplementedError("rank='ternary' is evaluated by one process on a whole database; the sharded form is not built "
+                                  "(its bins are additive over gallery shards)")
+    dev = _device()
+    db = torch.as_tensor(db_codes).to(dev, torch.float32)
+    g3 = rt.pack_ternary(db, margin)
+    q3 = rt.pack_ternary(torch.as_tensor(test_codes).to(dev, torch.float32), margin)
+    return rt.evaluate_ternary(q3, g3, db.shape[1], _labels(test_labels, dev), _labels(db_labels, dev), R=R, ks=ks,
+                               remove_first=remove_first, skip_queries_without_relevant=skip)
+
+
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8):
+                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8, margin=None):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
@@ -127,7 +142,14 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     rank (not a reference argument): "hamming" (default) or "asymmetric" -- the ranking `exp=search rank=asymmetric` serves (DESIGN.md
     section 2.0): `test_codes` stay real-valued and every query pays its own |code|, quantised to `weight_bits` (4 or 8) bits, for a
     disagreeing bit of the sign-packed database.  Same triple, same limits; no tie bracket and no radii under it (ValueError), and
-    single-process evaluation only (NotImplementedError for RowShards or a process group of more than one rank)."""
+    single-process evaluation only (NotImplementedError for RowShards or a process group of more than one rank).
+    rank="ternary", margin=m (not reference arguments): both code sets become ternary codes -- sign(x) where |x| > m, 0 otherwise -- and
+    the ranking is ascending K = nbit - t_q . t_g, twice the matmul distance 0.5 (nbit - q g^T) on those codes: a
+    bit either side is unsure of costs half a bit.  `margin` is required, finite and >= 0 (ValueError): there is no default, the scale of
+    the codes belongs to the run.  No tie bracket and no radii (ValueError); single-process only (NotImplementedError), as "asymmetric".
+    `threshold` is NOT this margin: the reference hands `ternary_threshold` to its un-vendored package, whose rule for it cannot be
+    read, so threshold != 0 keeps raising NotImplementedError (the situation that made skip_queries_without_relevant a switch) and the
+    ternary ranking is asked for by name."""
     global last_tie_bracket, last_hash_lookup
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
@@ -136,6 +158,10 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
             raise ValueError("rank='asymmetric' has no tie bracket and no radius lookup: both are defined on Hamming distances")
         if int(weight_bits) not in rt.WEIGHT_BITS:
             raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits}")
+    if rank == "ternary":
+        if tie_bracket or radii is not None:
+            raise ValueError("rank='ternary' has no tie bracket and no radius lookup: both are defined on Hamming distances")
+        margin = rt.check_margin(margin, "rank='ternary': margin")
     last_tie_bracket = None
     last_hash_lookup = None
     _check(dist_metric, threshold, landmark_gt)
@@ -147,6 +173,10 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     if rank == "asymmetric":
         res = _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
                                    bool(skip_queries_without_relevant), int(weight_bits))
+        return res["mAP"], res["recalls"], res["precisions"]
+    if rank == "ternary":
+        res = _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
+                                bool(skip_queries_without_relevant), margin)
         return res["mAP"], res["recalls"], res["precisions"]
     res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
                     bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
