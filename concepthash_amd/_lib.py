@@ -192,6 +192,17 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_ternary_rank_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                                       c_int32, c_void_p, c_void_p]),
+    "ch_dense_prepared_bytes": (c_size_t, [c_int64, c_int32]),
+    "ch_dense_prepare": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_dense_dist": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "ch_dense_topk_seg_rows": (c_int32, [c_int64, c_int64]),
+    "ch_dense_topk_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_dense_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                              c_void_p, c_size_t, c_void_p]),
+    "ch_dense_rank_collect": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ch_dense_rank_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                    c_int32, c_void_p, c_void_p]),
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

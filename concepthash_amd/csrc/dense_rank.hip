@@ -1,0 +1,460 @@
+// Real-valued codes (gfx950): the rankings by cosine, squared Euclidean and dot distance of the codes before sign() -- prepare,
+// distance matrix, exact top-k and the rank-counting evaluation ("real-valued codes").  Built with
+// -ffp-contract=off: every multiply-add below is an fmaf that is written down.
+//
+// The scan operand ("prepared" codes, ch_dense_prepare): rows in blocks of 64, dimension-major inside a block,
+//     prepared[(r / 64) * n * 64 + j * 64 + r % 64] = x^_r,j        (x^ = x, or x / |x| for cosine; rows past the end of the last block: zeros)
+// so the 64 lanes of a wave that own 64 consecutive rows load dimension j with one contiguous 256-byte access, and dimension j of 16
+// consecutive queries is one contiguous 64-byte scalar load.  Queries and gallery are prepared alike.
+//
+// The distance is ONE function, dense_tile<M, TQ>: TQ queries (wave-uniform: their values reach the fmaf as its scalar operand)
+// against one row per lane; for every (query, row) pair the chain
+//     acc = 0.0f;  for j = 0 .. n - 1 in this order:   dot, cosine: acc = fmaf(q_j, g_j, acc)     euclidean: t = q_j - g_j; acc = fmaf(t, t, acc)
+//     D = -acc + 0.0f (dot)      1.0f - acc + 0.0f (cosine)      acc + 0.0f (euclidean)              (+ 0.0f: -0 becomes +0)
+// The distance matrix (TQ = 1, one pair per lane), the top-k scan (TQ = 16), the collect pass (TQ = 1, relevant pairs only) and the
+// count pass (TQ = 1) all call it, so D(q, g) has the same bits in every pass whatever the tile or the segmentation -- a rank-counting
+// evaluation ranks a relevant row against its own collected key, and one ulp between two passes would move a rank by one.  No MFMA.
+//
+// Order: ord(D) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000), b = bits(D), ascending as unsigned as D ascends; every ranking is ascending
+// key = ord(D) << 32 | row index, the key layout of the other rank-counting evaluations (hamming_shared.h).
+//
+// Top-k: one workgroup per (tile of 16 queries, gallery segment), lanes own gallery rows.  Per query of the tile LDS holds a threshold
+// (a 64-bit key; at first above every key), a fill count and DT_CAP = 384 candidate keys.  A trip is 256 rows: a lane appends the key
+// of its row to the lists of the queries whose threshold it is below.  After a trip, every list longer than min(128, 4 k) is cut by
+// the whole workgroup to its k smallest, in order (each key's rank = the number of keys below it: keys are distinct), and the k-th
+// becomes the threshold; a list is at most 128 long before a trip, so 256 appends fit.  Segment lists are merged by one wave per query.
+#include <algorithm>
+#include <string>
+
+#include "../../include/concepthash_hip.h"
+#include "ch_common.h"
+#include "hamming_shared.h"
+
+namespace {
+
+constexpr int DM_COSINE = 0, DM_EUCLIDEAN = 1, DM_DOT = 2;
+constexpr int DB = 64;   // rows of a block of the prepared layout
+
+__host__ __device__ __forceinline__ int64_t prepared_floats(int64_t rows, int n) { return (rows + DB - 1) / DB * DB * n; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// the distance
+// ---------------------------------------------------------------------------------------------------------------
+template <int M>
+__device__ __forceinline__ float dense_step(float q, float g, float acc) {
+    if constexpr (M == DM_EUCLIDEAN) {
+        const float t = q - g;
+        return fmaf(t, t, acc);
+    } else {
+        return fmaf(q, g, acc);
+    }
+}
+
+template <int M>
+__device__ __forceinline__ float dense_finish(float acc) {
+    if constexpr (M == DM_EUCLIDEAN) return acc + 0.0f;
+    if constexpr (M == DM_COSINE) return (1.0f - acc) + 0.0f;
+    return (-acc) + 0.0f;
+}
+
+// qp: dimension 0 of the tile's first query, gp: dimension 0 of the lane's row, both inside their blocks (dimension j: + j * 64)
+template <int M, int TQ>
+__device__ __forceinline__ void dense_tile(const float *__restrict__ qp, const float *__restrict__ gp, int n, float (&D)[TQ]) {
+    float acc[TQ];
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) acc[t] = 0.0f;
+    auto dim = [&](int j) {
+        const float g = gp[(size_t)j * DB];
+#pragma unroll
+        for (int t = 0; t < TQ; ++t) acc[t] = dense_step<M>(qp[(size_t)j * DB + t], g, acc[t]);
+    };
+    // a tile of queries keeps its lanes busy with 4 dimensions in flight; one query per lane wants more loads out at a time
+    if constexpr (TQ == 1) {
+#pragma unroll 16
+        for (int j = 0; j < n; ++j) dim(j);
+    } else {
+#pragma unroll 4
+        for (int j = 0; j < n; ++j) dim(j);
+    }
+#pragma unroll
+    for (int t = 0; t < TQ; ++t) D[t] = dense_finish<M>(acc[t]);
+}
+
+__device__ __forceinline__ const float *row_ptr(const float *p, int64_t r, int n) { return p + (r >> 6) * (int64_t)n * DB + (r & 63); }
+
+__device__ __forceinline__ uint32_t dense_ord(float D) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, D);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float dense_unord(uint32_t o) {
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+// f(std::integral_constant<int, M>) for a checked metric id
+template <class F>
+int dispatch_metric(int metric, F &&f) {
+    switch (metric) {
+        case DM_COSINE: return f(std::integral_constant<int, DM_COSINE>{});
+        case DM_EUCLIDEAN: return f(std::integral_constant<int, DM_EUCLIDEAN>{});
+        default: return f(std::integral_constant<int, DM_DOT>{});
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// prepare: one lane per row of the padded operand
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dense_prepare_kernel(const float *__restrict__ codes, int64_t rows, int n, int metric,
+                                                            float *__restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= (rows + DB - 1) / DB * DB) return;
+    float *o = out + (r >> 6) * (int64_t)n * DB + (r & 63);
+    if (r >= rows) {
+        for (int j = 0; j < n; ++j) o[(size_t)j * DB] = 0.0f;
+        return;
+    }
+    const float *x = codes + r * n;
+    float scale = 1.0f;
+    if (metric == DM_COSINE) {
+        float s = 0.0f;
+        for (int j = 0; j < n; ++j) s = fmaf(x[j], x[j], s);
+        scale = s == 0.0f ? 0.0f : __fdiv_rn(1.0f, __fsqrt_rn(s));
+    }
+    if (metric == DM_COSINE)
+        for (int j = 0; j < n; ++j) o[(size_t)j * DB] = x[j] * scale;
+    else
+        for (int j = 0; j < n; ++j) o[(size_t)j * DB] = x[j];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the distance matrix: one pair per lane
+// ---------------------------------------------------------------------------------------------------------------
+template <int M>
+__global__ __launch_bounds__(256) void dense_dist_kernel(const float *__restrict__ q, int64_t Qn, const float *__restrict__ g, int64_t G,
+                                                         int n, float *__restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= Qn * G) return;
+    const int64_t qi = t / G, j = t - qi * G;
+    float D[1];
+    dense_tile<M, 1>(row_ptr(q, qi, n), row_ptr(g, j, n), n, D);
+    out[t] = D[0];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// top-k
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int DT_TQ = 16;      // queries of a tile (16 divides 64: a tile lies inside one block)
+constexpr int DT_BLK = 256;    // lanes of a workgroup = rows of a trip
+constexpr int DT_KMAX = 128;
+constexpr int DT_CAP = DT_KMAX + DT_BLK;   // keys a query's list can hold: at most 128 before a trip, which appends at most 256
+constexpr uint64_t DT_EMPTY = ~0ull;       // ord = 0xFFFFFFFF is a NaN's: no finite distance has it
+
+// cut list t to its k smallest keys, ascending; called by the whole workgroup with c = the list's fill, the same value in every lane
+__device__ __forceinline__ void dense_cut(uint64_t *list, uint32_t c, int k, uint64_t *thr, uint32_t *cnt) {
+    const int tid = threadIdx.x;
+    uint64_t key[2];
+    uint32_t rank[2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const uint32_t i = tid + e * DT_BLK;
+        key[e] = i < c ? list[i] : DT_EMPTY;
+        rank[e] = 0u;
+    }
+    for (uint32_t i = 0; i < c; ++i) {
+        const uint64_t other = list[i];
+        rank[0] += other < key[0] ? 1u : 0u;
+        rank[1] += other < key[1] ? 1u : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        if (tid + e * DT_BLK < (int)c && rank[e] < (uint32_t)k) {
+            list[rank[e]] = key[e];
+            if (rank[e] == (uint32_t)k - 1u) *thr = key[e];
+        }
+    }
+    if (tid == 0) *cnt = min(c, (uint32_t)k);
+    __syncthreads();
+}
+
+template <int M>
+__global__ __launch_bounds__(DT_BLK) void dense_topk_partial_kernel(const float *__restrict__ q, int64_t Qn, const float *__restrict__ g,
+                                                                    int64_t G, int n, int seg_rows, int k, uint64_t *__restrict__ part) {
+    __shared__ uint64_t cand[DT_TQ][DT_CAP];
+    __shared__ uint64_t thr[DT_TQ];
+    __shared__ uint32_t cnt[DT_TQ];
+    const int tid = threadIdx.x;
+    const int64_t q0 = (int64_t)blockIdx.x * DT_TQ;
+    const int seg = blockIdx.y;
+    const int64_t g0 = (int64_t)seg * seg_rows;
+    const int nrows = (int)min((int64_t)seg_rows, G - g0);
+    if (tid < DT_TQ) {
+        thr[tid] = DT_EMPTY;
+        cnt[tid] = 0u;
+    }
+    __syncthreads();
+    const float *qp = row_ptr(q, q0, n);   // queries past Qn inside the last block are zero rows: scanned, never stored
+    const uint32_t lim = (uint32_t)min(DT_KMAX, 4 * k);
+    for (int r0 = 0; r0 < nrows; r0 += DT_BLK) {   // the same trips for every lane: the barriers below are a workgroup's
+        const int r = r0 + tid;
+        const bool valid = r < nrows;
+        const int64_t row = g0 + (valid ? r : 0);
+        float D[DT_TQ];
+        dense_tile<M, DT_TQ>(qp, row_ptr(g, row, n), n, D);
+#pragma unroll
+        for (int t = 0; t < DT_TQ; ++t) {
+            const uint64_t key = ((uint64_t)dense_ord(D[t]) << 32) | (uint64_t)row;
+            if (valid && key < thr[t]) cand[t][atomicAdd(&cnt[t], 1u)] = key;
+        }
+        __syncthreads();
+        for (int t = 0; t < DT_TQ; ++t) {
+            const uint32_t c = cnt[t];   // the same value in every lane: nobody appends before the next trip
+            if (c > lim) dense_cut(cand[t], c, k, &thr[t], &cnt[t]);
+        }
+        __syncthreads();   // every lane has read every fill before the next trip appends
+    }
+    for (int t = 0; t < DT_TQ; ++t) {
+        const uint32_t c = cnt[t];
+        dense_cut(cand[t], c, k, &thr[t], &cnt[t]);
+        const int64_t qi = q0 + t;
+        if (qi < Qn && tid < k) part[((size_t)seg * Qn + qi) * k + tid] = tid < (int)min(c, (uint32_t)k) ? cand[t][tid] : DT_EMPTY;
+    }
+}
+
+// one wave per query: repeatedly extract the smallest key above the previous one (keys are distinct: they hold the row)
+__global__ __launch_bounds__(256) void dense_topk_merge_kernel(const uint64_t *__restrict__ part, int nseg, int64_t Qn, int k,
+                                                               int64_t g_index_base, int64_t *__restrict__ out_idx,
+                                                               float *__restrict__ out_dist) {
+    const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (qi >= Qn) return;
+    const int ncand = nseg * k;
+    bool any = false;
+    uint64_t prev = 0ull;   // the last output, once there is one
+    for (int r = 0; r < k; ++r) {
+        uint64_t best = DT_EMPTY;
+        for (int c = lane; c < ncand; c += 64) {
+            const int s = c / k, i = c - s * k;
+            const uint64_t key = part[((size_t)s * Qn + qi) * k + i];
+            if ((!any || key > prev) && key < best) best = key;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t other = __shfl_xor((unsigned long long)best, o, 64);
+            best = other < best ? other : best;
+        }
+        if (best == DT_EMPTY) {   // nothing left: fill the rest
+            for (int rr = r + lane; rr < k; rr += 64) {
+                out_idx[qi * k + rr] = -1;
+                out_dist[qi * k + rr] = __builtin_inff();
+            }
+            return;
+        }
+        if (lane == 0) {
+            out_idx[qi * k + r] = g_index_base + (int64_t)(best & 0xFFFFFFFFull);
+            out_dist[qi * k + r] = dense_unord((uint32_t)(best >> 32));
+        }
+        prev = best;
+        any = true;
+    }
+}
+
+// Rows per segment where the caller leaves it open: about three workgroups per CU (48 KB of LDS each) over the 256 CUs, segments of at
+// least 4,096 rows -- every segment starts with empty lists, and its first trips cut every list -- and a multiple of the trip.
+int dense_seg_rows(int64_t Qn, int64_t G) {
+    const int64_t tiles = ceil_div64(Qn, DT_TQ);
+    const int64_t nseg = std::max<int64_t>(1, std::min<int64_t>(ceil_div64(768, tiles), G / 4096));
+    int64_t rows = round_up64(ceil_div64(G, nseg), DT_BLK);
+    rows = std::max<int64_t>(rows, round_up64(ceil_div64(G, 65535), DT_BLK));
+    return (int)std::min<int64_t>(rows, 0x40000000);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// evaluation by rank counting: the collect pass is rank_collect_kernel of hamming_shared.h under this distance; the count pass keeps
+// its key, bin and LDS-list layout with a dense body (a dense row does not fit rank_count_rows' two rows of registers at n = 256)
+// ---------------------------------------------------------------------------------------------------------------
+template <int M>
+struct DenseRow {
+    const float *q;
+    int n;
+    // g: the prepared gallery behind the pointer type of the shared kernel; W is not used
+    __device__ __forceinline__ uint32_t row(int64_t qi, int, const uint64_t *__restrict__ g, int64_t j) const {
+        float D[1];
+        dense_tile<M, 1>(row_ptr(q, qi, n), row_ptr((const float *)g, j, n), n, D);
+        return dense_ord(D[0]);
+    }
+};
+
+template <int M>
+__device__ __forceinline__ void dense_count_rows(const float *__restrict__ qp, const float *__restrict__ g, int n, int64_t g0, int nrows,
+                                                 uint64_t row0, const uint64_t *list, uint32_t nkeys, uint64_t last, uint32_t *bins) {
+    for (int r = threadIdx.x; r < nrows; r += RC_BLK) {
+        float D[1];
+        dense_tile<M, 1>(qp, row_ptr(g, g0 + r, n), n, D);
+        const uint64_t key = ((uint64_t)dense_ord(D[0]) << 32) | (row0 + (uint64_t)r);
+        if (key <= last) atomicAdd(bins + keys_below(list, nkeys, key), 1u);
+    }
+}
+
+// One workgroup per (query, gallery segment), as rank_count_kernel: a list of at most list_cap keys lives in LDS with its bins, a
+// longer one is searched in global memory.
+template <int M>
+__global__ __launch_bounds__(RC_BLK) void dense_rank_count_kernel(const float *__restrict__ q, const float *__restrict__ g, int64_t G, int n,
+                                                                  int seg_rows, int64_t g_index_base, const int64_t *__restrict__ offsets,
+                                                                  const uint64_t *__restrict__ keys, int list_cap,
+                                                                  uint32_t *__restrict__ bins) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];   // [list_cap] keys, then [list_cap] uint32 bins
+    const int64_t qi = blockIdx.x;
+    const int64_t off = offsets[qi];
+    const int64_t n64 = offsets[qi + 1] - off;
+    if (n64 <= 0) return;   // workgroup-uniform
+    const uint32_t nkeys = (uint32_t)n64;
+    const int tid = threadIdx.x;
+    const int64_t g0 = (int64_t)blockIdx.y * seg_rows;
+    const int nrows = (int)min((int64_t)seg_rows, G - g0);
+    const uint64_t *list = keys + off;
+    const uint64_t last = list[nkeys - 1];
+    const float *qp = row_ptr(q, qi, n);
+    const uint64_t row0 = (uint64_t)(g_index_base + g0);
+    if (nkeys <= (uint32_t)list_cap) {
+        uint32_t *lds_bins = (uint32_t *)(lds_keys + list_cap);
+        for (uint32_t i = tid; i < nkeys; i += RC_BLK) {
+            lds_keys[i] = list[i];
+            lds_bins[i] = 0u;
+        }
+        __syncthreads();
+        dense_count_rows<M>(qp, g, n, g0, nrows, row0, lds_keys, nkeys, last, lds_bins);
+        __syncthreads();
+        for (uint32_t i = tid; i < nkeys; i += RC_BLK) {
+            const uint32_t c = lds_bins[i];
+            if (c != 0u) atomicAdd(bins + off + i, c);
+        }
+    } else {
+        dense_count_rows<M>(qp, g, n, g0, nrows, row0, list, nkeys, last, bins + off);
+    }
+}
+
+int check_dense(const char *who, int n, int metric) {
+    const std::string at = std::string(who) + ": ";
+    CH_REQUIRE(n >= 1 && n <= 256, at + "n must be in [1, 256]");
+    CH_REQUIRE(metric >= 0 && metric <= 2, at + "metric must be 0 (cosine), 1 (euclidean) or 2 (dot)");
+    return 0;
+}
+
+// what the collect and count entries check alike (W = 1 passes the shared check of W, which dense codes do not have)
+int check_dense_rank(const char *who, int64_t Qn, int64_t G, int n, int metric, int64_t g_index_base) {
+    if (int e = check_dense(who, n, metric)) return e;
+    return check_rank_sizes(who, Qn, G, 1, g_index_base);
+}
+
+}  // namespace
+
+extern "C" size_t ch_dense_prepared_bytes(int64_t rows, int32_t n) {
+    if (rows <= 0 || n < 1) return 0;
+    return (size_t)prepared_floats(rows, n) * sizeof(float);
+}
+
+extern "C" int ch_dense_prepare(const float *codes, int64_t rows, int32_t n, int32_t metric, float *out, void *stream) {
+    if (int e = check_dense("dense_prepare", n, metric)) return e;
+    CH_REQUIRE(rows >= 0, "dense_prepare: negative rows");
+    if (rows == 0) return 0;
+    CH_REQUIRE(codes && out, "dense_prepare: null pointer");
+    hipLaunchKernelGGL(dense_prepare_kernel, dim3((unsigned)ceil_div64(round_up64(rows, DB), 256)), dim3(256), 0, (hipStream_t)stream, codes,
+                       rows, (int)n, (int)metric, out);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ch_dense_dist(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, float *out, void *stream) {
+    if (int e = check_dense("dense_dist", n, metric)) return e;
+    CH_REQUIRE(Qn >= 0 && G >= 0, "dense_dist: negative sizes");
+    if (Qn == 0 || G == 0) return 0;
+    CH_REQUIRE(q && g && out, "dense_dist: null pointer");
+    CH_REQUIRE(ceil_div64(Qn * G, 256) <= 0x7FFFFFFFll, "dense_dist: Qn x G too large for one call (small problems)");
+    return dispatch_metric(metric, [&](auto m) {
+        hipLaunchKernelGGL((dense_dist_kernel<decltype(m)::value>), dim3((unsigned)ceil_div64(Qn * G, 256)), dim3(256), 0, (hipStream_t)stream,
+                           q, Qn, g, G, (int)n, out);
+        CH_LAUNCH_CHECK();
+        return 0;
+    });
+}
+
+extern "C" int32_t ch_dense_topk_seg_rows(int64_t Qn, int64_t G) {
+    if (Qn <= 0 || G <= 0) return DT_BLK;
+    return dense_seg_rows(Qn, G);
+}
+
+extern "C" size_t ch_dense_topk_workspace(int64_t Qn, int64_t G, int32_t k, int32_t seg_rows) {
+    if (Qn <= 0 || G <= 0 || k <= 0) return 16;
+    const int rows = seg_rows > 0 ? seg_rows : dense_seg_rows(Qn, G);
+    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint64_t) + 16;
+}
+
+extern "C" int ch_dense_topk(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int32_t k,
+                             int64_t g_index_base, int32_t seg_rows, int64_t *out_idx, float *out_dist, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    if (int e = check_dense("dense_topk", n, metric)) return e;
+    CH_REQUIRE(k >= 1 && k <= DT_KMAX, "dense_topk: 1 <= k <= 128");
+    CH_REQUIRE(Qn >= 0 && G >= 0, "dense_topk: negative sizes");
+    CH_REQUIRE(seg_rows >= 0, "dense_topk: seg_rows must be >= 0 (0: chosen here)");
+    CH_REQUIRE(g_index_base >= 0 && g_index_base + G <= 0x100000000ll, "dense_topk: keys hold 32-bit row indices (g_index_base + G <= 2^32)");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(q && out_idx && out_dist, "dense_topk: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = seg_rows > 0 ? seg_rows : dense_seg_rows(Qn, std::max<int64_t>(G, 1));
+    const int64_t nseg = ceil_div64(G, rows);
+    CH_REQUIRE(nseg <= 65535, "dense_topk: gallery too large for one call: more than 65,535 segments (shard it, or raise seg_rows)");
+    CH_REQUIRE(ceil_div64(Qn, DT_TQ) <= 0x7FFFFFFFll, "dense_topk: too many queries for one call");
+    uint64_t *part = (uint64_t *)workspace;
+    if (G > 0) {
+        CH_REQUIRE(g != nullptr, "dense_topk: null gallery");
+        CH_REQUIRE(workspace && workspace_bytes >= ch_dense_topk_workspace(Qn, G, k, seg_rows), "dense_topk: workspace too small");
+        const dim3 grid((unsigned)ceil_div64(Qn, DT_TQ), (unsigned)nseg);
+        if (int e = dispatch_metric(metric, [&](auto m) {
+                hipLaunchKernelGGL((dense_topk_partial_kernel<decltype(m)::value>), grid, dim3(DT_BLK), 0, s, q, Qn, g, G, (int)n, rows, (int)k,
+                                   part);
+                CH_LAUNCH_CHECK();
+                return 0;
+            }))
+            return e;
+    }
+    hipLaunchKernelGGL(dense_topk_merge_kernel, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, (int)nseg, Qn, (int)k, g_index_base,
+                       out_idx, out_dist);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ch_dense_rank_collect(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const void *q_labels,
+                                     const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count,
+                                     uint64_t *keys, void *stream) {
+    if (int e = check_dense_rank("dense_rank_collect", Qn, G, n, metric, g_index_base)) return e;
+    CH_REQUIRE(LW >= 0, "dense_rank_collect: negative LW");
+    if (Qn == 0 || G == 0) return 0;
+    CH_REQUIRE(g && q_labels && g_labels && count, "dense_rank_collect: null pointer");
+    CH_REQUIRE(offsets == nullptr || (q && keys), "dense_rank_collect: null pointer (q and keys go with offsets)");
+    return dispatch_metric(metric, [&](auto m) {
+        return rank_collect_launch(DenseRow<decltype(m)::value>{q, (int)n}, Qn, (const uint64_t *)g, G, 1, q_labels, g_labels, (int)LW,
+                                   g_index_base, offsets, count, keys, (hipStream_t)stream);
+    });
+}
+
+extern "C" int ch_dense_rank_count(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int64_t g_index_base,
+                                   int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins,
+                                   void *stream) {
+    if (int e = check_dense_rank("dense_rank_count", Qn, G, n, metric, g_index_base)) return e;
+    CH_REQUIRE(seg_rows >= 1, "dense_rank_count: seg_rows must be >= 1");
+    CH_REQUIRE(list_cap >= 1 && list_cap <= RC_MAX_LIST, "dense_rank_count: list_cap must be in [1, 8192]");
+    if (Qn == 0 || G == 0) return 0;
+    CH_REQUIRE(q && g && offsets && keys && bins, "dense_rank_count: null pointer");
+    CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "dense_rank_count: too many gallery segments (raise seg_rows)");
+    return dispatch_metric(metric, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        const dim3 grid((unsigned)Qn, (unsigned)ceil_div64(G, seg_rows));
+        const size_t lds = (size_t)list_cap * (sizeof(uint64_t) + sizeof(uint32_t));
+        static ch_once_per_device lds_once;   // one per instance of this body, i.e. per kernel
+        if (int e = ch_func_max_lds((const void *)dense_rank_count_kernel<M>, RC_MAX_LIST * 12, lds_once)) return e;
+        hipLaunchKernelGGL((dense_rank_count_kernel<M>), grid, dim3(RC_BLK), lds, (hipStream_t)stream, q, g, G, (int)n, (int)seg_rows,
+                           g_index_base, offsets, keys, (int)list_cap, bins);
+        CH_LAUNCH_CHECK();
+        return 0;
+    });
+}

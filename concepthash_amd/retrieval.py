@@ -3,7 +3,7 @@ gallery-sharded multi-GPU variants (one process per GPU, RCCL via ``torch.distri
 
 Replaces the reference's un-vendored ``utils.hashing`` arithmetic (call sites experiments/test_hashing.py:106-119,
 153-162).  PyTorch supplies device buffers, streams and collectives; all per-pair arithmetic runs in
-``csrc/hamming_topk.hip`` (top-k search), ``csrc/hamming.hip`` (distance matrix, mAP) and ``csrc/hamming_rankcount.hip`` (mAP under the weighted distance) and ``csrc/hamming_ternary.hip`` (ternary codes: two bit planes per row, [rows, 2, W]).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
+``csrc/hamming_topk.hip`` (top-k search), ``csrc/hamming.hip`` (distance matrix, mAP) and ``csrc/hamming_rankcount.hip`` (mAP under the weighted distance) and ``csrc/hamming_ternary.hip`` (ternary codes: two bit planes per row, [rows, 2, W]); ``csrc/dense_rank.hip`` ranks the real-valued codes themselves (cosine / Euclidean / dot).  Packed codes are ``int64`` tensors holding the uint64 bit patterns ([rows, W]).
 """
 from __future__ import annotations
 
@@ -1214,6 +1214,216 @@ def evaluate_ternary(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_labels: to
     keys = sort_slices(offsets, keys)
     cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
     bins = ternary_rank_count(q3, g3, nbit, offsets, keys, cap, seg_rows)
+    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
+    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
+    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
+                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# real-valued codes (csrc/dense_rank.hip; DESIGN.md section 2.0, "real-valued codes")
+# ---------------------------------------------------------------------------------------------------------------
+DENSE_METRICS = ("cosine", "euclidean", "dot")   # the position is the metric id of the C entries
+DENSE_MAX_DIM = 256
+DENSE_MAX_K = 128
+
+
+def dense_metric_id(metric) -> int:
+    if metric not in DENSE_METRICS:
+        raise ValueError(f"metric must be one of {DENSE_METRICS}, got {metric!r}")
+    return DENSE_METRICS.index(metric)
+
+
+def check_dense_codes(codes, what: str = "codes") -> torch.Tensor:
+    """Real-valued codes for a dense ranking: 2-D [rows, n], 1 <= n <= 256, every entry finite (ValueError otherwise: the kernels
+    do not define the order of NaN or infinite distances).  -> fp32, contiguous, where it was."""
+    codes = torch.as_tensor(codes)
+    if codes.dim() != 2:
+        raise ValueError(f"{what} must be 2-D [rows, n] real-valued codes")
+    if not 1 <= codes.shape[1] <= DENSE_MAX_DIM:
+        raise ValueError(f"{what} have {codes.shape[1]} dimensions; the dense rankings take 1 .. {DENSE_MAX_DIM}")
+    codes = codes.to(torch.float32).contiguous()
+    if codes.numel() and not bool(torch.isfinite(codes).all()):
+        raise ValueError(f"{what} hold NaN or infinite entries: the dense rankings are defined on finite codes")
+    return codes
+
+
+class DenseCodes:
+    """The scan operand of the dense entries (`prepare_dense`): `data`, fp32 in blocks of 64 rows, dimension-major inside a block
+    (include/concepthash_hip.h), with the rows, dimensions and metric it was prepared for."""
+
+    def __init__(self, data: torch.Tensor, rows: int, n: int, metric: str):
+        self.data, self.rows, self.n, self.metric = data, int(rows), int(n), metric
+
+    @property
+    def device(self):
+        return self.data.device
+
+
+def prepare_dense(codes, metric: str, stream=None) -> DenseCodes:
+    """[rows, n] real codes -> the operand of dense_dist / dense_topk / dense_rank_collect / dense_rank_count under `metric`: rows
+    normalised once for "cosine" (a zero row stays zero), copied for the others.  Non-finite codes: ValueError, before any launch."""
+    mid = dense_metric_id(metric)
+    codes = check_dense_codes(codes)
+    lib = _lib.load()
+    rows, n = codes.shape
+    out = torch.empty(int(lib.ch_dense_prepared_bytes(rows, n)) // 4, dtype=torch.float32, device=codes.device)
+    with _dev_guard(codes):
+        _lib.check(lib.ch_dense_prepare(_lib.ptr(codes), rows, n, mid, _lib.ptr(out), _lib.stream_ptr(stream)), "ch_dense_prepare")
+    return DenseCodes(out, rows, n, metric)
+
+
+def _check_dense_pair(q: DenseCodes, g: DenseCodes, metric=None) -> int:
+    if not isinstance(q, DenseCodes) or not isinstance(g, DenseCodes):
+        raise TypeError("dense rankings take prepare_dense(codes, metric) operands")
+    if metric is not None and (dense_metric_id(metric), metric) != (dense_metric_id(q.metric), q.metric):
+        raise ValueError(f"the queries were prepared for {q.metric!r}, not for {metric!r}")
+    if q.metric != g.metric:
+        raise ValueError(f"queries were prepared for {q.metric!r}, the gallery for {g.metric!r}")
+    if q.n != g.n:
+        raise ValueError(f"queries have {q.n} dimensions, the gallery {g.n}")
+    if q.device != g.device:
+        raise ValueError("query and gallery codes must be on the same device")
+    return dense_metric_id(q.metric)
+
+
+def dense_dist(q: DenseCodes, g: DenseCodes, metric: Optional[str] = None, stream=None) -> torch.Tensor:
+    """Full [Qn, G] fp32 matrix of the distance (small problems), the bits every other dense entry ranks by.  metric: the operands'
+    own where left out; another one is a ValueError (an operand is prepared for one metric)."""
+    lib = _lib.load()
+    mid = _check_dense_pair(q, g, metric)
+    out = torch.empty(q.rows, g.rows, dtype=torch.float32, device=q.device)
+    if q.rows and g.rows:
+        with _dev_guard(q.data):
+            _lib.check(lib.ch_dense_dist(_lib.ptr(q.data), q.rows, _lib.ptr(g.data), g.rows, q.n, mid, _lib.ptr(out),
+                                         _lib.stream_ptr(stream)), "ch_dense_dist")
+    return out
+
+
+def dense_topk(q: DenseCodes, g: DenseCodes, metric: Optional[str], k: int, g_index_base: int = 0, seg_rows: Optional[int] = None,
+               stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Top-k by ascending (distance, gallery index) under `metric` (None: the operands' own; another one is a ValueError): (idx int64 [Qn,k], dist fp32 [Qn,k]); idx -1 and dist
+    +inf where k > G.  1 <= k <= 128.  Lists of gallery shards merge exactly by ascending (`dense_order(dist)`, idx).  seg_rows
+    (tests): the scan's segmentation -- it changes no result."""
+    lib = _lib.load()
+    mid = _check_dense_pair(q, g, metric)
+    k = int(k)
+    if not 1 <= k <= DENSE_MAX_K:
+        raise ValueError(f"k must be in [1, {DENSE_MAX_K}], got {k}")
+    Qn, G = q.rows, g.rows
+    seg = int(seg_rows) if seg_rows else 0
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
+    dist = torch.empty(Qn, k, dtype=torch.float32, device=q.device)
+    if Qn == 0:
+        return idx, dist
+    wsb = int(lib.ch_dense_topk_workspace(Qn, G, k, seg))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    with _dev_guard(q.data):
+        _lib.check(lib.ch_dense_topk(_lib.ptr(q.data), Qn, _lib.ptr(g.data) if G else _lib.ptr(None), G, q.n, mid, k, int(g_index_base),
+                                     seg, _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), "ch_dense_topk")
+    return idx, dist
+
+
+def dense_order(dist: torch.Tensor) -> torch.Tensor:
+    """ord(D) of fp32 distances as int64 in [0, 2^32): ascending as D ascends, -0 with +0 (the high word of a dense key)."""
+    b = (dist.to(torch.float32) + 0.0).contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    return torch.where(b >= (1 << 31), b ^ 0xFFFFFFFF, b ^ 0x80000000)
+
+
+def dense_unorder(o: torch.Tensor) -> torch.Tensor:
+    """The fp32 distance of an ord value (int64 in [0, 2^32)): the inverse of `dense_order`."""
+    o = o.to(torch.int64) & 0xFFFFFFFF
+    b = torch.where(o >= (1 << 31), o ^ 0x80000000, o ^ 0xFFFFFFFF)
+    return torch.where(b >= (1 << 31), b - (1 << 32), b).to(torch.int32).view(torch.float32)
+
+
+def dense_rank_collect(q: DenseCodes, g: DenseCodes, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int, g_index_base: int = 0, stream=None):
+    """`rank_collect` under a dense metric: the keys ord(D) << 32 | global index of every query's relevant rows -> (offsets, keys,
+    longest slice).  The keys use all 64 bits (int64 holding uint64 bit patterns): `sort_slices_unsigned` puts them in order."""
+    lib = _lib.load()
+    mid = _check_dense_pair(q, g)
+    Qn, G = q.rows, g.rows
+    count = torch.zeros(Qn, dtype=torch.int32, device=q.device)
+    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q.device)
+    if Qn == 0 or G == 0:
+        return offsets, torch.empty(0, dtype=torch.int64, device=q.device), 0
+
+    def call(off, keys):
+        _lib.check(lib.ch_dense_rank_collect(_lib.ptr(q.data), Qn, _lib.ptr(g.data), G, q.n, mid, _lib.ptr(q_lab), _lib.ptr(g_lab), LW,
+                                             int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
+                                             _lib.stream_ptr(stream)), "ch_dense_rank_collect")
+
+    with _dev_guard(q.data):
+        call(None, None)
+        offsets[1:] = count.cumsum(0, dtype=torch.int64)
+        total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
+        keys = torch.empty(total, dtype=torch.int64, device=q.device)
+        if total:
+            count.zero_()
+            call(offsets, keys)
+    return offsets, keys, int(longest)
+
+
+def sort_slices_unsigned(offsets: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """Every CSR slice of `keys` ascending AS UINT64 (`sort_slices` needs keys below 2^48; dense keys use all 64 bits): flipping the
+    top bit maps uint64 order onto int64 order; one sort of the flat buffer, then a stable sort by slice."""
+    if keys.numel() == 0:
+        return keys
+    top = -(1 << 63)
+    n = offsets[1:] - offsets[:-1]
+    owner = torch.repeat_interleave(torch.arange(n.numel(), device=keys.device), n, output_size=keys.numel())
+    flipped, order = torch.sort(keys ^ top)
+    return (flipped[torch.sort(owner[order], stable=True)[1]] ^ top).contiguous()
+
+
+def dense_rank_count(q: DenseCodes, g: DenseCodes, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int, seg_rows: Optional[int] = None,
+                     g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """`rank_count` under a dense metric -> bins int32 [total]; keys: `sort_slices_unsigned(dense_rank_collect(...))`.  `bins`, where
+    given, is added into (gallery shards)."""
+    lib = _lib.load()
+    mid = _check_dense_pair(q, g)
+    Qn, G = q.rows, g.rows
+    if bins is None:
+        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q.device)
+    if Qn == 0 or G == 0 or keys.numel() == 0:
+        return bins
+    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
+    with _dev_guard(q.data):
+        _lib.check(lib.ch_dense_rank_count(_lib.ptr(q.data), Qn, _lib.ptr(g.data), G, q.n, mid, int(g_index_base), seg, _lib.ptr(offsets),
+                                           _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)), "ch_dense_rank_count")
+    return bins
+
+
+def evaluate_dense(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.Tensor, metric: str, R=-1, ks: Sequence[int] = (1, 5, 10),
+                   remove_first: bool = False, skip_queries_without_relevant: bool = False, seg_rows: Optional[int] = None,
+                   list_cap: Optional[int] = None) -> dict:
+    """`evaluate` under the ranking of the real-valued codes themselves: ascending (D, gallery index), D the
+    cosine, squared Euclidean or negated dot distance of `metric` between [Qn, n] and [G, n] fp32 codes -- what `dense_topk` serves,
+    and the upper end of the ladder Hamming < ternary / asymmetric < dense (mAP_dense - mAP is a run's quantisation gap).  Returns
+    the keys of `evaluate_weighted` -- mAP, precisions, recalls, hits, total, S, nrel, ap, lists under a list R -- exact for any R and
+    k under the fp32 distances of the kernels, by the same rank counting: collect and sort the keys of each query's relevant rows, one
+    Qn x G scan for the bins, one lane per query for the AP terms.  seg_rows / list_cap (tests) change no result."""
+    dense_metric_id(metric)
+    q_codes, g_codes = check_dense_codes(q_codes, "query codes"), check_dense_codes(g_codes, "gallery codes")
+    if q_codes.shape[1] != g_codes.shape[1]:
+        raise ValueError(f"queries have {q_codes.shape[1]} dimensions, the gallery {g_codes.shape[1]}")
+    Qn, G = q_codes.shape[0], g_codes.shape[0]
+    dev = g_codes.device
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    many = isinstance(R, (list, tuple))
+    Rs = [int(r) for r in R] if many else [int(R)]
+    if Qn == 0 or G == 0:
+        return empty_result(Qn, 1, dev, Rs, ks, many, False, None)
+    q, g = prepare_dense(q_codes.to(dev), metric), prepare_dense(g_codes, metric)
+    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
+    limits, idx_of = normalize_limits(Rs + ks)
+    offsets, keys, longest = dense_rank_collect(q, g, q_lab, g_lab, LW)
+    keys = sort_slices_unsigned(offsets, keys)
+    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
+    bins = dense_rank_count(q, g, offsets, keys, cap, seg_rows)
     S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
     sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
     pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])

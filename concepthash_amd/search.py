@@ -15,7 +15,7 @@ import torch
 from . import retrieval as rt
 
 FORMAT = 1
-RANKS = ("hamming", "asymmetric", "ternary")
+RANKS = ("hamming", "asymmetric", "ternary") + rt.DENSE_METRICS
 TOPK_MAX = 128    # the deepest list of the top-k scan (csrc/hamming_topk.hip); deeper ones: retrieval.hamming_ranked
 
 
@@ -39,12 +39,14 @@ class GalleryIndex:
     evaluation chain the database went through; fingerprint: `checkpoint_fingerprint` of the checkpoint that encoded it.
     mask: None, or the plane [G, W] int64 of the bits every database row is sure of, `retrieval.confidence_mask(codes, margin)` of the
     real codes that were packed, with `margin` the number it was built with -- what rank="ternary" needs; an index
-    without it serves every other ranking as before."""
+    without it serves every other ranking as before.
+    real: None, or the plane [G, nbit] fp32 of the real-valued codes that were packed (after the mean shift, where there is one) -- what
+    rank="cosine" | "euclidean" | "dot" need; optional in the same way."""
 
     def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
                  paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
                  transform: Optional[dict] = None, fingerprint: Optional[dict] = None, mask: Optional[torch.Tensor] = None,
-                 margin: Optional[float] = None):
+                 margin: Optional[float] = None, real: Optional[torch.Tensor] = None):
         nbit, ncontext = int(nbit), int(ncontext)
         if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
             raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
@@ -64,6 +66,12 @@ class GalleryIndex:
             margin = rt.check_margin(margin, "the mask plane's margin")
         elif margin is not None:
             raise ValueError("a margin without a mask plane")
+        if real is not None:
+            if tuple(real.shape) != (G, nbit) or real.device != codes.device:
+                raise ValueError(f"real must be the plane [{G}, {nbit}] of real-valued codes on the codes' device, got {tuple(real.shape)} "
+                                 f"on {real.device}")
+            real = rt.check_dense_codes(real, "the real plane")
+        self.real = real
         self.codes, self.nbit, self.ncontext = codes.contiguous(), nbit, ncontext
         self.mask, self.margin = (mask.contiguous() if mask is not None else None), margin
         self.labels = labels
@@ -83,7 +91,7 @@ class GalleryIndex:
     def to(self, device) -> "GalleryIndex":
         mv = lambda t: t.to(device) if t is not None else None
         return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
-                            self.transform, self.fingerprint, mv(self.mask), self.margin)
+                            self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real))
 
     # ---- file --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -96,6 +104,8 @@ class GalleryIndex:
              "fingerprint": self.fingerprint}
         if self.mask is not None:           # an index without the plane is the file it has always been
             d.update(mask=cpu(self.mask), margin=self.margin)
+        if self.real is not None:
+            d.update(real=cpu(self.real))
         torch.save(d, tmp)
         os.replace(tmp, path)
 
@@ -118,7 +128,7 @@ class GalleryIndex:
         if not isinstance(d, dict) or d.get("format") != FORMAT:
             raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
         index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
-                    d["fingerprint"], d.get("mask"), d.get("margin"))
+                    d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"))
         index.check(fingerprint, nbit, source=path)
         return index
 
@@ -159,9 +169,15 @@ class GalleryIndex:
         one raises ValueError), the queries under `margin` -- and dist is K = nbit - t_q . t_g in HALF bits (a bit either side is unsure of
         costs 1, a disagreement both are sure of 2); dist_bits = K / 2.  `concepts` clears the query's mask outside the chosen sub-codes and
         nbit becomes the number of bits in play, so K stays the distance on those bits; radius keeps K <= 2 radius; bits counts the
-        query's sure bits in play and dist_max = bits in play + bits; k <= 128.  The dict also holds rank and index_margin."""
+        query's sure bits in play and dist_max = bits in play + bits; k <= 128.  The dict also holds rank and index_margin.
+        rank="cosine" | "euclidean" | "dot": the ranking of the real-valued codes themselves (`retrieval.dense_topk`; DESIGN.md section
+        2.0) against the index's real plane (an index without one raises ValueError); dist is fp32 -- 1 - cos, the squared Euclidean
+        distance or the negated dot product -- and +inf where idx is -1.  No `concepts`, no margin, no radius (ValueError), k <= 128;
+        concept_dist and bits describe the sign codes of the hits as under "hamming"."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+        if rank in rt.DENSE_METRICS:
+            return self._search_dense(query_codes, int(k), concepts, margin, rank, radius, mean_shift)
         if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
             raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits!r}")
         k = int(k)
@@ -238,6 +254,34 @@ class GalleryIndex:
             idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
                    bits=keep.sum(1), labels=None, paths=None, **extra)
+        return self._name_hits(out)
+
+    def _search_dense(self, query_codes, k: int, concepts, margin, rank: str, radius, mean_shift: bool) -> dict:
+        """`search` under a dense rank"""
+        if concepts is not None or radius is not None or (margin is not None and float(margin) != 0.0):
+            raise ValueError(f"rank='{rank}' ranks by the whole real-valued code: concepts, a query margin and a radius are defined on bits "
+                             "and are not built under it")
+        if not 1 <= k <= rt.DENSE_MAX_K:
+            raise ValueError(f"k = {k} with rank='{rank}' is not built: the dense scan keeps lists of 1 .. {rt.DENSE_MAX_K}")
+        if self.real is None:
+            raise ValueError(f"rank='{rank}' needs the index's real plane, which this index was built without: rebuild it "
+                             f"(exp=search rank={rank} rebuilds it by itself; rebuild_index=true forces it)")
+        codes = torch.as_tensor(query_codes)
+        if codes.dim() != 2 or codes.shape[1] != self.nbit:
+            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
+        codes = rt.check_dense_codes(codes, "query codes")          # finite, before anything is launched
+        dev = self.device
+        codes = codes.to(dev)
+        if self.mean is not None and mean_shift:
+            codes = codes - self.mean[None, :]
+        idx, dist = rt.dense_topk(rt.prepare_dense(codes, rank), rt.prepare_dense(self.real, rank), rank, k)
+        q = rt.pack_sign(codes)
+        out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
+                   bits=torch.full((codes.shape[0],), self.nbit, dtype=torch.int64, device=dev), labels=None, paths=None, rank=rank)
+        return self._name_hits(out)
+
+    def _name_hits(self, out: dict) -> dict:
+        idx = out["idx"]
         if self.labels is not None:
             lab = self.labels[idx.clamp_min(0)]
             miss = idx < 0

@@ -1,7 +1,7 @@
 """`exp=search`: image or text queries -> ranked database hits of a finished run, optionally by chosen concepts.
 
     python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [radius=2] [concepts=[0,2]]
-        [query_margin=0.0] [rank=hamming|asymmetric] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
+        [query_margin=0.0] [rank=hamming|asymmetric|ternary|cosine|euclidean|dot] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
         [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
 
 Text queries ("text query") become codes through the CLIP text tower and the run's own `text_projection`
@@ -116,6 +116,8 @@ class SearchExperiment:
         # rank=ternary ranks against the database's own ternary codes: the index then carries the mask plane of index_margin
         self.ternary = str(config.get("rank", "hamming") or "hamming") == "ternary"
         self.index_margin = rt.check_margin(config.get("index_margin", 0.0) or 0.0, "index_margin") if self.ternary else None
+        # rank=cosine | euclidean | dot rank the real-valued codes themselves: the index then carries them as its real plane
+        self.dense = str(config.get("rank", "hamming") or "hamming") in rt.DENSE_METRICS
 
         # the index first: whether the database split has to be encoded decides what is loaded
         self.fingerprint = self._phase("fingerprint", checkpoint_fingerprint, self.checkpoint)
@@ -164,6 +166,9 @@ class SearchExperiment:
             have = "no mask plane" if index.mask is None else f"the mask plane of index_margin = {index.margin}"
             raise StaleIndexError(f"{self.index_path} holds {have}; rank=ternary index_margin={self.index_margin} needs its own: rebuild the "
                                   f"index (rebuild_index=true)")
+        if self.dense and index.real is None:
+            raise StaleIndexError(f"{self.index_path} holds no real plane; rank={self.config.get('rank')} ranks the real-valued codes and "
+                                  f"needs it: rebuild the index (rebuild_index=true)")
 
     def _build_index(self) -> GalleryIndex:
         _, out = self._phase("encode_db", self.trainer.inference_one_epoch, "db", True)
@@ -180,7 +185,8 @@ class SearchExperiment:
         index = GalleryIndex(rt.pack_sign(codes), self.nbit, self.ncontext, labels=_label_ids(out["labels"]),
                              paths=[p for p, _ in items] if items is not None else None,
                              data_root=getattr(ds, "root", None) if items is not None else None, mean=mean,
-                             transform=self._transform_settings(), fingerprint=self.fingerprint, mask=mask, margin=self.index_margin)
+                             transform=self._transform_settings(), fingerprint=self.fingerprint, mask=mask, margin=self.index_margin,
+                             real=codes if self.dense else None)
         self._phase("index_save", index.save, self.index_path)
         return index
 
@@ -294,6 +300,9 @@ class SearchExperiment:
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
         bits = res["bits"].tolist()
         dist_max = res["dist_max"].tolist() if "dist_max" in res else bits      # the distance of a row that disagrees on every unmasked bit
+        dense = rank in rt.DENSE_METRICS
+        if dense:
+            dist_max = [None] * len(idx)                                        # a real-valued distance has no such row
         dist_bits = res["dist_bits"].tolist() if "dist_bits" in res else None   # rank=ternary: the distance is in half bits
         hit_labels = res["labels"].cpu() if res["labels"] is not None else None
         queries = []
@@ -328,15 +337,15 @@ class SearchExperiment:
             np.save(os.path.join(self.search_logdir, "concept_attention.npy"), attn.cpu().numpy().astype(np.float32))
         what = "the whole code" if concepts is None else f"concepts {concepts}"
         print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}, " +
-              ("Hamming distance" if rank == "hamming" else f"ternary distance in half bits (database margin {index.margin})" if rank == "ternary"
+              (f"{rank} distance of the real-valued codes" if dense else "Hamming distance" if rank == "hamming" else f"ternary distance in half bits (database margin {index.margin})" if rank == "ternary"
                else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
               (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + (f", within {radius} bits" if radius is not None else "") + f"; index {self.index_note}")
         for e in queries[:PRINT_QUERIES]:
             print(f"query {e['query']}" + (f" (label {e['label']})" if e["label"] is not None and not isinstance(e["label"], list) else "") +
-                  f": {e['unmasked_bits']} bits, distance <= {e['distance_max']}")
+                  f": {e['unmasked_bits']} bits" + ("" if dense else f", distance <= {e['distance_max']}"))
             for h in e["hits"]:
                 mark = "" if h["relevant"] is None else (" +" if h["relevant"] else " -")
-                print(f"  {h['rank']:3d}. d={h['distance']:3d} per concept {h['concept_distances']}  #{h['index']}" +
+                print(f"  {h['rank']:3d}. d=" + (f"{h['distance']:.6g}" if dense else f"{h['distance']:3d}") + f" per concept {h['concept_distances']}  #{h['index']}" +
                       (f" {h['path']}" if h["path"] else "") + mark)
         print("Phases (s): " + ", ".join(f"{n} {v:.2f}" for n, v in self.timing.items()))
         print(f"Done: {self.search_logdir}")

@@ -561,6 +561,43 @@ int ch_ternary_rank_count(const uint64_t *q, int64_t Qn, const uint64_t *g, int6
                           int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins,
                           void *stream);
 
+/* Real-valued codes ("real-valued codes"): the rankings of the codes before sign().  Codes are fp32 [rows, n],
+ * 1 <= n <= 256; metric: 0 = cosine, 1 = euclidean, 2 = dot; anything else, or n out of range, is status 2.  Ascending in
+ *     dot:        D = -(q . g)
+ *     euclidean:  D = sum_j (q_j - g_j)^2                    (squared, from the differences)
+ *     cosine:     D = 1 - (q^ . g^),  x^ = x * (1 / sqrt(sum_j x_j^2)), sqrt and division correctly rounded; a zero row stays zero (D = 1)
+ * each an fmaf chain over j = 0 .. n - 1 in this order from 0.0f, with the same bits in every entry below.  Every ranking is ascending
+ * key = ord(D) << 32 | row index, ord(D) = b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000), b = bits(D + 0.0f).  Inputs must be finite (the
+ * Python wrapper refuses others; the kernels do not define them).
+ *
+ * ch_dense_prepare: codes [rows,n] -> the scan operand every other entry takes for q and g, ch_dense_prepared_bytes(rows, n) bytes:
+ * rows in blocks of 64, dimension-major inside a block -- out[(r / 64) * n * 64 + j * 64 + r % 64] = x^_r,j (x for euclidean and dot);
+ * the rows that fill the last block are zeros. */
+size_t ch_dense_prepared_bytes(int64_t rows, int32_t n);
+int ch_dense_prepare(const float *codes, int64_t rows, int32_t n, int32_t metric, float *out, void *stream);
+
+/* Full matrix of D (small problems): prepared q (Qn rows), prepared g (G rows) -> out [Qn,G] fp32. */
+int ch_dense_dist(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, float *out, void *stream);
+
+/* Top-k by ascending (ord(D), row index) over a prepared gallery: out_idx [Qn,k] int64 = g_index_base + row, out_dist [Qn,k] fp32 = D;
+ * slots past the end of the gallery hold -1 / +inf.  1 <= k <= 128; g_index_base + G <= 2^32.  seg_rows: gallery rows per segment of
+ * the scan, 0 = ch_dense_topk_seg_rows(Qn, G) (no result depends on it); workspace: ch_dense_topk_workspace() bytes for the same
+ * seg_rows.  Lists of gallery shards merge exactly by ascending (ord(D), index). */
+int32_t ch_dense_topk_seg_rows(int64_t Qn, int64_t G);
+size_t ch_dense_topk_workspace(int64_t Qn, int64_t G, int32_t k, int32_t seg_rows);
+int ch_dense_topk(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int32_t k, int64_t g_index_base,
+                  int32_t seg_rows, int64_t *out_idx, float *out_dist, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Evaluation under D by rank counting: ch_hamming_rank_collect and ch_hamming_rank_count with key(g) = ord(D(q, g)) << 32 | global
+ * index of g over prepared codes -- the same CSR buffers (offsets, count, keys, bins), the same offsets == NULL counting call, the
+ * same list_cap and seg_rows guarantees, the same labels.  Keys use all 64 bits: sort them as UNSIGNED.  Their bins go to
+ * ch_hamming_rank_ap as they are. */
+int ch_dense_rank_collect(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const void *q_labels,
+                          const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count, uint64_t *keys,
+                          void *stream);
+int ch_dense_rank_count(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int64_t g_index_base,
+                        int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins, void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

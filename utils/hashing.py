@@ -27,7 +27,9 @@ def _device():
 
 def _check(dist_metric, threshold, landmark_gt):
     if dist_metric != "hamming":
-        raise NotImplementedError(f"dist_metric='{dist_metric}': only 'hamming' is built (the shipped configs use it)")
+        raise NotImplementedError(f"dist_metric='{dist_metric}': only 'hamming' is built under this argument (what the reference's "
+                                  "un-vendored package does with another value cannot be read); the cosine, Euclidean and dot rankings "
+                                  "of the real-valued codes are asked for by name: rank=\"cosine\" | \"euclidean\" | \"dot\"")
     if threshold not in (0, 0.0):
         raise NotImplementedError("threshold != 0 is not built: what the reference's un-vendored package does with it cannot be read; "
                                   "ternary codes are ranked with rank=\"ternary\", margin=<m> (every reference call site passes 0)")
@@ -93,7 +95,8 @@ def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first,
                        skip_queries_without_relevant=skip, tie_bracket=tie, **look)
 
 
-RANKS = ("hamming", "asymmetric", "ternary")
+DENSE_RANKS = tuple(rt.DENSE_METRICS)      # "cosine", "euclidean", "dot": the rankings of the real-valued codes themselves
+RANKS = ("hamming", "asymmetric", "ternary") + DENSE_RANKS
 
 
 def _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits):
@@ -120,6 +123,23 @@ def _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, R, ks, remov
     q3 = rt.pack_ternary(torch.as_tensor(test_codes).to(dev, torch.float32), margin)
     return rt.evaluate_ternary(q3, g3, db.shape[1], _labels(test_labels, dev), _labels(db_labels, dev), R=R, ks=ks,
                                remove_first=remove_first, skip_queries_without_relevant=skip)
+
+
+def _dense_single_process(metric, *operands):
+    from concepthash_amd.distributed import RowShard
+    if any(isinstance(x, RowShard) for x in operands) or _sharded():
+        raise NotImplementedError(f"rank='{metric}' is evaluated by one process on a whole database; the sharded form is not built "
+                                  "(its bins are additive over gallery shards)")
+
+
+def _evaluate_dense(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, metric):
+    """rank="cosine" | "euclidean" | "dot": both code sets stay real-valued (`retrieval.evaluate_dense`)."""
+    _dense_single_process(metric, db_codes, db_labels, test_codes, test_labels)
+    # finiteness is checked where the codes are (a host tensor never reaches the GPU with a NaN in it)
+    q, g = rt.check_dense_codes(test_codes, "test_codes"), rt.check_dense_codes(db_codes, "db_codes")
+    dev = _device()
+    return rt.evaluate_dense(q.to(dev), g.to(dev), _labels(test_labels, dev), _labels(db_labels, dev), metric, R=R, ks=ks,
+                             remove_first=remove_first, skip_queries_without_relevant=skip)
 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
@@ -149,7 +169,12 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     the codes belongs to the run.  No tie bracket and no radii (ValueError); single-process only (NotImplementedError), as "asymmetric".
     `threshold` is NOT this margin: the reference hands `ternary_threshold` to its un-vendored package, whose rule for it cannot be
     read, so threshold != 0 keeps raising NotImplementedError (the situation that made skip_queries_without_relevant a switch) and the
-    ternary ranking is asked for by name."""
+    ternary ranking is asked for by name.
+    rank="cosine" | "euclidean" | "dot" (not reference arguments): the ranking of the real-valued codes themselves, before sign() --
+    ascending 1 - cos, squared Euclidean distance or negated dot product; neither code set is binarised, so
+    mAP under it minus the Hamming mAP is the run's quantisation gap.  Codes of 1 .. 256 finite dimensions (ValueError otherwise); no
+    tie bracket and no radii (ValueError); single-process only (NotImplementedError).  `dist_metric` is NOT this switch, for the
+    reason `threshold` is not the margin: dist_metric != "hamming" keeps raising NotImplementedError."""
     global last_tie_bracket, last_hash_lookup
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
@@ -162,6 +187,8 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
         if tie_bracket or radii is not None:
             raise ValueError("rank='ternary' has no tie bracket and no radius lookup: both are defined on Hamming distances")
         margin = rt.check_margin(margin, "rank='ternary': margin")
+    if rank in DENSE_RANKS and (tie_bracket or radii is not None):
+        raise ValueError(f"rank='{rank}' has no tie bracket and no radius lookup: both are defined on Hamming distances")
     last_tie_bracket = None
     last_hash_lookup = None
     _check(dist_metric, threshold, landmark_gt)
@@ -177,6 +204,10 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     if rank == "ternary":
         res = _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
                                 bool(skip_queries_without_relevant), margin)
+        return res["mAP"], res["recalls"], res["precisions"]
+    if rank in DENSE_RANKS:
+        res = _evaluate_dense(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
+                              bool(skip_queries_without_relevant), rank)
         return res["mAP"], res["recalls"], res["precisions"]
     res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
                     bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
@@ -202,15 +233,24 @@ def pr_curve_points(n_db: int) -> List[int]:
 
 
 def calculate_pr_curve(db_codes, db_labels, test_codes, test_labels, threshold=0., dist_metric="hamming",
-                       remove_first_retrieved=False, Rs: Sequence[int] = None):
+                       remove_first_retrieved=False, Rs: Sequence[int] = None, rank="hamming"):
     """-> (recalls, precisions, Rs): mean precision / recall at each retrieval depth R (experiments/test_hashing.py:153-167).
-    Every depth is a rank limit of ONE AP pass (16 limits per gallery scan): #relevant-in-top-R is that limit's `nrel`."""
+    Every depth is a rank limit of ONE AP pass (16 limits per gallery scan): #relevant-in-top-R is that limit's `nrel`.
+    rank (not a reference argument): "hamming" (default), or "cosine" | "euclidean" | "dot" -- the curve of the ranking of the
+    real-valued codes (`calculate_mAP`); the other ranks of `calculate_mAP` have no curve here (ValueError)."""
+    if rank != "hamming" and rank not in DENSE_RANKS:
+        raise ValueError(f"rank must be 'hamming' or one of {DENSE_RANKS}, got {rank!r}")
     _check(dist_metric, threshold, None)
+    if rank in DENSE_RANKS:
+        _dense_single_process(rank, db_codes, db_labels, test_codes, test_labels)
     n = db_codes.shape[0] - (1 if remove_first_retrieved else 0)
     Rs = [int(r) for r in (Rs if Rs is not None else pr_curve_points(max(n, 1)))]
     if not Rs:
         return [], [], []
-    res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved)
+    if rank in DENSE_RANKS:
+        res = _evaluate_dense(db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved, False, rank)
+    else:
+        res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved)
     total = res["total"].double()
     recalls, precisions = [], []
     for r, nrel in zip(Rs, res["nrel"]):
