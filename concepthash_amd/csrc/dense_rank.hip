@@ -269,14 +269,14 @@ int dense_seg_rows(int64_t Qn, int64_t G) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// evaluation by rank counting: the collect pass is rank_collect_kernel of hamming_shared.h under this distance; the count pass keeps
-// its key, bin and LDS-list layout with a dense body (a dense row does not fit rank_count_rows' two rows of registers at n = 256)
+// evaluation by rank counting: the collect and the count pass are rank_collect_kernel and rank_count_kernel of hamming_shared.h under
+// this distance, behind the shared launches and entry bodies.  The prepared gallery goes behind the pointer type of the shared kernels.
 // ---------------------------------------------------------------------------------------------------------------
 template <int M>
 struct DenseRow {
     const float *q;
     int n;
-    // g: the prepared gallery behind the pointer type of the shared kernel; W is not used
+    // W is not used
     __device__ __forceinline__ uint32_t row(int64_t qi, int, const uint64_t *__restrict__ g, int64_t j) const {
         float D[1];
         dense_tile<M, 1>(row_ptr(q, qi, n), row_ptr((const float *)g, j, n), n, D);
@@ -284,54 +284,30 @@ struct DenseRow {
     }
 };
 
+// What rank_count_kernel takes.  Its "registers" are the address of the query's dimension 0 and the segment; the row loop
+// (dense_count_rows) takes one row per lane and trip -- a dense row does not fit rank_count_rows' two rows of registers at n = 256 --
+// with its keys, list and bins.
 template <int M>
-__device__ __forceinline__ void dense_count_rows(const float *__restrict__ qp, const float *__restrict__ g, int n, int64_t g0, int nrows,
-                                                 uint64_t row0, const uint64_t *list, uint32_t nkeys, uint64_t last, uint32_t *bins) {
-    for (int r = threadIdx.x; r < nrows; r += RC_BLK) {
-        float D[1];
-        dense_tile<M, 1>(qp, row_ptr(g, g0 + r, n), n, D);
-        const uint64_t key = ((uint64_t)dense_ord(D[0]) << 32) | (row0 + (uint64_t)r);
-        if (key <= last) atomicAdd(bins + keys_below(list, nkeys, key), 1u);
+struct DenseCount {
+    struct Regs {
+        const float *qp, *g;
+        int64_t g0;
+    };
+    const float *q;
+    int n;
+    __device__ __forceinline__ void load(Regs &r, int64_t qi, const uint64_t *__restrict__ g, int64_t g0) const {
+        r = Regs{row_ptr(q, qi, n), (const float *)g, g0};
     }
-}
-
-// One workgroup per (query, gallery segment), as rank_count_kernel: a list of at most list_cap keys lives in LDS with its bins, a
-// longer one is searched in global memory.
-template <int M>
-__global__ __launch_bounds__(RC_BLK) void dense_rank_count_kernel(const float *__restrict__ q, const float *__restrict__ g, int64_t G, int n,
-                                                                  int seg_rows, int64_t g_index_base, const int64_t *__restrict__ offsets,
-                                                                  const uint64_t *__restrict__ keys, int list_cap,
-                                                                  uint32_t *__restrict__ bins) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t lds_keys[];   // [list_cap] keys, then [list_cap] uint32 bins
-    const int64_t qi = blockIdx.x;
-    const int64_t off = offsets[qi];
-    const int64_t n64 = offsets[qi + 1] - off;
-    if (n64 <= 0) return;   // workgroup-uniform
-    const uint32_t nkeys = (uint32_t)n64;
-    const int tid = threadIdx.x;
-    const int64_t g0 = (int64_t)blockIdx.y * seg_rows;
-    const int nrows = (int)min((int64_t)seg_rows, G - g0);
-    const uint64_t *list = keys + off;
-    const uint64_t last = list[nkeys - 1];
-    const float *qp = row_ptr(q, qi, n);
-    const uint64_t row0 = (uint64_t)(g_index_base + g0);
-    if (nkeys <= (uint32_t)list_cap) {
-        uint32_t *lds_bins = (uint32_t *)(lds_keys + list_cap);
-        for (uint32_t i = tid; i < nkeys; i += RC_BLK) {
-            lds_keys[i] = list[i];
-            lds_bins[i] = 0u;
+    __device__ __forceinline__ void rows(const Regs &s, int nrows, uint64_t row0, const uint64_t *list, uint32_t nkeys, uint64_t last,
+                                         uint32_t *bins) const {
+        for (int r = threadIdx.x; r < nrows; r += RC_BLK) {
+            float D[1];
+            dense_tile<M, 1>(s.qp, row_ptr(s.g, s.g0 + r, n), n, D);
+            const uint64_t key = ((uint64_t)dense_ord(D[0]) << 32) | (row0 + (uint64_t)r);
+            if (key <= last) atomicAdd(bins + keys_below(list, nkeys, key), 1u);
         }
-        __syncthreads();
-        dense_count_rows<M>(qp, g, n, g0, nrows, row0, lds_keys, nkeys, last, lds_bins);
-        __syncthreads();
-        for (uint32_t i = tid; i < nkeys; i += RC_BLK) {
-            const uint32_t c = lds_bins[i];
-            if (c != 0u) atomicAdd(bins + off + i, c);
-        }
-    } else {
-        dense_count_rows<M>(qp, g, n, g0, nrows, row0, list, nkeys, last, bins + off);
     }
-}
+};
 
 int check_dense(const char *who, int n, int metric) {
     const std::string at = std::string(who) + ": ";
@@ -340,11 +316,19 @@ int check_dense(const char *who, int n, int metric) {
     return 0;
 }
 
-// what the collect and count entries check alike (W = 1 passes the shared check of W, which dense codes do not have)
-int check_dense_rank(const char *who, int64_t Qn, int64_t G, int n, int metric, int64_t g_index_base) {
-    if (int e = check_dense(who, n, metric)) return e;
-    return check_rank_sizes(who, Qn, G, 1, g_index_base);
-}
+// what rank_collect_run / rank_count_run take as the ranking (W = 1 passes the shared check of W, which dense codes do not have)
+struct DenseRanking {
+    static constexpr const char *with_offsets = "q and keys";
+    const float *q;
+    int n, metric;
+    int check(const char *who, int64_t Qn, int64_t G, int64_t g_index_base) const {
+        if (int e = check_dense(who, n, metric)) return e;
+        return check_rank_sizes(who, Qn, G, 1, g_index_base);
+    }
+    bool operands() const { return q != nullptr; }
+    template <class F> int collect(F &&f) const { return dispatch_metric(metric, [&](auto m) { return f(DenseRow<decltype(m)::value>{q, n}, 1); }); }
+    template <class F> int count(F &&f) const { return dispatch_metric(metric, [&](auto m) { return f(DenseCount<decltype(m)::value>{q, n}); }); }
+};
 
 }  // namespace
 
@@ -426,35 +410,13 @@ extern "C" int ch_dense_topk(const float *q, int64_t Qn, const float *g, int64_t
 extern "C" int ch_dense_rank_collect(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const void *q_labels,
                                      const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count,
                                      uint64_t *keys, void *stream) {
-    if (int e = check_dense_rank("dense_rank_collect", Qn, G, n, metric, g_index_base)) return e;
-    CH_REQUIRE(LW >= 0, "dense_rank_collect: negative LW");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(g && q_labels && g_labels && count, "dense_rank_collect: null pointer");
-    CH_REQUIRE(offsets == nullptr || (q && keys), "dense_rank_collect: null pointer (q and keys go with offsets)");
-    return dispatch_metric(metric, [&](auto m) {
-        return rank_collect_launch(DenseRow<decltype(m)::value>{q, (int)n}, Qn, (const uint64_t *)g, G, 1, q_labels, g_labels, (int)LW,
-                                   g_index_base, offsets, count, keys, (hipStream_t)stream);
-    });
+    return rank_collect_run("dense_rank_collect", DenseRanking{q, (int)n, (int)metric}, Qn, (const uint64_t *)g, G, q_labels, g_labels, (int)LW,
+                            g_index_base, offsets, count, keys, (hipStream_t)stream);
 }
 
 extern "C" int ch_dense_rank_count(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int64_t g_index_base,
                                    int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins,
                                    void *stream) {
-    if (int e = check_dense_rank("dense_rank_count", Qn, G, n, metric, g_index_base)) return e;
-    CH_REQUIRE(seg_rows >= 1, "dense_rank_count: seg_rows must be >= 1");
-    CH_REQUIRE(list_cap >= 1 && list_cap <= RC_MAX_LIST, "dense_rank_count: list_cap must be in [1, 8192]");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(q && g && offsets && keys && bins, "dense_rank_count: null pointer");
-    CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "dense_rank_count: too many gallery segments (raise seg_rows)");
-    return dispatch_metric(metric, [&](auto m) {
-        constexpr int M = decltype(m)::value;
-        const dim3 grid((unsigned)Qn, (unsigned)ceil_div64(G, seg_rows));
-        const size_t lds = (size_t)list_cap * (sizeof(uint64_t) + sizeof(uint32_t));
-        static ch_once_per_device lds_once;   // one per instance of this body, i.e. per kernel
-        if (int e = ch_func_max_lds((const void *)dense_rank_count_kernel<M>, RC_MAX_LIST * 12, lds_once)) return e;
-        hipLaunchKernelGGL((dense_rank_count_kernel<M>), grid, dim3(RC_BLK), lds, (hipStream_t)stream, q, g, G, (int)n, (int)seg_rows,
-                           g_index_base, offsets, keys, (int)list_cap, bins);
-        CH_LAUNCH_CHECK();
-        return 0;
-    });
+    return rank_count_run("dense_rank_count", DenseRanking{q, (int)n, (int)metric}, Qn, (const uint64_t *)g, G, g_index_base, (int)seg_rows,
+                          offsets, keys, (int)list_cap, bins, (hipStream_t)stream);
 }

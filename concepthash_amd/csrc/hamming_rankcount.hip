@@ -10,8 +10,9 @@
 //     AP          one lane per query walks its bins: prefix, remove_first, the fixed-point AP terms under up to 16 rank limits.
 // bins are integer sums over gallery rows: gallery segments (blockIdx.y) add up in any order and give the same bits.
 // Nothing of size Qn x G is written.
-// The collect and the count kernel are templates on the distance (hamming_shared.h); this file holds the weighted distance's two forms
-// for them, the AP pass and the entries.  hamming_ternary.hip instantiates the same two templates under the ternary distance.
+// The collect and the count kernel, their launches and the bodies of their entries are templates on the ranking (hamming_shared.h);
+// this file holds what the weighted ranking supplies to them -- its distance in two forms, its operands and their checks -- and the AP
+// pass.  hamming_ternary.hip and dense_rank.hip supply the same under the ternary and the dense distances.
 #include <algorithm>
 #include <string>
 
@@ -74,9 +75,11 @@ struct WeightedUniform {
     static constexpr int ROW = W;
     struct Regs {
         uint32_t qs[2 * W], ps[P][2 * W];
+        const uint64_t *gp;   // the segment's first row
     };
     const uint64_t *q, *planes;
-    __device__ __forceinline__ void load(Regs &r, int64_t qi) const {
+    __device__ __forceinline__ void load(Regs &r, int64_t qi, const uint64_t *__restrict__ g, int64_t g0) const {
+        r.gp = g + g0 * ROW;
 #pragma unroll
         for (int w = 0; w < W; ++w) {
             const uint64_t v = q[qi * W + w];
@@ -94,6 +97,10 @@ struct WeightedUniform {
         }
     }
     __device__ __forceinline__ static uint32_t at(const Regs &r, const uint64_t (&g)[W]) { return weighted_dist_uniform<W, P>(r.qs, r.ps, g); }
+    __device__ __forceinline__ void rows(const Regs &r, int nrows, uint64_t row0, const uint64_t *list, uint32_t n, uint64_t last,
+                                         uint32_t *bins) const {
+        rank_count_rows<WeightedUniform>(r, r.gp, nrows, row0, list, n, last, bins);
+    }
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -146,48 +153,40 @@ __global__ __launch_bounds__(256) void rank_ap_kernel(int64_t Qn, const int64_t 
     if (out_total != nullptr) out_total[qi] = (int32_t)(n - (remove_first ? frel : 0u));
 }
 
-// f(std::integral_constant<int, P>) for P in {4, 8}
-template <class F>
-int dispatch_p(int P, F &&f) {
-    if (P == 4) return f(std::integral_constant<int, 4>{});
-    return f(std::integral_constant<int, 8>{});
-}
-
-// what the collect and count entries check alike
-int check_scan_sizes(const char *who, int P, int64_t Qn, int64_t G, int W, int64_t g_index_base) {
-    CH_REQUIRE(P == 4 || P == 8, std::string(who) + ": P (weight bits) must be 4 or 8");
-    return check_rank_sizes(who, Qn, G, W, g_index_base);
-}
+// what rank_collect_run / rank_count_run (hamming_shared.h) take as the ranking
+struct WeightedRanking {
+    static constexpr const char *with_offsets = "q, planes and keys";
+    const uint64_t *q, *planes;
+    int P, W;
+    int check(const char *who, int64_t Qn, int64_t G, int64_t g_index_base) const {
+        CH_REQUIRE(P == 4 || P == 8, std::string(who) + ": P (weight bits) must be 4 or 8");
+        return check_rank_sizes(who, Qn, G, W, g_index_base);
+    }
+    bool operands() const { return q && planes; }
+    template <class F> int collect(F &&f) const { return f(WeightedRow{q, planes, P}, W); }
+    template <class F>
+    int count(F &&f) const {
+        return dispatch_w(W, [&](auto w) {
+            constexpr int Wc = decltype(w)::value;
+            return P == 4 ? f(WeightedUniform<Wc, 4>{q, planes}) : f(WeightedUniform<Wc, 8>{q, planes});
+        });
+    }
+};
 
 }  // namespace
 
 extern "C" int ch_hamming_rank_collect(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
                                        int32_t W, const void *q_labels, const void *g_labels, int32_t LW, int64_t g_index_base,
                                        const int64_t *offsets, uint32_t *count, uint64_t *keys, void *stream) {
-    if (int e = check_scan_sizes("hamming_rank_collect", P, Qn, G, W, g_index_base)) return e;
-    CH_REQUIRE(LW >= 0, "hamming_rank_collect: negative LW");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(g && q_labels && g_labels && count, "hamming_rank_collect: null pointer");
-    CH_REQUIRE(offsets == nullptr || (q && planes && keys), "hamming_rank_collect: null pointer (q, planes and keys go with offsets)");
-    return rank_collect_launch(WeightedRow{q, planes, (int)P}, Qn, g, G, (int)W, q_labels, g_labels, (int)LW, g_index_base, offsets, count,
-                               keys, (hipStream_t)stream);
+    return rank_collect_run("hamming_rank_collect", WeightedRanking{q, planes, (int)P, (int)W}, Qn, g, G, q_labels, g_labels, (int)LW,
+                            g_index_base, offsets, count, keys, (hipStream_t)stream);
 }
 
 extern "C" int ch_hamming_rank_count(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
                                      int32_t W, int64_t g_index_base, int32_t seg_rows, const int64_t *offsets, const uint64_t *keys,
                                      int32_t list_cap, uint32_t *bins, void *stream) {
-    if (int e = check_scan_sizes("hamming_rank_count", P, Qn, G, W, g_index_base)) return e;
-    CH_REQUIRE(seg_rows >= 1, "hamming_rank_count: seg_rows must be >= 1");
-    CH_REQUIRE(list_cap >= 1 && list_cap <= RC_MAX_LIST, "hamming_rank_count: list_cap must be in [1, 8192]");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(q && planes && g && offsets && keys && bins, "hamming_rank_count: null pointer");
-    CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "hamming_rank_count: too many gallery segments (raise seg_rows)");
-    return dispatch_w(W, [&](auto w) {
-        return dispatch_p(P, [&](auto p) {
-            return rank_count_launch(WeightedUniform<decltype(w)::value, decltype(p)::value>{q, planes}, Qn, g, G, g_index_base, (int)seg_rows,
-                                     offsets, keys, (int)list_cap, bins, (hipStream_t)stream);
-        });
-    });
+    return rank_count_run("hamming_rank_count", WeightedRanking{q, planes, (int)P, (int)W}, Qn, g, G, g_index_base, (int)seg_rows, offsets,
+                          keys, (int)list_cap, bins, (hipStream_t)stream);
 }
 
 extern "C" int ch_hamming_rank_ap(int64_t Qn, const int64_t *offsets, const uint32_t *bins, const int64_t *rank_limits, int32_t nlimits,

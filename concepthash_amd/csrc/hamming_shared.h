@@ -346,8 +346,9 @@ int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Evaluation by rank counting (hamming_rankcount.hip: the weighted distance; hamming_ternary.hip: the ternary one): the collect and
-// the count pass, with the distance a template argument.  The ranking is ascending key(g) = dist(q, g) << 32 | global index of g.
+// Evaluation by rank counting: the collect and the count pass -- kernels, launches and the body of their entries -- once, with the
+// ranking a template argument (hamming_rankcount.hip: the weighted distance; hamming_ternary.hip: the ternary one; dense_rank.hip: the
+// three dense ones).  The ranking is ascending key(g) = dist(q, g) << 32 | global index of g.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int RC_BLK = 256;          // lanes of a workgroup of the two scans
 constexpr int RC_MAX_LIST = 8192;    // longest list held in LDS: 8 B per key + 4 B per bin = 96 KB
@@ -463,8 +464,8 @@ __device__ __forceinline__ uint32_t keys_below(const uint64_t *list, uint32_t n,
 // The rows [0, nrows) of a segment against one query, two rows per lane and trip (both rows' loads are out before the first distance).
 // list / bins: the query's sorted keys and its bins, in LDS or in global memory.  A key above `last` = list[n - 1] is done after the
 // compare; any other has keys_below <= n - 1, so bins[n] does not exist.
-// UniDist: the distance with the query's words WAVE-UNIFORM (UniDist::Regs, filled by load(regs, qi)) and the gallery row -- ROW
-// 64-bit words -- the lane's own: UniDist::at(regs, row words) -> uint32_t.
+// UniDist: a bit-plane distance with the query's words WAVE-UNIFORM (UniDist::Regs, filled by its load()) and the gallery row -- ROW
+// 64-bit words -- the lane's own: UniDist::at(regs, row words) -> uint32_t.  Its rows() (below) is one call of this on regs.gp.
 template <class UniDist>
 __device__ __forceinline__ void rank_count_rows(const typename UniDist::Regs &regs, const uint64_t *__restrict__ gp, int nrows,
                                                 uint64_t row0, const uint64_t *list, uint32_t n, uint64_t last, uint32_t *bins) {
@@ -488,8 +489,11 @@ __device__ __forceinline__ void rank_count_rows(const typename UniDist::Regs &re
 // One workgroup per (query, gallery segment).  A query without a relevant row ends at its first branch.  A list of at most list_cap
 // keys lives in LDS with its bins, which leave through global atomic adds at the end (segments add up); a longer one is searched where
 // it lies, in global memory, and its bins are added to directly.
-template <class UniDist>
-__global__ __launch_bounds__(RC_BLK) void rank_count_kernel(UniDist dist, const uint64_t *__restrict__ g, int64_t G, int seg_rows,
+// Count: what a ranking brings to this shell -- the workgroup's registers (Count::Regs, filled by load(regs, qi, g, g0): the query and
+// where the segment's rows begin) and the row loop rows(regs, nrows, row0, list, n, last, bins): rank_count_rows for the bit-plane
+// distances, its own for the dense ones.
+template <class Count>
+__global__ __launch_bounds__(RC_BLK) void rank_count_kernel(Count dist, const uint64_t *__restrict__ g, int64_t G, int seg_rows,
                                                             int64_t g_index_base, const int64_t *__restrict__ offsets,
                                                             const uint64_t *__restrict__ keys, int list_cap,
                                                             uint32_t *__restrict__ bins) {
@@ -502,11 +506,10 @@ __global__ __launch_bounds__(RC_BLK) void rank_count_kernel(UniDist dist, const 
     const int tid = threadIdx.x;
     const int64_t g0 = (int64_t)blockIdx.y * seg_rows;
     const int nrows = (int)min((int64_t)seg_rows, G - g0);
-    typename UniDist::Regs regs;
-    dist.load(regs, qi);
+    typename Count::Regs regs;
+    dist.load(regs, qi, g, g0);
     const uint64_t *list = keys + off;
     const uint64_t last = list[n - 1];
-    const uint64_t *gp = g + g0 * UniDist::ROW;
     const uint64_t row0 = (uint64_t)(g_index_base + g0);
     if (n <= (uint32_t)list_cap) {
         uint32_t *lds_bins = (uint32_t *)(lds_keys + list_cap);
@@ -515,18 +518,18 @@ __global__ __launch_bounds__(RC_BLK) void rank_count_kernel(UniDist dist, const 
             lds_bins[i] = 0u;
         }
         __syncthreads();
-        rank_count_rows<UniDist>(regs, gp, nrows, row0, lds_keys, n, last, lds_bins);
+        dist.rows(regs, nrows, row0, lds_keys, n, last, lds_bins);
         __syncthreads();
         for (uint32_t i = tid; i < n; i += RC_BLK) {
             const uint32_t c = lds_bins[i];
             if (c != 0u) atomicAdd(bins + off + i, c);
         }
     } else {
-        rank_count_rows<UniDist>(regs, gp, nrows, row0, list, n, last, bins + off);
+        dist.rows(regs, nrows, row0, list, n, last, bins + off);
     }
 }
 
-// what the collect and count entries of either distance check alike, behind the checks of their own operands
+// what the collect and count entries of every ranking check alike, next to the checks of their own operands
 int check_rank_sizes(const char *who, int64_t Qn, int64_t G, int W, int64_t g_index_base) {
     const std::string at = std::string(who) + ": ";
     CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
@@ -536,8 +539,7 @@ int check_rank_sizes(const char *who, int64_t Qn, int64_t G, int W, int64_t g_in
     return 0;
 }
 
-// the launch of a collect pass on checked arguments: segments so that a small query set still fills the chip; a workgroup walks at
-// least 1,024 labels
+// the launch of a collect pass on checked arguments: segments so that a small query set fills the chip, of at least 1,024 labels
 template <class RowDist>
 int rank_collect_launch(const RowDist &dist, int64_t Qn, const uint64_t *g, int64_t G, int W, const void *q_labels, const void *g_labels,
                         int LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count, uint64_t *keys, hipStream_t s) {
@@ -546,28 +548,57 @@ int rank_collect_launch(const RowDist &dist, int64_t Qn, const uint64_t *g, int6
                                            std::min<int64_t>(std::min<int64_t>(65535, ceil_div64(G, 1024)), ceil_div64(4096, tiles)));
     const int64_t rows = ceil_div64(G, nseg);   // at most 2^27: a queue entry of the write pass holds the row in its segment
     const dim3 grid((unsigned)tiles, (unsigned)ceil_div64(G, rows));
-    if (offsets == nullptr)
-        hipLaunchKernelGGL((rank_collect_kernel<false, RowDist>), grid, dim3(RC_BLK), 0, s, dist, Qn, g, G, W, q_labels, g_labels, LW,
-                           (int)rows, g_index_base, offsets, count, keys);
-    else
-        hipLaunchKernelGGL((rank_collect_kernel<true, RowDist>), grid, dim3(RC_BLK), 0, s, dist, Qn, g, G, W, q_labels, g_labels, LW,
-                           (int)rows, g_index_base, offsets, count, keys);
+    const auto kernel = offsets == nullptr ? rank_collect_kernel<false, RowDist> : rank_collect_kernel<true, RowDist>;
+    hipLaunchKernelGGL(kernel, grid, dim3(RC_BLK), 0, s, dist, Qn, g, G, W, q_labels, g_labels, LW, (int)rows, g_index_base, offsets, count,
+                       keys);
     CH_LAUNCH_CHECK();
     return 0;
 }
 
 // ... and of a count pass
-template <class UniDist>
-int rank_count_launch(const UniDist &dist, int64_t Qn, const uint64_t *g, int64_t G, int64_t g_index_base, int seg_rows,
+template <class Count>
+int rank_count_launch(const Count &dist, int64_t Qn, const uint64_t *g, int64_t G, int64_t g_index_base, int seg_rows,
                       const int64_t *offsets, const uint64_t *keys, int list_cap, uint32_t *bins, hipStream_t s) {
     const dim3 grid((unsigned)Qn, (unsigned)ceil_div64(G, seg_rows));
     const size_t lds = (size_t)list_cap * (sizeof(uint64_t) + sizeof(uint32_t));
     static ch_once_per_device lds_once;   // one per instance of this body, i.e. per kernel
-    if (int e = ch_func_max_lds((const void *)rank_count_kernel<UniDist>, RC_MAX_LIST * 12, lds_once)) return e;
-    hipLaunchKernelGGL((rank_count_kernel<UniDist>), grid, dim3(RC_BLK), lds, s, dist, g, G, seg_rows, g_index_base, offsets, keys, list_cap,
+    if (int e = ch_func_max_lds((const void *)rank_count_kernel<Count>, RC_MAX_LIST * 12, lds_once)) return e;
+    hipLaunchKernelGGL((rank_count_kernel<Count>), grid, dim3(RC_BLK), lds, s, dist, g, G, seg_rows, g_index_base, offsets, keys, list_cap,
                        bins);
     CH_LAUNCH_CHECK();
     return 0;
+}
+
+// The bodies of the ch_*_rank_collect and ch_*_rank_count entries, in the manner of topk_run: the checks in the order the entries have
+// always made them (`who` opens the messages), then the launch.  A ranking holds its operands: check() makes its own checks and
+// check_rank_sizes in its own order, operands() says whether the query side is there (with_offsets names it in a refusal), and
+// collect(f) / count(f) call f(RowDist, W) / f(Count) under the instance that its sizes select.
+template <class Ranking>
+int rank_collect_run(const char *who, const Ranking &rk, int64_t Qn, const uint64_t *g, int64_t G, const void *q_labels,
+                     const void *g_labels, int LW, int64_t g_index_base, const int64_t *offsets, uint32_t *count, uint64_t *keys,
+                     hipStream_t s) {
+    const std::string at = std::string(who) + ": ";
+    if (int e = rk.check(who, Qn, G, g_index_base)) return e;
+    CH_REQUIRE(LW >= 0, at + "negative LW");
+    if (Qn == 0 || G == 0) return 0;
+    CH_REQUIRE(g && q_labels && g_labels && count, at + "null pointer");
+    CH_REQUIRE(offsets == nullptr || (rk.operands() && keys), at + "null pointer (" + Ranking::with_offsets + " go with offsets)");
+    return rk.collect([&](const auto &dist, int W) {
+        return rank_collect_launch(dist, Qn, g, G, W, q_labels, g_labels, LW, g_index_base, offsets, count, keys, s);
+    });
+}
+
+template <class Ranking>
+int rank_count_run(const char *who, const Ranking &rk, int64_t Qn, const uint64_t *g, int64_t G, int64_t g_index_base, int seg_rows,
+                   const int64_t *offsets, const uint64_t *keys, int list_cap, uint32_t *bins, hipStream_t s) {
+    const std::string at = std::string(who) + ": ";
+    if (int e = rk.check(who, Qn, G, g_index_base)) return e;
+    CH_REQUIRE(seg_rows >= 1, at + "seg_rows must be >= 1");
+    CH_REQUIRE(list_cap >= 1 && list_cap <= RC_MAX_LIST, at + "list_cap must be in [1, 8192]");
+    if (Qn == 0 || G == 0) return 0;
+    CH_REQUIRE(rk.operands() && g && offsets && keys && bins, at + "null pointer");
+    CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, at + "too many gallery segments (raise seg_rows)");
+    return rk.count([&](const auto &dist) { return rank_count_launch(dist, Qn, g, G, g_index_base, seg_rows, offsets, keys, list_cap, bins, s); });
 }
 
 }  // namespace

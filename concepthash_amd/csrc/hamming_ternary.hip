@@ -23,9 +23,9 @@
 // separate instruction for the sign word.  No instance uses scratch; W <= 2 scans blocks of 4 rows, W >= 3 of 2 (two buffers of
 // 16 W SGPRs would not fit at 4).  The rank-count scan holds the QUERY's words in SGPRs and compiles to the same four from C++.
 //
-// The evaluation (ch_ternary_rank_collect / ch_ternary_rank_count) is the collect and count passes of hamming_shared.h under K, with
-// the CSR buffers and the key K << 32 | global index of hamming_rankcount.hip; ch_hamming_rank_ap turns the bins into AP integers
-// unchanged.  K does not go through the LDS-histogram passes of hamming.hip: 2 nbit + 1 buckets do not fit their counters at W = 4.
+// The evaluation (ch_ternary_rank_collect / ch_ternary_rank_count) is the collect and count passes of hamming_shared.h -- kernels,
+// launches and entry bodies -- under K (TernaryRanking below), with the CSR buffers and the key K << 32 | global index of
+// hamming_rankcount.hip; ch_hamming_rank_ap turns the bins into AP integers unchanged.  K does not go through the LDS-histogram passes of hamming.hip: 2 nbit + 1 buckets do not fit their counters at W = 4.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -113,10 +113,12 @@ struct TernaryUniform {
     static constexpr int ROW = 2 * W;
     struct Regs {
         uint32_t sq[2 * W], mq[2 * W], nbit;
+        const uint64_t *gp;   // the segment's first row
     };
     const uint64_t *q;
     uint32_t nbit;
-    __device__ __forceinline__ void load(Regs &r, int64_t qi) const {
+    __device__ __forceinline__ void load(Regs &r, int64_t qi, const uint64_t *__restrict__ g, int64_t g0) const {
+        r.gp = g + g0 * ROW;
 #pragma unroll
         for (int w = 0; w < W; ++w) {
             const uint64_t s = q[qi * 2 * W + w], m = q[qi * 2 * W + W + w];
@@ -138,6 +140,10 @@ struct TernaryUniform {
             x = bcnt_acc((r.sq[2 * w + 1] ^ (uint32_t)(g[w] >> 32)) & t1, x);
         }
         return r.nbit - a + 2u * x;
+    }
+    __device__ __forceinline__ void rows(const Regs &r, int nrows, uint64_t row0, const uint64_t *list, uint32_t n, uint64_t last,
+                                         uint32_t *bins) const {
+        rank_count_rows<TernaryUniform>(r, r.gp, nrows, row0, list, n, last, bins);
     }
 };
 
@@ -216,12 +222,23 @@ struct TernaryScan {
     }
 };
 
-// what the collect and count entries check alike
-int check_ternary_sizes(const char *who, int64_t Qn, int64_t G, int W, int nbit, int64_t g_index_base) {
-    if (int e = check_rank_sizes(who, Qn, G, W, g_index_base)) return e;
-    CH_REQUIRE(nbit >= 1 && nbit <= 64 * W, std::string(who) + ": nbit must be in [1, 64 W]");
-    return 0;
-}
+// what rank_collect_run / rank_count_run (hamming_shared.h) take as the ranking
+struct TernaryRanking {
+    static constexpr const char *with_offsets = "q and keys";
+    const uint64_t *q;
+    int W, nbit;
+    int check(const char *who, int64_t Qn, int64_t G, int64_t g_index_base) const {
+        if (int e = check_rank_sizes(who, Qn, G, W, g_index_base)) return e;
+        CH_REQUIRE(nbit >= 1 && nbit <= 64 * W, std::string(who) + ": nbit must be in [1, 64 W]");
+        return 0;
+    }
+    bool operands() const { return q != nullptr; }
+    template <class F> int collect(F &&f) const { return f(TernaryRow{q, (uint32_t)nbit}, W); }
+    template <class F>
+    int count(F &&f) const {
+        return dispatch_w(W, [&](auto w) { return f(TernaryUniform<decltype(w)::value>{q, (uint32_t)nbit}); });
+    }
+};
 
 }  // namespace
 
@@ -266,26 +283,13 @@ extern "C" int ch_ternary_topk(const uint64_t *q, int64_t Qn, const uint64_t *g,
 extern "C" int ch_ternary_rank_collect(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit,
                                        const void *q_labels, const void *g_labels, int32_t LW, int64_t g_index_base, const int64_t *offsets,
                                        uint32_t *count, uint64_t *keys, void *stream) {
-    if (int e = check_ternary_sizes("ternary_rank_collect", Qn, G, W, nbit, g_index_base)) return e;
-    CH_REQUIRE(LW >= 0, "ternary_rank_collect: negative LW");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(g && q_labels && g_labels && count, "ternary_rank_collect: null pointer");
-    CH_REQUIRE(offsets == nullptr || (q && keys), "ternary_rank_collect: null pointer (q and keys go with offsets)");
-    return rank_collect_launch(TernaryRow{q, (uint32_t)nbit}, Qn, g, G, (int)W, q_labels, g_labels, (int)LW, g_index_base, offsets, count,
-                               keys, (hipStream_t)stream);
+    return rank_collect_run("ternary_rank_collect", TernaryRanking{q, (int)W, (int)nbit}, Qn, g, G, q_labels, g_labels, (int)LW, g_index_base,
+                            offsets, count, keys, (hipStream_t)stream);
 }
 
 extern "C" int ch_ternary_rank_count(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit,
                                      int64_t g_index_base, int32_t seg_rows, const int64_t *offsets, const uint64_t *keys,
                                      int32_t list_cap, uint32_t *bins, void *stream) {
-    if (int e = check_ternary_sizes("ternary_rank_count", Qn, G, W, nbit, g_index_base)) return e;
-    CH_REQUIRE(seg_rows >= 1, "ternary_rank_count: seg_rows must be >= 1");
-    CH_REQUIRE(list_cap >= 1 && list_cap <= RC_MAX_LIST, "ternary_rank_count: list_cap must be in [1, 8192]");
-    if (Qn == 0 || G == 0) return 0;
-    CH_REQUIRE(q && g && offsets && keys && bins, "ternary_rank_count: null pointer");
-    CH_REQUIRE(ceil_div64(G, seg_rows) <= 65535, "ternary_rank_count: too many gallery segments (raise seg_rows)");
-    return dispatch_w(W, [&](auto w) {
-        return rank_count_launch(TernaryUniform<decltype(w)::value>{q, (uint32_t)nbit}, Qn, g, G, g_index_base, (int)seg_rows, offsets, keys,
-                                 (int)list_cap, bins, (hipStream_t)stream);
-    });
+    return rank_count_run("ternary_rank_count", TernaryRanking{q, (int)W, (int)nbit}, Qn, g, G, g_index_base, (int)seg_rows, offsets, keys,
+                          (int)list_cap, bins, (hipStream_t)stream);
 }

@@ -132,13 +132,7 @@ def hamming_topk_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor
                           stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """hamming_topk with dist = sum_p 2^p popcount((q ^ g) & planes[:, p]): the weighted distance of `weight_planes(codes)` with
     q = pack_sign(codes).  Lists of gallery shards merge with `topk_merge` as the unweighted ones do."""
-    q, g = _check_packed(q, g)
-    Qn, W = q.shape
-    if planes.dtype != torch.int64 or planes.device != q.device or planes.dim() != 3 or planes.shape[0] != Qn or planes.shape[2] != W \
-            or planes.shape[1] not in WEIGHT_BITS:
-        raise ValueError(f"planes must be an int64 tensor [{Qn}, 4 or 8, {W}] on the queries' device, got {planes.dtype} "
-                         f"{tuple(planes.shape)} on {planes.device}")
-    planes = planes.contiguous()
+    q, planes, g = _check_weighted(q, planes, g)
     return _topk("ch_hamming_topk_weighted", q, g, k, g_index_base, stream, (_lib.ptr(planes), planes.shape[1]),
                  workspace="ch_hamming_topk_weighted_workspace")
 
@@ -437,6 +431,27 @@ def tie_hits(bucket_counts: torch.Tensor, ks: Sequence[int], remove_first: bool 
     return out
 
 
+def parse_limits(R, ks: Sequence[int]):
+    """The R (an int, or a list or tuple of them) and ks of an evaluation -> (Rs, ks, many): lists of ints, and whether R was a list, i.e.
+    whether mAP / S / nrel / ap come back as lists.  k < 1: ValueError."""
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    many = isinstance(R, (list, tuple))
+    return ([int(r) for r in R] if many else [int(R)]), ks, many
+
+
+def pick_limits(x, idx_of, nR: int, many: bool):
+    """The rows of a per-limit result x (`normalize_limits`' idx_of) that belong to the R: a list of them, or the one of a scalar R."""
+    return [x[idx_of[i]] for i in range(nR)] if many else x[idx_of[0]]
+
+
+def result_dict(sm: dict, S, nrel, total, idx_of, nR: int, many: bool) -> dict:
+    """The keys every evaluation returns, from `summarize`'s statistics and the integers of the AP pass."""
+    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total, mAP=sm["mAPs"] if many else sm["mAPs"][0],
+                S=pick_limits(S, idx_of, nR, many), nrel=pick_limits(nrel, idx_of, nR, many), ap=sm["aps"] if many else sm["aps"][0])
+
+
 TIE_KEYS = ("mAP_low", "mAP_high", "ap_low", "ap_high", "S_low", "S_high", "nrel_low", "nrel_high", "precisions_low", "precisions_high",
             "recalls_low", "recalls_high", "hits_low", "hits_high")
 
@@ -450,7 +465,7 @@ def tie_results(bucket_counts: torch.Tensor, Rs: Sequence[int], ks: Sequence[int
     total = torch.zeros(Qn, dtype=torch.int32, device=bucket_counts.device)      # no k here: summarize() uses it for R@k only
     lo = summarize(S_lo, n_lo, total, idx_of, Rs, [], skip_queries_without_relevant)
     hi = summarize(S_hi, n_hi, total, idx_of, Rs, [], skip_queries_without_relevant)
-    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
+    pick = lambda x: pick_limits(x, idx_of, len(Rs), many)
     first = (lambda x: x) if many else (lambda x: x[0])
     out = dict(mAP_low=first(lo["mAPs"]), mAP_high=first(hi["mAPs"]), ap_low=first(lo["aps"]), ap_high=first(hi["aps"]),
                S_low=pick(S_lo), S_high=pick(S_hi), nrel_low=pick(n_lo), nrel_high=pick(n_hi))
@@ -858,11 +873,7 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
     Qn, W = q.shape
     ql, gl = q_labels.to(dev), gal.labels.to(dev)
     q_lab, g_lab, LW = ops.prepare_labels(ql, gl, single)
-    ks = [int(k) for k in ks]
-    if any(k <= 0 for k in ks):
-        raise ValueError("P@k / R@k need k >= 1")
-    many = isinstance(R, (list, tuple))
-    Rs = [int(r) for r in R] if many else [int(R)]
+    Rs, ks, many = parse_limits(R, ks)
     if Qn == 0 or gal.rows == 0:
         return empty_result(Qn, W, dev, Rs, ks, many, tie_bracket, radii)
     # relevance of every query's rank-1 row (the self-match when the test set is the database)
@@ -882,9 +893,7 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
     if remove_first:
         total = total - first_rel
     sm = ops.summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
-    out = dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
-               mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+    out = result_dict(sm, S, nrel, total, idx_of, len(Rs), many)
     if tie_bracket:
         out.update(ops.tie_results(counts2, Rs, ks, remove_first, many, skip_queries_without_relevant))
     if radii is not None:
@@ -916,9 +925,11 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# evaluation under the weighted (asymmetric) distance, by rank counting (csrc/hamming_rankcount.hip)
+# evaluation by rank counting: ONE pipeline (collect, sort, count, AP) under the weighted (asymmetric) distance
+# (csrc/hamming_rankcount.hip), the ternary one (csrc/hamming_ternary.hip) and the dense ones (csrc/dense_rank.hip); the sections
+# below hold what each of those rankings supplies to it
 # ---------------------------------------------------------------------------------------------------------------
-RANK_LIST_MAX = 8192   # longest list of relevant keys a workgroup of the rank-count scan holds in LDS (csrc/hamming_rankcount.hip)
+RANK_LIST_MAX = 8192   # longest list of relevant keys a workgroup of the rank-count scan holds in LDS (csrc/hamming_shared.h)
 
 
 def rank_seg_rows(Qn: int, G: int) -> int:
@@ -938,69 +949,65 @@ def _check_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor):
     return q, planes.contiguous(), g
 
 
-def rank_collect(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,
-                 g_index_base: int = 0, stream=None):
-    """The keys D << 32 | global index of every query's relevant rows, as CSR -> (offsets int64 [Qn + 1], keys int64 [total], UNSORTED
-    inside a slice, longest slice).  Two ch_hamming_rank_collect launches (count, then write) around the prefix; reads the total and the
-    longest slice back (one synchronisation).  q_lab / g_lab / LW: `prepare_labels`."""
+def _collect_pass(entry: str, operands, Qn: int, G: int, dev, q_lab, g_lab, LW: int, g_index_base: int, stream):
+    """The collect pass of a ranking on checked operands -> (offsets int64 [Qn + 1], keys int64 [total], UNSORTED inside a slice, longest
+    slice).  Two launches of the ch_*_rank_collect `entry` (count, then write) around the prefix; reads the total and the longest slice
+    back (one synchronisation).  `operands` are the entry's own arguments, in front of the labels."""
     lib = _lib.load()
-    q, planes, g = _check_weighted(q, planes, g)
-    Qn, W = q.shape
-    G, P = g.shape[0], planes.shape[1]
-    count = torch.zeros(Qn, dtype=torch.int32, device=q.device)
-    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q.device)
+    count = torch.zeros(Qn, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=dev)
     if Qn == 0 or G == 0:
-        return offsets, torch.empty(0, dtype=torch.int64, device=q.device), 0
+        return offsets, torch.empty(0, dtype=torch.int64, device=dev), 0
 
     def call(off, keys):
-        _lib.check(lib.ch_hamming_rank_collect(_lib.ptr(q), _lib.ptr(planes), P, Qn, _lib.ptr(g), G, W, _lib.ptr(q_lab), _lib.ptr(g_lab),
-                                               LW, int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
-                                               _lib.stream_ptr(stream)), "ch_hamming_rank_collect")
+        _lib.check(getattr(lib, entry)(*operands, _lib.ptr(q_lab), _lib.ptr(g_lab), LW, int(g_index_base), _lib.ptr(off), _lib.ptr(count),
+                                       _lib.ptr(keys), _lib.stream_ptr(stream)), entry)
 
-    with _dev_guard(q):
+    with _dev_guard(count):
         call(None, None)
         offsets[1:] = count.cumsum(0, dtype=torch.int64)
         total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
-        keys = torch.empty(total, dtype=torch.int64, device=q.device)
+        keys = torch.empty(total, dtype=torch.int64, device=dev)
         if total:
             count.zero_()
             call(offsets, keys)
     return offsets, keys, int(longest)
 
 
-def sort_slices(offsets: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
-    """Every CSR slice of `keys` ascending.  The keys are below 2^48 (D < 2^16, a 32-bit index), so their order as int64 is their order
-    as uint64, and up to 32,767 slices the slice number fits above them: ONE sort of slice << 48 | key.  More slices: a sort of the flat
-    buffer, then a stable sort by slice."""
+def _count_pass(entry: str, operands, Qn: int, G: int, dev, offsets, keys, list_cap: int, seg_rows, g_index_base: int, bins, stream):
+    """The count pass of a ranking on checked operands: the Qn x G scan of the ch_*_rank_count `entry` -> bins int32 [total] (uint32 bit
+    patterns); `bins`, where given, is added into (gallery shards).  `operands` are the entry's own arguments, in front of g_index_base."""
+    lib = _lib.load()
+    if bins is None:
+        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=dev)
+    if Qn == 0 or G == 0 or keys.numel() == 0:
+        return bins
+    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
+    with _dev_guard(bins):
+        _lib.check(getattr(lib, entry)(*operands, int(g_index_base), seg, _lib.ptr(offsets), _lib.ptr(keys), int(list_cap), _lib.ptr(bins),
+                                       _lib.stream_ptr(stream)), entry)
+    return bins
+
+
+def sort_slices(offsets: torch.Tensor, keys: torch.Tensor, wide: bool = False) -> torch.Tensor:
+    """Every CSR slice of `keys` ascending AS UINT64.  Keys below 2^48 (a distance below 2^16 over a 32-bit index; `wide` = False says
+    so) order alike as int64, and up to 32,767 slices the slice number fits above them: ONE sort of slice << 48 | key.  Keys that use all
+    64 bits (`wide`: the dense ones), or more slices: flipping the top bit maps uint64 order onto int64 order -- harmless for small
+    keys --; one sort of the flat buffer, then a stable sort by slice."""
     if keys.numel() == 0:
         return keys
     n = offsets[1:] - offsets[:-1]
     owner = torch.repeat_interleave(torch.arange(n.numel(), device=keys.device), n, output_size=keys.numel())
-    if n.numel() <= 0x7FFF:
+    if not wide and n.numel() <= 0x7FFF:
         return (torch.sort(keys | (owner << 48))[0] & ((1 << 48) - 1)).contiguous()
-    keys, order = torch.sort(keys)
-    return keys[torch.sort(owner[order], stable=True)[1]].contiguous()
+    top = -(1 << 63)
+    flipped, order = torch.sort(keys ^ top)
+    return (flipped[torch.sort(owner[order], stable=True)[1]] ^ top).contiguous()
 
 
-def rank_count(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int,
-               seg_rows: Optional[int] = None, g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
-    """The Qn x G scan -> bins int32 [total] (uint32 bit patterns): bins[offsets[i] + pos] = gallery rows with exactly pos of query i's
-    relevant keys below their own key (rows above the largest relevant key are not counted).  keys: `sort_slices(rank_collect(...))`.
-    `bins`, where given, is added into (gallery shards)."""
-    lib = _lib.load()
-    q, planes, g = _check_weighted(q, planes, g)
-    Qn, W = q.shape
-    G = g.shape[0]
-    if bins is None:
-        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q.device)
-    if Qn == 0 or G == 0 or keys.numel() == 0:
-        return bins
-    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
-    with _dev_guard(q):
-        _lib.check(lib.ch_hamming_rank_count(_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W, int(g_index_base), seg,
-                                             _lib.ptr(offsets), _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)),
-                   "ch_hamming_rank_count")
-    return bins
+def sort_slices_unsigned(offsets: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
+    """`sort_slices` of keys that use all 64 bits (int64 holding uint64 bit patterns)."""
+    return sort_slices(offsets, keys, wide=True)
 
 
 def rank_ap(offsets: torch.Tensor, bins: torch.Tensor, rank_limits: Sequence[int], remove_first: bool = False, stream=None):
@@ -1023,6 +1030,56 @@ def rank_ap(offsets: torch.Tensor, bins: torch.Tensor, rank_limits: Sequence[int
     return S, nrel, total
 
 
+def _evaluate_by_rank_counting(Qn: int, G: int, W: int, dev, operands, collect, count, wide: bool, q_labels, g_labels, R, ks,
+                               remove_first: bool, skip_queries_without_relevant: bool, seg_rows, list_cap) -> dict:
+    """The evaluation behind `evaluate_weighted`, `evaluate_ternary` and `evaluate_dense`, which have checked their arguments: the keys
+    of each query's relevant rows are collected and sorted, one Qn x G scan counts how many gallery rows fall between consecutive ones,
+    and one lane per query turns the counts into ranks and AP terms (`rank_ap`; more than 16 limits repeat that last launch only).
+    What describes the ranking: Qn, G, the device, the W that `empty_result` wants; `operands()` -> the scan operands, prepared only
+    once there is something to scan; its two passes, collect(*operands, q_lab, g_lab, LW) and count(*operands, offsets, keys, list_cap,
+    seg_rows); `wide`: its keys use all 64 bits (`sort_slices`)."""
+    Rs, ks, many = parse_limits(R, ks)
+    if Qn == 0 or G == 0:
+        return empty_result(Qn, W, dev, Rs, ks, many, False, None)
+    ops = operands()
+    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
+    limits, idx_of = normalize_limits(Rs + ks)
+    offsets, keys, longest = collect(*ops, q_lab, g_lab, LW)
+    keys = sort_slices(offsets, keys, wide)
+    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
+    bins = count(*ops, offsets, keys, cap, seg_rows)
+    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
+    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
+    return result_dict(sm, S, nrel, total, idx_of, len(Rs), many)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ... under the weighted (asymmetric) distance (csrc/hamming_rankcount.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def rank_collect(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,
+                 g_index_base: int = 0, stream=None):
+    """The keys D << 32 | global index of every query's relevant rows, as CSR -> (offsets int64 [Qn + 1], keys int64 [total], UNSORTED
+    inside a slice, longest slice).  Two ch_hamming_rank_collect launches (count, then write) around the prefix; reads the total and the
+    longest slice back (one synchronisation).  q_lab / g_lab / LW: `prepare_labels`."""
+    q, planes, g = _check_weighted(q, planes, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    return _collect_pass("ch_hamming_rank_collect", (_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W), Qn, G, q.device,
+                         q_lab, g_lab, LW, g_index_base, stream)
+
+
+def rank_count(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int,
+               seg_rows: Optional[int] = None, g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """The Qn x G scan -> bins int32 [total] (uint32 bit patterns): bins[offsets[i] + pos] = gallery rows with exactly pos of query i's
+    relevant keys below their own key (rows above the largest relevant key are not counted).  keys: `sort_slices(rank_collect(...))`.
+    `bins`, where given, is added into (gallery shards)."""
+    q, planes, g = _check_weighted(q, planes, g)
+    Qn, W = q.shape
+    G = g.shape[0]
+    return _count_pass("ch_hamming_rank_count", (_lib.ptr(q), _lib.ptr(planes), planes.shape[1], Qn, _lib.ptr(g), G, W), Qn, G, q.device,
+                       offsets, keys, list_cap, seg_rows, g_index_base, bins, stream)
+
+
 def evaluate_weighted(codes: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, bits: int = 8,
                       mask: Optional[torch.Tensor] = None, R=-1, ks: Sequence[int] = (1, 5, 10), remove_first: bool = False,
                       skip_queries_without_relevant: bool = False, seg_rows: Optional[int] = None,
@@ -1031,11 +1088,9 @@ def evaluate_weighted(codes: torch.Tensor, g: torch.Tensor, q_labels: torch.Tens
     (D, gallery index), D = sum_j w_ij [bit_j(q_i) != bit_j(g)] with the query's own |code| quantised to `bits` (4 or 8) bits as its
     weights.  codes: [Qn, nbit] fp32, the real-valued query codes (the queries are pack_sign(codes) and weight_planes(codes, bits,
     mask)); g: the packed gallery; mask as `weight_planes` takes it.  Returns the keys of `evaluate` -- mAP, precisions, recalls, hits,
-    total, S, nrel, ap, lists under a list R -- with the same integers' meaning, exact for any R and k.
-    The keys of each query's relevant rows are collected and sorted, one Qn x G scan counts how many gallery rows fall between
-    consecutive ones (`rank_count`), and one lane per query turns the counts into ranks and AP terms; more than 16 limits repeat that
-    last launch only.  seg_rows / list_cap (tests): the scan's segmentation and the list length up to which a list is searched in LDS
-    -- neither changes a result."""
+    total, S, nrel, ap, lists under a list R -- with the same integers' meaning, exact for any R and k, by rank counting
+    (`_evaluate_by_rank_counting`).  seg_rows / list_cap (tests): the scan's segmentation and the list length up to which a list is
+    searched in LDS -- neither changes a result."""
     if codes.dim() != 2:
         raise ValueError("codes must be 2-D [Qn, nbit] real-valued query codes")
     if g.dtype != torch.int64 or g.dim() != 2:
@@ -1046,29 +1101,13 @@ def evaluate_weighted(codes: torch.Tensor, g: torch.Tensor, q_labels: torch.Tens
         raise ValueError(f"query codes of {nbit} bits take {W} words per code, the gallery has {g.shape[1]}")
     if int(bits) not in WEIGHT_BITS:
         raise ValueError(f"weight bits must be one of {WEIGHT_BITS}, got {bits}")
-    dev = g.device
-    ks = [int(k) for k in ks]
-    if any(k <= 0 for k in ks):
-        raise ValueError("P@k / R@k need k >= 1")
-    many = isinstance(R, (list, tuple))
-    Rs = [int(r) for r in R] if many else [int(R)]
-    G = g.shape[0]
-    if Qn == 0 or G == 0:
-        return empty_result(Qn, W, dev, Rs, ks, many, False, None)
-    codes = codes.to(dev, torch.float32).contiguous()
-    q = pack_sign(codes)
-    planes, _ = weight_planes(codes, bits, mask)
-    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
-    limits, idx_of = normalize_limits(Rs + ks)
-    offsets, keys, longest = rank_collect(q, planes, g, q_lab, g_lab, LW)
-    keys = sort_slices(offsets, keys)
-    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
-    bins = rank_count(q, planes, g, offsets, keys, cap, seg_rows)
-    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
-    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
-    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
-                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+
+    def operands():
+        c = codes.to(g.device, torch.float32).contiguous()
+        return pack_sign(c), weight_planes(c, bits, mask)[0], g
+
+    return _evaluate_by_rank_counting(Qn, g.shape[0], W, g.device, operands, rank_collect, rank_count, False, q_labels, g_labels, R, ks,
+                                      remove_first, skip_queries_without_relevant, seg_rows, list_cap)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1146,48 +1185,21 @@ def ternary_topk(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, g_index_
 def ternary_rank_collect(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,
                          g_index_base: int = 0, stream=None):
     """`rank_collect` under K: the keys K << 32 | global index of every query's relevant rows -> (offsets, keys, longest slice)."""
-    lib = _lib.load()
     q3, g3 = _check_ternary(q3, g3, nbit)
     Qn, _, W = q3.shape
     G = g3.shape[0]
-    count = torch.zeros(Qn, dtype=torch.int32, device=q3.device)
-    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q3.device)
-    if Qn == 0 or G == 0:
-        return offsets, torch.empty(0, dtype=torch.int64, device=q3.device), 0
-
-    def call(off, keys):
-        _lib.check(lib.ch_ternary_rank_collect(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), _lib.ptr(q_lab), _lib.ptr(g_lab), LW,
-                                               int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
-                                               _lib.stream_ptr(stream)), "ch_ternary_rank_collect")
-
-    with _dev_guard(q3):
-        call(None, None)
-        offsets[1:] = count.cumsum(0, dtype=torch.int64)
-        total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
-        keys = torch.empty(total, dtype=torch.int64, device=q3.device)
-        if total:
-            count.zero_()
-            call(offsets, keys)
-    return offsets, keys, int(longest)
+    return _collect_pass("ch_ternary_rank_collect", (_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit)), Qn, G, q3.device, q_lab, g_lab, LW,
+                         g_index_base, stream)
 
 
 def ternary_rank_count(q3: torch.Tensor, g3: torch.Tensor, nbit: int, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int,
                        seg_rows: Optional[int] = None, g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """`rank_count` under K -> bins int32 [total]; keys: `sort_slices(ternary_rank_collect(...))`."""
-    lib = _lib.load()
     q3, g3 = _check_ternary(q3, g3, nbit)
     Qn, _, W = q3.shape
     G = g3.shape[0]
-    if bins is None:
-        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q3.device)
-    if Qn == 0 or G == 0 or keys.numel() == 0:
-        return bins
-    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
-    with _dev_guard(q3):
-        _lib.check(lib.ch_ternary_rank_count(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), int(g_index_base), seg, _lib.ptr(offsets),
-                                             _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)),
-                   "ch_ternary_rank_count")
-    return bins
+    return _count_pass("ch_ternary_rank_count", (_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit)), Qn, G, q3.device, offsets, keys, list_cap,
+                       seg_rows, g_index_base, bins, stream)
 
 
 def evaluate_ternary(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
@@ -1195,30 +1207,12 @@ def evaluate_ternary(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_labels: to
                      seg_rows: Optional[int] = None, list_cap: Optional[int] = None) -> dict:
     """`evaluate` under the ternary ranking that `ternary_topk` serves: ascending (K, gallery index) on
     `pack_ternary` codes of both sides.  Returns the keys of `evaluate_weighted` -- mAP, precisions, recalls, hits, total, S, nrel, ap,
-    lists under a list R -- exact for any R and k, by the same rank counting: collect and sort the keys of each query's relevant rows,
-    one Qn x G scan for the bins, one lane per query for the AP terms.  seg_rows / list_cap (tests) change no result."""
+    lists under a list R -- exact for any R and k, by the same rank counting (`_evaluate_by_rank_counting`).  seg_rows / list_cap
+    (tests) change no result."""
     q3, g3 = _check_ternary(q3, g3, nbit)
-    Qn, _, W = q3.shape
-    G = g3.shape[0]
-    dev = g3.device
-    ks = [int(k) for k in ks]
-    if any(k <= 0 for k in ks):
-        raise ValueError("P@k / R@k need k >= 1")
-    many = isinstance(R, (list, tuple))
-    Rs = [int(r) for r in R] if many else [int(R)]
-    if Qn == 0 or G == 0:
-        return empty_result(Qn, W, dev, Rs, ks, many, False, None)
-    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
-    limits, idx_of = normalize_limits(Rs + ks)
-    offsets, keys, longest = ternary_rank_collect(q3, g3, nbit, q_lab, g_lab, LW)
-    keys = sort_slices(offsets, keys)
-    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
-    bins = ternary_rank_count(q3, g3, nbit, offsets, keys, cap, seg_rows)
-    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
-    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
-    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
-                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+    return _evaluate_by_rank_counting(q3.shape[0], g3.shape[0], q3.shape[2], g3.device, lambda: (q3, g3, nbit), ternary_rank_collect,
+                                      ternary_rank_count, False, q_labels, g_labels, R, ks, remove_first, skip_queries_without_relevant,
+                                      seg_rows, list_cap)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1341,58 +1335,18 @@ def dense_unorder(o: torch.Tensor) -> torch.Tensor:
 def dense_rank_collect(q: DenseCodes, g: DenseCodes, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int, g_index_base: int = 0, stream=None):
     """`rank_collect` under a dense metric: the keys ord(D) << 32 | global index of every query's relevant rows -> (offsets, keys,
     longest slice).  The keys use all 64 bits (int64 holding uint64 bit patterns): `sort_slices_unsigned` puts them in order."""
-    lib = _lib.load()
     mid = _check_dense_pair(q, g)
-    Qn, G = q.rows, g.rows
-    count = torch.zeros(Qn, dtype=torch.int32, device=q.device)
-    offsets = torch.zeros(Qn + 1, dtype=torch.int64, device=q.device)
-    if Qn == 0 or G == 0:
-        return offsets, torch.empty(0, dtype=torch.int64, device=q.device), 0
-
-    def call(off, keys):
-        _lib.check(lib.ch_dense_rank_collect(_lib.ptr(q.data), Qn, _lib.ptr(g.data), G, q.n, mid, _lib.ptr(q_lab), _lib.ptr(g_lab), LW,
-                                             int(g_index_base), _lib.ptr(off), _lib.ptr(count), _lib.ptr(keys),
-                                             _lib.stream_ptr(stream)), "ch_dense_rank_collect")
-
-    with _dev_guard(q.data):
-        call(None, None)
-        offsets[1:] = count.cumsum(0, dtype=torch.int64)
-        total, longest = torch.stack([offsets[-1], count.max().to(torch.int64)]).tolist()
-        keys = torch.empty(total, dtype=torch.int64, device=q.device)
-        if total:
-            count.zero_()
-            call(offsets, keys)
-    return offsets, keys, int(longest)
-
-
-def sort_slices_unsigned(offsets: torch.Tensor, keys: torch.Tensor) -> torch.Tensor:
-    """Every CSR slice of `keys` ascending AS UINT64 (`sort_slices` needs keys below 2^48; dense keys use all 64 bits): flipping the
-    top bit maps uint64 order onto int64 order; one sort of the flat buffer, then a stable sort by slice."""
-    if keys.numel() == 0:
-        return keys
-    top = -(1 << 63)
-    n = offsets[1:] - offsets[:-1]
-    owner = torch.repeat_interleave(torch.arange(n.numel(), device=keys.device), n, output_size=keys.numel())
-    flipped, order = torch.sort(keys ^ top)
-    return (flipped[torch.sort(owner[order], stable=True)[1]] ^ top).contiguous()
+    return _collect_pass("ch_dense_rank_collect", (_lib.ptr(q.data), q.rows, _lib.ptr(g.data), g.rows, q.n, mid), q.rows, g.rows, q.device,
+                         q_lab, g_lab, LW, g_index_base, stream)
 
 
 def dense_rank_count(q: DenseCodes, g: DenseCodes, offsets: torch.Tensor, keys: torch.Tensor, list_cap: int, seg_rows: Optional[int] = None,
                      g_index_base: int = 0, bins: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
     """`rank_count` under a dense metric -> bins int32 [total]; keys: `sort_slices_unsigned(dense_rank_collect(...))`.  `bins`, where
     given, is added into (gallery shards)."""
-    lib = _lib.load()
     mid = _check_dense_pair(q, g)
-    Qn, G = q.rows, g.rows
-    if bins is None:
-        bins = torch.zeros(keys.numel(), dtype=torch.int32, device=q.device)
-    if Qn == 0 or G == 0 or keys.numel() == 0:
-        return bins
-    seg = int(seg_rows) if seg_rows else rank_seg_rows(Qn, G)
-    with _dev_guard(q.data):
-        _lib.check(lib.ch_dense_rank_count(_lib.ptr(q.data), Qn, _lib.ptr(g.data), G, q.n, mid, int(g_index_base), seg, _lib.ptr(offsets),
-                                           _lib.ptr(keys), int(list_cap), _lib.ptr(bins), _lib.stream_ptr(stream)), "ch_dense_rank_count")
-    return bins
+    return _count_pass("ch_dense_rank_count", (_lib.ptr(q.data), q.rows, _lib.ptr(g.data), g.rows, q.n, mid), q.rows, g.rows, q.device,
+                       offsets, keys, list_cap, seg_rows, g_index_base, bins, stream)
 
 
 def evaluate_dense(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.Tensor, metric: str, R=-1, ks: Sequence[int] = (1, 5, 10),
@@ -1402,30 +1356,14 @@ def evaluate_dense(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.Ten
     cosine, squared Euclidean or negated dot distance of `metric` between [Qn, n] and [G, n] fp32 codes -- what `dense_topk` serves,
     and the upper end of the ladder Hamming < ternary / asymmetric < dense (mAP_dense - mAP is a run's quantisation gap).  Returns
     the keys of `evaluate_weighted` -- mAP, precisions, recalls, hits, total, S, nrel, ap, lists under a list R -- exact for any R and
-    k under the fp32 distances of the kernels, by the same rank counting: collect and sort the keys of each query's relevant rows, one
-    Qn x G scan for the bins, one lane per query for the AP terms.  seg_rows / list_cap (tests) change no result."""
+    k under the fp32 distances of the kernels, by the same rank counting (`_evaluate_by_rank_counting`).  seg_rows / list_cap (tests)
+    change no result."""
     dense_metric_id(metric)
     q_codes, g_codes = check_dense_codes(q_codes, "query codes"), check_dense_codes(g_codes, "gallery codes")
     if q_codes.shape[1] != g_codes.shape[1]:
         raise ValueError(f"queries have {q_codes.shape[1]} dimensions, the gallery {g_codes.shape[1]}")
-    Qn, G = q_codes.shape[0], g_codes.shape[0]
     dev = g_codes.device
-    ks = [int(k) for k in ks]
-    if any(k <= 0 for k in ks):
-        raise ValueError("P@k / R@k need k >= 1")
-    many = isinstance(R, (list, tuple))
-    Rs = [int(r) for r in R] if many else [int(R)]
-    if Qn == 0 or G == 0:
-        return empty_result(Qn, 1, dev, Rs, ks, many, False, None)
-    q, g = prepare_dense(q_codes.to(dev), metric), prepare_dense(g_codes, metric)
-    q_lab, g_lab, LW = prepare_labels(q_labels.to(dev), g_labels.to(dev))
-    limits, idx_of = normalize_limits(Rs + ks)
-    offsets, keys, longest = dense_rank_collect(q, g, q_lab, g_lab, LW)
-    keys = sort_slices_unsigned(offsets, keys)
-    cap = int(list_cap) if list_cap else max(1, min(RANK_LIST_MAX, longest))
-    bins = dense_rank_count(q, g, offsets, keys, cap, seg_rows)
-    S, nrel, total = rank_ap(offsets, bins, limits, remove_first)
-    sm = summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant)
-    pick = (lambda x: [x[idx_of[i]] for i in range(len(Rs))]) if many else (lambda x: x[idx_of[0]])
-    return dict(precisions=sm["precisions"], recalls=sm["recalls"], hits=sm["hits"], total=total,
-                mAP=sm["mAPs"] if many else sm["mAPs"][0], S=pick(S), nrel=pick(nrel), ap=sm["aps"] if many else sm["aps"][0])
+    return _evaluate_by_rank_counting(q_codes.shape[0], g_codes.shape[0], 1, dev,
+                                      lambda: (prepare_dense(q_codes.to(dev), metric), prepare_dense(g_codes, metric)), dense_rank_collect,
+                                      dense_rank_count, True, q_labels, g_labels, R, ks, remove_first, skip_queries_without_relevant,
+                                      seg_rows, list_cap)

@@ -11,12 +11,8 @@ the radii and the per-concept table stay Hamming statistics).
 """
 from __future__ import annotations
 
-import json
-import os
-
-import experiments.test_hashing as base
-import utils.hashing
 from experiments.hash_lookup_eval import HashLookupEvaluation
+from experiments.rank_rescoring import main_under_rank
 
 KEYS = ("mAP_asymmetric", "recalls_asymmetric", "precisions_asymmetric")
 
@@ -27,54 +23,9 @@ class AsymmetricEvaluation(HashLookupEvaluation):
         if not (cfg.get("asymmetric_eval") and cfg.get("compute_mAP") and cfg.exp != "extract"):
             return super().main()
         bits = int(cfg.get("weight_bits", 8))
-        metric, name = utils.hashing.calculate_mAP, base.calculate_mAP
-        calls = []                          # (the mAP object of a whole-code call, its triple under the asymmetric ranking)
-        # Under concept_eval the metric is reached Q times on the concepts' column slices in front of the call on the whole code
-        # (experiments/concept_eval.py); only the whole-code call is repeated under the asymmetric ranking.
-        Q = int(cfg.model.ncontext) if cfg.get("concept_eval") else 0
-        slices = []                         # widths of the per-concept calls since the last whole-code call
-
-        def with_asymmetric(db_codes, db_labels, test_codes, test_labels, R, **k):
-            out = metric(db_codes, db_labels, test_codes, test_labels, R, **k)
-            width = int(db_codes.shape[1])
-            if len(slices) < Q:
-                slices.append(width)
-                return out
-            if any(w * Q != width for w in slices):
-                raise RuntimeError(f"asymmetric_eval: expected {Q} per-concept calls of {width // max(Q, 1)} columns in front of a call on "
-                                   f"{width} columns, saw widths {slices}")
-            slices.clear()
-            # the bracket and the lookup the Hamming call left behind are read by the evaluators around this one after it returns
-            left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup
-            own = {key: v for key, v in k.items() if key not in ("tie_bracket", "radii")}
-            asym = metric(db_codes, db_labels, test_codes, test_labels, R, rank="asymmetric", weight_bits=bits, **own)
-            utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup = left
-            calls.append((out[0], asym))
-            many = isinstance(asym[0], list)
-            for r_, m in (zip(R, asym[0]) if many else [(R, asym[0])]):
-                print(f"mAP@{r_} (asymmetric, {bits}-bit weights): {m:.4f}")
-            for kk, r, p in zip(k.get("PRs") or [], asym[1], asym[2]):
-                print(f"P@{kk} (asymmetric): {p:.4f}; R@{kk} (asymmetric): {r:.4f}")
-            return out
-        # This wrapper stands where the metric itself stood, under both names it is reached by: the evaluator calls `calculate_mAP` of its
-        # own module, and the evaluators this one extends rebind that name (or utils.hashing's) for their run and end up in
-        # `utils.hashing.calculate_mAP`.
-        utils.hashing.calculate_mAP = base.calculate_mAP = with_asymmetric
-        try:
-            res = super().main()
-        finally:
-            utils.hashing.calculate_mAP, base.calculate_mAP = metric, name
-        # the evaluator stored each call's mAP object under "mAP" + postfix: find it by identity, not by position or key order
-        for mAP, asym in calls:
-            keys = [k for k, v in res.items() if v is mAP and k.startswith("mAP")]
-            if len(keys) != 1:
-                raise RuntimeError(f"asymmetric_eval: a calculate_mAP result is stored under {keys} in the results, expected one key")
-            postfix = keys[0][len("mAP"):]
-            for key, v in zip(KEYS, asym):
-                res[key + postfix] = v
-        res["weight_bits"] = bits
-        if self.rank == 0:
-            with open(os.path.join(self.eval_logdir, "history.json"), "w") as f:
-                json.dump(res, f)
-        self.results = res
-        return res
+        # The shared body passes a call under another rank and the text evaluator's call through.  Neither reaches this evaluator -- no
+        # caller below it passes a `rank`, and the text evaluator extends it, so its call is made after this main() has returned -- so
+        # the guard changes nothing here.
+        return main_under_rank(self, super().main, "asymmetric_eval", dict(rank="asymmetric", weight_bits=bits), ("tie_bracket", "radii"),
+                               f"asymmetric, {bits}-bit weights", "asymmetric", KEYS,
+                               finish=lambda res, calls: res.update(weight_bits=bits))

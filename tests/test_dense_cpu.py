@@ -169,6 +169,36 @@ def test_python_entries_check_their_arguments_without_a_gpu():
     assert np.array_equal(got, want) and got[3] == 2 ** 64 - 1
 
 
+def test_the_one_slice_sort_against_numpy_on_each_of_its_paths():
+    """`sort_slices` (and `sort_slices_unsigned`, its `wide` form) against np.sort per slice: keys below 2^48 with few slices (the
+    single sort of slice << 48 | key), keys that use all 64 bits, and more than 32,767 slices of keys below 2^48 (the flipped-top-bit
+    two-sort, told to expect small keys)."""
+    from concepthash_amd import retrieval as rt
+    rng = np.random.default_rng(11)
+
+    def case(lengths, keys_u64, sort):
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        assert offsets[-1] == keys_u64.size
+        got = sort(torch.from_numpy(offsets), torch.from_numpy(keys_u64.view(np.int64).copy())).numpy().view(np.uint64)
+        want = np.concatenate([np.sort(keys_u64[a:b]) for a, b in zip(offsets[:-1], offsets[1:])])
+        assert np.array_equal(got, want)
+
+    few = rng.integers(0, 40, 300)
+    few[[0, 7, 299]] = 0                                                   # empty slices, the first and the last among them
+    small = rng.integers(0, 1 << 48, int(few.sum()), dtype=np.uint64)
+    small[:5] = [0, (1 << 48) - 1, 65279 << 32, (1 << 32) - 1, 1 << 47]    # the ends of the range, of the distance and of the index
+    case(few, small, rt.sort_slices)
+    case(few, small, rt.sort_slices_unsigned)                              # the flip is harmless for small keys
+    wide = rng.integers(0, 1 << 64, int(few.sum()), dtype=np.uint64, endpoint=False)
+    wide[:4] = [0, 2 ** 64 - 1, 1 << 63, (1 << 63) - 1]
+    case(few, wide, rt.sort_slices_unsigned)
+    case(few, wide, lambda o, k: rt.sort_slices(o, k, wide=True))
+    many = rng.integers(0, 3, 0x7FFF + 2)                                  # 32,769 slices: their number does not fit above a key
+    small = rng.integers(0, 1 << 48, int(many.sum()), dtype=np.uint64)
+    small[:2] = [(1 << 48) - 1, 0]
+    case(many, small, rt.sort_slices)
+
+
 # ---- calculate_mAP / calculate_pr_curve ------------------------------------------------------------------------------------------
 def test_calculate_map_refuses_before_it_touches_a_gpu(monkeypatch):
     import utils.hashing as hashing

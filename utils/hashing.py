@@ -99,47 +99,32 @@ DENSE_RANKS = tuple(rt.DENSE_METRICS)      # "cosine", "euclidean", "dot": the r
 RANKS = ("hamming", "asymmetric", "ternary") + DENSE_RANKS
 
 
-def _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits):
-    """rank="asymmetric": the queries keep their real values (`retrieval.evaluate_weighted`), the database is sign-packed as ever."""
-    from concepthash_amd.distributed import RowShard
-    if any(isinstance(x, RowShard) for x in (db_codes, db_labels, test_codes, test_labels)) or _sharded():
-        raise NotImplementedError("rank='asymmetric' is evaluated by one process on a whole database; the sharded form is not built "
-                                  "(its bins are additive over gallery shards)")
-    dev = _device()
-    g = rt.pack_sign(torch.as_tensor(db_codes).to(dev, torch.float32))
-    return rt.evaluate_weighted(torch.as_tensor(test_codes).to(dev, torch.float32), g, _labels(test_labels, dev), _labels(db_labels, dev),
-                                bits=weight_bits, R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
-
-
-def _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, margin):
-    """rank="ternary": both code sets become ternary codes under one margin (`retrieval.pack_ternary`), ranked by K."""
-    from concepthash_amd.distributed import RowShard
-    if any(isinstance(x, RowShard) for x in (db_codes, db_labels, test_codes, test_labels)) or _sharded():
-        raise NotImplementedError("rank='ternary' is evaluated by one process on a whole database; the sharded form is not built "
-                                  "(its bins are additive over gallery shards)")
-    dev = _device()
-    db = torch.as_tensor(db_codes).to(dev, torch.float32)
-    g3 = rt.pack_ternary(db, margin)
-    q3 = rt.pack_ternary(torch.as_tensor(test_codes).to(dev, torch.float32), margin)
-    return rt.evaluate_ternary(q3, g3, db.shape[1], _labels(test_labels, dev), _labels(db_labels, dev), R=R, ks=ks,
-                               remove_first=remove_first, skip_queries_without_relevant=skip)
-
-
-def _dense_single_process(metric, *operands):
+def _single_process(rank, *operands):
     from concepthash_amd.distributed import RowShard
     if any(isinstance(x, RowShard) for x in operands) or _sharded():
-        raise NotImplementedError(f"rank='{metric}' is evaluated by one process on a whole database; the sharded form is not built "
+        raise NotImplementedError(f"rank='{rank}' is evaluated by one process on a whole database; the sharded form is not built "
                                   "(its bins are additive over gallery shards)")
 
 
-def _evaluate_dense(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, metric):
-    """rank="cosine" | "euclidean" | "dot": both code sets stay real-valued (`retrieval.evaluate_dense`)."""
-    _dense_single_process(metric, db_codes, db_labels, test_codes, test_labels)
-    # finiteness is checked where the codes are (a host tensor never reaches the GPU with a NaN in it)
-    q, g = rt.check_dense_codes(test_codes, "test_codes"), rt.check_dense_codes(db_codes, "db_codes")
+def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits=None, margin=None):
+    """Every rank but "hamming": one process on a whole database; what differs is how the two code sets are prepared.
+    "asymmetric": the queries keep their real values (`retrieval.evaluate_weighted`), the database is sign-packed as ever.
+    "ternary": both code sets become ternary codes under one margin (`retrieval.pack_ternary`), ranked by K.
+    "cosine" | "euclidean" | "dot": both code sets stay real-valued (`retrieval.evaluate_dense`)."""
+    _single_process(rank, db_codes, db_labels, test_codes, test_labels)
+    how = dict(R=R, ks=ks, remove_first=remove_first, skip_queries_without_relevant=skip)
+    if rank in DENSE_RANKS:
+        # finiteness is checked where the codes are (a host tensor never reaches the GPU with a NaN in it)
+        q, g = rt.check_dense_codes(test_codes, "test_codes"), rt.check_dense_codes(db_codes, "db_codes")
+        dev = _device()
+        return rt.evaluate_dense(q.to(dev), g.to(dev), _labels(test_labels, dev), _labels(db_labels, dev), rank, **how)
     dev = _device()
-    return rt.evaluate_dense(q.to(dev), g.to(dev), _labels(test_labels, dev), _labels(db_labels, dev), metric, R=R, ks=ks,
-                             remove_first=remove_first, skip_queries_without_relevant=skip)
+    db = torch.as_tensor(db_codes).to(dev, torch.float32)
+    test = torch.as_tensor(test_codes).to(dev, torch.float32)
+    if rank == "asymmetric":
+        return rt.evaluate_weighted(test, rt.pack_sign(db), _labels(test_labels, dev), _labels(db_labels, dev), bits=int(weight_bits), **how)
+    g3 = rt.pack_ternary(db, margin)
+    return rt.evaluate_ternary(rt.pack_ternary(test, margin), g3, db.shape[1], _labels(test_labels, dev), _labels(db_labels, dev), **how)
 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
@@ -178,17 +163,12 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     global last_tie_bracket, last_hash_lookup
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
-    if rank == "asymmetric":
-        if tie_bracket or radii is not None:
-            raise ValueError("rank='asymmetric' has no tie bracket and no radius lookup: both are defined on Hamming distances")
-        if int(weight_bits) not in rt.WEIGHT_BITS:
-            raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits}")
-    if rank == "ternary":
-        if tie_bracket or radii is not None:
-            raise ValueError("rank='ternary' has no tie bracket and no radius lookup: both are defined on Hamming distances")
-        margin = rt.check_margin(margin, "rank='ternary': margin")
-    if rank in DENSE_RANKS and (tie_bracket or radii is not None):
+    if rank != "hamming" and (tie_bracket or radii is not None):
         raise ValueError(f"rank='{rank}' has no tie bracket and no radius lookup: both are defined on Hamming distances")
+    if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
+        raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits}")
+    if rank == "ternary":
+        margin = rt.check_margin(margin, "rank='ternary': margin")
     last_tie_bracket = None
     last_hash_lookup = None
     _check(dist_metric, threshold, landmark_gt)
@@ -197,20 +177,12 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     Rs = [int(r) for r in R] if many else int(R)
     if many and not Rs:
         return [], [], []
-    if rank == "asymmetric":
-        res = _evaluate_asymmetric(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
-                                   bool(skip_queries_without_relevant), int(weight_bits))
-        return res["mAP"], res["recalls"], res["precisions"]
-    if rank == "ternary":
-        res = _evaluate_ternary(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
-                                bool(skip_queries_without_relevant), margin)
-        return res["mAP"], res["recalls"], res["precisions"]
-    if rank in DENSE_RANKS:
-        res = _evaluate_dense(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
-                              bool(skip_queries_without_relevant), rank)
-        return res["mAP"], res["recalls"], res["precisions"]
-    res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
-                    bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
+    if rank != "hamming":     # neither tie bracket nor radii from here (refused above)
+        res = _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
+                               bool(skip_queries_without_relevant), weight_bits, margin)
+    else:
+        res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
+                        bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
     if radii is not None:
         last_hash_lookup = dict({k: res[k] for k in ("precisions_radius", "recalls_radius", "retrieved_radius", "empty_radius")},
                                 radii=[int(r) for r in radii])
@@ -242,13 +214,13 @@ def calculate_pr_curve(db_codes, db_labels, test_codes, test_labels, threshold=0
         raise ValueError(f"rank must be 'hamming' or one of {DENSE_RANKS}, got {rank!r}")
     _check(dist_metric, threshold, None)
     if rank in DENSE_RANKS:
-        _dense_single_process(rank, db_codes, db_labels, test_codes, test_labels)
+        _single_process(rank, db_codes, db_labels, test_codes, test_labels)
     n = db_codes.shape[0] - (1 if remove_first_retrieved else 0)
     Rs = [int(r) for r in (Rs if Rs is not None else pr_curve_points(max(n, 1)))]
     if not Rs:
         return [], [], []
     if rank in DENSE_RANKS:
-        res = _evaluate_dense(db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved, False, rank)
+        res = _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved, False)
     else:
         res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, [], remove_first_retrieved)
     total = res["total"].double()
