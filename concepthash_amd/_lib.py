@@ -203,6 +203,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_dense_rank_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,
                                     c_int32, c_void_p, c_void_p]),
+    "ch_dense_rerank": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int64, c_void_p,
+                                c_void_p, c_void_p]),
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),

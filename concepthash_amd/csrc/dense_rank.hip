@@ -23,6 +23,8 @@
 // of its row to the lists of the queries whose threshold it is below.  After a trip, every list longer than min(128, 4 k) is cut by
 // the whole workgroup to its k smallest, in order (each key's rank = the number of keys below it: keys are distinct), and the k-th
 // becomes the threshold; a list is at most 128 long before a trip, so 256 appends fit.  Segment lists are merged by one wave per query.
+//
+// Rerank (ch_dense_rerank): the same distance over a shortlist of rows per query, read from the RAW row-major codes -- see there.
 #include <algorithm>
 #include <string>
 
@@ -100,6 +102,18 @@ int dispatch_metric(int metric, F &&f) {
     }
 }
 
+// The cosine scale of one row-major row: 1 / |x| by the chain s = fmaf(x_j, x_j, s) from 0.0f over j = 0 .. n - 1, 0 for a zero row.  A
+// normalised entry is x_j * scale, rounded on its own.  Prepare and the rerank both normalise through here, so a row has the same
+// normalised bits in the prepared operand and on the fly.  A pass that meets a row piece by piece (the staged rerank) walks the same
+// chain through dense_sq_step and ends it with dense_scale_of.
+__device__ __forceinline__ float dense_sq_step(float x, float s) { return fmaf(x, x, s); }
+__device__ __forceinline__ float dense_scale_of(float s) { return s == 0.0f ? 0.0f : __fdiv_rn(1.0f, __fsqrt_rn(s)); }
+__device__ __forceinline__ float dense_row_scale(const float *__restrict__ x, int n) {
+    float s = 0.0f;
+    for (int j = 0; j < n; ++j) s = dense_sq_step(x[j], s);
+    return dense_scale_of(s);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // prepare: one lane per row of the padded operand
 // ---------------------------------------------------------------------------------------------------------------
@@ -113,12 +127,7 @@ __global__ __launch_bounds__(256) void dense_prepare_kernel(const float *__restr
         return;
     }
     const float *x = codes + r * n;
-    float scale = 1.0f;
-    if (metric == DM_COSINE) {
-        float s = 0.0f;
-        for (int j = 0; j < n; ++j) s = fmaf(x[j], x[j], s);
-        scale = s == 0.0f ? 0.0f : __fdiv_rn(1.0f, __fsqrt_rn(s));
-    }
+    const float scale = metric == DM_COSINE ? dense_row_scale(x, n) : 1.0f;
     if (metric == DM_COSINE)
         for (int j = 0; j < n; ++j) o[(size_t)j * DB] = x[j] * scale;
     else
@@ -255,6 +264,145 @@ __global__ __launch_bounds__(256) void dense_topk_merge_kernel(const uint64_t *_
         }
         prev = best;
         any = true;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// rerank: the second stage of a two-stage search ("two-stage").  One workgroup per query; the codes are the raw
+// row-major ones, so a candidate row is one contiguous read.  The query goes into LDS once (normalised there for cosine, by
+// dense_row_scale and x * scale as prepare does it); a lane owns a candidate and walks its row against the query -- every lane reads
+// the same query entry: an LDS broadcast -- through dense_step / dense_finish over j = 0 .. n - 1, and leaves key = ord(D) << 32 | row
+// in LDS.  An empty slot (id < 0 or row outside [0, G)) is never dereferenced and leaves DT_EMPTY.  The P = 2^ceil(log2 m) keys (the
+// pad is DT_EMPTY) are sorted by a bitonic network, and the first k go out.
+// How a lane gets its row.  WIDE (n a multiple of 4, a 16-byte aligned plane): a trip takes 256 candidates, and their rows come through
+// an LDS tile in chunks of RR_DC = 16 dimensions -- four lanes load the 64 bytes of one row's chunk with one 16-byte load each, so a
+// wave's load instruction covers 16 rows in whole 64-byte pieces instead of 64 rows in 16-byte ones; a lane then reads its own row's
+// chunk from the tile (row stride 17 floats: the 64 lanes of a wave read 64 different banks).  cosine sweeps the row twice, first for
+// the scale.  Otherwise a lane reads its row from global memory with scalar loads.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int RR_BLK = 256;
+constexpr int RR_MAX = 4096;      // candidates per query: 32 KB of keys
+constexpr int RR_DC = 16;         // dimensions of a staged chunk
+constexpr int RR_TS = RR_DC + 1;  // floats between two rows of the tile
+
+// the distance of the LDS query qs (normalised already for cosine) to the raw row x, read where it lies
+template <int M>
+__device__ __forceinline__ float rerank_dist(const float *qs, const float *__restrict__ x, int n) {
+    float scale = 1.0f;
+    if constexpr (M == DM_COSINE) scale = dense_row_scale(x, n);
+    float acc = 0.0f;
+#pragma unroll 4
+    for (int j = 0; j < n; ++j) {
+        float v = x[j];
+        if constexpr (M == DM_COSINE) v = v * scale;
+        acc = dense_step<M>(qs[j], v, acc);
+    }
+    return dense_finish<M>(acc);
+}
+
+template <int M, bool WIDE>
+__global__ __launch_bounds__(RR_BLK) void dense_rerank_kernel(const float *__restrict__ q, const float *__restrict__ g, int64_t G, int n,
+                                                              const int64_t *__restrict__ cand, int m, int P, int k, int64_t g_index_base,
+                                                              int64_t *__restrict__ out_idx, float *__restrict__ out_dist) {
+    extern __shared__ __align__(16) uint64_t rr_lds[];   // P keys, the query (256 floats) and, WIDE, the tile (256 rows of RR_TS floats)
+    uint64_t *keys = rr_lds;
+    float *qs = (float *)(rr_lds + P);
+    const int tid = threadIdx.x;
+    const int64_t qi = blockIdx.x;
+    if (tid < n) qs[tid] = q[qi * n + tid];
+    for (int c = tid; c < P; c += RR_BLK) keys[c] = DT_EMPTY;
+    __syncthreads();
+    if constexpr (M == DM_COSINE) {
+        const float scale = dense_row_scale(qs, n);   // every lane walks the same chain: LDS broadcasts
+        __syncthreads();
+        if (tid < n) qs[tid] = qs[tid] * scale;
+        __syncthreads();
+    }
+    for (int c0 = 0; c0 < m; c0 += RR_BLK) {   // the same trips for every lane: the barriers below are a workgroup's
+        const int c = c0 + tid;
+        int64_t row = -1;
+        if (c < m) {
+            const int64_t id = cand[qi * m + c];
+            if (id >= 0 && id - g_index_base >= 0 && id - g_index_base < G) row = id - g_index_base;
+        }
+        float D = 0.0f;
+        if constexpr (WIDE) {
+            float *tile = qs + 256;
+            const int lane = tid & 63, piece = (lane & 3) * 4;
+            // the four rows of this wave that the lane loads a piece of: row i * 16 + lane / 4, dimensions piece .. piece + 3 of a chunk
+            const float *src[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t rrow = __shfl((long long)row, i * 16 + (lane >> 2), 64);
+                src[i] = rrow >= 0 ? g + rrow * n + piece : nullptr;
+            }
+            float4 next[4];
+            auto load = [&](int d0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (src[i] && d0 + piece < n) next[i] = *(const float4 *)(src[i] + d0);
+            };
+            // use(j, x_j) for j = 0 .. n - 1 in this order, x the lane's own row; the loads of a chunk fly while the one before it is used
+            auto sweep = [&](auto &&use) {
+                load(0);
+                for (int d0 = 0; d0 < n; d0 += RR_DC) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (src[i] && d0 + piece < n) {
+                            float *t = tile + ((tid & ~63) + i * 16 + (lane >> 2)) * RR_TS + piece;
+                            t[0] = next[i].x;
+                            t[1] = next[i].y;
+                            t[2] = next[i].z;
+                            t[3] = next[i].w;
+                        }
+                    }
+                    __syncthreads();
+                    if (d0 + RR_DC < n) load(d0 + RR_DC);
+                    if (row >= 0) {
+                        const float *t = tile + tid * RR_TS;
+                        const int dn = min(RR_DC, n - d0);
+#pragma unroll 4
+                        for (int j = 0; j < dn; ++j) use(d0 + j, t[j]);
+                    }
+                    __syncthreads();   // the tile is read before the next chunk overwrites it
+                }
+            };
+            float scale = 1.0f;
+            if constexpr (M == DM_COSINE) {
+                float s = 0.0f;
+                sweep([&](int, float v) { s = dense_sq_step(v, s); });
+                scale = dense_scale_of(s);
+            }
+            float acc = 0.0f;
+            sweep([&](int j, float v) {
+                if constexpr (M == DM_COSINE) v = v * scale;
+                acc = dense_step<M>(qs[j], v, acc);
+            });
+            D = dense_finish<M>(acc);
+        } else {
+            if (row >= 0) D = rerank_dist<M>(qs, g + row * n, n);
+        }
+        if (row >= 0) keys[c] = ((uint64_t)dense_ord(D) << 32) | (uint64_t)row;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < (P >> 1); i += RR_BLK) {
+                const int lo = ((i & ~(stride - 1)) << 1) | (i & (stride - 1)), hi = lo | stride;
+                const uint64_t a = keys[lo], b = keys[hi];
+                if ((a > b) == ((lo & size) == 0)) {
+                    keys[lo] = b;
+                    keys[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int r = tid; r < k; r += RR_BLK) {
+        const uint64_t key = keys[r];
+        const bool empty = key == DT_EMPTY;
+        out_idx[qi * k + r] = empty ? -1 : g_index_base + (int64_t)(key & 0xFFFFFFFFull);
+        out_dist[qi * k + r] = empty ? __builtin_inff() : dense_unord((uint32_t)(key >> 32));
     }
 }
 
@@ -405,6 +553,33 @@ extern "C" int ch_dense_topk(const float *q, int64_t Qn, const float *g, int64_t
                        out_idx, out_dist);
     CH_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ch_dense_rerank(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const int64_t *cand,
+                               int32_t m, int32_t k, int64_t g_index_base, int64_t *out_idx, float *out_dist, void *stream) {
+    if (int e = check_dense("dense_rerank", n, metric)) return e;
+    CH_REQUIRE(m >= 1 && m <= RR_MAX && k >= 1 && k <= m, "dense_rerank: 1 <= k <= m <= 4096");
+    CH_REQUIRE(Qn >= 0 && G >= 0, "dense_rerank: negative sizes");
+    CH_REQUIRE(g_index_base >= 0 && g_index_base + G <= 0x100000000ll, "dense_rerank: keys hold 32-bit row indices (g_index_base + G <= 2^32)");
+    if (Qn == 0) return 0;
+    CH_REQUIRE(q && cand && out_idx && out_dist, "dense_rerank: null pointer");
+    CH_REQUIRE(G == 0 || g != nullptr, "dense_rerank: null gallery");
+    CH_REQUIRE(Qn <= 0x7FFFFFFFll, "dense_rerank: too many queries for one call");
+    int P = 2;
+    while (P < m) P <<= 1;
+    const bool wide = n % 4 == 0 && ((uintptr_t)g & 15) == 0;
+    const size_t lds = (size_t)P * sizeof(uint64_t) + 256 * sizeof(float) + (wide ? RR_BLK * RR_TS * sizeof(float) : 0);   // at most 51,200 bytes
+    return dispatch_metric(metric, [&](auto mt) {
+        constexpr int M = decltype(mt)::value;
+        if (wide)
+            hipLaunchKernelGGL((dense_rerank_kernel<M, true>), dim3((unsigned)Qn), dim3(RR_BLK), lds, (hipStream_t)stream, q, g, G, (int)n, cand,
+                               (int)m, P, (int)k, g_index_base, out_idx, out_dist);
+        else
+            hipLaunchKernelGGL((dense_rerank_kernel<M, false>), dim3((unsigned)Qn), dim3(RR_BLK), lds, (hipStream_t)stream, q, g, G, (int)n, cand,
+                               (int)m, P, (int)k, g_index_base, out_idx, out_dist);
+        CH_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int ch_dense_rank_collect(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const void *q_labels,

@@ -1367,3 +1367,138 @@ def evaluate_dense(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.Ten
                                       lambda: (prepare_dense(q_codes.to(dev), metric), prepare_dense(g_codes, metric)), dense_rank_collect,
                                       dense_rank_count, True, q_labels, g_labels, R, ks, remove_first, skip_queries_without_relevant,
                                       seg_rows, list_cap)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# two-stage search ("two-stage"): a Hamming shortlist, ordered by a dense distance
+# ---------------------------------------------------------------------------------------------------------------
+RERANK_MAX = 4096      # rows of a shortlist: their keys are sorted in 32 KB of LDS per query (csrc/dense_rank.hip)
+
+
+def check_shortlist(k, shortlist) -> Tuple[int, int]:
+    """(k, m) of a two-stage list: 1 <= k <= m <= 4096 (ValueError otherwise)"""
+    k, m = int(k), int(shortlist)
+    if not 1 <= m <= RERANK_MAX:
+        raise ValueError(f"shortlist must be in [1, {RERANK_MAX}], got {m}")
+    if not 1 <= k <= m:
+        raise ValueError(f"k must be in [1, shortlist = {m}], got {k}")
+    return k, m
+
+
+def _check_rerank_codes(q_codes, g_codes, metric):
+    mid = dense_metric_id(metric)
+    q, g = check_dense_codes(q_codes, "query codes"), check_dense_codes(g_codes, "gallery codes")
+    if q.shape[1] != g.shape[1]:
+        raise ValueError(f"queries have {q.shape[1]} dimensions, the gallery {g.shape[1]}")
+    if q.device != g.device:
+        raise ValueError("query and gallery codes must be on the same device")
+    return mid, q, g
+
+
+def dense_rerank(q_codes, g_codes, cand: torch.Tensor, metric: str, k: int, g_index_base: int = 0, validate: bool = True,
+                 stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The second stage: every query's candidate rows cand [Qn, m] (int64 global ids, row = id - g_index_base; a negative id is an
+    empty slot) ordered by ascending (D, index) under `metric` and cut at k -> (idx int64 [Qn, k], dist fp32 [Qn, k]), -1 / +inf past
+    the filled slots.  q_codes [Qn, n] and g_codes [G, n] are the RAW real-valued codes (`check_dense_codes`), not `prepare_dense`
+    operands; D has the bits of `dense_dist` for the pair.  1 <= k <= m <= 4096.  A row listed twice appears twice.  validate: an id
+    >= g_index_base + G is a ValueError before anything is launched (False: the caller vouches for the ids, e.g. `hamming_ranked`'s;
+    the kernel treats such an id as an empty slot)."""
+    mid, q, g = _check_rerank_codes(q_codes, g_codes, metric)
+    cand = torch.as_tensor(cand)
+    if cand.dtype != torch.int64 or cand.dim() != 2 or cand.shape[0] != q.shape[0]:
+        raise ValueError(f"cand must be int64 [Qn = {q.shape[0]}, m] row ids, got {cand.dtype} {tuple(cand.shape)}")
+    k, m = check_shortlist(k, cand.shape[1])
+    Qn, G, base = q.shape[0], g.shape[0], int(g_index_base)
+    if base < 0 or base + G > 1 << 32:
+        raise ValueError(f"g_index_base = {base} with {G} rows: keys hold 32-bit row indices (0 <= g_index_base, g_index_base + G <= 2^32)")
+    if cand.device != g.device:
+        raise ValueError("cand and the codes must be on the same device")
+    if validate and cand.numel() and int(cand.max()) >= base + G:
+        raise ValueError(f"cand holds the id {int(cand.max())}, outside the gallery's [{base}, {base + G}) (negative ids are empty slots)")
+    cand = cand.contiguous()
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=g.device)
+    dist = torch.empty(Qn, k, dtype=torch.float32, device=g.device)
+    if Qn == 0:
+        return idx, dist
+    lib = _lib.load()
+    with _dev_guard(g):
+        _lib.check(lib.ch_dense_rerank(_lib.ptr(q), Qn, _lib.ptr(g) if G else _lib.ptr(None), G, q.shape[1], mid, _lib.ptr(cand), m, k, base,
+                                       _lib.ptr(idx), _lib.ptr(dist), _lib.stream_ptr(stream)), "ch_dense_rerank")
+    return idx, dist
+
+
+def rerank_topk(q_codes, g_codes, metric: str, k: int, shortlist: int, radius: Optional[int] = None, q_packed: Optional[torch.Tensor] = None,
+                g_packed: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two-stage list: the first `shortlist` rows by ascending (Hamming distance, index) of the sign codes -- `hamming_ranked`, at
+    every depth; with `radius`, only rows within that many bits -- ordered by ascending (D, index) under `metric` of the real-valued
+    codes and cut at k -> (idx int64 [Qn, k], dist fp32 [Qn, k]), -1 / +inf past the filled slots.  q_packed / g_packed: the packed
+    sign codes where the caller holds them (an index's); otherwise `pack_sign` of the codes.  1 <= k <= shortlist <= 4096."""
+    k, m = check_shortlist(k, shortlist)
+    _, q, g = _check_rerank_codes(q_codes, g_codes, metric)
+    qp = pack_sign(q) if q_packed is None else q_packed
+    gp = pack_sign(g) if g_packed is None else g_packed
+    if qp.shape[0] != q.shape[0] or gp.shape[0] != g.shape[0]:
+        raise ValueError(f"{qp.shape[0]} / {gp.shape[0]} packed codes for {q.shape[0]} / {g.shape[0]} real-valued codes")
+    cand, _ = hamming_ranked(qp, gp, m, radius=radius)
+    return dense_rerank(q, g, cand, metric, k, validate=False)
+
+
+def _relevant_total(q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int) -> torch.Tensor:
+    """[Qn] int64: every query's relevant rows in the whole gallery (`prepare_labels` operands), a block of queries at a time"""
+    Qn, G = q_lab.shape[0], g_lab.shape[0]
+    out = torch.zeros(Qn, dtype=torch.int64, device=q_lab.device)
+    step = max(1, (1 << 26) // max(G * max(LW, 1), 1))
+    for c0 in range(0, Qn, step):
+        qc = q_lab[c0:c0 + step]
+        rel = g_lab[None, :] == qc[:, None] if LW == 0 else (g_lab[None, :, :] & qc[:, None, :]).ne(0).any(-1)
+        out[c0:c0 + step] = rel.sum(1)
+    return out
+
+
+def evaluate_reranked(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.Tensor, metric: str, shortlist: int, R=-1,
+                      ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, skip_queries_without_relevant: bool = False,
+                      radius: Optional[int] = None, q_packed: Optional[torch.Tensor] = None, g_packed: Optional[torch.Tensor] = None) -> dict:
+    """AP@R, P@k and R@k of the two-stage list of depth `shortlist` (`rerank_topk`) under the AP definition of `evaluate`: the keys of
+    `evaluate_dense` -- mAP, precisions, recalls, hits, total (relevant rows of the WHOLE gallery: a relevant row the shortlist misses
+    costs recall), S, nrel, ap, lists under a list R -- and
+      R: the effective R (R = -1 means the shortlist), shortlist;
+      agreement: {k: mean share of the exhaustive `dense_topk` top-k found in the two-stage top-k} for each k <= 128 of ks.
+    R and every k must lie in [1, shortlist] (ValueError).  remove_first drops rank 1 of the final list.  The list arithmetic on
+    [Qn, shortlist] is torch's; the lists are the kernels'."""
+    Rs, ks, many = parse_limits(R, ks)
+    _, m = check_shortlist(1, shortlist)
+    Rs = [m if r == -1 else r for r in Rs]
+    for what, vals in (("R", Rs), ("k", ks)):
+        if any(not 1 <= v <= m for v in vals):
+            raise ValueError(f"every {what} of a two-stage evaluation must lie in [1, shortlist = {m}] (R = -1: the shortlist), got {vals}")
+    _, q, g = _check_rerank_codes(q_codes, g_codes, metric)
+    dev = g.device
+    q_lab, g_lab, LW = prepare_labels(torch.as_tensor(q_labels).to(dev), torch.as_tensor(g_labels).to(dev))
+    if q_lab.shape[0] != q.shape[0] or g_lab.shape[0] != g.shape[0]:
+        raise ValueError(f"{q_lab.shape[0]} / {g_lab.shape[0]} labels for {q.shape[0]} / {g.shape[0]} codes")
+    idx, _ = rerank_topk(q, g, metric, m, m, radius, q_packed, g_packed)
+    rel = _relevance_of(idx, q_lab, g_lab, LW)
+    total = _relevant_total(q_lab, g_lab, LW)
+    if remove_first:
+        total = total - rel[:, 0].to(torch.int64)
+        rel = rel[:, 1:]
+    Qn, L = rel.shape
+    seen = rel.to(torch.int64).cumsum(1)
+    ranks = torch.arange(1, L + 1, dtype=torch.int64, device=dev)
+    terms = torch.where(rel, torch.div(seen << 32, ranks[None, :], rounding_mode="floor"), torch.zeros_like(seen))   # floor(relrank 2^32 / rank)
+    limits, idx_of = normalize_limits(Rs + ks)
+    S = torch.stack([terms[:, :lim].sum(1) for lim in limits]) if limits else torch.zeros(0, Qn, dtype=torch.int64, device=dev)
+    nrel = torch.stack([rel[:, :lim].sum(1).to(torch.int32) for lim in limits]) if limits else torch.zeros(0, Qn, dtype=torch.int32, device=dev)
+    total = total.to(torch.int32)
+    out = result_dict(summarize(S, nrel, total, idx_of, Rs, ks, skip_queries_without_relevant), S, nrel, total, idx_of, len(Rs), many)
+    out.update(R=Rs if many else Rs[0], shortlist=m, agreement={})
+    deep = [k for k in ks if k <= DENSE_MAX_K]
+    if deep and Qn:
+        full, _ = dense_topk(prepare_dense(q, metric), prepare_dense(g, metric), metric, max(deep))
+        shares = []
+        for k in deep:
+            want = full[:, :k]
+            found = ((want[:, :, None] == idx[:, None, :k]).any(-1) & (want >= 0)).sum(1).double()
+            shares.append((found / (want >= 0).sum(1).clamp_min(1).double()).mean())
+        out["agreement"] = dict(zip(deep, torch.stack(shares).tolist()))
+    return out

@@ -146,7 +146,8 @@ class GalleryIndex:
         return os.path.join(self.data_root, rel)
 
     def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0,
-               rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None, mean_shift: bool = True) -> dict:
+               rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None, mean_shift: bool = True,
+               shortlist: Optional[int] = None) -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here;
         mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0).
         Ranks the database by ascending (distance, index) and returns
@@ -173,11 +174,17 @@ class GalleryIndex:
         rank="cosine" | "euclidean" | "dot": the ranking of the real-valued codes themselves (`retrieval.dense_topk`; DESIGN.md section
         2.0) against the index's real plane (an index without one raises ValueError); dist is fp32 -- 1 - cos, the squared Euclidean
         distance or the negated dot product -- and +inf where idx is -1.  No `concepts`, no margin, no radius (ValueError), k <= 128;
-        concept_dist and bits describe the sign codes of the hits as under "hamming"."""
+        concept_dist and bits describe the sign codes of the hits as under "hamming".
+        shortlist = m under a dense rank: the two-stage list (`retrieval.rerank_topk`; DESIGN.md section 2.0, "two-stage") -- the first m
+        rows by ascending (Hamming distance, index) of the sign codes, ordered by the dense distance and cut at k.  1 <= k <= m <= 4096,
+        so k may exceed 128; `radius` is then allowed and restricts the shortlist to rows within that many bits.  The dict also holds
+        shortlist.  Under any other rank a shortlist is a ValueError."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+        if shortlist is not None and rank not in rt.DENSE_METRICS:
+            raise ValueError(f"shortlist with rank='{rank}' is not built: a shortlist is reranked by a dense rank, one of {rt.DENSE_METRICS}")
         if rank in rt.DENSE_METRICS:
-            return self._search_dense(query_codes, int(k), concepts, margin, rank, radius, mean_shift)
+            return self._search_dense(query_codes, int(k), concepts, margin, rank, radius, mean_shift, shortlist)
         if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
             raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits!r}")
         k = int(k)
@@ -256,13 +263,18 @@ class GalleryIndex:
                    bits=keep.sum(1), labels=None, paths=None, **extra)
         return self._name_hits(out)
 
-    def _search_dense(self, query_codes, k: int, concepts, margin, rank: str, radius, mean_shift: bool) -> dict:
+    def _search_dense(self, query_codes, k: int, concepts, margin, rank: str, radius, mean_shift: bool, shortlist=None) -> dict:
         """`search` under a dense rank"""
-        if concepts is not None or radius is not None or (margin is not None and float(margin) != 0.0):
+        if concepts is not None or (radius is not None and shortlist is None) or (margin is not None and float(margin) != 0.0):
             raise ValueError(f"rank='{rank}' ranks by the whole real-valued code: concepts, a query margin and a radius are defined on bits "
-                             "and are not built under it")
-        if not 1 <= k <= rt.DENSE_MAX_K:
-            raise ValueError(f"k = {k} with rank='{rank}' is not built: the dense scan keeps lists of 1 .. {rt.DENSE_MAX_K}")
+                             "and are not built under it" + (" (a radius restricts a shortlist: shortlist=<m>)" if radius is not None else ""))
+        if shortlist is not None:
+            k, shortlist = rt.check_shortlist(k, shortlist)
+            if radius is not None and not 0 <= int(radius) <= 64 * self.codes.shape[1]:
+                raise ValueError(f"radius must be in [0, {64 * self.codes.shape[1]}], got {radius}")
+        elif not 1 <= k <= rt.DENSE_MAX_K:
+            raise ValueError(f"k = {k} with rank='{rank}' is not built: the dense scan keeps lists of 1 .. {rt.DENSE_MAX_K} "
+                             f"(a two-stage list goes to {rt.RERANK_MAX}: shortlist=<m>)")
         if self.real is None:
             raise ValueError(f"rank='{rank}' needs the index's real plane, which this index was built without: rebuild it "
                              f"(exp=search rank={rank} rebuilds it by itself; rebuild_index=true forces it)")
@@ -274,10 +286,15 @@ class GalleryIndex:
         codes = codes.to(dev)
         if self.mean is not None and mean_shift:
             codes = codes - self.mean[None, :]
-        idx, dist = rt.dense_topk(rt.prepare_dense(codes, rank), rt.prepare_dense(self.real, rank), rank, k)
         q = rt.pack_sign(codes)
+        extra = {}
+        if shortlist is not None:
+            idx, dist = rt.rerank_topk(codes, self.real, rank, k, shortlist, None if radius is None else int(radius), q, self.codes)
+            extra = dict(shortlist=shortlist)
+        else:
+            idx, dist = rt.dense_topk(rt.prepare_dense(codes, rank), rt.prepare_dense(self.real, rank), rank, k)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
-                   bits=torch.full((codes.shape[0],), self.nbit, dtype=torch.int64, device=dev), labels=None, paths=None, rank=rank)
+                   bits=torch.full((codes.shape[0],), self.nbit, dtype=torch.int64, device=dev), labels=None, paths=None, rank=rank, **extra)
         return self._name_hits(out)
 
     def _name_hits(self, out: dict) -> dict:

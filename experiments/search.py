@@ -1,7 +1,7 @@
 """`exp=search`: image or text queries -> ranked database hits of a finished run, optionally by chosen concepts.
 
     python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [radius=2] [concepts=[0,2]]
-        [query_margin=0.0] [rank=hamming|asymmetric|ternary|cosine|euclidean|dot] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
+        [query_margin=0.0] [rank=hamming|asymmetric|ternary|cosine|euclidean|dot] [shortlist=1000] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
         [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
 
 Text queries ("text query") become codes through the CLIP text tower and the run's own `text_projection`
@@ -283,6 +283,8 @@ class SearchExperiment:
         weight_bits = int(cfg.get("weight_bits", 8) or 8)
         radius = cfg.get("radius")
         radius = int(radius) if radius is not None else None
+        shortlist = cfg.get("shortlist")
+        shortlist = int(shortlist) if shortlist is not None else None
         print("Search Start")
         index = self.index if self.index is not None else self._build_index()
         index = index.to(self.trainer.device)
@@ -294,7 +296,8 @@ class SearchExperiment:
         else:
             loader, names, labelled = self._query_loader()
             q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
-        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius, mean_shift=self.text is None)
+        res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius, mean_shift=self.text is None,
+                          shortlist=shortlist)
         t0 = time.perf_counter()
         q_ids = _label_ids(q_labels.cpu()) if labelled else None
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
@@ -324,7 +327,7 @@ class SearchExperiment:
             queries.append({"query": names[i] if names is not None else i, "label": ql.tolist() if ql is not None else None,
                             "unmasked_bits": bits[i], "distance_max": dist_max[i], "hits": hits})
         self.timing["results"] = round(time.perf_counter() - t0, 3)
-        out = {"k": k, "radius": radius, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "index_margin": index.margin, "nbit": index.nbit, "ncontext": index.ncontext,
+        out = {"k": k, "radius": radius, "shortlist": shortlist, "concepts": concepts, "query_margin": margin, "rank": rank, "weight_bits": weight_bits, "index_margin": index.margin, "nbit": index.nbit, "ncontext": index.ncontext,
                "index": os.path.abspath(self.index_path), "index_status": self.index_note, "index_rows": len(index),
                "checkpoint": self.fingerprint, "query_kind": "image" if self.text is None else "text",
                "query": self.query if self.text is None else list(self.text["prompts"]),
@@ -337,7 +340,7 @@ class SearchExperiment:
             np.save(os.path.join(self.search_logdir, "concept_attention.npy"), attn.cpu().numpy().astype(np.float32))
         what = "the whole code" if concepts is None else f"concepts {concepts}"
         print(f"{len(queries)} queries x top {k} of {len(index)} database rows, ranked by {what}, " +
-              (f"{rank} distance of the real-valued codes" if dense else "Hamming distance" if rank == "hamming" else f"ternary distance in half bits (database margin {index.margin})" if rank == "ternary"
+              (f"{rank} distance of the real-valued codes" + (f" over a Hamming shortlist of {shortlist}" if shortlist is not None else "") if dense else "Hamming distance" if rank == "hamming" else f"ternary distance in half bits (database margin {index.margin})" if rank == "ternary"
                else f"asymmetric distance ({weight_bits}-bit |code| weights)") +
               (f", ignoring bits with |code| <= {margin}" if margin > 0 else "") + (f", within {radius} bits" if radius is not None else "") + f"; index {self.index_note}")
         for e in queries[:PRINT_QUERIES]:

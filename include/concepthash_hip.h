@@ -598,6 +598,16 @@ int ch_dense_rank_collect(const float *q, int64_t Qn, const float *g, int64_t G,
 int ch_dense_rank_count(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, int64_t g_index_base,
                         int32_t seg_rows, const int64_t *offsets, const uint64_t *keys, int32_t list_cap, uint32_t *bins, void *stream);
 
+/* Two-stage search ("two-stage"): order a shortlist of rows per query by D.  q [Qn,n] and g [G,n] are the RAW
+ * row-major fp32 codes, NOT the prepared layout (a shortlisted row is one contiguous read); cosine normalises both sides on the fly
+ * with the arithmetic of ch_dense_prepare, so D(q, g) has the bits ch_dense_dist gives for the pair under all three metrics.
+ * cand [Qn,m] int64: global row ids, row = id - g_index_base; an id < 0 or a row outside [0, G) is an empty slot and is never
+ * dereferenced (the -1 tails of ch_hamming_rank_scatter's lists are such slots).  out_idx / out_dist [Qn,k]: the k first of the m
+ * candidates by ascending key = ord(D) << 32 | row, -1 / +inf past the filled slots; a row listed twice appears twice.
+ * 1 <= k <= m <= 4096 (32 KB of keys in LDS per query); g_index_base + G <= 2^32. */
+int ch_dense_rerank(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const int64_t *cand, int32_t m,
+                    int32_t k, int64_t g_index_base, int64_t *out_idx, float *out_dist, void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

@@ -31,11 +31,12 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
 LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits", "text_eval",
-             "prompt_prefix", "text_model", "ternary_eval", "ternary_margin", "dense_eval", "dense_metric")
+             "prompt_prefix", "text_model", "ternary_eval", "ternary_margin", "dense_eval", "dense_metric", "rerank_eval", "rerank_metric",
+             "rerank_shortlist")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
                "query_margin", "index", "rebuild_index", "save_attention", "rank", "index_margin", "weight_bits", "radius", "query_text", "query_text_file",
-               "prompt_prefix", "text_model")
+               "prompt_prefix", "text_model", "shortlist")
 
 
 def _run_config(config, exp, keys):
@@ -78,6 +79,8 @@ def run(config):
             from experiments.ternary_eval import TernaryEvaluation as RetrievalEvaluation
         if load_config.get("dense_eval"):       # ... + every score once more under the ranking of the real-valued codes (it extends all six)
             from experiments.dense_eval import DenseEvaluation as RetrievalEvaluation
+        if load_config.get("rerank_eval"):      # ... + every score once more on the two-stage list: Hamming shortlist, dense rerank (it extends all seven)
+            from experiments.rerank_eval import RerankEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp == "search":
         from experiments.search import SearchExperiment

@@ -53,6 +53,10 @@ last_tie_bracket = None
 # Hash lookup of the last calculate_mAP(..., radii=[...]) call, the same pattern: {"radii", "precisions_radius", "recalls_radius",
 # "retrieved_radius", "empty_radius"} (lists, one entry per radius); None after any other call.
 last_hash_lookup = None
+# The two-stage figures of the last calculate_mAP(..., rank=<dense>, shortlist=m) call, the same pattern: {"metric", "shortlist", "R"
+# (the effective R: -1 becomes the shortlist), "agreement" ({k: share of the exhaustive dense top-k found in the two-stage top-k})};
+# None after any other call.
+last_rerank = None
 
 
 def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False, radii=None):
@@ -106,7 +110,8 @@ def _single_process(rank, *operands):
                                   "(its bins are additive over gallery shards)")
 
 
-def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits=None, margin=None):
+def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip, weight_bits=None, margin=None,
+                     shortlist=None):
     """Every rank but "hamming": one process on a whole database; what differs is how the two code sets are prepared.
     "asymmetric": the queries keep their real values (`retrieval.evaluate_weighted`), the database is sign-packed as ever.
     "ternary": both code sets become ternary codes under one margin (`retrieval.pack_ternary`), ranked by K.
@@ -117,6 +122,8 @@ def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, 
         # finiteness is checked where the codes are (a host tensor never reaches the GPU with a NaN in it)
         q, g = rt.check_dense_codes(test_codes, "test_codes"), rt.check_dense_codes(db_codes, "db_codes")
         dev = _device()
+        if shortlist is not None:       # the two-stage list: a Hamming shortlist of the sign codes, ordered by the dense distance
+            return rt.evaluate_reranked(q.to(dev), g.to(dev), _labels(test_labels, dev), _labels(db_labels, dev), rank, shortlist, **how)
         return rt.evaluate_dense(q.to(dev), g.to(dev), _labels(test_labels, dev), _labels(db_labels, dev), rank, **how)
     dev = _device()
     db = torch.as_tensor(db_codes).to(dev, torch.float32)
@@ -129,7 +136,7 @@ def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8, margin=None):
+                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8, margin=None, shortlist=None):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
@@ -159,10 +166,20 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     ascending 1 - cos, squared Euclidean distance or negated dot product; neither code set is binarised, so
     mAP under it minus the Hamming mAP is the run's quantisation gap.  Codes of 1 .. 256 finite dimensions (ValueError otherwise); no
     tie bracket and no radii (ValueError); single-process only (NotImplementedError).  `dist_metric` is NOT this switch, for the
-    reason `threshold` is not the margin: dist_metric != "hamming" keeps raising NotImplementedError."""
-    global last_tie_bracket, last_hash_lookup
+    reason `threshold` is not the margin: dist_metric != "hamming" keeps raising NotImplementedError.
+    shortlist=m with a dense rank (not a reference argument): the triple of the two-stage list `exp=search rank=<dense> shortlist=m`
+    serves (`retrieval.evaluate_reranked`; DESIGN.md section 2.0, "two-stage") -- the first m rows by Hamming distance of the sign
+    codes, ordered by the dense distance.  1 <= m <= 4096; R and every k must lie in [1, m] and R = -1 means m (ValueError otherwise);
+    recall counts the relevant rows of the whole database.  The effective R and agreement@k with the exhaustive dense list are left
+    in the module attribute `last_rerank`.  Under any other rank a shortlist is a ValueError."""
+    global last_tie_bracket, last_hash_lookup, last_rerank
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+    if shortlist is not None:
+        if rank not in DENSE_RANKS:
+            raise ValueError(f"shortlist with rank='{rank}' is not built: a shortlist is reranked by a dense rank, one of {DENSE_RANKS}")
+        shortlist = rt.check_shortlist(1, shortlist)[1]
+    last_rerank = None
     if rank != "hamming" and (tie_bracket or radii is not None):
         raise ValueError(f"rank='{rank}' has no tie bracket and no radius lookup: both are defined on Hamming distances")
     if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
@@ -179,7 +196,9 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
         return [], [], []
     if rank != "hamming":     # neither tie bracket nor radii from here (refused above)
         res = _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved,
-                               bool(skip_queries_without_relevant), weight_bits, margin)
+                               bool(skip_queries_without_relevant), weight_bits, margin, shortlist)
+        if shortlist is not None:
+            last_rerank = dict(metric=rank, shortlist=shortlist, R=res["R"], agreement=res["agreement"])
     else:
         res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
                         bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
