@@ -208,6 +208,8 @@ SIGNATURES = {
     "ch_debug_set_hamming_scalar_loads": (None, [c_int32]),
     "ch_hamming_tie_bracket": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "ch_hamming_tie_expected": (c_int, [c_void_p, c_int64, c_int32, POINTER(c_int64), c_int32, POINTER(c_int64), c_int32, c_int32, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     "ch_text_create": (c_int, [POINTER(TextConfig), POINTER(Tensor), c_int32, POINTER(c_void_p)]),
     "ch_text_destroy": (None, [c_void_p]),
     "ch_text_device_bytes": (c_size_t, [c_void_p]),

@@ -325,12 +325,14 @@ class ShardedRetrieval(retrieval.WholeGallery):
     # ---- mAP / P@k / R@k -----------------------------------------------------------------------------------------
     def evaluate(self, q_all: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Sequence[int] = (1, 5, 10),
                  remove_first: bool = False, seg_rows: Optional[int] = None, skip_queries_without_relevant: bool = False,
-                 tie_bracket: bool = False, radii: Optional[Sequence[int]] = None) -> dict:
+                 tie_bracket: bool = False, radii: Optional[Sequence[int]] = None, tie_expected: bool = False) -> dict:
         """Same statistics as ``retrieval.evaluate`` (R an int or a list; `skip_queries_without_relevant` as there), gallery sharded by rows: per-shard histograms are
         all-gathered, every rank builds the same global bases, ONE local AP pass accumulates every rank limit (each R and each
         k), and the integer sums are all-reduced -- bit-identical to the single-GPU result for any shard count.
         tie_bracket: as ``retrieval.evaluate``: the whole-gallery bucket counts are the sum over ranks of the per-shard totals that were
         all-gathered anyway, and every rank runs the bracket kernel on the same integers (replicated; no further collective).
+        tie_expected: as ``retrieval.evaluate``, from the same summed integers after they have crossed the ranks: every rank runs the
+        expectation kernel on identical counts, so any sharding gives the single-process bits.
         radii (hash lookup, ``retrieval.hash_lookup_stats``): not built for the sharded evaluator."""
         if radii is not None:
             raise NotImplementedError("ShardedRetrieval.evaluate(radii=...): hash lookup is not built for a sharded gallery (it would take "
@@ -345,7 +347,7 @@ class ShardedRetrieval(retrieval.WholeGallery):
             dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
             single = bool(flag.item())
         return retrieval.evaluate_gallery(self, q_all, q_labels, R, ks, remove_first, seg_rows, None, None, skip_queries_without_relevant,
-                                          tie_bracket, None, single)
+                                          tie_bracket, None, single, tie_expected=tie_expected)
 
     # ---- the steps of `retrieval.evaluate_gallery` that cross ranks ------------------------------------------------
     def first_relevant(self, q_all, q_lab, g_lab, LW):

@@ -473,6 +473,60 @@ def tie_results(bucket_counts: torch.Tensor, Rs: Sequence[int], ks: Sequence[int
     return out
 
 
+def tie_expected(bucket_counts: torch.Tensor, limits: Sequence[int], ks: Sequence[int] = (), remove_first: bool = False, stream=None):
+    """Mean of AP@R, hits@k and R@k over every order of the rows that share a distance, every bucket uniformly permuted (DESIGN.md
+    section 2.0, "tie expectation").  bucket_counts and limits as `tie_bracket` takes them; ks: depths >= 1, any order.
+    -> (ap [n, Qn], hits [nk, Qn], recall [nk, Qn]), float64; one launch per 16 limits / 16 ks."""
+    lib = _lib.load()
+    if bucket_counts.dim() != 3 or bucket_counts.shape[2] != 2 or bucket_counts.dtype != torch.int32:
+        raise TypeError("bucket_counts must be an int32 tensor [Qn, nb, 2]")
+    ks = [int(k) for k in ks]
+    if any(k <= 0 for k in ks):
+        raise ValueError("P@k / R@k need k >= 1")
+    bc = bucket_counts.contiguous()
+    Qn, nb, _ = bc.shape
+    ap = torch.zeros(len(limits), Qn, dtype=torch.float64, device=bc.device)
+    hits, recall = (torch.zeros(len(ks), Qn, dtype=torch.float64, device=bc.device) for _ in range(2))
+    if Qn == 0:
+        return ap, hits, recall
+    lim_chunks = list(_limit_chunks(limits))
+    k_chunks = list(_limit_chunks(ks))      # the entry takes as many depths as limits: the same chunks of 16
+    with _dev_guard(bc):
+        for i in range(max(len(lim_chunks), len(k_chunks))):
+            rows, arr, cnt = lim_chunks[i] if i < len(lim_chunks) else (None, None, 0)
+            krows, karr, kcnt = k_chunks[i] if i < len(k_chunks) else (None, None, 0)
+            _lib.check(lib.ch_hamming_tie_expected(_lib.ptr(bc), Qn, nb, arr, cnt, karr, kcnt, int(bool(remove_first)),
+                                                   _lib.ptr(ap[rows]) if cnt else None, _lib.ptr(hits[krows]) if kcnt else None,
+                                                   _lib.ptr(recall[krows]) if kcnt else None, _lib.stream_ptr(stream)),
+                       "ch_hamming_tie_expected")
+    return ap, hits, recall
+
+
+EXPECTED_KEYS = ("mAP_expected", "ap_expected", "precisions_expected", "recalls_expected", "hits_expected")
+
+EXPECTED_NEEDS_ALL_QUERIES = ("tie_expected with skip_queries_without_relevant=True: which queries have a relevant row inside R -- the set the "
+                              "mean would run over -- itself depends on the tie order, so that mean is no per-query expectation; the tie "
+                              "expectation is defined for the mean over all queries only")
+
+
+def expected_results(bucket_counts: torch.Tensor, Rs: Sequence[int], ks: Sequence[int], remove_first: bool, many: bool) -> dict:
+    """The EXPECTED_KEYS of evaluate(tie_expected=True) from the whole-gallery bucket counts [Qn, nb, 2]: mAP_expected (per R),
+    ap_expected (float64 [Qn] per R), precisions_expected / recalls_expected (per k), hits_expected (float64 [Qn, nk]).  Means run over
+    all queries."""
+    limits, idx_of = normalize_limits(Rs)
+    ap, hits, recall = tie_expected(bucket_counts, limits, ks, remove_first)
+    Qn = bucket_counts.shape[0]
+    aps = [ap[idx_of[i]] for i in range(len(Rs))]
+    if Qn:
+        kf = torch.tensor([float(k) for k in ks], dtype=torch.float64, device=ap.device)
+        vals = torch.cat([ap.mean(1)[idx_of], (hits / kf[:, None]).mean(1), recall.mean(1)]).tolist()
+    else:
+        vals = [0.0] * (len(Rs) + 2 * len(ks))
+    nR, nk = len(Rs), len(ks)
+    return dict(mAP_expected=vals[:nR] if many else vals[0], ap_expected=aps if many else aps[0], precisions_expected=vals[nR:nR + nk],
+                recalls_expected=vals[nR + nk:], hits_expected=hits.t().contiguous())
+
+
 REC_BUDGET_BYTES = 4 << 30     # upper bound of the record buffer of one evaluation
 REC_COMFORT_BYTES = 1 << 30    # ... and what is spent without need, for long lists (class-sorted galleries)
 
@@ -818,7 +872,8 @@ def use_records(ops, Qn: int, rows: int, W: int, LW: int, seg_rows: int, q_lab, 
     return True
 
 
-def empty_result(Qn: int, W: int, dev, Rs: Sequence[int], ks: Sequence[int], many: bool, tie_bracket: bool, radii) -> dict:
+def empty_result(Qn: int, W: int, dev, Rs: Sequence[int], ks: Sequence[int], many: bool, tie_bracket: bool, radii,
+                 tie_expected: bool = False) -> dict:
     """What the evaluation returns without a query or without a gallery row: zeros in every key's type and shape."""
     z64 = torch.zeros(Qn, dtype=torch.int64, device=dev)
     z32 = torch.zeros(Qn, dtype=torch.int32, device=dev)
@@ -831,6 +886,9 @@ def empty_result(Qn: int, W: int, dev, Rs: Sequence[int], ks: Sequence[int], man
             out.update({"mAP_" + side: out["mAP"], "ap_" + side: out["ap"], "S_" + side: out["S"], "nrel_" + side: out["nrel"],
                         "precisions_" + side: list(out["precisions"]), "recalls_" + side: list(out["recalls"]),
                         "hits_" + side: out["hits"]})
+    if tie_expected:
+        out.update(mAP_expected=out["mAP"], ap_expected=out["ap"], precisions_expected=list(out["precisions"]),
+                   recalls_expected=list(out["recalls"]), hits_expected=torch.zeros(Qn, len(ks), dtype=torch.float64, device=dev))
     if radii is not None:
         out.update(hash_lookup_stats(torch.zeros(Qn, 64 * W + 1, 2, dtype=torch.int32, device=dev), radii))
     return out
@@ -863,11 +921,13 @@ class WholeGallery:
 def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Sequence[int] = (1, 5, 10), remove_first: bool = False,
                      seg_rows: Optional[int] = None, records: Optional[bool] = None, rec_cap: Optional[int] = None,
                      skip_queries_without_relevant: bool = False, tie_bracket: bool = False,
-                     radii: Optional[Sequence[int]] = None, single: Optional[bool] = None) -> dict:
+                     radii: Optional[Sequence[int]] = None, single: Optional[bool] = None, tie_expected: bool = False) -> dict:
     """The evaluation behind `evaluate` and `ShardedRetrieval.evaluate`: labels, rank-1 relevance, histogram pass (with records or
     without), prefix, ONE AP pass over every R and k, the statistics.  `gal` (`WholeGallery` or a `ShardedRetrieval`) holds the rows
     this process scans, the `ops` that scan them and the steps that cross ranks; every process of a sharded evaluation gets here with
     the same q and takes the same path through this body.  single: `prepare_labels`' decision, where the caller has made it."""
+    if tie_expected and skip_queries_without_relevant:
+        raise ValueError(EXPECTED_NEEDS_ALL_QUERIES)
     ops, g = gal.ops, gal.gallery
     dev = q.device
     Qn, W = q.shape
@@ -875,7 +935,7 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
     q_lab, g_lab, LW = ops.prepare_labels(ql, gl, single)
     Rs, ks, many = parse_limits(R, ks)
     if Qn == 0 or gal.rows == 0:
-        return empty_result(Qn, W, dev, Rs, ks, many, tie_bracket, radii)
+        return empty_result(Qn, W, dev, Rs, ks, many, tie_bracket, radii, tie_expected)
     # relevance of every query's rank-1 row (the self-match when the test set is the database)
     first_rel = gal.first_relevant(q, q_lab, g_lab, LW) if remove_first else None
     seg = seg_rows or ops.map_seg_rows(Qn, gal.scan_rows, W)
@@ -883,7 +943,7 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
     # one distance scan (histogram + records of the relevant rows, prefix, the AP terms from the records) or two
     rec = use_records(ops, Qn, gal.scan_rows, W, LW, seg, q_lab, g_lab, records, rec_cap)
     hist, recs = ops.hamming_hist_rec(q, g, q_lab, g_lab, LW, seg, rec_cap=rec_cap) if rec else (ops.hamming_hist(q, g, q_lab, g_lab, LW, seg), None)
-    base, totals, counts2 = gal.bases(hist, tie_bracket or radii is not None)
+    base, totals, counts2 = gal.bases(hist, tie_bracket or tie_expected or radii is not None)
     if rec:
         S, nrel = ops.hamming_ap_rec(q, g, q_lab, g_lab, LW, seg, base, recs, limits, first_rel=first_rel)
     else:
@@ -896,6 +956,8 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
     out = result_dict(sm, S, nrel, total, idx_of, len(Rs), many)
     if tie_bracket:
         out.update(ops.tie_results(counts2, Rs, ks, remove_first, many, skip_queries_without_relevant))
+    if tie_expected:     # from the integers every process holds alike: the same bits under any sharding
+        out.update(ops.expected_results(counts2, Rs, ks, remove_first, many))
     if radii is not None:
         out.update(hash_lookup_stats(counts2, radii, (lowest_bucket(counts2), first_rel) if remove_first else None))
     return out
@@ -904,7 +966,7 @@ def evaluate_gallery(gal, q: torch.Tensor, q_labels: torch.Tensor, R=-1, ks: Seq
 def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels: torch.Tensor, R=-1,
              ks: Sequence[int] = (1, 5, 10), remove_first: bool = False, seg_rows: Optional[int] = None,
              records: Optional[bool] = None, rec_cap: Optional[int] = None, skip_queries_without_relevant: bool = False,
-             tie_bracket: bool = False, radii: Optional[Sequence[int]] = None) -> dict:
+             tie_bracket: bool = False, radii: Optional[Sequence[int]] = None, tie_expected: bool = False) -> dict:
     """Single-GPU mAP@R + P@k + R@k on packed codes: histogram pass, prefix, ONE AP pass whose rank limits are R (an int or
     a list) and every k -- the number of relevant rows inside limit k is exactly hits@k, for any k.  Returns python
     floats/lists plus the raw integer statistics (S, nrel, hits, total) that the parity tests compare bit-for-bit with the
@@ -917,11 +979,15 @@ def evaluate(q: torch.Tensor, g: torch.Tensor, q_labels: torch.Tensor, g_labels:
     tie_bracket: also report, for every statistic, the smallest and the largest value any order of equal-distance rows can give
     (TIE_KEYS: mAP_low / mAP_high ... hits_low / hits_high) -- one more small kernel on the histogram this
     call holds anyway.  Off: exactly the keys, integers and launches of before.
+    tie_expected: also report the MEAN of every statistic over the tie orders, every bucket uniformly permuted (EXPECTED_KEYS:
+    mAP_expected, ap_expected, precisions_expected, recalls_expected, hits_expected) -- the value that depends on no
+    sort, inside the bracket; one more small kernel on the same histogram, with or without tie_bracket.  The means run over all queries:
+    together with skip_queries_without_relevant it is a ValueError.
     radii: a list of Hamming radii adds the hash-lookup statistics of `hash_lookup_stats` (LOOKUP_KEYS) from the same histogram -- a few
     elementwise launches; None adds nothing and costs nothing."""
     q, g = _check_packed(q, g)
     return evaluate_gallery(WholeGallery(g, g_labels, sys.modules[__name__]), q, q_labels, R, ks, remove_first, seg_rows, records, rec_cap,
-                            skip_queries_without_relevant, tie_bracket, radii)
+                            skip_queries_without_relevant, tie_bracket, radii, tie_expected=tie_expected)
 
 
 # ---------------------------------------------------------------------------------------------------------------

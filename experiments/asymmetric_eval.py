@@ -26,6 +26,6 @@ class AsymmetricEvaluation(HashLookupEvaluation):
         # The shared body passes a call under another rank and the text evaluator's call through.  Neither reaches this evaluator -- no
         # caller below it passes a `rank`, and the text evaluator extends it, so its call is made after this main() has returned -- so
         # the guard changes nothing here.
-        return main_under_rank(self, super().main, "asymmetric_eval", dict(rank="asymmetric", weight_bits=bits), ("tie_bracket", "radii"),
+        return main_under_rank(self, super().main, "asymmetric_eval", dict(rank="asymmetric", weight_bits=bits), ("tie_bracket", "tie_expected", "radii"),
                                f"asymmetric, {bits}-bit weights", "asymmetric", KEYS,
                                finish=lambda res, calls: res.update(weight_bits=bits))

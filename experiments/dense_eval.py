@@ -40,5 +40,5 @@ class DenseEvaluation(TernaryEvaluation):
                 res["quantisation_gap" + postfix] = [d - h for d, h in zip(real[0], mAP)] if isinstance(mAP, list) else real[0] - mAP
             res["dense_metric"] = dense
 
-        return main_under_rank(self, super().main, "dense_eval", dict(rank=dense), ("tie_bracket", "radii", "rank", "weight_bits", "margin"),
+        return main_under_rank(self, super().main, "dense_eval", dict(rank=dense), ("tie_bracket", "tie_expected", "radii", "rank", "weight_bits", "margin"),
                                f"{dense}, real-valued codes", dense, KEYS, finish=finish)

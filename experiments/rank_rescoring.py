@@ -42,9 +42,9 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
                                f"{width} columns, saw widths {slices}")
         slices.clear()
         # the bracket and the lookup the Hamming call left behind are read by the evaluators around this one after it returns
-        left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup
+        left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected
         other = metric(db_codes, db_labels, test_codes, test_labels, R, **again, **{key: v for key, v in k.items() if key not in drop})
-        utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup = left
+        utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected = left
         calls.append((out[0], other))
         if on_call is not None:
             on_call(db_codes, test_codes)

@@ -47,6 +47,6 @@ class RerankEvaluation(DenseEvaluation):
             res["rerank_metric"], res["rerank_shortlist"] = metric, m
 
         return main_under_rank(self, super().main, "rerank_eval", dict(rank=metric, shortlist=m),
-                               ("tie_bracket", "radii", "rank", "weight_bits", "margin", "shortlist"),
+                               ("tie_bracket", "tie_expected", "radii", "rank", "weight_bits", "margin", "shortlist"),
                                f"{metric} over a Hamming shortlist of {m}", f"{metric}@{m}", KEYS,
                                on_call=lambda db_codes, test_codes: left.append(utils.hashing.last_rerank), finish=finish)

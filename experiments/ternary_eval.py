@@ -41,5 +41,5 @@ class TernaryEvaluation(TextEvaluation):
             shares[:] = [zero_share(db_codes, margin), zero_share(test_codes, margin)]
 
         return main_under_rank(self, super().main, "ternary_eval", dict(rank="ternary", margin=margin),
-                               ("tie_bracket", "radii", "rank", "weight_bits"), f"ternary, margin {margin:g}", "ternary", KEYS, on_call,
+                               ("tie_bracket", "tie_expected", "radii", "rank", "weight_bits"), f"ternary, margin {margin:g}", "ternary", KEYS, on_call,
                                lambda res, calls: res.update(ternary_margin=margin, ternary_zero_share=list(shares)))

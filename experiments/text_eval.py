@@ -24,7 +24,7 @@ from experiments.search import class_name_file
 
 KEYS = ("mAP_text", "recalls_text", "precisions_text")
 # what a wrapped evaluator adds to a call for its own bookkeeping, and what only makes sense when the queries are database rows
-NOT_FOR_TEXT = ("tie_bracket", "radii", "remove_first_retrieved", "rank", "weight_bits")
+NOT_FOR_TEXT = ("tie_bracket", "tie_expected", "radii", "remove_first_retrieved", "rank", "weight_bits")
 
 
 def text_eval_request(config):
@@ -85,9 +85,9 @@ class TextEvaluation(AsymmetricEvaluation):
             text_codes = self._phase("encode_text", enc.text_codes, prompts).cpu()
             res["center_agreement"] = enc.center_agreement(names, run_prefix)     # the tower check: the run's own prefix
         text_labels = torch.eye(len(prompts), dtype=db_labels.dtype)
-        left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup      # what the evaluators above read stays the image queries'
+        left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected      # what the evaluators above read stays the image queries'
         out = self._phase("retrieval_text", metric, db_codes, db_labels, text_codes, text_labels, R, **kw)
-        utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup = left
+        utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected = left
         for key, v in zip(KEYS, out):
             res[key] = v
         res["text_prompt_prefix"], res["text_model"] = prefix, source

@@ -100,14 +100,19 @@ class RetrievalExperiment:
                 mean = g.mean(dim=0, keepdim=True)
                 q, g = q - mean, g - mean
             tie = dict(tie_bracket=True) if config.get("tie_bracket") else {}
+            if config.get("tie_expected"):
+                tie["tie_expected"] = True
             mAP, recalls, precisions = calculate_mAP(g, db_out["labels"], q, test_out["labels"], config.dataset.R,
                                                      dist_metric=config.dist_metric, PRs=[1, 5, 10],
                                                      multiclass=config.dataset.get("multiclass", False), **tie)
             res["mAP" + postfix], res["recalls" + postfix], res["precisions" + postfix] = mAP, recalls, precisions
-            if tie:   # smallest / largest mAP over every order of equal-distance rows (utils.hashing.last_tie_bracket)
+            if tie.get("tie_bracket"):   # smallest / largest mAP over every order of equal-distance rows (utils.hashing.last_tie_bracket)
                 import utils.hashing
                 res["mAP_tie_low" + postfix] = utils.hashing.last_tie_bracket["mAP_low"]
                 res["mAP_tie_high" + postfix] = utils.hashing.last_tie_bracket["mAP_high"]
+            if tie.get("tie_expected"):  # ... and the mean over those orders (utils.hashing.last_tie_expected)
+                import utils.hashing
+                res["mAP_tie_expected" + postfix] = utils.hashing.last_tie_expected["mAP_expected"]
             logging.info("mAP%s: %.6f  R@10 %.6f  P@10 %.6f", postfix, mAP, recalls[-1], precisions[-1])
         return res, test_out, db_out
 

@@ -628,6 +628,23 @@ int ch_hamming_tie_bracket(const uint32_t *bucket_counts, int64_t Qn, int32_t nb
                            int32_t remove_first, unsigned long long *out_S_low, uint32_t *out_nrel_low,
                            unsigned long long *out_S_high, uint32_t *out_nrel_high, void *stream);
 
+/* Tie expectation: for every query the MEAN of AP@R, hits@k and R@k over every order of the rows sharing a Hamming distance, each
+ * bucket independently and uniformly permuted -- the value that depends on no sort implementation; it lies inside
+ * the bracket of ch_hamming_tie_bracket.  bucket_counts, rank_limits and remove_first as there (0 <= nlimits <= 16); ks: host array of
+ * 0 <= nk <= 16 depths k >= 1, in any order.  remove_first != 0: the dropped rank-1 row is uniform among the rows of the lowest non-empty
+ * bucket, and every output is the mixture of the two kinds of dropped row (the recall of a kind divides by the relevant rows it leaves).
+ * out_ap [nlimits, Qn], out_hits [nk, Qn], out_recall [nk, Qn]: fp64, WRITTEN; a query without a gallery row, or without a relevant
+ * one, gets zeros.  bucket_counts and the outputs must be 8-byte aligned (checked).
+ * Arithmetic: fp64, one rounding per operation (no contraction); the hypergeometric weights of the bucket a limit cuts come from the
+ * ratio recurrence outward from the mode, normalised by their sum, and a direction stops early only once the log-concave tail bound
+ * w rho / (1 - rho) is under 2^-70.  |out - exact| is bounded per query by tests/tie_expected_ref.py `error_bound` (a few 1e-13 at a
+ * few thousand rows per bucket).  Cost: one fp64 division per gallery row inside the largest limit plus, per limit that cuts a bucket,
+ * one per row of that bucket inside the limit and a few per kept weight (about 20 standard deviations of the hypergeometric count):
+ * linear, never take^2. */
+int ch_hamming_tie_expected(const uint32_t *bucket_counts, int64_t Qn, int32_t nb, const int64_t *rank_limits, int32_t nlimits,
+                            const int64_t *ks, int32_t nk, int32_t remove_first, double *out_ap, double *out_hits, double *out_recall,
+                            void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * CLIP text tower (language-guided class centres)
  * ------------------------------------------------------------------------------------------------------------- */

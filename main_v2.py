@@ -30,7 +30,7 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
              "dist_metric", "batch_size", "save_code", "sub_code_eval", "sub_code_eval_setting", "zero_mean_eval",
              "test_as_database")
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
-LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits", "text_eval",
+LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "tie_expected", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits", "text_eval",
              "prompt_prefix", "text_model", "ternary_eval", "ternary_margin", "dense_eval", "dense_metric", "rerank_eval", "rerank_metric",
              "rerank_shortlist")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
@@ -67,7 +67,9 @@ def run(config):
         load_config = _run_config(config, "validation", EVAL_KEYS)
         if load_config.get("tie_bracket"):      # the evaluator + the mAP bracket over tie orders
             from experiments.tie_bracket_eval import TieBracketEvaluation as RetrievalEvaluation
-        if load_config.get("concept_eval"):     # ... + the per-concept table (it extends the tie-bracket evaluator)
+        if load_config.get("tie_expected"):     # ... + the mean over those orders (it extends the tie-bracket evaluator)
+            from experiments.tie_expected_eval import TieExpectedEvaluation as RetrievalEvaluation
+        if load_config.get("concept_eval"):     # ... + the per-concept table (it extends both)
             from experiments.concept_eval import ConceptEvaluation as RetrievalEvaluation
         if load_config.get("hash_lookup_radii") is not None:   # ... + hash lookup within Hamming radii (it extends both)
             from experiments.hash_lookup_eval import HashLookupEvaluation as RetrievalEvaluation

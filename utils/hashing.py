@@ -53,15 +53,20 @@ last_tie_bracket = None
 # Hash lookup of the last calculate_mAP(..., radii=[...]) call, the same pattern: {"radii", "precisions_radius", "recalls_radius",
 # "retrieved_radius", "empty_radius"} (lists, one entry per radius); None after any other call.
 last_hash_lookup = None
+# The tie expectation of the last calculate_mAP(..., tie_expected=True) call, the same pattern: {"mAP_expected", "precisions_expected",
+# "recalls_expected"} -- the mean over every order of equal-distance rows; None after any other call.
+last_tie_expected = None
 # The two-stage figures of the last calculate_mAP(..., rank=<dense>, shortlist=m) call, the same pattern: {"metric", "shortlist", "R"
 # (the effective R: -1 becomes the shortlist), "agreement" ({k: share of the exhaustive dense top-k found in the two-stage top-k})};
 # None after any other call.
 last_rerank = None
 
 
-def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False, radii=None):
+def _evaluate(db_codes, db_labels, test_codes, test_labels, R, ks, remove_first, skip=False, tie=False, radii=None, expected=False):
     dev = _device()
     look = {} if radii is None else {"radii": radii}    # the sharded evaluator refuses it (NotImplementedError)
+    if expected:
+        look["tie_expected"] = True
     from concepthash_amd.distributed import RowShard
     if isinstance(db_codes, RowShard) or isinstance(test_codes, RowShard):
         # multi-rank evaluation on the outputs of BaseTrainer.inference_one_epoch: every rank's block of the DATABASE stays on the
@@ -136,7 +141,8 @@ def _evaluate_ranked(rank, db_codes, db_labels, test_codes, test_labels, R, ks, 
 
 def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0., dist_metric="hamming", PRs=None,
                   remove_first_retrieved=False, landmark_gt=None, db_id=None, test_id=None, multiclass=False,
-                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8, margin=None, shortlist=None):
+                  skip_queries_without_relevant=False, tie_bracket=False, radii=None, rank="hamming", weight_bits=8, margin=None, shortlist=None,
+                  tie_expected=False):
     """-> (mAP, recalls, precisions); `mAP` is a list when `R` is a list (experiments/test_hashing.py:124-128).
     R <= 0 means the whole database.  One histogram pass + one AP pass whatever the length of R and PRs: every R and every k
     is a rank limit of the same gallery scan.
@@ -148,6 +154,11 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     database rows that share a Hamming distance -- the one thing another implementation's sort may do
     differently.  The triple returned is unchanged; the bracket is left in the module attribute `last_tie_bracket` (a dict with
     mAP_low, mAP_high, precisions_low/high, recalls_low/high; lists where the triple has lists), which is None after a call without it.
+    tie_expected (not a reference argument): also compute the MEAN of every statistic over those orders, every set of equal-distance
+    rows uniformly permuted ("tie expectation") -- the figure that depends on no sort implementation, inside the
+    bracket.  The triple is unchanged; `last_tie_expected` holds mAP_expected, precisions_expected, recalls_expected, and is None after
+    a call without it.  Hamming rank only, and not together with skip_queries_without_relevant (ValueError: the set of counted queries
+    would depend on the tie order).
     radii (not a reference argument): a list of Hamming radii -- also compute hash lookup within each ("P@H<=r": precision, recall, rows
     retrieved and the share of queries retrieving nothing) from the histogram the call holds anyway; left in the
     module attribute `last_hash_lookup` in the same way.  Single-process evaluation only.
@@ -172,7 +183,7 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     codes, ordered by the dense distance.  1 <= m <= 4096; R and every k must lie in [1, m] and R = -1 means m (ValueError otherwise);
     recall counts the relevant rows of the whole database.  The effective R and agreement@k with the exhaustive dense list are left
     in the module attribute `last_rerank`.  Under any other rank a shortlist is a ValueError."""
-    global last_tie_bracket, last_hash_lookup, last_rerank
+    global last_tie_bracket, last_hash_lookup, last_rerank, last_tie_expected
     if rank not in RANKS:
         raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
     if shortlist is not None:
@@ -182,12 +193,17 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
     last_rerank = None
     if rank != "hamming" and (tie_bracket or radii is not None):
         raise ValueError(f"rank='{rank}' has no tie bracket and no radius lookup: both are defined on Hamming distances")
+    if rank != "hamming" and tie_expected:
+        raise ValueError(f"rank='{rank}' has no tie expectation: it is defined on Hamming distances, as the tie bracket is")
+    if tie_expected and skip_queries_without_relevant:
+        raise ValueError(rt.EXPECTED_NEEDS_ALL_QUERIES)
     if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
         raise ValueError(f"weight_bits must be one of {rt.WEIGHT_BITS}, got {weight_bits}")
     if rank == "ternary":
         margin = rt.check_margin(margin, "rank='ternary': margin")
     last_tie_bracket = None
     last_hash_lookup = None
+    last_tie_expected = None
     _check(dist_metric, threshold, landmark_gt)
     ks = [int(k) for k in (PRs or [])]
     many = isinstance(R, (list, tuple)) or (hasattr(R, "__iter__") and not isinstance(R, (int, float)))
@@ -201,12 +217,14 @@ def calculate_mAP(db_codes, db_labels, test_codes, test_labels, R, threshold=0.,
             last_rerank = dict(metric=rank, shortlist=shortlist, R=res["R"], agreement=res["agreement"])
     else:
         res = _evaluate(db_codes, db_labels, test_codes, test_labels, Rs, ks, remove_first_retrieved, bool(skip_queries_without_relevant),
-                        bool(tie_bracket), [int(r) for r in radii] if radii is not None else None)
+                        bool(tie_bracket), [int(r) for r in radii] if radii is not None else None, bool(tie_expected))
     if radii is not None:
         last_hash_lookup = dict({k: res[k] for k in ("precisions_radius", "recalls_radius", "retrieved_radius", "empty_radius")},
                                 radii=[int(r) for r in radii])
     if tie_bracket:
         last_tie_bracket = {k: res[k] for k in ("mAP_low", "mAP_high", "precisions_low", "precisions_high", "recalls_low", "recalls_high")}
+    if tie_expected:
+        last_tie_expected = {k: res[k] for k in ("mAP_expected", "precisions_expected", "recalls_expected")}
     return res["mAP"], res["recalls"], res["precisions"]
 
 
