@@ -106,6 +106,13 @@ SIGNATURES = {
     "ch_hamming_topk_weighted_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "ch_hamming_topk_weighted": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ch_hamming_topk_filtered_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_hamming_topk_filtered": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p,
+                                         c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ch_hamming_topk_weighted_filtered_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_hamming_topk_weighted_filtered": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64,
+                                                  c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_void_p]),
     "ch_hamming_subcode_dist": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int64, c_int32, c_int32,
                                         c_void_p, c_void_p]),
     "ch_topk_merge": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -188,6 +195,9 @@ SIGNATURES = {
     "ch_ternary_topk_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "ch_ternary_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
+    "ch_ternary_topk_filtered_workspace": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "ch_ternary_topk_filtered": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ch_ternary_rank_collect": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int64,
                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "ch_ternary_rank_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_int32, c_void_p, c_void_p,

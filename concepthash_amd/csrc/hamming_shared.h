@@ -142,14 +142,41 @@ __device__ __forceinline__ uint32_t make_key(uint32_t d, uint32_t row_uniform) {
     return key;
 }
 
+// The filter of a scan (ch_*_topk_filtered; DESIGN.md section 2.0, "filtered search"): which gallery rows may be hits at all.  Row r of
+// THIS call's gallery is admitted for query i iff
+//     allow == NULL or bit r & 63 of allow[r >> 6] is set                               (one bitmap for all queries), and
+//     want == NULL or want[i] < 0 or (grp(r) == want[i]) != exclude                     (per query),
+// grp(r) = group[r] (int32 >= 0) or, where group == NULL, base + r: a row is its own group.  A row that is not admitted for a lane gets
+// the empty-slot key 0xFFFFFFFF, which is above every real key of every scan (asserted beside KEY_SHIFT / WKEY_SHIFT in hamming_topk.hip
+// and beside TKEY_SHIFT in hamming_ternary.hip), so the insertion network and the merge see nothing new.  The unfiltered scans carry
+// TopkNoFilter, an empty argument, and none of the filter's code.
+struct TopkNoFilter {
+    static constexpr bool ON = false;
+};
+struct TopkFilter {
+    static constexpr bool ON = true;
+    const uint64_t *allow;   // [ceil(G / 64)] or NULL
+    const int32_t *group;    // [G] or NULL
+    const int64_t *want;     // [Qn] or NULL
+    int64_t base;            // g_index_base: the group of row r where group == NULL
+    int exclude;             // 0: only the wanted group, 1: every group but it
+};
+
 // Segment blockIdx.y of the gallery against query qi (a lane past Qn scans too -- its registers hold zeros -- and stores nothing):
 // from the empty list to the store of its k smallest keys.  W: the 64-bit words of a gallery ROW (a two-plane row has twice the words
 // of a code); dist: const uint64_t * (those words) -> uint32_t.  UB (4 or 2): the rows of one block of scalar loads -- two buffers of
 // UB * W * 2 SGPRs have to fit beside everything else that is wave-uniform.
-template <int W, int KREG, int SHIFT, int UB = 4, class Dist>
+// Under a TopkFilter both of its parts are run-time, wave-uniform conditions of ONE instance.  The allow-list lives on the scalar path:
+// the gallery walk is wave-uniform, so the word of the bitmap that holds a block's rows is an SGPR pair, loaded once per 64 rows (a
+// segment starts anywhere, so a block may straddle two words: the second one is loaded then and stays for the rows behind), and a block
+// whose UB bits are all zero is left by a wave-uniform branch in front of its distances, keys and threshold test.  The group part costs
+// one compare and one select per row: the row's group id (or its number in the segment) is wave-uniform, the lane holds its query's
+// wanted id as 32 bits (-2, which no row has, where the query wants nothing or an id that no row of this segment can have).
+template <int W, int KREG, int SHIFT, int UB = 4, class Dist, class Filter = TopkNoFilter>
 __device__ __forceinline__ void topk_scan(const Dist &dist, int64_t qi, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
-                                          int seg_rows, int k, uint32_t *__restrict__ part) {
+                                          int seg_rows, int k, uint32_t *__restrict__ part, const Filter &flt = Filter{}) {
     static_assert(UB == 4 || UB == 2, "rows per block");
+    constexpr bool FILTERED = Filter::ON;
     const int seg = blockIdx.y;
     const int64_t g0 = (int64_t)seg * seg_rows;
     const int n = (int)min((int64_t)seg_rows, G - g0);
@@ -167,17 +194,98 @@ __device__ __forceinline__ void topk_scan(const Dist &dist, int64_t qi, int64_t 
             }
         }
     };
+    // the filter's registers: per lane the wanted id and whether there is one; wave-uniform the bitmap word in hand and its number
+    [[maybe_unused]] int32_t wv = -2;
+    [[maybe_unused]] bool has = false;
+    [[maybe_unused]] bool grouped = false, own_row = false;
+    [[maybe_unused]] uint64_t aword = 0ull;
+    [[maybe_unused]] int aword_at = -1;              // ... counted from the word of the segment's first row, so 32 bits do
+    [[maybe_unused]] const uint64_t *ap = nullptr;   // that word
+    [[maybe_unused]] int a0 = 0;                     // the segment's first row in it
+    if constexpr (FILTERED) {
+        if (flt.allow != nullptr) ap = flt.allow + (g0 >> 6);
+        a0 = (int)(g0 & 63);
+        grouped = flt.want != nullptr;
+        own_row = grouped && flt.group == nullptr && flt.exclude != 0;   // "every row but the query's own"
+        if (grouped && qi < Qn) {
+            const int64_t w = flt.want[qi];
+            // group == NULL: the one row base + r == w, as its number in this segment; a group plane: ids are int32 >= 0
+            const int64_t v = flt.group != nullptr ? w : w - flt.base - g0;
+            has = w >= 0;
+            wv = (has && v >= 0 && v <= 0x7FFFFFFFll) ? (int32_t)v : -2;
+        }
+    }
+    // bits [0, cnt) = the allow bits of rows [row, row + cnt) of the segment (cnt <= UB; all of them < n)
+    [[maybe_unused]] auto allow_bits = [&](int row, int cnt) -> uint32_t {
+        const uint32_t all = (1u << cnt) - 1u;
+        if constexpr (FILTERED) {
+            if (ap == nullptr) return all;
+            const int r = a0 + row;
+            const int w = r >> 6;
+            const int b = r & 63;
+            if (w != aword_at) {
+                aword = ap[w];
+                aword_at = w;
+            }
+            uint64_t bits = aword >> b;
+            if (b + cnt > 64) {   // the block's last rows are in the next word (it exists: they are rows of the gallery)
+                aword = ap[w + 1];
+                aword_at = w + 1;
+                bits |= aword << (64 - b);
+            }
+            return (uint32_t)bits & all;
+        } else {
+            return all;
+        }
+    };
+    // a lane's key of a row under the group part: the empty slot where the row's group is not admitted for its query
+    [[maybe_unused]] auto group_key = [&](uint32_t key, int32_t grp) -> uint32_t {
+        if constexpr (FILTERED) {
+            const bool hit = grp == wv;
+            const bool rej = flt.exclude != 0 ? hit : (has && !hit);
+            return rej ? 0xFFFFFFFFu : key;
+        } else {
+            return key;
+        }
+    };
     // UB gallery rows per trip: one wide scalar load (the next block is requested before this one is consumed), UB keys, ONE
     // threshold test on their minimum; the insertion network runs only if some lane beats its list.
     uint64_t bufA[UB * W], bufB[UB * W];
-    auto load_block = [&](uint64_t (&dst)[UB * W], int row) {
+    [[maybe_unused]] int32_t grpA[UB], grpB[UB];   // FILTERED: the rows' group ids (or their numbers in the segment) beside their words
+    auto load_block = [&](uint64_t (&dst)[UB * W], [[maybe_unused]] int32_t (&grp)[UB], int row) {
 #pragma unroll
         for (int t = 0; t < UB * W; ++t) dst[t] = gp[(size_t)row * W + t];
+        if constexpr (FILTERED) {
+            if (grouped) {
+#pragma unroll
+                for (int u = 0; u < UB; ++u) grp[u] = flt.group != nullptr ? flt.group[g0 + row + u] : row + u;
+            }
+        }
     };
-    auto scan_block = [&](const uint64_t (&blk)[UB * W], int row) {
+    auto scan_block = [&](const uint64_t (&blk)[UB * W], [[maybe_unused]] const int32_t (&grp)[UB], int row) {
+        [[maybe_unused]] uint32_t bits = 0u;
+        if constexpr (FILTERED) {
+            bits = allow_bits(row, UB);
+            if (bits == 0u) return;   // wave-uniform: no row of the block is admitted for anybody
+        }
         uint32_t key[UB];
 #pragma unroll
         for (int u = 0; u < UB; ++u) key[u] = make_key<SHIFT>(dist(blk + u * W), (uint32_t)(row + u));
+        if constexpr (FILTERED) {
+            if (grouped) {
+                // own_row: a lane's one row is in one block of one segment -- one test per block says whether any lane's is in this one
+                bool any = true;
+                if (own_row) any = __builtin_amdgcn_ballot_w64((uint32_t)(wv - row) < (uint32_t)UB) != 0ull;
+                if (any) {
+#pragma unroll
+                    for (int u = 0; u < UB; ++u) key[u] = group_key(key[u], grp[u]);
+                }
+            }
+            if (bits != (1u << UB) - 1u) {
+#pragma unroll
+                for (int u = 0; u < UB; ++u) key[u] = ((bits >> u) & 1u) != 0u ? key[u] : 0xFFFFFFFFu;
+            }
+        }
         uint32_t kmin;
         if constexpr (UB == 4)
             kmin = min(min(key[0], key[1]), min(key[2], key[3]));
@@ -190,18 +298,27 @@ __device__ __forceinline__ void topk_scan(const Dist &dist, int64_t qi, int64_t 
     };
     // two blocks per iteration with the two SGPR buffers taking turns: no register copies between trips
     int j = 0;
-    if (n >= UB) load_block(bufA, 0);
+    if (n >= UB) load_block(bufA, grpA, 0);
     for (; j + 2 * UB <= n; j += 2 * UB) {
-        load_block(bufB, j + UB);
-        scan_block(bufA, j);
-        if (j + 3 * UB <= n) load_block(bufA, j + 2 * UB);
-        scan_block(bufB, j + UB);
+        load_block(bufB, grpB, j + UB);
+        scan_block(bufA, grpA, j);
+        if (j + 3 * UB <= n) load_block(bufA, grpA, j + 2 * UB);
+        scan_block(bufB, grpB, j + UB);
     }
     if (j + UB <= n) {  // an odd number of whole blocks: the last one is already in bufA
-        scan_block(bufA, j);
+        scan_block(bufA, grpA, j);
         j += UB;
     }
-    for (; j < n; ++j) insert((dist(gp + (size_t)j * W) << SHIFT) | (uint32_t)j);
+    if constexpr (FILTERED) {
+        for (; j < n; ++j) {   // the tail filters row by row
+            if (allow_bits(j, 1) == 0u) continue;
+            uint32_t key = (dist(gp + (size_t)j * W) << SHIFT) | (uint32_t)j;
+            if (grouped) key = group_key(key, flt.group != nullptr ? flt.group[g0 + j] : j);
+            insert(key);
+        }
+    } else {
+        for (; j < n; ++j) insert((dist(gp + (size_t)j * W) << SHIFT) | (uint32_t)j);
+    }
     if (qi < Qn) {
         uint32_t *o = part + ((size_t)seg * Qn + qi) * k;
 #pragma unroll
@@ -278,6 +395,10 @@ int topk_seg_rows_for(int64_t Qn, int64_t G, int per_cu, int64_t max_rows) {
     return (int)rows;
 }
 
+// Workgroups of four waves that a CU keeps of a scan kernel with `vgprs` registers (the scans have no LDS): min(8, 512 / VGPRs rounded
+// up to the allocation unit of 8) -- the table form of the segment rules.
+int topk_per_cu(int vgprs) { return std::max(1, std::min(8, 512 / std::max(8, (vgprs + 7) / 8 * 8))); }
+
 // host: one launch path.  A "scan" names one kernel family, holds its extra arguments and knows its key split, its segmentation, its
 // workspace and the wording of its own refusals; topk_run is the body of every top-k entry point.
 struct TopkCall {   // what every partial launch takes
@@ -289,6 +410,7 @@ struct TopkCall {   // what every partial launch takes
     uint32_t *part;
     dim3 grid;
     hipStream_t s;
+    const TopkFilter *flt;   // NULL: the unfiltered kernel; otherwise the filtered one with *flt
 };
 
 // lists of KREG = 10 / 16 / 32 / 64 / 128 keys.  k <= 10 (PRs = [1, 5, 10]): exactly k entries, so the insertion threshold is the
@@ -312,16 +434,19 @@ void topk_launch(const Scan &scan, int W, const TopkCall &c) {
     }
 }
 
-// The body of ch_hamming_topk / _masked / _weighted and ch_ternary_topk: the checks in the order the entries have always made them
-// (`name` opens the messages), partial lists, merge.  A segment's rows must fit under the key's distance: the scan's seg_rows() answers
-// at most 2^SHIFT, checked here in front of the launch.
+// The body of ch_hamming_topk / _masked / _weighted and ch_ternary_topk and of their _filtered forms: the checks in the order the
+// entries have always made them (`name` opens the messages), partial lists, merge.  A segment's rows must fit under the key's distance:
+// the scan's seg_rows() answers at most 2^SHIFT, checked here in front of the launch.  flt: NULL, or the filter of a _filtered entry
+// (its base is the call's g_index_base); the scan's seg_rows() and workspace() know on their own whether they answer for the filtered kernels.
 template <class Scan>
 int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W,
-             int k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, hipStream_t s) {
+             int k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, hipStream_t s,
+             const TopkFilter *flt = nullptr) {
     const std::string at = std::string(name) + ": ";
     CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
     CH_REQUIRE(k >= 1 && k <= 128, at + "1 <= k <= 128");
     CH_REQUIRE(Qn >= 0 && G >= 0, at + "negative sizes");
+    CH_REQUIRE(flt == nullptr || flt->exclude == 0 || flt->exclude == 1, at + "exclude must be 0 or 1");
     if (int e = scan.check(W)) return e;
     if (Qn == 0) return 0;
     CH_REQUIRE(q && scan.operands() && out_idx && out_dist, at + "null pointer");
@@ -337,7 +462,7 @@ int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, 
     CH_REQUIRE(nseg <= 65535, Scan::too_many_segments);
     CH_REQUIRE(workspace && workspace_bytes >= scan.workspace(Qn, G, W, k), at + "workspace too small");
     uint32_t *part = (uint32_t *)workspace;
-    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s});
+    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s, flt});
     CH_LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_merge_keys_kernel<Scan::SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, (int)nseg, Qn, k,
                        seg_rows, g_index_base, out_idx, out_dist);

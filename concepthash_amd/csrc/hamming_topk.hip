@@ -14,6 +14,9 @@
 // network unless some lane beats its current threshold; the network itself is branch free (min/max chain).
 //     SHIFT = 23 (plain, masked): dist <= 256, segments of < 2^23 rows.
 //     SHIFT = 16 (weighted): D <= 255 * 256 = 65,280 < 2^16 - 1, so 0xFFFFFFFF stays the empty slot; segments hold <= 65,536 rows.
+// Filtered search (ch_hamming_topk_filtered, ch_hamming_topk_weighted_filtered): the same scans with the TopkFilter of hamming_shared.h --
+// an allow-list bitmap on the scalar path and a per-query group test -- as one more instance per (W, KREG, MASKED) and (W, KREG, P);
+// a row that is not admitted gets the empty-slot key 0xFFFFFFFF, which the static_asserts below keep above every real key.
 // topk_merge_keys_kernel<SHIFT> merges the per-segment lists of a call, topk_merge_lists_kernel the final lists of several shards;
 // subcode_dist_kernel breaks the distance of retrieved hits down by concept.
 #include <algorithm>
@@ -28,6 +31,12 @@ namespace {
 
 constexpr int KEY_SHIFT = 23;
 constexpr int WKEY_SHIFT = 16;
+// the empty slot -- also the key of a row a filter does not admit -- is above every real key: the largest distance with the last row
+// of the longest segment (topk_seg_rows: < 2^23 rows; wtopk_seg_rows: <= 2^16)
+static_assert((256u << KEY_SHIFT | ((1u << KEY_SHIFT) - 2u)) < 0xFFFFFFFFu && (256u << KEY_SHIFT) >> KEY_SHIFT == 256u,
+              "dist <= 256 and a row of the segment share a 32-bit key below the empty slot");
+static_assert((65280u << WKEY_SHIFT | ((1u << WKEY_SHIFT) - 1u)) < 0xFFFFFFFFu && (65280u << WKEY_SHIFT) >> WKEY_SHIFT == 65280u,
+              "D <= 255 * 256 and a row of the segment share a 32-bit key below the empty slot");
 
 // ---------------------------------------------------------------------------------------------------------------
 // the three distances of one gallery row (bcnt_acc, load_query and the plain hamming<W>: hamming_shared.h)
@@ -77,10 +86,11 @@ struct TopkMask<true> {
     int stride;
 };
 
-template <int W, int KREG, bool MASKED>
-__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm) {
+// the body of topk_partial_kernel and of its filtered form (Filter: TopkNoFilter or TopkFilter, hamming_shared.h)
+template <int W, int KREG, bool MASKED, class Filter>
+__device__ __forceinline__ void topk_partial(const uint64_t *__restrict__ q, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
+                                             int seg_rows, int k, uint32_t *__restrict__ part, const TopkMask<MASKED> &qm,
+                                             const Filter &flt) {
     const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t qw[2 * W];
     load_query<W>(qw, q, qi, Qn);
@@ -93,17 +103,32 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__res
             mw[2 * w + 1] = (uint32_t)(v >> 32);
         }
         topk_scan<W, KREG, KEY_SHIFT>([&](const uint64_t *gw) { return (uint32_t)hamming_masked<W>(qw, mw, gw); }, qi, Qn, g, G, seg_rows, k,
-                                      part);
+                                      part, flt);
     } else {
-        topk_scan<W, KREG, KEY_SHIFT>([&](const uint64_t *gw) { return (uint32_t)hamming<W>(qw, gw); }, qi, Qn, g, G, seg_rows, k, part);
+        topk_scan<W, KREG, KEY_SHIFT>([&](const uint64_t *gw) { return (uint32_t)hamming<W>(qw, gw); }, qi, Qn, g, G, seg_rows, k, part,
+                                      flt);
     }
 }
 
-template <int W, int KREG, int P>
-__global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64_t *__restrict__ q,
-                                                                    const uint64_t *__restrict__ planes, int64_t Qn,
+template <int W, int KREG, bool MASKED>
+__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
+                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm) {
+    topk_partial<W, KREG, MASKED>(q, Qn, g, G, seg_rows, k, part, qm, TopkNoFilter{});
+}
+
+// ch_hamming_topk_filtered: one instance per instance above, every part of the filter a run-time condition of it
+template <int W, int KREG, bool MASKED>
+__global__ __launch_bounds__(256) void topk_partial_filtered_kernel(const uint64_t *__restrict__ q, int64_t Qn,
                                                                     const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                                    uint32_t *__restrict__ part) {
+                                                                    uint32_t *__restrict__ part, TopkMask<MASKED> qm, TopkFilter flt) {
+    topk_partial<W, KREG, MASKED>(q, Qn, g, G, seg_rows, k, part, qm, flt);
+}
+
+template <int W, int KREG, int P, class Filter>
+__device__ __forceinline__ void topk_weighted_partial(const uint64_t *__restrict__ q, const uint64_t *__restrict__ planes, int64_t Qn,
+                                                      const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                      uint32_t *__restrict__ part, const Filter &flt) {
     const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t qw[2 * W];
     load_query<W>(qw, q, qi, Qn);
@@ -117,7 +142,25 @@ __global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64
             pl[p][2 * w + 1] = (uint32_t)(v >> 32);
         }
     }
-    topk_scan<W, KREG, WKEY_SHIFT>([&](const uint64_t *gw) { return weighted_dist<W, P>(qw, pl, gw); }, qi, Qn, g, G, seg_rows, k, part);
+    topk_scan<W, KREG, WKEY_SHIFT>([&](const uint64_t *gw) { return weighted_dist<W, P>(qw, pl, gw); }, qi, Qn, g, G, seg_rows, k, part,
+                                   flt);
+}
+
+template <int W, int KREG, int P>
+__global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64_t *__restrict__ q,
+                                                                    const uint64_t *__restrict__ planes, int64_t Qn,
+                                                                    const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                                    uint32_t *__restrict__ part) {
+    topk_weighted_partial<W, KREG, P>(q, planes, Qn, g, G, seg_rows, k, part, TopkNoFilter{});
+}
+
+// ch_hamming_topk_weighted_filtered
+template <int W, int KREG, int P>
+__global__ __launch_bounds__(256) void topk_weighted_partial_filtered_kernel(const uint64_t *__restrict__ q,
+                                                                             const uint64_t *__restrict__ planes, int64_t Qn,
+                                                                             const uint64_t *__restrict__ g, int64_t G, int seg_rows,
+                                                                             int k, uint32_t *__restrict__ part, TopkFilter flt) {
+    topk_weighted_partial<W, KREG, P>(q, planes, Qn, g, G, seg_rows, k, part, flt);
 }
 
 // merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
@@ -240,6 +283,21 @@ int topk_seg_rows(int64_t Qn, int64_t G, int k) {
     return topk_seg_rows_for(Qn, G, per_cu, (int64_t)(1 << KEY_SHIFT) - 1);
 }
 
+// The filtered scans follow their OWN registers (profiles/search_filtered_topk.txt: 1 to 7 VGPRs above their siblings, no scratch),
+// in the table form.  It differs from the rule above at lists of 32 keys only (7, 6 or 5 workgroups per CU, not 7 throughout).
+// VGPRs of topk_partial_filtered_kernel<W, KREG, MASKED> from the code-object metadata of this build:
+constexpr int FTOPK_VGPRS[2][4][5] = {
+    // KREG 10, 16, 32, 64, 128
+    {{28, 40, 72, 134, 259}, {30, 41, 73, 136, 259}, {33, 45, 77, 139, 259}, {35, 47, 79, 141, 259}},   // plain, W = 1..4
+    {{30, 42, 74, 136, 259}, {34, 46, 78, 140, 259}, {39, 51, 83, 145, 259}, {43, 55, 87, 149, 259}},   // masked, W = 1..4
+};
+
+int topk_list_index(int k) { return k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4; }
+
+int ftopk_seg_rows(int64_t Qn, int64_t G, int W, int k, bool masked) {
+    return topk_seg_rows_for(Qn, G, topk_per_cu(FTOPK_VGPRS[masked][W - 1][topk_list_index(k)]), (int64_t)(1 << KEY_SHIFT) - 1);
+}
+
 // VGPRs of topk_weighted_partial_kernel<W, KREG, P> from the code-object metadata of this build (profiles/search_weighted_topk.txt;
 // no instance uses scratch): a CU holds min(8, 512 / VGPRs rounded up to the allocation unit of 8) workgroups of four waves.
 constexpr int WTOPK_VGPRS[2][4][5] = {
@@ -248,9 +306,15 @@ constexpr int WTOPK_VGPRS[2][4][5] = {
     {{47, 53, 84, 148, 258}, {67, 73, 102, 166, 258}, {85, 91, 120, 184, 258}, {103, 109, 138, 202, 266}},  // P = 8, W = 1..4
 };
 
-int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P) {
+// ... and of topk_weighted_partial_filtered_kernel<W, KREG, P> (profiles/search_filtered_topk.txt)
+constexpr int FWTOPK_VGPRS[2][4][5] = {
+    {{36, 48, 80, 142, 259}, {47, 58, 90, 152, 259}, {58, 69, 101, 163, 259}, {68, 79, 111, 173, 259}},     // P = 4, W = 1..4
+    {{48, 56, 88, 150, 259}, {68, 74, 106, 168, 259}, {88, 94, 125, 187, 259}, {106, 112, 143, 205, 268}},  // P = 8, W = 1..4
+};
+
+int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P, bool filtered = false) {
     const int ki = k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4;
-    const int vgprs = (WTOPK_VGPRS[P == 8][W - 1][ki] + 7) / 8 * 8;
+    const int vgprs = ((filtered ? FWTOPK_VGPRS : WTOPK_VGPRS)[P == 8][W - 1][ki] + 7) / 8 * 8;
     const int per_cu = std::max(1, std::min(8, 512 / std::max(8, vgprs)));
     return topk_seg_rows_for(Qn, G, per_cu, (int64_t)1 << WKEY_SHIFT);
 }
@@ -264,6 +328,7 @@ struct HammingScan {
     static constexpr int SHIFT = KEY_SHIFT;
     static constexpr const char *too_many_segments = "hamming_topk: gallery too large for one call (shard it)";
     TopkMask<MASKED> qm;
+    bool filtered = false;   // ch_hamming_topk_filtered: the segments and the workspace of the filtered kernels
     int check(int W) const {   // the masked entry's own refusals
         if constexpr (MASKED) {
             CH_REQUIRE(qm.stride == 0 || qm.stride == W,
@@ -273,12 +338,20 @@ struct HammingScan {
         return 0;
     }
     bool operands() const { return true; }   // the mask was checked above
-    int seg_rows(int64_t Qn, int64_t G, int, int k) const { return topk_seg_rows(Qn, G, k); }
-    size_t workspace(int64_t Qn, int64_t G, int W, int k) const { return ch_hamming_topk_workspace(Qn, G, W, k); }
+    int seg_rows(int64_t Qn, int64_t G, int W, int k) const {
+        return filtered ? ftopk_seg_rows(Qn, G, W, k, MASKED) : topk_seg_rows(Qn, G, k);
+    }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k) const {
+        return filtered ? ch_hamming_topk_filtered_workspace(Qn, G, W, k) : ch_hamming_topk_workspace(Qn, G, W, k);
+    }
     template <int W, int KREG>
     void launch(const TopkCall &c) const {
-        hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows, c.k, c.part,
-                           qm);
+        if (c.flt != nullptr)
+            hipLaunchKernelGGL((topk_partial_filtered_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows,
+                               c.k, c.part, qm, *c.flt);
+        else
+            hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows, c.k,
+                               c.part, qm);
     }
 };
 
@@ -288,14 +361,21 @@ struct WeightedScan {
     static constexpr const char *too_many_segments =
         "hamming_topk_weighted: gallery too large for one call: more than 65,535 segments (shard it)";
     const uint64_t *planes;
+    bool filtered = false;   // ch_hamming_topk_weighted_filtered
     int check(int) const { return 0; }
     bool operands() const { return planes != nullptr; }
-    int seg_rows(int64_t Qn, int64_t G, int W, int k) const { return wtopk_seg_rows(Qn, G, W, k, P); }
-    size_t workspace(int64_t Qn, int64_t G, int W, int k) const { return ch_hamming_topk_weighted_workspace(Qn, G, W, k); }
+    int seg_rows(int64_t Qn, int64_t G, int W, int k) const { return wtopk_seg_rows(Qn, G, W, k, P, filtered); }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k) const {
+        return filtered ? ch_hamming_topk_weighted_filtered_workspace(Qn, G, W, k) : ch_hamming_topk_weighted_workspace(Qn, G, W, k);
+    }
     template <int W, int KREG>
     void launch(const TopkCall &c) const {
-        hipLaunchKernelGGL((topk_weighted_partial_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G, c.seg_rows,
-                           c.k, c.part);
+        if (c.flt != nullptr)
+            hipLaunchKernelGGL((topk_weighted_partial_filtered_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G,
+                               c.seg_rows, c.k, c.part, *c.flt);
+        else
+            hipLaunchKernelGGL((topk_weighted_partial_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G,
+                               c.seg_rows, c.k, c.part);
     }
 };
 
@@ -337,6 +417,46 @@ extern "C" int ch_hamming_topk_weighted(const uint64_t *q, const uint64_t *plane
                         out_dist, workspace, workspace_bytes, (hipStream_t)stream);
     return topk_run("hamming_topk_weighted", WeightedScan<8>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist,
                     workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// The filtered entries: their siblings' scans and checks under the filtered kernels (topk_run with a TopkFilter).  Their segments
+// follow the filtered kernels' registers, so they have workspace functions of their own; the calls name neither the mask nor P: room
+// for the finer of the two segmentations.
+extern "C" size_t ch_hamming_topk_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
+    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
+    const int rows = std::min(ftopk_seg_rows(Qn, G, W, k, false), ftopk_seg_rows(Qn, G, W, k, true));
+    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+}
+
+extern "C" size_t ch_hamming_topk_weighted_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
+    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
+    const int rows = std::min(wtopk_seg_rows(Qn, G, W, k, 4, true), wtopk_seg_rows(Qn, G, W, k, 8, true));
+    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+}
+
+extern "C" int ch_hamming_topk_filtered(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g,
+                                        int64_t G, int32_t W, int32_t k, int64_t g_index_base, const uint64_t *allow, const int32_t *group,
+                                        const int64_t *want, int32_t exclude, int64_t *out_idx, int32_t *out_dist, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    const TopkFilter flt{allow, group, want, g_index_base, (int)exclude};
+    if (q_mask == nullptr)
+        return topk_run("hamming_topk_filtered", HammingScan<false>{{}, true}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
+                        workspace_bytes, (hipStream_t)stream, &flt);
+    return topk_run("hamming_topk_filtered", HammingScan<true>{{q_mask, mask_stride}, true}, q, Qn, g, G, W, k, g_index_base,
+                    out_idx, out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
+}
+
+extern "C" int ch_hamming_topk_weighted_filtered(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g,
+                                                 int64_t G, int32_t W, int32_t k, int64_t g_index_base, const uint64_t *allow,
+                                                 const int32_t *group, const int64_t *want, int32_t exclude, int64_t *out_idx,
+                                                 int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream) {
+    CH_REQUIRE(P == 4 || P == 8, "hamming_topk_weighted_filtered: P (weight bits) must be 4 or 8");
+    const TopkFilter flt{allow, group, want, g_index_base, (int)exclude};
+    if (P == 4)
+        return topk_run("hamming_topk_weighted_filtered", WeightedScan<4>{planes, true}, q, Qn, g, G, W, k, g_index_base, out_idx,
+                        out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
+    return topk_run("hamming_topk_weighted_filtered", WeightedScan<8>{planes, true}, q, Qn, g, G, W, k, g_index_base, out_idx,
+                    out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
 }
 
 extern "C" int ch_weight_planes(const float *codes, int64_t Qn, int32_t nbit, const uint64_t *mask, int32_t mask_stride, int32_t P,

@@ -69,9 +69,9 @@ def _check_mask(mask: torch.Tensor, Qn: int, W: int, device, whose: str) -> Tupl
 
 
 def _topk(entry: str, q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int, stream, operands=(),
-          workspace: str = "ch_hamming_topk_workspace") -> Tuple[torch.Tensor, torch.Tensor]:
+          workspace: str = "ch_hamming_topk_workspace", filt=()) -> Tuple[torch.Tensor, torch.Tensor]:
     """The call of a ch_hamming_topk* entry on checked codes: allocates idx / dist / the workspace; `operands` are the entry's own
-    arguments, between q and Qn."""
+    arguments, between q and Qn; `filt` those of a filtered entry (`_check_filter`), behind g_index_base."""
     lib = _lib.load()
     Qn, W = q.shape
     G = g.shape[0]
@@ -80,8 +80,8 @@ def _topk(entry: str, q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: in
     wsb = int(getattr(lib, workspace)(Qn, G, W, k))
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     with _dev_guard(q):
-        _lib.check(getattr(lib, entry)(_lib.ptr(q), *operands, Qn, _lib.ptr(g), G, W, k, int(g_index_base), _lib.ptr(idx), _lib.ptr(dist),
-                                       _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), entry)
+        _lib.check(getattr(lib, entry)(_lib.ptr(q), *operands, Qn, _lib.ptr(g), G, W, k, int(g_index_base), *_filter_args(filt),
+                                       _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), entry)
     return idx, dist
 
 
@@ -135,6 +135,92 @@ def hamming_topk_weighted(q: torch.Tensor, planes: torch.Tensor, g: torch.Tensor
     q, planes, g = _check_weighted(q, planes, g)
     return _topk("ch_hamming_topk_weighted", q, g, k, g_index_base, stream, (_lib.ptr(planes), planes.shape[1]),
                  workspace="ch_hamming_topk_weighted_workspace")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# filtered search: the top-k among admitted rows only ("filtered search")
+# ---------------------------------------------------------------------------------------------------------------
+def row_bitmap(allow: torch.Tensor) -> torch.Tensor:
+    """bool [G] (on any device, the CPU included: torch ops only) -> int64 [ceil(G / 64)], the allow-list of the filtered entries: bit
+    r & 63 of word r >> 6 is allow[r]; the bits past G in the last word are zero."""
+    if allow.dtype != torch.bool or allow.dim() != 1:
+        raise TypeError(f"allow must be a bool tensor [G], got {allow.dtype} {tuple(allow.shape)}")
+    G = allow.shape[0]
+    words = (G + 63) // 64
+    bits = torch.zeros(words * 64, dtype=torch.int64, device=allow.device)
+    bits[:G] = allow
+    shifts = torch.arange(64, dtype=torch.int64, device=allow.device)
+    return (bits.view(words, 64) << shifts[None, :]).sum(1)           # distinct bits: the sum is their OR (bit 63 = the sign)
+
+
+def bitmap_count(bitmap: torch.Tensor, G: int) -> int:
+    """The set bits among the first G of a `row_bitmap` (what lies past G in the last word is not counted)."""
+    shifts = torch.arange(64, dtype=torch.int64, device=bitmap.device)
+    return int(((bitmap[:, None] >> shifts[None, :]) & 1).reshape(-1)[:G].sum())
+
+
+def _check_filter(allow, group, want, exclude, Qn: int, G: int, device):
+    """The filter of a filtered entry on checked codes -> (bitmap or None, group or None, want or None, exclude).  allow: bool [G]
+    (packed here) or a packed int64 [ceil(G / 64)]; group: int32 [G]; want: int64 [Qn]; all on the codes' device."""
+    if not isinstance(exclude, bool):
+        raise TypeError(f"exclude must be a bool, got {exclude!r}")
+    words = (G + 63) // 64
+    if allow is not None:
+        if not isinstance(allow, torch.Tensor) or allow.device != device or \
+                (allow.dtype, tuple(allow.shape)) not in ((torch.bool, (G,)), (torch.int64, (words,))):
+            raise ValueError(f"allow must be a bool tensor [{G}] or a packed int64 bitmap [{words}] (row_bitmap) on the codes' device, got "
+                             f"{getattr(allow, 'dtype', type(allow))} {tuple(getattr(allow, 'shape', ()))} on {getattr(allow, 'device', None)}")
+        allow = row_bitmap(allow) if allow.dtype == torch.bool else allow.contiguous()
+    if group is not None:
+        if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or tuple(group.shape) != (G,) or group.device != device:
+            raise ValueError(f"group must be an int32 tensor [{G}] on the codes' device, got {getattr(group, 'dtype', type(group))} "
+                             f"{tuple(getattr(group, 'shape', ()))} on {getattr(group, 'device', None)}")
+        if want is None:
+            raise ValueError("group without want: a group plane is read for the queries' wanted groups, int64 [Qn]")
+        group = group.contiguous()
+    if want is not None:
+        if not isinstance(want, torch.Tensor) or want.dtype != torch.int64 or tuple(want.shape) != (Qn,) or want.device != device:
+            raise ValueError(f"want must be an int64 tensor [{Qn}] on the codes' device (-1 = no group filter for that query), got "
+                             f"{getattr(want, 'dtype', type(want))} {tuple(getattr(want, 'shape', ()))} on {getattr(want, 'device', None)}")
+        want = want.contiguous()
+    return allow, group, want, exclude
+
+
+def _filter_args(filt):
+    """allow, group, want, exclude of a C entry; () for the unfiltered ones"""
+    if not filt:
+        return ()
+    allow, group, want, exclude = filt
+    return _lib.ptr(allow), _lib.ptr(group), _lib.ptr(want), int(exclude)
+
+
+def hamming_topk_filtered(q: torch.Tensor, g: torch.Tensor, k: int, allow: Optional[torch.Tensor] = None,
+                          group: Optional[torch.Tensor] = None, want: Optional[torch.Tensor] = None, exclude: bool = False,
+                          mask: Optional[torch.Tensor] = None, planes: Optional[torch.Tensor] = None, g_index_base: int = 0,
+                          stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`hamming_topk` (neither mask nor planes), `hamming_topk_masked` (mask) or `hamming_topk_weighted` (planes) among ADMITTED rows only:
+    the k smallest by ascending (distance, global index) of the rows that pass the filter, -1 behind them where fewer than k do.
+    Row r of THIS gallery is admitted for query i iff
+      allow is None or allow[r] -- bool [G], or the packed int64 [ceil(G / 64)] of `row_bitmap` (bits past G are ignored) -- and
+      want is None or want[i] < 0 or (grp(r) == want[i]) != exclude, with grp(r) = group[r] (int32 [G], values >= 0) or, without a group
+      plane, g_index_base + r: a row is its own group, so want = the query's own global index and exclude=True drops exactly that row.
+    With every row admitted the result equals the unfiltered entry's bit for bit; lists of gallery shards (each with its own base,
+    bitmap and slice of group) merge with `topk_merge`."""
+    if planes is not None:
+        if mask is not None:
+            raise ValueError("mask with planes: the planes of `weight_planes(codes, bits, mask)` already carry the mask")
+        q, planes, g = _check_weighted(q, planes, g)
+    else:
+        q, g = _check_packed(q, g)
+    filt = _check_filter(allow, group, want, exclude, q.shape[0], g.shape[0], q.device)
+    if planes is not None:
+        return _topk("ch_hamming_topk_weighted_filtered", q, g, k, g_index_base, stream, (_lib.ptr(planes), planes.shape[1]),
+                     workspace="ch_hamming_topk_weighted_filtered_workspace", filt=filt)
+    stride = 0
+    if mask is not None:
+        mask, stride = _check_mask(mask, q.shape[0], q.shape[1], q.device, "queries")
+    return _topk("ch_hamming_topk_filtered", q, g, k, g_index_base, stream, (_lib.ptr(mask), stride),
+                 workspace="ch_hamming_topk_filtered_workspace", filt=filt)
 
 
 def subcode_dist(q: torch.Tensor, g: torch.Tensor, idx: torch.Tensor, nbit: int, nsub: int, g_index_base: int = 0,
@@ -1245,6 +1331,28 @@ def ternary_topk(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, g_index_
     with _dev_guard(q3):
         _lib.check(lib.ch_ternary_topk(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), k, int(g_index_base), _lib.ptr(idx), _lib.ptr(dist),
                                        _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), "ch_ternary_topk")
+    return idx, dist
+
+
+def ternary_topk_filtered(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, allow: Optional[torch.Tensor] = None,
+                          group: Optional[torch.Tensor] = None, want: Optional[torch.Tensor] = None, exclude: bool = False,
+                          g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`ternary_topk` among ADMITTED rows only; allow, group, want and exclude as `hamming_topk_filtered` takes them (a row of the
+    two-plane gallery is one row of the bitmap and of the group plane)."""
+    lib = _lib.load()
+    q3, g3 = _check_ternary(q3, g3, nbit)
+    Qn, _, W = q3.shape
+    G = g3.shape[0]
+    filt = _check_filter(allow, group, want, exclude, Qn, G, q3.device)
+    k = int(k)
+    idx = torch.empty(Qn, k, dtype=torch.int64, device=q3.device)
+    dist = torch.empty(Qn, k, dtype=torch.int32, device=q3.device)
+    wsb = int(lib.ch_ternary_topk_filtered_workspace(Qn, G, W, k))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q3.device)
+    with _dev_guard(q3):
+        _lib.check(lib.ch_ternary_topk_filtered(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), k, int(g_index_base), *_filter_args(filt),
+                                                _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)),
+                   "ch_ternary_topk_filtered")
     return idx, dist
 
 

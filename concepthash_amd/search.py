@@ -41,12 +41,14 @@ class GalleryIndex:
     real codes that were packed, with `margin` the number it was built with -- what rank="ternary" needs; an index
     without it serves every other ranking as before.
     real: None, or the plane [G, nbit] fp32 of the real-valued codes that were packed (after the mean shift, where there is one) -- what
-    rank="cosine" | "euclidean" | "dot" need; optional in the same way."""
+    rank="cosine" | "euclidean" | "dot" need; optional in the same way.
+    groups: None, or the plane [G] int32 (values >= 0, checked here, once) of the group every row belongs to -- its album, video or
+    source -- what `search(query_group=..., group_by="groups")` filters by; optional in the same way."""
 
     def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
                  paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
                  transform: Optional[dict] = None, fingerprint: Optional[dict] = None, mask: Optional[torch.Tensor] = None,
-                 margin: Optional[float] = None, real: Optional[torch.Tensor] = None):
+                 margin: Optional[float] = None, real: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None):
         nbit, ncontext = int(nbit), int(ncontext)
         if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
             raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
@@ -71,7 +73,14 @@ class GalleryIndex:
                 raise ValueError(f"real must be the plane [{G}, {nbit}] of real-valued codes on the codes' device, got {tuple(real.shape)} "
                                  f"on {real.device}")
             real = rt.check_dense_codes(real, "the real plane")
-        self.real = real
+        if groups is not None:
+            if groups.dtype != torch.int32 or tuple(groups.shape) != (G,) or groups.device != codes.device:
+                raise ValueError(f"groups must be the int32 plane [{G}] of the rows' groups on the codes' device, got {groups.dtype} "
+                                 f"{tuple(groups.shape)} on {groups.device}")
+            if G and int(groups.min()) < 0:
+                raise ValueError(f"groups must be >= 0 (a query's -1 means no group filter), got {int(groups.min())}")
+            groups = groups.contiguous()
+        self.real, self.groups = real, groups
         self.codes, self.nbit, self.ncontext = codes.contiguous(), nbit, ncontext
         self.mask, self.margin = (mask.contiguous() if mask is not None else None), margin
         self.labels = labels
@@ -91,7 +100,7 @@ class GalleryIndex:
     def to(self, device) -> "GalleryIndex":
         mv = lambda t: t.to(device) if t is not None else None
         return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
-                            self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real))
+                            self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real), mv(self.groups))
 
     # ---- file --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -106,6 +115,8 @@ class GalleryIndex:
             d.update(mask=cpu(self.mask), margin=self.margin)
         if self.real is not None:
             d.update(real=cpu(self.real))
+        if self.groups is not None:
+            d.update(groups=cpu(self.groups))
         torch.save(d, tmp)
         os.replace(tmp, path)
 
@@ -128,7 +139,7 @@ class GalleryIndex:
         if not isinstance(d, dict) or d.get("format") != FORMAT:
             raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
         index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
-                    d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"))
+                    d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"), d.get("groups"))
         index.check(fingerprint, nbit, source=path)
         return index
 
@@ -147,7 +158,9 @@ class GalleryIndex:
 
     def search(self, query_codes: torch.Tensor, k: int, concepts: Optional[Sequence[int]] = None, margin: float = 0.0,
                rank: str = "hamming", weight_bits: int = 8, radius: Optional[int] = None, mean_shift: bool = True,
-               shortlist: Optional[int] = None) -> dict:
+               shortlist: Optional[int] = None, rows: Optional[torch.Tensor] = None, labels_in: Optional[Sequence[int]] = None,
+               labels_out: Optional[Sequence[int]] = None, query_group: Optional[torch.Tensor] = None, group_mode: str = "only",
+               group_by: str = "groups") -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here;
         mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0).
         Ranks the database by ascending (distance, index) and returns
@@ -178,11 +191,37 @@ class GalleryIndex:
         shortlist = m under a dense rank: the two-stage list (`retrieval.rerank_topk`; DESIGN.md section 2.0, "two-stage") -- the first m
         rows by ascending (Hamming distance, index) of the sign codes, ordered by the dense distance and cut at k.  1 <= k <= m <= 4096,
         so k may exceed 128; `radius` is then allowed and restricts the shortlist to rows within that many bits.  The dict also holds
-        shortlist.  Under any other rank a shortlist is a ValueError."""
+        shortlist.  Under any other rank a shortlist is a ValueError.
+        Filtered search ("filtered search"): which rows may be hits at all, decided inside the scan, so a list
+        is as full as the admitted rows allow (idx = dist = -1 behind them).
+          rows: bool [G], or the packed bitmap of `retrieval.row_bitmap`: the rows that may be hits (e.g. not deleted).
+          labels_in / labels_out: class ids; the row's class is in the set / is not in it (single-label index), the row has any of the
+            classes / none of them (indicator rows).  They need the index's labels and combine with `rows` by AND into ONE bitmap for
+            all queries (torch ops on the index's device).
+          query_group: int64 [Qn], one group per query (-1: no group filter for that query), with group_mode "only" (hits of that group
+            alone) or "exclude" (of every other group) and group_by = where a row's group comes from: "groups" (the index's groups
+            plane), "labels" (the row's class id; single-label indexes) or "row" (the row's own index: query_group = the query's own
+            database row with group_mode="exclude" is "neighbours of a database image without the image itself").
+        They compose with `concepts`, `margin`, `radius` (cut after the filter) and rank "hamming" | "asymmetric" | "ternary" at
+        k <= 128: those lists come from the one top-k scan (`retrieval.hamming_topk_filtered`, `ternary_topk_filtered`).  Lists deeper
+        than 128, the dense ranks and a shortlist do not go through that scan, and a filter under them raises ValueError.
+        Under a filter the dict also holds rows_admitted: the number of rows the shared bitmap admits (G where there is none), so a
+        short list explains itself."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
         if shortlist is not None and rank not in rt.DENSE_METRICS:
             raise ValueError(f"shortlist with rank='{rank}' is not built: a shortlist is reranked by a dense rank, one of {rt.DENSE_METRICS}")
+        filtered = any(v is not None for v in (rows, labels_in, labels_out, query_group))
+        if filtered:
+            names = ", ".join(n for n, v in (("rows", rows), ("labels_in", labels_in), ("labels_out", labels_out), ("query_group", query_group))
+                              if v is not None)
+            why = f"the filter is a predicate of the top-k scan (k <= {TOPK_MAX}, rank 'hamming', 'asymmetric' or 'ternary')"
+            if shortlist is not None:
+                raise ValueError(f"a filter ({names}) with a shortlist is not built: {why}, and a two-stage list does not go through it")
+            if rank in rt.DENSE_METRICS:
+                raise ValueError(f"a filter ({names}) with rank='{rank}' is not built: {why}, and the dense ranks do not go through it")
+            if int(k) > TOPK_MAX:
+                raise ValueError(f"a filter ({names}) with k = {int(k)} > {TOPK_MAX} is not built: {why}, and deeper lists do not go through it")
         if rank in rt.DENSE_METRICS:
             return self._search_dense(query_codes, int(k), concepts, margin, rank, radius, mean_shift, shortlist)
         if rank == "asymmetric" and int(weight_bits) not in rt.WEIGHT_BITS:
@@ -212,6 +251,7 @@ class GalleryIndex:
         if self.mean is not None and mean_shift:
             codes = codes - self.mean[None, :]
         Qn = codes.shape[0]
+        flt = self._filter(Qn, rows, labels_in, labels_out, query_group, group_mode, group_by) if filtered else None
         q = rt.pack_sign(codes)
         keep = torch.ones(self.nbit, dtype=torch.bool, device=dev)
         mask = None
@@ -237,13 +277,14 @@ class GalleryIndex:
         extra = {}
         if rank == "asymmetric":
             planes, wsum = rt.weight_planes(codes, int(weight_bits), mask)
-            idx, dist = rt.hamming_topk_weighted(q, planes, self.codes, k)
+            idx, dist = (rt.hamming_topk_weighted(q, planes, self.codes, k) if flt is None else
+                         rt.hamming_topk_filtered(q, self.codes, k, planes=planes, **flt))
             extra = dict(rank=rank, weight_bits=int(weight_bits), dist_max=wsum)
         elif rank == "ternary":
             g3 = torch.stack([self.codes & self.mask, self.mask], dim=1)
             if nbit_play == 0:
                 raise ValueError("rank='ternary' with an empty set of concepts leaves no bit in play")
-            idx, dist = rt.ternary_topk(q3, g3, nbit_play, k)
+            idx, dist = rt.ternary_topk(q3, g3, nbit_play, k) if flt is None else rt.ternary_topk_filtered(q3, g3, nbit_play, k, **flt)
             if radius is not None:
                 far = dist > 2 * radius
                 idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
@@ -252,16 +293,78 @@ class GalleryIndex:
                          dist_max=(bits_sure + nbit_play).to(torch.int32))
         elif deep:
             idx, dist = rt.hamming_ranked(q, self.codes, k, radius=radius, mask=mask)
+        elif flt is not None:
+            idx, dist = rt.hamming_topk_filtered(q, self.codes, k, mask=mask, **flt)
         elif mask is None:
             idx, dist = rt.hamming_topk(q, self.codes, k)
         else:
             idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
+        if flt is not None:              # an unfiltered search returns the keys it always has
+            extra["rows_admitted"] = len(self) if flt["allow"] is None else rt.bitmap_count(flt["allow"], len(self))
         if radius is not None and not deep and rank != "ternary":
             far = dist > radius
             idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
                    bits=keep.sum(1), labels=None, paths=None, **extra)
         return self._name_hits(out)
+
+    def _label_rows(self, ids, what: str) -> torch.Tensor:
+        """bool [G]: the rows that carry one of the classes `ids` (labels_in / labels_out)"""
+        if self.labels is None:
+            raise ValueError(f"{what} needs the index's labels, which this index was built without")
+        ids = [int(c) for c in ids]
+        if self.labels.dim() == 1:
+            return torch.isin(self.labels, torch.tensor(ids, dtype=self.labels.dtype, device=self.labels.device))
+        C = self.labels.shape[1]
+        if any(c < 0 or c >= C for c in ids):
+            raise ValueError(f"{what} = {ids} outside the index's classes [0, {C})")
+        return (self.labels[:, ids] != 0).any(1)
+
+    def _filter(self, Qn: int, rows, labels_in, labels_out, query_group, group_mode: str, group_by: str) -> dict:
+        """The filter arguments of `retrieval.hamming_topk_filtered` / `ternary_topk_filtered` for one `search`: allow (ONE packed
+        bitmap: rows AND labels_in AND NOT labels_out, None where none of them is given), group, want, exclude.  Every refusal comes
+        before anything is launched."""
+        G, dev = len(self), self.device
+        words = (G + 63) // 64
+        if group_mode not in ("only", "exclude"):
+            raise ValueError(f"group_mode must be 'only' or 'exclude', got {group_mode!r}")
+        if group_by not in ("groups", "labels", "row"):
+            raise ValueError(f"group_by must be 'groups', 'labels' or 'row', got {group_by!r}")
+        packed = None
+        adm = None
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or (rows.dtype, tuple(rows.shape)) not in ((torch.bool, (G,)), (torch.int64, (words,))):
+                raise ValueError(f"rows must be a bool tensor [{G}] or a packed int64 bitmap [{words}] (retrieval.row_bitmap), got "
+                                 f"{getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
+            rows = rows.to(dev)
+            if rows.dtype == torch.bool:
+                adm = rows
+            else:
+                packed = rows
+        if labels_in is not None:
+            hit = self._label_rows(labels_in, "labels_in").to(dev)
+            adm = hit if adm is None else adm & hit
+        if labels_out is not None:
+            hit = ~self._label_rows(labels_out, "labels_out").to(dev)
+            adm = hit if adm is None else adm & hit
+        if adm is not None:
+            packed = rt.row_bitmap(adm) if packed is None else packed & rt.row_bitmap(adm)
+        group = want = None
+        if query_group is not None:
+            if not isinstance(query_group, torch.Tensor) or query_group.dtype != torch.int64 or tuple(query_group.shape) != (Qn,):
+                raise ValueError(f"query_group must be an int64 tensor [{Qn}] (-1 = no group filter for that query), got "
+                                 f"{getattr(query_group, 'dtype', type(query_group))} {tuple(getattr(query_group, 'shape', ()))}")
+            want = query_group.to(dev)
+            if group_by == "groups":
+                if self.groups is None:
+                    raise ValueError("group_by='groups' needs the index's groups plane, which this index was built without")
+                group = self.groups
+            elif group_by == "labels":
+                if self.labels is None or self.labels.dim() != 1:
+                    raise ValueError("group_by='labels' needs single-label class ids; this index holds " +
+                                     ("no labels" if self.labels is None else "indicator rows (filter them with labels_in / labels_out)"))
+                group = self.labels.to(dev, torch.int32)
+        return dict(allow=packed, group=group, want=want, exclude=group_mode == "exclude")
 
     def _search_dense(self, query_codes, k: int, concepts, margin, rank: str, radius, mean_shift: bool, shortlist=None) -> dict:
         """`search` under a dense rank"""

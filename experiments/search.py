@@ -3,6 +3,12 @@
     python main_v2.py --config-name search.yaml logdir=<run> dataset=<name> [query=test] [k=10] [radius=2] [concepts=[0,2]]
         [query_margin=0.0] [rank=hamming|asymmetric|ternary|cosine|euclidean|dot] [shortlist=1000] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
         [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
+        [only_classes=[3,"Painted Bunting"]] [exclude_classes=[...]] [exclude_self=true] [same_class=only|exclude]
+
+Filtered search ("filtered search"; rank hamming, asymmetric or ternary, k <= 128): `only_classes` / `exclude_classes`
+admit only database rows of (not of) these classes -- ids, or names of the dataset's class_names.txt; `exclude_self=true` keeps an image
+query that IS a database image (query=db, or a path the index holds) from returning its own row; `same_class=only|exclude` keeps every
+labelled query to hits of its own class (of every other class).  `results.json` records the filter under "filter".
 
 Text queries ("text query") become codes through the CLIP text tower and the run's own `text_projection`
 (`concepthash_amd.text.TextQueryEncoder`) and go through the same `GalleryIndex.search` call as image codes, never shifted by an index's mean.
@@ -92,6 +98,45 @@ def text_request(config):
     return {"prompts": prompts, "labels": labels, "prefix": prefix, "run_prefix": run_prefix, "text_model": source}
 
 
+def filter_request(config):
+    """The filter of an invocation, from its config alone (no model, no GPU): None without one of the four keys, else a dict with
+    `only_classes` / `exclude_classes` (class ids or None; names are looked up in the dataset's class_names.txt), `exclude_self` (bool)
+    and `same_class` (None, "only" or "exclude").  An error names the key."""
+    only, out = config.get("only_classes"), config.get("exclude_classes")
+    self_, same = bool(config.get("exclude_self")), config.get("same_class")
+    if only is None and out is None and not self_ and same is None:
+        return None
+    if same is not None and str(same) not in ("only", "exclude"):
+        raise ValueError(f"same_class must be only or exclude, got {same!r}")
+    if same is not None and self_:
+        raise ValueError("same_class with exclude_self=true is not built: a query has ONE group per search (its class, or its own row)")
+    names = None
+
+    def ids(key, values):
+        nonlocal names
+        got = []
+        for v in ([values] if isinstance(values, (str, int)) else list(values)):
+            if isinstance(v, int) or str(v).lstrip("-").isdigit():
+                got.append(int(v))
+                continue
+            if names is None:
+                path = class_name_file(config)
+                if not os.path.isfile(path):
+                    raise ValueError(f"{key}: the class name {v!r} is looked up in {path}, which does not exist")
+                with open(path, encoding="utf-8") as f:
+                    names = [line.strip() for line in f]
+            if str(v) not in names:
+                raise ValueError(f"{key}: unknown class name {v!r} (not a line of {class_name_file(config)})")
+            got.append(names.index(str(v)))
+        if any(c < 0 for c in got):
+            raise ValueError(f"{key}: class ids must be >= 0, got {got}")
+        return got
+
+    return {"only_classes": ids("only_classes", only) if only is not None else None,
+            "exclude_classes": ids("exclude_classes", out) if out is not None else None,
+            "exclude_self": self_, "same_class": str(same) if same is not None else None}
+
+
 class SearchExperiment:
     def __init__(self, config: DictConfig):
         import torch.distributed as dist
@@ -102,6 +147,9 @@ class SearchExperiment:
         self.config = config
         self.query = str(config.get("query", "test") or "test")
         self.text = text_request(config)              # None: image queries.  Argument errors surface here, before anything is loaded
+        self.filter = filter_request(config)          # None: every row may be a hit
+        if self.filter is not None and self.filter["exclude_self"] and self.text is not None:
+            raise ValueError("exclude_self=true needs image queries: a text query is no database row")
         engine.seeding(config["seed"])
         self.timing = {}
         logdir = config.logdir
@@ -272,6 +320,35 @@ class SearchExperiment:
             agreement = enc.center_agreement(names, self.text["run_prefix"]) if os.path.isfile(names) else None
         return codes, agreement
 
+    def _filter_arguments(self, index: GalleryIndex, names, labelled: bool, q_labels: torch.Tensor) -> dict:
+        """what `GalleryIndex.search` takes for this invocation's filter (`filter_request`)"""
+        f = self.filter
+        args = {}
+        if f["only_classes"] is not None:
+            args["labels_in"] = f["only_classes"]
+        if f["exclude_classes"] is not None:
+            args["labels_out"] = f["exclude_classes"]
+        if f["exclude_self"]:
+            n = q_labels.shape[0] if names is None else len(names)
+            if self.query == "db":                       # query i is database row i
+                rows = list(range(n))
+            elif names is None or index.paths is None:
+                rows = [-1] * n                          # nothing to compare: no query is a known database row
+            else:
+                at = {}
+                for r, p in enumerate(index.paths):
+                    at.setdefault(p, r)
+                    at.setdefault(os.path.abspath(index.resolve(p)), r)
+                rows = [at.get(p, at.get(os.path.abspath(index.resolve(p)), -1)) for p in names]
+            args.update(query_group=torch.tensor(rows, dtype=torch.int64), group_mode="exclude", group_by="row")
+        if f["same_class"] is not None:
+            ids = _label_ids(q_labels.cpu()) if labelled else None
+            if ids is None or ids.dim() != 1 or ids.shape[0] == 0:
+                raise ValueError(f"same_class={f['same_class']} needs labelled queries with one class each; these queries carry " +
+                                 ("no labels" if ids is None or ids.shape[0] == 0 else "indicator rows"))
+            args.update(query_group=ids.to(torch.int64), group_mode=f["same_class"], group_by="labels")
+        return args
+
     # ---- main --------------------------------------------------------------------------------------------------------------------
     def main(self):
         cfg = self.config
@@ -297,7 +374,7 @@ class SearchExperiment:
             loader, names, labelled = self._query_loader()
             q_codes, q_labels, attn = self._phase("encode_query", self._encode_queries, loader, bool(cfg.get("save_attention")))
         res = self._phase("search", index.search, q_codes, k, concepts, margin, rank, weight_bits, radius, mean_shift=self.text is None,
-                          shortlist=shortlist)
+                          shortlist=shortlist, **(self._filter_arguments(index, names, labelled, q_labels) if self.filter is not None else {}))
         t0 = time.perf_counter()
         q_ids = _label_ids(q_labels.cpu()) if labelled else None
         idx, dist, cdist = res["idx"].tolist(), res["dist"].tolist(), res["concept_dist"].tolist()
@@ -332,6 +409,7 @@ class SearchExperiment:
                "checkpoint": self.fingerprint, "query_kind": "image" if self.text is None else "text",
                "query": self.query if self.text is None else list(self.text["prompts"]),
                "prefix": None if self.text is None else self.text["prefix"], "text_model": None if self.text is None else self.text["text_model"],
+               "filter": None if self.filter is None else dict(self.filter, rows_admitted=int(res["rows_admitted"])),
                "center_agreement": agreement, "mean_shift": self.text is None and index.mean is not None, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
         with open(os.path.join(self.search_logdir, "results.json"), "w") as f:

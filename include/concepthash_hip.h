@@ -414,6 +414,35 @@ int ch_hamming_topk_weighted(const uint64_t *q, const uint64_t *planes, int32_t 
                              int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* Filtered search: the top-k among ADMITTED rows only.  Row r in [0, G) of THIS call's gallery is admitted for query i iff
+ *     allow == NULL, or bit r & 63 of allow[r >> 6] is set: allow is uint64 [ceil(G / 64)], one bitmap for all queries, indexed by the
+ *         row's position in this call's gallery (not by g_index_base + r); bits past G in its last word are ignored; and
+ *     want == NULL, or want[i] < 0, or (grp(r) == want[i]) != exclude: want is int64 [Qn], grp(r) = group[r] where a plane group (int32
+ *         [G], values >= 0) is given and g_index_base + r where group == NULL (a row is its own group: "not the query's own row"
+ *         without storing anything); exclude is one flag per call, 0 = only that group, 1 = every group but it -- any other value is
+ *         status 2.
+ * The result is the unfiltered entry's restricted to admitted rows: the k smallest by ascending (distance, global index) with the
+ * sibling's own distances, idx = dist = -1 behind them where fewer than k rows are admitted; with every row admitted it equals the
+ * sibling's bit for bit, and lists of gallery shards (each with its own g_index_base, bitmap and slice of group) merge with
+ * ch_topk_merge.  The filter is a predicate inside the scan: rows that are not admitted cost no list slot, nothing of size Qn x G is
+ * written.  The filtered kernels hold a few more registers than their siblings and their segments follow their own figures, so each
+ * entry has its own workspace function.
+ * ch_hamming_topk_filtered adds the filter to ch_hamming_topk (q_mask == NULL; mask_stride is then ignored) and to
+ * ch_hamming_topk_masked (q_mask and mask_stride as there). */
+size_t ch_hamming_topk_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
+int ch_hamming_topk_filtered(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g, int64_t G,
+                             int32_t W, int32_t k, int64_t g_index_base, const uint64_t *allow, const int32_t *group,
+                             const int64_t *want, int32_t exclude, int64_t *out_idx, int32_t *out_dist, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+/* ch_hamming_topk_weighted among admitted rows only: its arguments and distance D, plus the filter as described above.  The workspace
+ * covers both P. */
+size_t ch_hamming_topk_weighted_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
+int ch_hamming_topk_weighted_filtered(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
+                                      int32_t W, int32_t k, int64_t g_index_base, const uint64_t *allow, const int32_t *group,
+                                      const int64_t *want, int32_t exclude, int64_t *out_idx, int32_t *out_dist, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+
 /* Per-sub-code distances of retrieved hits: idx [Qn,k] int64 as written by ch_hamming_topk(_masked) / ch_topk_merge (global index =
  * gallery row + g_index_base, -1 = absent).  The code's first nbit bits are nsub equal sub-codes of nbit / nsub bits (sub-code c =
  * bits [c nbit/nsub, (c+1) nbit/nsub); it may straddle a 64-bit word); out [Qn,k,nsub] int32 = popcount of q xor g inside each, -1 in
@@ -550,6 +579,13 @@ int ch_ternary_dist(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G,
 size_t ch_ternary_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
 int ch_ternary_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t k,
                     int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ch_ternary_topk among admitted rows only: its arguments and distance K, plus the filter (allow, group, want, exclude) as described
+ * at ch_hamming_topk_filtered; a row of the two-plane gallery is one row of the bitmap and of group. */
+size_t ch_ternary_topk_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k);
+int ch_ternary_topk_filtered(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t k,
+                             int64_t g_index_base, const uint64_t *allow, const int32_t *group, const int64_t *want, int32_t exclude,
+                             int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Evaluation under K by rank counting: ch_hamming_rank_collect and ch_hamming_rank_count with key(g) = K(q, g) << 32 | global index
  * of g over two-plane codes -- the same CSR buffers (offsets, count, keys, bins), the same offsets == NULL counting call, the same

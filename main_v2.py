@@ -36,7 +36,7 @@ LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "tie_expected", "c
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
                "query_margin", "index", "rebuild_index", "save_attention", "rank", "index_margin", "weight_bits", "radius", "query_text", "query_text_file",
-               "prompt_prefix", "text_model", "shortlist")
+               "prompt_prefix", "text_model", "shortlist", "only_classes", "exclude_classes", "exclude_self", "same_class")
 
 
 def _run_config(config, exp, keys):
