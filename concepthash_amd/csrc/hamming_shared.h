@@ -2,8 +2,8 @@
 // rank-counting evaluations (hamming_rankcount.hip: weighted; hamming_ternary.hip: ternary) share: the chained popcount, the query load
 // and the plain Hamming distance built on them; for the mAP and rank passes, which keep a tile's per-distance counters in LDS, the
 // shape of a workgroup and the W -> instance dispatch; the Horner chain of the weighted distance; the fixed-point quotient and the
-// rank limits of an AP pass; the top-k scan, its merge and its launch path, and the collect and count passes of rank counting, each
-// with the distance as a template argument.  Everything here has internal linkage.
+// rank limits of an AP pass; the top-k scan with the distance and the filter as template arguments, the merge of its segment
+// lists, the list-length table, the residency rule, the workspace formula and the launch path, and the collect and count passes of rank counting, each with the distance as a template argument.  Everything here has internal linkage.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -148,8 +148,9 @@ __device__ __forceinline__ uint32_t make_key(uint32_t d, uint32_t row_uniform) {
 //     want == NULL or want[i] < 0 or (grp(r) == want[i]) != exclude                     (per query),
 // grp(r) = group[r] (int32 >= 0) or, where group == NULL, base + r: a row is its own group.  A row that is not admitted for a lane gets
 // the empty-slot key 0xFFFFFFFF, which is above every real key of every scan (asserted beside KEY_SHIFT / WKEY_SHIFT in hamming_topk.hip
-// and beside TKEY_SHIFT in hamming_ternary.hip), so the insertion network and the merge see nothing new.  The unfiltered scans carry
-// TopkNoFilter, an empty argument, and none of the filter's code.
+// and beside TKEY_SHIFT in hamming_ternary.hip), so the insertion network and the merge see nothing new.  The filter is a template
+// argument from the entry to the kernel (topk_run, topk_launch, a scan's launch, the one __global__ template of each distance, which
+// takes it by value): the unfiltered scans carry TopkNoFilter, an empty argument as TopkMask<false> is, and none of the filter's code.
 struct TopkNoFilter {
     static constexpr bool ON = false;
 };
@@ -395,12 +396,36 @@ int topk_seg_rows_for(int64_t Qn, int64_t G, int per_cu, int64_t max_rows) {
     return (int)rows;
 }
 
-// Workgroups of four waves that a CU keeps of a scan kernel with `vgprs` registers (the scans have no LDS): min(8, 512 / VGPRs rounded
-// up to the allocation unit of 8) -- the table form of the segment rules.
+// THE residency rule: workgroups of four waves that a CU keeps of a scan kernel with `vgprs` registers (the scans have no LDS):
+// min(8, 512 / VGPRs rounded up to the allocation unit of 8).
 int topk_per_cu(int vgprs) { return std::max(1, std::min(8, 512 / std::max(8, (vgprs + 7) / 8 * 8))); }
 
+// ... and the table form of a segment rule: the segments of a kernel from its VGPR count in the family's table of code-object metadata
+int topk_seg_rows_table(int64_t Qn, int64_t G, int vgprs, int64_t max_rows) {
+    return topk_seg_rows_for(Qn, G, topk_per_cu(vgprs), max_rows);
+}
+
+// The list lengths: a scan keeps KREG = 10 / 16 / 32 / 64 / 128 keys per lane, the shortest list that holds k.  k <= 10
+// (PRs = [1, 5, 10]): exactly k entries, so the insertion threshold is the k-th key.  topk_list_index: the position of k's list, which
+// is also the last index of every VGPR table.
+constexpr int TOPK_KREG[5] = {10, 16, 32, 64, 128};
+int topk_list_index(int k) {
+    int i = 0;
+    while (i < 4 && k > TOPK_KREG[i]) ++i;
+    return i;
+}
+
+// The workspace of a call: one list of k keys per (segment, query), and 16 bytes where the sizes have no segmentation.  rows: () -> the
+// rows of a segment, asked for sizes that have one only.
+template <class Rows>
+size_t topk_workspace_bytes(int64_t Qn, int64_t G, int k, const Rows &rows) {
+    if (Qn <= 0 || G <= 0 || k <= 0) return 16;
+    return (size_t)(ceil_div64(G, rows()) * Qn * k) * sizeof(uint32_t) + 16;
+}
+
 // host: one launch path.  A "scan" names one kernel family, holds its extra arguments and knows its key split, its segmentation, its
-// workspace and the wording of its own refusals; topk_run is the body of every top-k entry point.
+// workspace and the wording of its own refusals; topk_run is the body of every top-k entry point.  The filter (TopkNoFilter or
+// TopkFilter) is a typed argument from the entry to the kernel: seg_rows() and workspace() take Filter::ON, launch() the filter.
 struct TopkCall {   // what every partial launch takes
     const uint64_t *q;
     int64_t Qn;
@@ -410,43 +435,42 @@ struct TopkCall {   // what every partial launch takes
     uint32_t *part;
     dim3 grid;
     hipStream_t s;
-    const TopkFilter *flt;   // NULL: the unfiltered kernel; otherwise the filtered one with *flt
 };
 
-// lists of KREG = 10 / 16 / 32 / 64 / 128 keys.  k <= 10 (PRs = [1, 5, 10]): exactly k entries, so the insertion threshold is the
-// k-th key
-template <int W, class Scan>
-void topk_launch_k(const Scan &scan, const TopkCall &c) {
-    if (c.k <= 10) return scan.template launch<W, 10>(c);
-    if (c.k <= 16) return scan.template launch<W, 16>(c);
-    if (c.k <= 32) return scan.template launch<W, 32>(c);
-    if (c.k <= 64) return scan.template launch<W, 64>(c);
-    return scan.template launch<W, 128>(c);
+template <int W, class Scan, class Filter>
+void topk_launch_k(const Scan &scan, const TopkCall &c, const Filter &flt) {
+    switch (topk_list_index(c.k)) {
+        case 0: return scan.template launch<W, TOPK_KREG[0]>(c, flt);
+        case 1: return scan.template launch<W, TOPK_KREG[1]>(c, flt);
+        case 2: return scan.template launch<W, TOPK_KREG[2]>(c, flt);
+        case 3: return scan.template launch<W, TOPK_KREG[3]>(c, flt);
+        default: return scan.template launch<W, TOPK_KREG[4]>(c, flt);
+    }
 }
 
-template <class Scan>
-void topk_launch(const Scan &scan, int W, const TopkCall &c) {
+template <class Scan, class Filter>
+void topk_launch(const Scan &scan, int W, const TopkCall &c, const Filter &flt) {
     switch (W) {
-        case 1: return topk_launch_k<1>(scan, c);
-        case 2: return topk_launch_k<2>(scan, c);
-        case 3: return topk_launch_k<3>(scan, c);
-        default: return topk_launch_k<4>(scan, c);
+        case 1: return topk_launch_k<1>(scan, c, flt);
+        case 2: return topk_launch_k<2>(scan, c, flt);
+        case 3: return topk_launch_k<3>(scan, c, flt);
+        default: return topk_launch_k<4>(scan, c, flt);
     }
 }
 
 // The body of ch_hamming_topk / _masked / _weighted and ch_ternary_topk and of their _filtered forms: the checks in the order the
 // entries have always made them (`name` opens the messages), partial lists, merge.  A segment's rows must fit under the key's distance:
-// the scan's seg_rows() answers at most 2^SHIFT, checked here in front of the launch.  flt: NULL, or the filter of a _filtered entry
-// (its base is the call's g_index_base); the scan's seg_rows() and workspace() know on their own whether they answer for the filtered kernels.
-template <class Scan>
+// the scan's seg_rows() answers at most 2^SHIFT, checked here in front of the launch.  flt: TopkNoFilter{}, or the TopkFilter of a
+// _filtered entry (its base is the call's g_index_base).
+template <class Scan, class Filter>
 int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int W,
              int k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, hipStream_t s,
-             const TopkFilter *flt = nullptr) {
+             const Filter &flt) {
     const std::string at = std::string(name) + ": ";
     CH_REQUIRE(W >= 1 && W <= 4, at + "1 <= W <= 4 (nbit <= 256)");
     CH_REQUIRE(k >= 1 && k <= 128, at + "1 <= k <= 128");
     CH_REQUIRE(Qn >= 0 && G >= 0, at + "negative sizes");
-    CH_REQUIRE(flt == nullptr || flt->exclude == 0 || flt->exclude == 1, at + "exclude must be 0 or 1");
+    if constexpr (Filter::ON) CH_REQUIRE(flt.exclude == 0 || flt.exclude == 1, at + "exclude must be 0 or 1");
     if (int e = scan.check(W)) return e;
     if (Qn == 0) return 0;
     CH_REQUIRE(q && scan.operands() && out_idx && out_dist, at + "null pointer");
@@ -456,13 +480,13 @@ int topk_run(const char *name, const Scan &scan, const uint64_t *q, int64_t Qn, 
         return 0;
     }
     CH_REQUIRE(g != nullptr, at + "null gallery");
-    const int seg_rows = scan.seg_rows(Qn, G, W, k);
+    const int seg_rows = scan.seg_rows(Qn, G, W, k, Filter::ON);
     CH_REQUIRE(seg_rows >= 1 && (int64_t)seg_rows <= ((int64_t)1 << Scan::SHIFT), at + "segment longer than the key's row field");
     const int64_t nseg = ceil_div64(G, seg_rows);
     CH_REQUIRE(nseg <= 65535, Scan::too_many_segments);
-    CH_REQUIRE(workspace && workspace_bytes >= scan.workspace(Qn, G, W, k), at + "workspace too small");
+    CH_REQUIRE(workspace && workspace_bytes >= scan.workspace(Qn, G, W, k, Filter::ON), at + "workspace too small");
     uint32_t *part = (uint32_t *)workspace;
-    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s, flt});
+    topk_launch(scan, W, TopkCall{q, Qn, g, G, seg_rows, k, part, dim3((unsigned)ceil_div64(Qn, 256), (unsigned)nseg), s}, flt);
     CH_LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_merge_keys_kernel<Scan::SHIFT>, dim3((unsigned)ceil_div64(Qn, 4)), dim3(256), 0, s, part, (int)nseg, Qn, k,
                        seg_rows, g_index_base, out_idx, out_dist);

@@ -10,8 +10,8 @@
 // Top-k (ch_ternary_topk) is topk_scan of hamming_shared.h with this distance: one lane per query, its two planes in 4 W VGPRs, the
 // gallery row's 2 W words wave-uniform through the scalar load path.  key = K << 22 | row in segment: K <= 512 takes 10 bits (the
 // plain scan's shift of 23 leaves 9), so a segment holds at most 2^22 = 4,194,304 rows (checked on the host in topk_run) and the
-// largest key, 512 << 22 | 2^22 - 1, stays below the empty slot 0xFFFFFFFF.  ch_ternary_topk_filtered is the same scan under the
-// TopkFilter of hamming_shared.h (allow-list bitmap, per-query group test): one more instance per (W, KREG).
+// largest key, 512 << 22 | 2^22 - 1, stays below the empty slot 0xFFFFFFFF.  ch_ternary_topk_filtered is the same kernel template with
+// the TopkFilter of hamming_shared.h (allow-list bitmap, per-query group test) as its Filter argument: one more instance per (W, KREG).
 // What the compiler emits per 32-bit word of the top-k distance (disassembly of topk_ternary_partial_kernel, every W and KREG):
 //     v_and_b32       t, s[mg], v[mq]            mq & mg
 //     v_bcnt_u32_b32  A, t, A                    chained
@@ -170,9 +170,12 @@ __global__ __launch_bounds__(256) void ternary_dist_kernel(const uint64_t *__res
 // rows of one block of scalar loads: a row is 2 W words = 4 W SGPRs, and two buffers of blocks are in flight
 constexpr int ternary_ub(int W) { return W <= 2 ? 4 : 2; }
 
+// Filter: TopkNoFilter (ch_ternary_topk) or TopkFilter (ch_ternary_topk_filtered), hamming_shared.h: one more instance per (W, KREG).
+// The key of a row that is not admitted is the empty slot, which the static_assert beside TKEY_SHIFT keeps above every real key.
 template <int W, int KREG, class Filter>
-__device__ __forceinline__ void topk_ternary_partial(const uint64_t *__restrict__ q, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
-                                                     uint32_t nbit, int seg_rows, int k, uint32_t *__restrict__ part, const Filter &flt) {
+__global__ __launch_bounds__(256) void topk_ternary_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
+                                                                   const uint64_t *__restrict__ g, int64_t G, uint32_t nbit, int seg_rows,
+                                                                   int k, uint32_t *__restrict__ part, Filter flt) {
     const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t sq[2 * W], mq[2 * W];   // a lane past Qn holds zero planes: K = nbit for every row, and nothing of it is stored
 #pragma unroll
@@ -187,67 +190,45 @@ __device__ __forceinline__ void topk_ternary_partial(const uint64_t *__restrict_
                                                       G, seg_rows, k, part, flt);
 }
 
-template <int W, int KREG>
-__global__ __launch_bounds__(256) void topk_ternary_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                                   const uint64_t *__restrict__ g, int64_t G, uint32_t nbit, int seg_rows,
-                                                                   int k, uint32_t *__restrict__ part) {
-    topk_ternary_partial<W, KREG>(q, Qn, g, G, nbit, seg_rows, k, part, TopkNoFilter{});
-}
-
-// ch_ternary_topk_filtered: one instance per instance above (TopkFilter: hamming_shared.h).  The key of a row that is not admitted is
-// the empty slot, which the static_assert beside TKEY_SHIFT keeps above every real key.
-template <int W, int KREG>
-__global__ __launch_bounds__(256) void topk_ternary_partial_filtered_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                                            const uint64_t *__restrict__ g, int64_t G, uint32_t nbit,
-                                                                            int seg_rows, int k, uint32_t *__restrict__ part,
-                                                                            TopkFilter flt) {
-    topk_ternary_partial<W, KREG>(q, Qn, g, G, nbit, seg_rows, k, part, flt);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
-// VGPRs of topk_ternary_partial_kernel<W, KREG> from the code-object metadata of this build (no instance uses scratch): a CU holds
-// min(8, 512 / VGPRs rounded up to the allocation unit of 8) workgroups of four waves.
+// VGPRs of topk_ternary_partial_kernel<W, KREG, TopkNoFilter> from the code-object metadata of this build (no instance uses scratch);
+// topk_seg_rows_table (hamming_shared.h) turns them into segments
 constexpr int TTOPK_VGPRS[4][5] = {
     // KREG 10, 16, 32, 64, 128
     {26, 38, 70, 134, 258}, {30, 42, 74, 138, 258}, {34, 46, 78, 142, 258}, {38, 50, 82, 146, 258},   // W = 1..4
 };
 
-// ... and of topk_ternary_partial_filtered_kernel<W, KREG> (profiles/search_filtered_topk.txt): its segments follow its own figures
+// ... and of topk_ternary_partial_kernel<W, KREG, TopkFilter> (profiles/search_filtered_topk.txt): its segments follow its own figures
 constexpr int FTTOPK_VGPRS[4][5] = {
     {30, 41, 73, 136, 259}, {35, 47, 79, 141, 259}, {41, 53, 85, 147, 260}, {45, 57, 89, 151, 260},   // W = 1..4
 };
 
-int ttopk_seg_rows(int64_t Qn, int64_t G, int W, int k, bool filtered = false) {
-    const int ki = k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4;
-    const int vgprs = ((filtered ? FTTOPK_VGPRS : TTOPK_VGPRS)[W - 1][ki] + 7) / 8 * 8;
-    const int per_cu = std::max(1, std::min(8, 512 / std::max(8, vgprs)));
-    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)1 << TKEY_SHIFT);
+int ttopk_seg_rows(int64_t Qn, int64_t G, int W, int k, bool filtered) {
+    return topk_seg_rows_table(Qn, G, (filtered ? FTTOPK_VGPRS : TTOPK_VGPRS)[W - 1][topk_list_index(k)], (int64_t)1 << TKEY_SHIFT);
+}
+
+size_t ttopk_workspace(int64_t Qn, int64_t G, int W, int k, bool filtered) {
+    if (W < 1 || W > 4) return 16;
+    return topk_workspace_bytes(Qn, G, k, [&] { return ttopk_seg_rows(Qn, G, W, k, filtered); });
 }
 
 struct TernaryScan {
     static constexpr int SHIFT = TKEY_SHIFT;
     static constexpr const char *too_many_segments = "ternary_topk: gallery too large for one call: more than 65,535 segments (shard it)";
     int nbit;
-    bool filtered = false;   // ch_ternary_topk_filtered: the segments and the workspace of the filtered kernels
     int check(int W) const {
         CH_REQUIRE(nbit >= 1 && nbit <= 64 * W, "ternary_topk: nbit must be in [1, 64 W]");
         return 0;
     }
     bool operands() const { return true; }
-    int seg_rows(int64_t Qn, int64_t G, int W, int k) const { return ttopk_seg_rows(Qn, G, W, k, filtered); }
-    size_t workspace(int64_t Qn, int64_t G, int W, int k) const {
-        return filtered ? ch_ternary_topk_filtered_workspace(Qn, G, W, k) : ch_ternary_topk_workspace(Qn, G, W, k);
-    }
-    template <int W, int KREG>
-    void launch(const TopkCall &c) const {
-        if (c.flt != nullptr)
-            hipLaunchKernelGGL((topk_ternary_partial_filtered_kernel<W, KREG>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G,
-                               (uint32_t)nbit, c.seg_rows, c.k, c.part, *c.flt);
-        else
-            hipLaunchKernelGGL((topk_ternary_partial_kernel<W, KREG>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, (uint32_t)nbit,
-                               c.seg_rows, c.k, c.part);
+    int seg_rows(int64_t Qn, int64_t G, int W, int k, bool filtered) const { return ttopk_seg_rows(Qn, G, W, k, filtered); }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k, bool filtered) const { return ttopk_workspace(Qn, G, W, k, filtered); }
+    template <int W, int KREG, class Filter>
+    void launch(const TopkCall &c, const Filter &flt) const {
+        hipLaunchKernelGGL((topk_ternary_partial_kernel<W, KREG, Filter>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, (uint32_t)nbit,
+                           c.seg_rows, c.k, c.part, flt);
     }
 };
 
@@ -298,29 +279,26 @@ extern "C" int ch_ternary_dist(const uint64_t *q, int64_t Qn, const uint64_t *g,
 }
 
 extern "C" size_t ch_ternary_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
-    return (size_t)(ceil_div64(G, ttopk_seg_rows(Qn, G, W, k)) * Qn * k) * sizeof(uint32_t) + 16;
+    return ttopk_workspace(Qn, G, W, k, false);
 }
 
 extern "C" int ch_ternary_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t k,
                                int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes,
                                void *stream) {
     return topk_run("ternary_topk", TernaryScan{(int)nbit}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, workspace_bytes,
-                    (hipStream_t)stream);
+                    (hipStream_t)stream, TopkNoFilter{});
 }
 
 extern "C" size_t ch_ternary_topk_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
-    return (size_t)(ceil_div64(G, ttopk_seg_rows(Qn, G, W, k, true)) * Qn * k) * sizeof(uint32_t) + 16;
+    return ttopk_workspace(Qn, G, W, k, true);
 }
 
 extern "C" int ch_ternary_topk_filtered(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit, int32_t k,
                                         int64_t g_index_base, const uint64_t *allow, const int32_t *group, const int64_t *want,
                                         int32_t exclude, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes,
                                         void *stream) {
-    const TopkFilter flt{allow, group, want, g_index_base, (int)exclude};
-    return topk_run("ternary_topk_filtered", TernaryScan{(int)nbit, true}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist,
-                    workspace, workspace_bytes, (hipStream_t)stream, &flt);
+    return topk_run("ternary_topk_filtered", TernaryScan{(int)nbit}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
+                    workspace_bytes, (hipStream_t)stream, TopkFilter{allow, group, want, g_index_base, (int)exclude});
 }
 
 extern "C" int ch_ternary_rank_collect(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t nbit,

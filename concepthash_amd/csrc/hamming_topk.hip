@@ -15,8 +15,10 @@
 //     SHIFT = 23 (plain, masked): dist <= 256, segments of < 2^23 rows.
 //     SHIFT = 16 (weighted): D <= 255 * 256 = 65,280 < 2^16 - 1, so 0xFFFFFFFF stays the empty slot; segments hold <= 65,536 rows.
 // Filtered search (ch_hamming_topk_filtered, ch_hamming_topk_weighted_filtered): the same scans with the TopkFilter of hamming_shared.h --
-// an allow-list bitmap on the scalar path and a per-query group test -- as one more instance per (W, KREG, MASKED) and (W, KREG, P);
-// a row that is not admitted gets the empty-slot key 0xFFFFFFFF, which the static_asserts below keep above every real key.
+// an allow-list bitmap on the scalar path and a per-query group test -- as the Filter argument of the one kernel template per distance,
+// topk_partial_kernel<W, KREG, MASKED, Filter> and topk_weighted_partial_kernel<W, KREG, P, Filter>: one more instance per
+// (W, KREG, MASKED) and (W, KREG, P), and TopkNoFilter, an empty argument, for the unfiltered ones.  A row that is not admitted gets
+// the empty-slot key 0xFFFFFFFF, which the static_asserts below keep above every real key.
 // topk_merge_keys_kernel<SHIFT> merges the per-segment lists of a call, topk_merge_lists_kernel the final lists of several shards;
 // subcode_dist_kernel breaks the distance of retrieved hits down by concept.
 #include <algorithm>
@@ -86,11 +88,12 @@ struct TopkMask<true> {
     int stride;
 };
 
-// the body of topk_partial_kernel and of its filtered form (Filter: TopkNoFilter or TopkFilter, hamming_shared.h)
+// Filter: TopkNoFilter (ch_hamming_topk, ch_hamming_topk_masked) or TopkFilter (ch_hamming_topk_filtered), hamming_shared.h: one more
+// instance per (W, KREG, MASKED), every part of the filter a run-time condition of it
 template <int W, int KREG, bool MASKED, class Filter>
-__device__ __forceinline__ void topk_partial(const uint64_t *__restrict__ q, int64_t Qn, const uint64_t *__restrict__ g, int64_t G,
-                                             int seg_rows, int k, uint32_t *__restrict__ part, const TopkMask<MASKED> &qm,
-                                             const Filter &flt) {
+__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
+                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm, Filter flt) {
     const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t qw[2 * W];
     load_query<W>(qw, q, qi, Qn);
@@ -110,25 +113,12 @@ __device__ __forceinline__ void topk_partial(const uint64_t *__restrict__ q, int
     }
 }
 
-template <int W, int KREG, bool MASKED>
-__global__ __launch_bounds__(256) void topk_partial_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                           const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                           uint32_t *__restrict__ part, TopkMask<MASKED> qm) {
-    topk_partial<W, KREG, MASKED>(q, Qn, g, G, seg_rows, k, part, qm, TopkNoFilter{});
-}
-
-// ch_hamming_topk_filtered: one instance per instance above, every part of the filter a run-time condition of it
-template <int W, int KREG, bool MASKED>
-__global__ __launch_bounds__(256) void topk_partial_filtered_kernel(const uint64_t *__restrict__ q, int64_t Qn,
-                                                                    const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                                    uint32_t *__restrict__ part, TopkMask<MASKED> qm, TopkFilter flt) {
-    topk_partial<W, KREG, MASKED>(q, Qn, g, G, seg_rows, k, part, qm, flt);
-}
-
+// Filter: TopkNoFilter (ch_hamming_topk_weighted) or TopkFilter (ch_hamming_topk_weighted_filtered)
 template <int W, int KREG, int P, class Filter>
-__device__ __forceinline__ void topk_weighted_partial(const uint64_t *__restrict__ q, const uint64_t *__restrict__ planes, int64_t Qn,
-                                                      const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                      uint32_t *__restrict__ part, const Filter &flt) {
+__global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64_t *__restrict__ q,
+                                                                    const uint64_t *__restrict__ planes, int64_t Qn,
+                                                                    const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
+                                                                    uint32_t *__restrict__ part, Filter flt) {
     const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t qw[2 * W];
     load_query<W>(qw, q, qi, Qn);
@@ -144,23 +134,6 @@ __device__ __forceinline__ void topk_weighted_partial(const uint64_t *__restrict
     }
     topk_scan<W, KREG, WKEY_SHIFT>([&](const uint64_t *gw) { return weighted_dist<W, P>(qw, pl, gw); }, qi, Qn, g, G, seg_rows, k, part,
                                    flt);
-}
-
-template <int W, int KREG, int P>
-__global__ __launch_bounds__(256) void topk_weighted_partial_kernel(const uint64_t *__restrict__ q,
-                                                                    const uint64_t *__restrict__ planes, int64_t Qn,
-                                                                    const uint64_t *__restrict__ g, int64_t G, int seg_rows, int k,
-                                                                    uint32_t *__restrict__ part) {
-    topk_weighted_partial<W, KREG, P>(q, planes, Qn, g, G, seg_rows, k, part, TopkNoFilter{});
-}
-
-// ch_hamming_topk_weighted_filtered
-template <int W, int KREG, int P>
-__global__ __launch_bounds__(256) void topk_weighted_partial_filtered_kernel(const uint64_t *__restrict__ q,
-                                                                             const uint64_t *__restrict__ planes, int64_t Qn,
-                                                                             const uint64_t *__restrict__ g, int64_t G, int seg_rows,
-                                                                             int k, uint32_t *__restrict__ part, TopkFilter flt) {
-    topk_weighted_partial<W, KREG, P>(q, planes, Qn, g, G, seg_rows, k, part, flt);
 }
 
 // merge already-final lists (idx,dist) from several shards: same extraction on composite (dist, idx)
@@ -272,51 +245,53 @@ __global__ __launch_bounds__(256) void weight_planes_kernel(const float *__restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host: segment sizing (topk_seg_rows_for: hamming_shared.h)
+// host: segment sizing (topk_seg_rows_for, topk_seg_rows_table, topk_list_index: hamming_shared.h)
 // ---------------------------------------------------------------------------------------------------------------
-// The scan kernels have no LDS, so residency is set by their registers.  The two rules below are the ones each distance was tuned
-// and measured with; they are NOT the same function of the register count (the table form gives 6, not 7, workgroups for the plain
-// lists of 32 keys), so they stay apart.
+// The scan kernels have no LDS, so residency is set by their registers.  The rule below is the one the plain and masked unfiltered
+// scans were tuned and measured with; it is NOT the table form (which gives 6, not 7, workgroups for the plain lists of 32 keys), so
+// it stays apart.
+// 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four waves per CU), 68-74 for 32 (7), ~136 for 64 (3), the whole file for 128 (1)
+constexpr int TOPK_PER_CU[5] = {8, 8, 7, 3, 1};   // by list length (topk_list_index)
 int topk_seg_rows(int64_t Qn, int64_t G, int k) {
-    // 24-42 VGPRs for lists of <= 16 keys (8 workgroups of four waves per CU), 68-74 for 32 (7), ~136 for 64 (3), the whole file for 128 (1)
-    const int per_cu = k <= 16 ? 8 : k <= 32 ? 7 : k <= 64 ? 3 : 1;
-    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)(1 << KEY_SHIFT) - 1);
+    return topk_seg_rows_for(Qn, G, TOPK_PER_CU[topk_list_index(k)], (int64_t)(1 << KEY_SHIFT) - 1);
 }
 
 // The filtered scans follow their OWN registers (profiles/search_filtered_topk.txt: 1 to 7 VGPRs above their siblings, no scratch),
 // in the table form.  It differs from the rule above at lists of 32 keys only (7, 6 or 5 workgroups per CU, not 7 throughout).
-// VGPRs of topk_partial_filtered_kernel<W, KREG, MASKED> from the code-object metadata of this build:
+// VGPRs of topk_partial_kernel<W, KREG, MASKED, TopkFilter> from the code-object metadata of this build:
 constexpr int FTOPK_VGPRS[2][4][5] = {
     // KREG 10, 16, 32, 64, 128
     {{28, 40, 72, 134, 259}, {30, 41, 73, 136, 259}, {33, 45, 77, 139, 259}, {35, 47, 79, 141, 259}},   // plain, W = 1..4
     {{30, 42, 74, 136, 259}, {34, 46, 78, 140, 259}, {39, 51, 83, 145, 259}, {43, 55, 87, 149, 259}},   // masked, W = 1..4
 };
 
-int topk_list_index(int k) { return k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4; }
-
 int ftopk_seg_rows(int64_t Qn, int64_t G, int W, int k, bool masked) {
-    return topk_seg_rows_for(Qn, G, topk_per_cu(FTOPK_VGPRS[masked][W - 1][topk_list_index(k)]), (int64_t)(1 << KEY_SHIFT) - 1);
+    return topk_seg_rows_table(Qn, G, FTOPK_VGPRS[masked][W - 1][topk_list_index(k)], (int64_t)(1 << KEY_SHIFT) - 1);
 }
 
-// VGPRs of topk_weighted_partial_kernel<W, KREG, P> from the code-object metadata of this build (profiles/search_weighted_topk.txt;
-// no instance uses scratch): a CU holds min(8, 512 / VGPRs rounded up to the allocation unit of 8) workgroups of four waves.
+// VGPRs of topk_weighted_partial_kernel<W, KREG, P, TopkNoFilter> from the code-object metadata of this build
+// (profiles/search_weighted_topk.txt; no instance uses scratch)
 constexpr int WTOPK_VGPRS[2][4][5] = {
     // KREG 10, 16, 32, 64, 128
     {{32, 44, 76, 140, 258}, {43, 54, 86, 150, 258}, {53, 64, 96, 160, 258}, {63, 74, 106, 170, 258}},     // P = 4, W = 1..4
     {{47, 53, 84, 148, 258}, {67, 73, 102, 166, 258}, {85, 91, 120, 184, 258}, {103, 109, 138, 202, 266}},  // P = 8, W = 1..4
 };
 
-// ... and of topk_weighted_partial_filtered_kernel<W, KREG, P> (profiles/search_filtered_topk.txt)
+// ... and of topk_weighted_partial_kernel<W, KREG, P, TopkFilter> (profiles/search_filtered_topk.txt)
 constexpr int FWTOPK_VGPRS[2][4][5] = {
     {{36, 48, 80, 142, 259}, {47, 58, 90, 152, 259}, {58, 69, 101, 163, 259}, {68, 79, 111, 173, 259}},     // P = 4, W = 1..4
     {{48, 56, 88, 150, 259}, {68, 74, 106, 168, 259}, {88, 94, 125, 187, 259}, {106, 112, 143, 205, 268}},  // P = 8, W = 1..4
 };
 
-int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P, bool filtered = false) {
-    const int ki = k <= 10 ? 0 : k <= 16 ? 1 : k <= 32 ? 2 : k <= 64 ? 3 : 4;
-    const int vgprs = ((filtered ? FWTOPK_VGPRS : WTOPK_VGPRS)[P == 8][W - 1][ki] + 7) / 8 * 8;
-    const int per_cu = std::max(1, std::min(8, 512 / std::max(8, vgprs)));
-    return topk_seg_rows_for(Qn, G, per_cu, (int64_t)1 << WKEY_SHIFT);
+int wtopk_seg_rows(int64_t Qn, int64_t G, int W, int k, int P, bool filtered) {
+    return topk_seg_rows_table(Qn, G, (filtered ? FWTOPK_VGPRS : WTOPK_VGPRS)[P == 8][W - 1][topk_list_index(k)], (int64_t)1 << WKEY_SHIFT);
+}
+
+// the workspace of either weighted entry: its call does not name P, so room for the finer of the two segmentations
+size_t wtopk_workspace(int64_t Qn, int64_t G, int W, int k, bool filtered) {
+    if (W < 1 || W > 4) return 16;
+    return topk_workspace_bytes(Qn, G, k,
+                                [&] { return std::min(wtopk_seg_rows(Qn, G, W, k, 4, filtered), wtopk_seg_rows(Qn, G, W, k, 8, filtered)); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -328,7 +303,6 @@ struct HammingScan {
     static constexpr int SHIFT = KEY_SHIFT;
     static constexpr const char *too_many_segments = "hamming_topk: gallery too large for one call (shard it)";
     TopkMask<MASKED> qm;
-    bool filtered = false;   // ch_hamming_topk_filtered: the segments and the workspace of the filtered kernels
     int check(int W) const {   // the masked entry's own refusals
         if constexpr (MASKED) {
             CH_REQUIRE(qm.stride == 0 || qm.stride == W,
@@ -338,20 +312,16 @@ struct HammingScan {
         return 0;
     }
     bool operands() const { return true; }   // the mask was checked above
-    int seg_rows(int64_t Qn, int64_t G, int W, int k) const {
+    int seg_rows(int64_t Qn, int64_t G, int W, int k, bool filtered) const {
         return filtered ? ftopk_seg_rows(Qn, G, W, k, MASKED) : topk_seg_rows(Qn, G, k);
     }
-    size_t workspace(int64_t Qn, int64_t G, int W, int k) const {
+    size_t workspace(int64_t Qn, int64_t G, int W, int k, bool filtered) const {
         return filtered ? ch_hamming_topk_filtered_workspace(Qn, G, W, k) : ch_hamming_topk_workspace(Qn, G, W, k);
     }
-    template <int W, int KREG>
-    void launch(const TopkCall &c) const {
-        if (c.flt != nullptr)
-            hipLaunchKernelGGL((topk_partial_filtered_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows,
-                               c.k, c.part, qm, *c.flt);
-        else
-            hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows, c.k,
-                               c.part, qm);
+    template <int W, int KREG, class Filter>
+    void launch(const TopkCall &c, const Filter &flt) const {
+        hipLaunchKernelGGL((topk_partial_kernel<W, KREG, MASKED, Filter>), c.grid, dim3(256), 0, c.s, c.q, c.Qn, c.g, c.G, c.seg_rows, c.k,
+                           c.part, qm, flt);
     }
 };
 
@@ -361,77 +331,72 @@ struct WeightedScan {
     static constexpr const char *too_many_segments =
         "hamming_topk_weighted: gallery too large for one call: more than 65,535 segments (shard it)";
     const uint64_t *planes;
-    bool filtered = false;   // ch_hamming_topk_weighted_filtered
     int check(int) const { return 0; }
     bool operands() const { return planes != nullptr; }
-    int seg_rows(int64_t Qn, int64_t G, int W, int k) const { return wtopk_seg_rows(Qn, G, W, k, P, filtered); }
-    size_t workspace(int64_t Qn, int64_t G, int W, int k) const {
-        return filtered ? ch_hamming_topk_weighted_filtered_workspace(Qn, G, W, k) : ch_hamming_topk_weighted_workspace(Qn, G, W, k);
-    }
-    template <int W, int KREG>
-    void launch(const TopkCall &c) const {
-        if (c.flt != nullptr)
-            hipLaunchKernelGGL((topk_weighted_partial_filtered_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G,
-                               c.seg_rows, c.k, c.part, *c.flt);
-        else
-            hipLaunchKernelGGL((topk_weighted_partial_kernel<W, KREG, P>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G,
-                               c.seg_rows, c.k, c.part);
+    int seg_rows(int64_t Qn, int64_t G, int W, int k, bool filtered) const { return wtopk_seg_rows(Qn, G, W, k, P, filtered); }
+    size_t workspace(int64_t Qn, int64_t G, int W, int k, bool filtered) const { return wtopk_workspace(Qn, G, W, k, filtered); }
+    template <int W, int KREG, class Filter>
+    void launch(const TopkCall &c, const Filter &flt) const {
+        hipLaunchKernelGGL((topk_weighted_partial_kernel<W, KREG, P, Filter>), c.grid, dim3(256), 0, c.s, c.q, planes, c.Qn, c.g, c.G,
+                           c.seg_rows, c.k, c.part, flt);
     }
 };
 
+// the body of ch_hamming_topk_weighted and of its _filtered form: the check of P, then topk_run under that P's scan
+template <class Filter>
+int wtopk_run(const char *name, const uint64_t *q, const uint64_t *planes, int P, int64_t Qn, const uint64_t *g, int64_t G, int W, int k,
+              int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream,
+              const Filter &flt) {
+    CH_REQUIRE(P == 4 || P == 8, std::string(name) + ": P (weight bits) must be 4 or 8");
+    if (P == 4)
+        return topk_run(name, WeightedScan<4>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, workspace_bytes,
+                        (hipStream_t)stream, flt);
+    return topk_run(name, WeightedScan<8>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, workspace_bytes,
+                    (hipStream_t)stream, flt);
+}
+
 }  // namespace
 
+// ch_hamming_topk_workspace has never looked at W: 16 for non-positive Qn, G or k only
 extern "C" size_t ch_hamming_topk_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
     (void)W;
-    if (Qn <= 0 || G <= 0 || k <= 0) return 16;
-    return (size_t)(ceil_div64(G, topk_seg_rows(Qn, G, k)) * Qn * k) * sizeof(uint32_t) + 16;
+    return topk_workspace_bytes(Qn, G, k, [&] { return topk_seg_rows(Qn, G, k); });
 }
 
 extern "C" size_t ch_hamming_topk_weighted_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
-    // the call does not name P: room for the finer of the two segmentations
-    const int rows = std::min(wtopk_seg_rows(Qn, G, W, k, 4), wtopk_seg_rows(Qn, G, W, k, 8));
-    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+    return wtopk_workspace(Qn, G, W, k, false);
 }
 
 extern "C" int ch_hamming_topk(const uint64_t *q, int64_t Qn, const uint64_t *g, int64_t G, int32_t W, int32_t k,
                                int64_t g_index_base, int64_t *out_idx, int32_t *out_dist, void *workspace,
                                size_t workspace_bytes, void *stream) {
     return topk_run("hamming_topk", HammingScan<false>{}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
-                    workspace_bytes, (hipStream_t)stream);
+                    workspace_bytes, (hipStream_t)stream, TopkNoFilter{});
 }
 
 extern "C" int ch_hamming_topk_masked(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g,
                                       int64_t G, int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
                                       void *workspace, size_t workspace_bytes, void *stream) {
     return topk_run("hamming_topk_masked", HammingScan<true>{{q_mask, mask_stride}}, q, Qn, g, G, W, k, g_index_base, out_idx,
-                    out_dist, workspace, workspace_bytes, (hipStream_t)stream);
+                    out_dist, workspace, workspace_bytes, (hipStream_t)stream, TopkNoFilter{});
 }
 
 extern "C" int ch_hamming_topk_weighted(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g, int64_t G,
                                         int32_t W, int32_t k, int64_t g_index_base, int64_t *out_idx, int32_t *out_dist,
                                         void *workspace, size_t workspace_bytes, void *stream) {
-    CH_REQUIRE(P == 4 || P == 8, "hamming_topk_weighted: P (weight bits) must be 4 or 8");
-    if (P == 4)
-        return topk_run("hamming_topk_weighted", WeightedScan<4>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx,
-                        out_dist, workspace, workspace_bytes, (hipStream_t)stream);
-    return topk_run("hamming_topk_weighted", WeightedScan<8>{planes}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist,
-                    workspace, workspace_bytes, (hipStream_t)stream);
+    return wtopk_run("hamming_topk_weighted", q, planes, P, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace, workspace_bytes,
+                     stream, TopkNoFilter{});
 }
 
-// The filtered entries: their siblings' scans and checks under the filtered kernels (topk_run with a TopkFilter).  Their segments
-// follow the filtered kernels' registers, so they have workspace functions of their own; the calls name neither the mask nor P: room
-// for the finer of the two segmentations.
+// The filtered entries: their siblings' scans and checks with a TopkFilter.  Their segments follow the filtered instances' registers,
+// so they have workspace functions of their own; the calls name neither the mask nor P: room for the finer of the two segmentations.
 extern "C" size_t ch_hamming_topk_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
-    const int rows = std::min(ftopk_seg_rows(Qn, G, W, k, false), ftopk_seg_rows(Qn, G, W, k, true));
-    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+    if (W < 1 || W > 4) return 16;
+    return topk_workspace_bytes(Qn, G, k, [&] { return std::min(ftopk_seg_rows(Qn, G, W, k, false), ftopk_seg_rows(Qn, G, W, k, true)); });
 }
 
 extern "C" size_t ch_hamming_topk_weighted_filtered_workspace(int64_t Qn, int64_t G, int32_t W, int32_t k) {
-    if (Qn <= 0 || G <= 0 || k <= 0 || W < 1 || W > 4) return 16;
-    const int rows = std::min(wtopk_seg_rows(Qn, G, W, k, 4, true), wtopk_seg_rows(Qn, G, W, k, 8, true));
-    return (size_t)(ceil_div64(G, rows) * Qn * k) * sizeof(uint32_t) + 16;
+    return wtopk_workspace(Qn, G, W, k, true);
 }
 
 extern "C" int ch_hamming_topk_filtered(const uint64_t *q, const uint64_t *q_mask, int32_t mask_stride, int64_t Qn, const uint64_t *g,
@@ -440,23 +405,18 @@ extern "C" int ch_hamming_topk_filtered(const uint64_t *q, const uint64_t *q_mas
                                         size_t workspace_bytes, void *stream) {
     const TopkFilter flt{allow, group, want, g_index_base, (int)exclude};
     if (q_mask == nullptr)
-        return topk_run("hamming_topk_filtered", HammingScan<false>{{}, true}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
-                        workspace_bytes, (hipStream_t)stream, &flt);
-    return topk_run("hamming_topk_filtered", HammingScan<true>{{q_mask, mask_stride}, true}, q, Qn, g, G, W, k, g_index_base,
-                    out_idx, out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
+        return topk_run("hamming_topk_filtered", HammingScan<false>{}, q, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
+                        workspace_bytes, (hipStream_t)stream, flt);
+    return topk_run("hamming_topk_filtered", HammingScan<true>{{q_mask, mask_stride}}, q, Qn, g, G, W, k, g_index_base, out_idx,
+                    out_dist, workspace, workspace_bytes, (hipStream_t)stream, flt);
 }
 
 extern "C" int ch_hamming_topk_weighted_filtered(const uint64_t *q, const uint64_t *planes, int32_t P, int64_t Qn, const uint64_t *g,
                                                  int64_t G, int32_t W, int32_t k, int64_t g_index_base, const uint64_t *allow,
                                                  const int32_t *group, const int64_t *want, int32_t exclude, int64_t *out_idx,
                                                  int32_t *out_dist, void *workspace, size_t workspace_bytes, void *stream) {
-    CH_REQUIRE(P == 4 || P == 8, "hamming_topk_weighted_filtered: P (weight bits) must be 4 or 8");
-    const TopkFilter flt{allow, group, want, g_index_base, (int)exclude};
-    if (P == 4)
-        return topk_run("hamming_topk_weighted_filtered", WeightedScan<4>{planes, true}, q, Qn, g, G, W, k, g_index_base, out_idx,
-                        out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
-    return topk_run("hamming_topk_weighted_filtered", WeightedScan<8>{planes, true}, q, Qn, g, G, W, k, g_index_base, out_idx,
-                    out_dist, workspace, workspace_bytes, (hipStream_t)stream, &flt);
+    return wtopk_run("hamming_topk_weighted_filtered", q, planes, P, Qn, g, G, W, k, g_index_base, out_idx, out_dist, workspace,
+                     workspace_bytes, stream, TopkFilter{allow, group, want, g_index_base, (int)exclude});
 }
 
 extern "C" int ch_weight_planes(const float *codes, int64_t Qn, int32_t nbit, const uint64_t *mask, int32_t mask_stride, int32_t P,

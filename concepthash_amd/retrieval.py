@@ -69,18 +69,18 @@ def _check_mask(mask: torch.Tensor, Qn: int, W: int, device, whose: str) -> Tupl
 
 
 def _topk(entry: str, q: torch.Tensor, g: torch.Tensor, k: int, g_index_base: int, stream, operands=(),
-          workspace: str = "ch_hamming_topk_workspace", filt=()) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The call of a ch_hamming_topk* entry on checked codes: allocates idx / dist / the workspace; `operands` are the entry's own
-    arguments, between q and Qn; `filt` those of a filtered entry (`_check_filter`), behind g_index_base."""
+          workspace: str = "ch_hamming_topk_workspace", filt=(), behind_w=()) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The call of a ch_hamming_topk* / ch_ternary_topk* entry on checked codes ([rows, W] or [rows, 2, W]): allocates idx / dist / the
+    workspace; `operands` are the entry's own arguments between q and Qn, `behind_w` those between W and k (the ternary nbit); `filt`
+    those of a filtered entry (`_check_filter`), behind g_index_base."""
     lib = _lib.load()
-    Qn, W = q.shape
-    G = g.shape[0]
+    Qn, W, G = q.shape[0], q.shape[-1], g.shape[0]
     idx = torch.empty(Qn, k, dtype=torch.int64, device=q.device)
     dist = torch.empty(Qn, k, dtype=torch.int32, device=q.device)
     wsb = int(getattr(lib, workspace)(Qn, G, W, k))
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     with _dev_guard(q):
-        _lib.check(getattr(lib, entry)(_lib.ptr(q), *operands, Qn, _lib.ptr(g), G, W, k, int(g_index_base), *_filter_args(filt),
+        _lib.check(getattr(lib, entry)(_lib.ptr(q), *operands, Qn, _lib.ptr(g), G, W, *behind_w, k, int(g_index_base), *_filter_args(filt),
                                        _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), entry)
     return idx, dist
 
@@ -1319,19 +1319,8 @@ def ternary_dist(q3: torch.Tensor, g3: torch.Tensor, nbit: int, stream=None) -> 
 def ternary_topk(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-k by ascending (K, gallery index) on `pack_ternary` codes: (idx int64 [Qn,k], dist int32 [Qn,k] = K); -1 where k > G.  Lists of
     gallery shards merge with `topk_merge`."""
-    lib = _lib.load()
     q3, g3 = _check_ternary(q3, g3, nbit)
-    Qn, _, W = q3.shape
-    G = g3.shape[0]
-    k = int(k)
-    idx = torch.empty(Qn, k, dtype=torch.int64, device=q3.device)
-    dist = torch.empty(Qn, k, dtype=torch.int32, device=q3.device)
-    wsb = int(lib.ch_ternary_topk_workspace(Qn, G, W, k))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q3.device)
-    with _dev_guard(q3):
-        _lib.check(lib.ch_ternary_topk(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), k, int(g_index_base), _lib.ptr(idx), _lib.ptr(dist),
-                                       _lib.ptr(ws), wsb, _lib.stream_ptr(stream)), "ch_ternary_topk")
-    return idx, dist
+    return _topk("ch_ternary_topk", q3, g3, int(k), g_index_base, stream, workspace="ch_ternary_topk_workspace", behind_w=(int(nbit),))
 
 
 def ternary_topk_filtered(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int, allow: Optional[torch.Tensor] = None,
@@ -1339,21 +1328,10 @@ def ternary_topk_filtered(q3: torch.Tensor, g3: torch.Tensor, nbit: int, k: int,
                           g_index_base: int = 0, stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """`ternary_topk` among ADMITTED rows only; allow, group, want and exclude as `hamming_topk_filtered` takes them (a row of the
     two-plane gallery is one row of the bitmap and of the group plane)."""
-    lib = _lib.load()
     q3, g3 = _check_ternary(q3, g3, nbit)
-    Qn, _, W = q3.shape
-    G = g3.shape[0]
-    filt = _check_filter(allow, group, want, exclude, Qn, G, q3.device)
-    k = int(k)
-    idx = torch.empty(Qn, k, dtype=torch.int64, device=q3.device)
-    dist = torch.empty(Qn, k, dtype=torch.int32, device=q3.device)
-    wsb = int(lib.ch_ternary_topk_filtered_workspace(Qn, G, W, k))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=q3.device)
-    with _dev_guard(q3):
-        _lib.check(lib.ch_ternary_topk_filtered(_lib.ptr(q3), Qn, _lib.ptr(g3), G, W, int(nbit), k, int(g_index_base), *_filter_args(filt),
-                                                _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(ws), wsb, _lib.stream_ptr(stream)),
-                   "ch_ternary_topk_filtered")
-    return idx, dist
+    filt = _check_filter(allow, group, want, exclude, q3.shape[0], g3.shape[0], q3.device)
+    return _topk("ch_ternary_topk_filtered", q3, g3, int(k), g_index_base, stream, workspace="ch_ternary_topk_filtered_workspace", filt=filt,
+                 behind_w=(int(nbit),))
 
 
 def ternary_rank_collect(q3: torch.Tensor, g3: torch.Tensor, nbit: int, q_lab: torch.Tensor, g_lab: torch.Tensor, LW: int,

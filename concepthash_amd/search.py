@@ -245,14 +245,9 @@ class GalleryIndex:
             raise ValueError(f"k = {k} > {TOPK_MAX} with margin > 0 is not built: lists deeper than {TOPK_MAX} take one mask shared by all "
                              f"queries (concepts), not a mask per query")
         dev = self.device
-        codes = query_codes.to(dev, torch.float32)
-        if codes.dim() != 2 or codes.shape[1] != self.nbit:
-            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
-        if self.mean is not None and mean_shift:
-            codes = codes - self.mean[None, :]
+        codes, q, flt = self._query(query_codes, mean_shift, refuse=None if not filtered else
+                                    lambda Qn: self._filter(Qn, rows, labels_in, labels_out, query_group, group_mode, group_by))
         Qn = codes.shape[0]
-        flt = self._filter(Qn, rows, labels_in, labels_out, query_group, group_mode, group_by) if filtered else None
-        q = rt.pack_sign(codes)
         keep = torch.ones(self.nbit, dtype=torch.bool, device=dev)
         mask = None
         if concepts is not None:
@@ -277,14 +272,13 @@ class GalleryIndex:
         extra = {}
         if rank == "asymmetric":
             planes, wsum = rt.weight_planes(codes, int(weight_bits), mask)
-            idx, dist = (rt.hamming_topk_weighted(q, planes, self.codes, k) if flt is None else
-                         rt.hamming_topk_filtered(q, self.codes, k, planes=planes, **flt))
+            idx, dist = self._asymmetric_list(q, planes, k, flt)
             extra = dict(rank=rank, weight_bits=int(weight_bits), dist_max=wsum)
         elif rank == "ternary":
             g3 = torch.stack([self.codes & self.mask, self.mask], dim=1)
             if nbit_play == 0:
                 raise ValueError("rank='ternary' with an empty set of concepts leaves no bit in play")
-            idx, dist = rt.ternary_topk(q3, g3, nbit_play, k) if flt is None else rt.ternary_topk_filtered(q3, g3, nbit_play, k, **flt)
+            idx, dist = self._ternary_list(q3, g3, nbit_play, k, flt)
             if radius is not None:
                 far = dist > 2 * radius
                 idx, dist = idx.masked_fill(far, -1), dist.masked_fill(far, -1)
@@ -293,12 +287,8 @@ class GalleryIndex:
                          dist_max=(bits_sure + nbit_play).to(torch.int32))
         elif deep:
             idx, dist = rt.hamming_ranked(q, self.codes, k, radius=radius, mask=mask)
-        elif flt is not None:
-            idx, dist = rt.hamming_topk_filtered(q, self.codes, k, mask=mask, **flt)
-        elif mask is None:
-            idx, dist = rt.hamming_topk(q, self.codes, k)
         else:
-            idx, dist = rt.hamming_topk_masked(q, self.codes, mask, k)
+            idx, dist = self._hamming_list(q, mask, k, flt)
         if flt is not None:              # an unfiltered search returns the keys it always has
             extra["rows_admitted"] = len(self) if flt["allow"] is None else rt.bitmap_count(flt["allow"], len(self))
         if radius is not None and not deep and rank != "ternary":
@@ -307,6 +297,37 @@ class GalleryIndex:
         out = dict(idx=idx, dist=dist, concept_dist=rt.subcode_dist(q, self.codes, idx, self.nbit, self.ncontext),
                    bits=keep.sum(1), labels=None, paths=None, **extra)
         return self._name_hits(out)
+
+    def _query(self, query_codes: torch.Tensor, mean_shift: bool, dense: bool = False, refuse=None):
+        """The prologue of a search: the checked query codes on the index's device as fp32 (dense: finite too, checked before
+        anything is launched), minus the database mean where there is one and mean_shift asks for it -> (codes, their packed signs,
+        refuse(Qn) or None).  refuse: the caller's checks that need the number of queries (the filter); they raise behind the checks
+        of the codes and in front of the first kernel."""
+        if query_codes.dim() != 2 or query_codes.shape[1] != self.nbit:
+            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(query_codes.shape)}")
+        if dense:
+            query_codes = rt.check_dense_codes(query_codes, "query codes")
+        codes = query_codes.to(self.device, torch.float32)
+        if self.mean is not None and mean_shift:
+            codes = codes - self.mean[None, :]
+        checked = None if refuse is None else refuse(codes.shape[0])
+        return codes, rt.pack_sign(codes), checked
+
+    # the list of one rank at k <= TOPK_MAX; flt: None, or the arguments of `_filter`
+    def _hamming_list(self, q, mask, k: int, flt):
+        if flt is not None:
+            return rt.hamming_topk_filtered(q, self.codes, k, mask=mask, **flt)
+        return rt.hamming_topk(q, self.codes, k) if mask is None else rt.hamming_topk_masked(q, self.codes, mask, k)
+
+    def _asymmetric_list(self, q, planes, k: int, flt):
+        if flt is not None:
+            return rt.hamming_topk_filtered(q, self.codes, k, planes=planes, **flt)
+        return rt.hamming_topk_weighted(q, planes, self.codes, k)
+
+    def _ternary_list(self, q3, g3, nbit: int, k: int, flt):
+        if flt is not None:
+            return rt.ternary_topk_filtered(q3, g3, nbit, k, **flt)
+        return rt.ternary_topk(q3, g3, nbit, k)
 
     def _label_rows(self, ids, what: str) -> torch.Tensor:
         """bool [G]: the rows that carry one of the classes `ids` (labels_in / labels_out)"""
@@ -381,15 +402,8 @@ class GalleryIndex:
         if self.real is None:
             raise ValueError(f"rank='{rank}' needs the index's real plane, which this index was built without: rebuild it "
                              f"(exp=search rank={rank} rebuilds it by itself; rebuild_index=true forces it)")
-        codes = torch.as_tensor(query_codes)
-        if codes.dim() != 2 or codes.shape[1] != self.nbit:
-            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(codes.shape)}")
-        codes = rt.check_dense_codes(codes, "query codes")          # finite, before anything is launched
+        codes, q, _ = self._query(torch.as_tensor(query_codes), mean_shift, dense=True)
         dev = self.device
-        codes = codes.to(dev)
-        if self.mean is not None and mean_shift:
-            codes = codes - self.mean[None, :]
-        q = rt.pack_sign(codes)
         extra = {}
         if shortlist is not None:
             idx, dist = rt.rerank_topk(codes, self.real, rank, k, shortlist, None if radius is None else int(radius), q, self.codes)

@@ -130,6 +130,26 @@ def test_dense_topk_short_gallery_fills_with_minus_one_and_infinity(dev, metric)
         assert _same_lists(rt.dense_topk(q, rt.prepare_dense(_t(xg[:rows], dev), metric), metric, 10), want), rows
     g = rt.prepare_dense(_t(xg, dev), metric)
     assert rt.dense_topk(rt.prepare_dense(_t(xq[:0], dev), metric), g, metric, 10)[0].shape == (0, 10)
+    # the longest list over a gallery shorter than it: 100 hits, then 28 x (-1, +inf)
+    rng = np.random.default_rng(128)
+    yq, yg = _grid(rng, 3, 8), _grid(rng, 100, 8)
+    want = dref.topk(dref.dist(yq, yg, metric), 128)
+    assert np.all(want[0][:, :100] >= 0) and np.all(want[0][:, 100:] == -1) and np.all(np.isposinf(want[1][:, 100:]))
+    assert _same_lists(rt.dense_topk(rt.prepare_dense(_t(yq, dev), metric), rt.prepare_dense(_t(yg, dev), metric), metric, 128), want)
+
+
+@pytest.mark.parametrize("metric", ["dot", "euclidean"])
+def test_dense_topk_equal_rows_on_both_sides_of_a_segment_boundary_come_out_in_row_order(dev, metric):
+    """rows 255, 256 and 257 are copies of one another and 256-row segments part them: their equal distances merge in row order"""
+    from concepthash_amd import retrieval as rt
+    xq, xg, _ = _seg_problem(metric)
+    xg = xg.copy()
+    xg[256] = xg[257] = xg[255] = xq[1]                                 # query 1 itself: the three are at the head of its list
+    D = dref.dist(xq[:3], xg, metric)
+    want = dref.topk(D, 128)
+    assert np.array_equal(want[0][1][np.isin(want[0][1], (255, 256, 257))], (255, 256, 257))
+    got = rt.dense_topk(rt.prepare_dense(_t(xq[:3], dev), metric), rt.prepare_dense(_t(xg, dev), metric), metric, 128, seg_rows=256)
+    assert _same_lists(got, want)
 
 
 # ---- exact inputs: the evaluation --------------------------------------------------------------------------------------------------

@@ -297,6 +297,22 @@ def test_two_unequal_shards_merge_into_the_whole_call(dev, k):
         assert _same(call(rt.hamming_topk_filtered, tg, 0, G, tq, k), ref.topk(D, adm, k, base))
 
 
+def test_a_shard_without_an_admitted_row_merges_as_empty_lists(dev):
+    """topk_merge with a list that is empty throughout: one shard's lists are all -1, the other's hold 10 hits and 6 x -1"""
+    from concepthash_amd import retrieval as rt
+    nbit, Qn, G, cut, k = 64, 3, 771, 301, 16
+    _, _, q, g, D = _problem(nbit, Qn, G)
+    tq, tg = _t(q, dev), _t(g, dev)
+    allow = np.zeros(G, bool)
+    allow[np.random.default_rng(16).permutation(np.arange(cut, G))[:10]] = True
+    parts = [rt.hamming_topk_filtered(tq, tg[lo:hi], k, allow=_t(allow[lo:hi], dev), g_index_base=lo) for lo, hi in ((0, cut), (cut, G))]
+    assert (parts[0][0] == -1).all() and (parts[0][1] == -1).all()
+    assert ((parts[1][0] >= 0).sum(1) == 10).all() and (parts[1][0][:, 10:] == -1).all()
+    want = ref.topk(D, ref.admitted(Qn, G, allow=allow), k)
+    for order in (parts, parts[::-1]):
+        assert _same(rt.topk_merge(torch.stack([p[0] for p in order]), torch.stack([p[1] for p in order])), want)
+
+
 # ---- GalleryIndex.search -------------------------------------------------------------------------------------------------------------
 
 def _index(dev, labels, nbit=64, Qn=70, G=771):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Weighted (asymmetric) against plain Hamming top-k (profiles/search_weighted_topk.txt):
     python tools/weighted_topk_bench.py [--out FILE] [--asm FILE.s]
-1. Registers: VGPRs and scratch bytes of every topk_weighted_partial_kernel<W, KREG, P> instance, from the code-object metadata
+1. Registers: VGPRs and scratch bytes of every unfiltered topk_weighted_partial_kernel<W, KREG, P, TopkNoFilter> instance, from the code-object metadata
    (`amdhsa.kernels`) of csrc/hamming_topk.hip compiled to assembly for gfx950 -- compiled here, or read from --asm.
 2. Timing: hamming_topk, hamming_topk_weighted with 4-bit and with 8-bit weights, k = 10, at 5,794 x 5,994 x 64 bit and
    16,384 x 1M x 128 bit; one process, the three variants taking turns over --rounds rounds of --calls calls each (torch.cuda.Event
@@ -41,12 +41,12 @@ def register_table(asm_path):
     rows = {}
     for blk in meta.split("  - .agpr_count:")[1:]:
         field = lambda k: int(re.search(r"\." + k + r":\s*(\d+)", blk).group(1))
-        m = re.search(r"topk_weighted_partial_kernelILi(\d+)ELi(\d+)ELi(\d+)E", blk)
+        m = re.search(r"topk_weighted_partial_kernelILi(\d+)ELi(\d+)ELi(\d+)ENS_12TopkNoFilterEE", blk)   # the unfiltered instances
         if m:
             W, kreg, P = (int(v) for v in m.groups())
             rows[(P, W, kreg)] = (field("vgpr_count"), int(re.match(r"\s*(\d+)", blk).group(1)), field("sgpr_count"),
                                   field("private_segment_fixed_size"), field("vgpr_spill_count"))
-    lines = ["topk_weighted_partial_kernel<W, KREG, P>: registers from the code-object metadata (vgpr_count includes the AGPRs)",
+    lines = ["topk_weighted_partial_kernel<W, KREG, P, TopkNoFilter>: registers from the code-object metadata (vgpr_count includes the AGPRs)",
              "  P  W  KREG  VGPRs  of which AGPRs  SGPRs  scratch bytes  spilled VGPRs"]
     for (P, W, kreg), (v, ag, s, scratch, spill) in sorted(rows.items()):
         lines.append(f"  {P}  {W}  {kreg:4d}  {v:5d}  {ag:14d}  {s:5d}  {scratch:13d}  {spill:13d}")
