@@ -66,6 +66,9 @@ SIGNATURES = {
                                  c_void_p]),
     "ch_debug_gemm_train": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_void_p]),
+    "ch_debug_gemm_fwd": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                  c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int32,
+                                  c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ch_debug_gemm_patch": (c_int, [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                     c_int32, c_int32, c_void_p]),
     "ch_debug_gemm_dispatch_count": (c_int64, [c_int32]),

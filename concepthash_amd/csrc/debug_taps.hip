@@ -11,8 +11,9 @@
 static bool g_debug_splitk = false;
 static float *g_debug_ws = nullptr;
 static unsigned *g_debug_cnt = nullptr;
-static int debug_attach_splitk(GemmParams &p) {
-    if (!g_debug_splitk) return 0;
+// force: the call asks for the split itself (ch_debug_gemm_fwd); otherwise ch_debug_set_gemm_splitk decides
+static int debug_attach_splitk(GemmParams &p, bool force = false) {
+    if (!g_debug_splitk && !force) return 0;
     if (!g_debug_ws) {
         CH_CHECK_HIP(hipMalloc((void **)&g_debug_ws, CH_SPLITK_WS_BYTES));
         CH_CHECK_HIP(hipMalloc((void **)&g_debug_cnt, CH_SPLITK_CNT_BYTES));
@@ -67,12 +68,13 @@ extern "C" int ch_debug_gemm_ln(int32_t variant, const void *X, int64_t X_rows_a
     return debug_gemm_launch(p, epi, stream, direct || forced ? variant : 0, direct, true);
 }
 // variant of the two taps below: 0 = dispatcher, 1 = 128x128 two-phase, 2 / 4 = 256x256 ping-pong (fine / coarse schedule), 7 = ring
-static int debug_gemm_launch_checked(GemmParams &p, int epi, void *stream, int variant, const char *what) {
+// direct: a named kernel by itself (the training and patch taps); false: the same kernel through the dispatcher (ch_debug_gemm_fwd)
+static int debug_gemm_launch_checked(GemmParams &p, int epi, void *stream, int variant, const char *what, bool direct = true) {
     if (variant != 0 && variant != 1 && variant != 2 && variant != 4 && variant != 7) {
         ch_set_error(std::string(what) + ": variant must be 0 (dispatcher), 1, 2, 4 or 7");
         return 2;
     }
-    return debug_gemm_launch(p, epi, stream, variant, variant != 0, false);
+    return debug_gemm_launch(p, epi, stream, variant, direct && variant != 0, false);
 }
 // The training-step epilogues (kernels.h): 11 / 12 = (*scale_ptr, 12 only) * bf16(acc + bias) * act'(aux), aux [M, ldo] bf16 in the layout
 // of out_bf16; 13 / 14 = out_bf16 = the LN-folded linear (stats_in, fold_c, ln_eps as ch_debug_gemm_ln), hb_out [M, ld_hb] = act(out_bf16).
@@ -100,6 +102,63 @@ extern "C" int ch_debug_gemm_train(int32_t variant, const void *X, int64_t X_row
     p.aux = (const bf16_t *)aux;
     p.stats_in = stats_in; p.fold_c = fold_c; p.ln_eps = ln_eps; p.hb_out = (bf16_t *)hb_out; p.ld_hb = ld_hb;
     return debug_gemm_launch_checked(p, epi, stream, variant, "debug_gemm_train");
+}
+// The ten forward epilogues (0 .. 4, 6 .. 10) with every leading dimension and launch option of GemmParams the product sets, always
+// THROUGH the dispatcher: variant 0 is its rule, 1 / 2 / 4 / 7 that kernel after the dispatcher's cache-policy choice and checks (so the
+// non-temporal instances are reachable and counted).  The alignment each leading dimension needs is the widest access of store_tile /
+// resid_prefetch to that tensor: 16-byte stores of out_bf16 (8-byte ones in EPI_BIAS_RESID), 16-byte loads / stores of resid, 8-byte loads
+// of addend and 8-byte stores of hb_out.
+extern "C" int ch_debug_gemm_fwd(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M, int32_t N,
+                                 int32_t K, int32_t epi, void *out_bf16, int32_t ldo, float *resid, int32_t ldr, const float *scale_ptr,
+                                 const void *addend, int32_t ld_addend, const float *stats_in, const float *fold_c, float ln_eps,
+                                 float *stats_out, void *hb_out, int32_t ld_hb, int32_t nt_resid_opt, int32_t nt_out_opt, int32_t group_n_opt,
+                                 int32_t rev, int32_t splitk, void *stream) {
+    CH_REQUIRE(X && W && bias, "debug_gemm_fwd: null operand");
+    CH_REQUIRE((epi >= EPI_BIAS && epi <= EPI_SCALE_RESID) || (epi >= EPI_BIAS_STATS && epi <= EPI_FOLD_GELU),
+               "debug_gemm_fwd: epilogue must be one of the forward modes (0 .. 4, 6 .. 10)");
+    CH_REQUIRE(M > 0 && N > 0 && K > 0, "debug_gemm_fwd: empty problem");
+    CH_REQUIRE(nt_resid_opt >= -1 && nt_resid_opt <= 1 && nt_out_opt >= -1 && nt_out_opt <= 1 && group_n_opt >= 0 && (rev == 0 || rev == 1) &&
+               (splitk == 0 || splitk == 1), "debug_gemm_fwd: nt_*_opt must be -1, 0 or 1, group_n_opt >= 0, rev and splitk 0 or 1");
+    const bool scale_resid = epi == EPI_SCALE_RESID || epi == EPI_SCALE_RESID_STATS;
+    const bool fold = epi >= EPI_FOLD_BIAS && epi <= EPI_FOLD_GELU;
+    if (!scale_resid) {
+        CH_REQUIRE(out_bf16 != nullptr, "debug_gemm_fwd: this epilogue writes out_bf16");
+        if (epi == EPI_BIAS_RESID)
+            CH_REQUIRE(ldo >= N && ldo % 4 == 0, "debug_gemm_fwd: ldo must be >= N and a multiple of 4 (8-byte stores of the bf16 copy)");
+        else
+            CH_REQUIRE(ldo >= N && ldo % 8 == 0, "debug_gemm_fwd: ldo must be >= N and a multiple of 8 (16-byte row chunks)");
+    }
+    if (epi == EPI_BIAS_RESID || scale_resid) {
+        CH_REQUIRE(resid != nullptr, "debug_gemm_fwd: the residual epilogues need resid");
+        CH_REQUIRE(ldr >= N && ldr % 4 == 0, "debug_gemm_fwd: ldr must be >= N and a multiple of 4 (16-byte row chunks)");
+    }
+    if (epi == EPI_BIAS_RESID) CH_REQUIRE((const void *)resid != (const void *)out_bf16, "debug_gemm_fwd: resid and out_bf16 must be distinct");
+    if (scale_resid) {
+        CH_REQUIRE(scale_ptr != nullptr, "debug_gemm_fwd: the scale + residual epilogues need scale_ptr");
+        if (addend) CH_REQUIRE(ld_addend >= N && ld_addend % 4 == 0, "debug_gemm_fwd: ld_addend must be >= N and a multiple of 4 (8-byte loads)");
+    }
+    if (epi == EPI_BIAS_STATS || epi == EPI_SCALE_RESID_STATS) CH_REQUIRE(stats_out != nullptr, "debug_gemm_fwd: the statistics epilogues need stats_out");
+    if (epi == EPI_SCALE_RESID_STATS) {
+        CH_REQUIRE(hb_out != nullptr, "debug_gemm_fwd: epilogue 7 needs hb_out");
+        CH_REQUIRE(ld_hb >= N && ld_hb % 4 == 0, "debug_gemm_fwd: ld_hb must be >= N and a multiple of 4 (8-byte stores)");
+        CH_REQUIRE((const void *)hb_out != (const void *)resid, "debug_gemm_fwd: hb_out and resid must be distinct");
+    }
+    if (fold)
+        CH_REQUIRE(stats_in && fold_c && K % 128 == 0 && K <= 1280 && ln_eps > 0.f,
+                   "debug_gemm_fwd: LN-folded epilogue needs stats_in, fold_c, K % 128 == 0, K <= 1280, ln_eps > 0");
+    CH_REQUIRE(!splitk || variant == 2, "debug_gemm_fwd: the split-K tail belongs to the 256x256 kernel (variant 2)");
+    GemmParams p = debug_gemm_params(X, X_rows_alloc, W, bias, M, N, K, out_bf16, ldo, scale_ptr);
+    p.resid = resid; p.ldr = ldr; p.addend = (const bf16_t *)addend; p.ld_addend = ld_addend;
+    p.stats_in = stats_in; p.fold_c = fold_c; p.ln_eps = ln_eps; p.stats_out = stats_out; p.hb_out = (bf16_t *)hb_out; p.ld_hb = ld_hb;
+    p.nt_resid_opt = nt_resid_opt; p.nt_out_opt = nt_out_opt; p.group_n_opt = group_n_opt; p.rev = rev;
+    if (variant == 7) {
+        // the dispatcher takes 7 as "the ring wherever it is supported" and would fall back to its rule: here 7 means the ring or an error
+        CH_REQUIRE(ch_gemm_r4_supported(p, epi), "debug_gemm_fwd: the ring kernel needs N % 128 == 0, K % 32 == 0, K >= 96, X padded to 128 rows");
+        CH_REQUIRE(((int64_t)M + 255) / 256 * (N / 256) < 128, "debug_gemm_fwd: at this size the dispatcher's rule takes the 256x256 kernel, not the ring");
+    }
+    if (splitk)
+        if (int e = debug_attach_splitk(p, true)) return e;
+    return debug_gemm_launch_checked(p, epi, stream, variant, "debug_gemm_fwd", false);
 }
 // The patch-embedding epilogue: resid[(img * tokens_per_img + 1 + patch) * ldr + n] = acc + pos[(1 + patch) * N + n] for row
 // m = img * patches_per_img + patch of X W^T (no bias); every other row of resid is left alone.

@@ -37,6 +37,17 @@ int ch_debug_gemm_ln(int32_t variant, const void *X, int64_t X_rows_alloc, const
 int ch_debug_gemm_train(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M, int32_t N,
                         int32_t K, int32_t epi, void *out_bf16, int32_t ldo, const void *aux, const float *scale_ptr,
                         const float *stats_in, const float *fold_c, float ln_eps, void *hb_out, int32_t ld_hb, void *stream);
+/* One forward-epilogue launch (epi 0 .. 4, 6 .. 10 as in the two taps above) with every leading dimension and launch option explicit:
+ * out_bf16 [M, ldo], resid [M, ldr], addend [M, ld_addend], hb_out [M, ld_hb]; nt_resid_opt / nt_out_opt: 0 = by tensor size, 1 = the
+ * non-temporal instance, -1 = the default-policy instance; group_n_opt > 0: n-tiles per weight group; rev = 1: serpentine tile order;
+ * splitk = 1 (variant 2 only): cut EVERY tile of the last partial round along K (the tap's own workspace).  variant: 0 = the dispatcher's
+ * rule, 1 / 2 / 4 / 7 = that kernel reached THROUGH the dispatcher (its cache-policy choice, its checks and the non-temporal counters
+ * apply); a kernel that does not take the shape or the epilogue is an error, never another kernel. */
+int ch_debug_gemm_fwd(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, const float *bias, int32_t M, int32_t N,
+                      int32_t K, int32_t epi, void *out_bf16, int32_t ldo, float *resid, int32_t ldr, const float *scale_ptr,
+                      const void *addend, int32_t ld_addend, const float *stats_in, const float *fold_c, float ln_eps, float *stats_out,
+                      void *hb_out, int32_t ld_hb, int32_t nt_resid_opt, int32_t nt_out_opt, int32_t group_n_opt, int32_t rev,
+                      int32_t splitk, void *stream);
 /* The patch-embedding epilogue (epi 5): row m = img * patches_per_img + patch of X W^T, plus pos[1 + patch] (pos [1 + patches_per_img, N]
  * fp32), goes to row img * tokens_per_img + 1 + patch of resid [*, ldr] fp32; every other row of resid is left alone. */
 int ch_debug_gemm_patch(int32_t variant, const void *X, int64_t X_rows_alloc, const void *W, int32_t M, int32_t N, int32_t K, float *resid,

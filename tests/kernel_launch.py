@@ -1,4 +1,5 @@
-"""The launch discipline that the single-kernel GPU tests share (tests/test_train_rowkernels_gpu.py, tests/test_forward_kernels_gpu.py):
+"""The launch discipline that the single-kernel GPU tests share (tests/test_train_rowkernels_gpu.py, tests/test_forward_kernels_gpu.py,
+tests/test_gemm_fwd_epilogues_gpu.py; tests/test_gemm_train_epilogues_gpu.py takes its sentinel buffers from here):
 each output lies between two guard blocks of a sentinel (a NaN bit pattern no kernel produces) that must come back untouched, and starts as
 the sentinel itself, so an element the kernel failed to write is seen; every input is followed by NaN inside the same allocation; a second
 identical launch must give identical bytes; the worst error / bound ratio of every group of comparisons is kept and printed."""
@@ -47,6 +48,16 @@ class Out:
     def untouched(self, mask):
         """True when every payload element under `mask` (CPU bool tensor of the payload's shape) is still the sentinel"""
         return bool((self.raw()[mask] == self.sent).all())
+
+
+def sentinel(rows, ld):
+    """a [rows, ld] bf16 buffer (as int16) on the GPU, all of it SENT16"""
+    return torch.full((rows, ld), SENT16, dtype=torch.int16, device="cuda")
+
+
+def untouched(buf, M, N):
+    """rows >= M and the gap columns >= N of a sentinel-filled [rows, ld] bf16 buffer"""
+    return bool((buf[M:] == SENT16).all()) and bool((buf[:M, N:] == SENT16).all())
 
 
 def inp(dev, x):

@@ -5,7 +5,8 @@ activations -- where a fused epilogue goes wrong first.  u = 2^-8 (bf16), gamma_
 DACT (11 quick_gelu', 12 s * gelu'):  want = s (X W^T + bias) act'(aux);
     |got - want| <= (2u + u^2) |want| + gamma_K (|X||W|^T + |bias|) |s act'| + |s z| delta
     (two bf16 roundings: the staged acc + bias and the output; the fp32 accumulation; the derivative approximation).
-ACT2 (13, 14):  the first output takes the bound of the LayerNorm-folded consumers (tests/test_gemm_gpu.py); the second is checked
+ACT2 (13, 14):  the first output takes the bound of the LayerNorm-folded consumers (tests/test_gemm_gpu.py) and, on top of it, the
+    derived bound of epilogue 8 (tests/gemm_ref.py: the exact function of the operands, the fp32 partials included); the second is checked
     against the activation of the kernel's OWN first output, in fp64: |hb - act(pre_got)| <= u |act| + delta_act.
 PATCH (5):  patch rows of the fp32 residual within gamma_K |X||W|^T + 2^-24 |want| of X W^T + pos[1 + patch]; every other row untouched.
 
@@ -17,22 +18,20 @@ delta_act quick_gelu 6.3e-7, gelu 4.4e-7.
 Which kernel takes which epilogue is listed in `_train_supported` / `_patch_supported`, not asked of the library: a narrowed
 `*_supported` predicate fails here.
 Every case prints its worst error / bound ratio (-s)."""
-import math
-
 import pytest
 import torch
+
+from gemm_ref import SPECIAL, SPECIAL_COLS, Ops, _deltas, _dgelu, _dquick, _gelu, _quick, fold_operands, operands, out_ref
+from kernel_launch import SENT16, sentinel as _sentinel, untouched as _untouched
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -8
 U32 = 2.0 ** -24
 EPI_PATCH, DACT_QUICK, DACT_GELU, ACT2_QUICK, ACT2_GELU = 5, 11, 12, 13, 14
-SENT16 = 0x7FC1                          # bf16 NaN pattern no kernel produces
 MS = (1, 127, 129, 255, 257, 300)
 SHAPES = ((128, 128), (384, 768), (768, 384), (256, 1280))      # (N, K)
 VARIANTS = (0, 1, 2, 4, 7)               # dispatcher, 128x128 two-phase, 256x256 ping-pong (fine, coarse schedule), ring
-SPECIAL = (0.0, -0.0, 8.0, -8.0, 30.0, -30.0, 88.0, -88.0, 1e4, -1e4)
-SPECIAL_COLS = (0, 9, 18, 27, 36, 45, 54, 63, 70, 127)         # every 16-byte chunk position of a 64-column slice, both slices
 
 
 def _experiments(lib):
@@ -62,62 +61,6 @@ def gamma(n):
     return n * U32 / (1.0 - n * U32)
 
 
-# ---- exact activations / derivatives (fp64) and the kernels' formulas (fp32, CPU) -----------------------------------------------------
-def _quick(x):
-    return x * torch.sigmoid(1.702 * x)
-
-
-def _gelu(x):
-    return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
-
-
-def _dquick(x):
-    s = torch.sigmoid(1.702 * x)
-    return s * (1.0 + 1.702 * x * (1.0 - s))
-
-
-def _dgelu(x):
-    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
-
-
-def _kernel_formulas(x):
-    """gemm_epilogue.h in fp32: (dquick_gelu_f, dgelu_erf_f, quick_gelu_f, gelu_erf_f)(x)"""
-    f = lambda c: torch.tensor(c, dtype=torch.float32)
-    exp2, rcp = torch.exp2, torch.reciprocal
-    s = rcp(1.0 + exp2(f(-2.4554669595930157) * x))
-    dquick = s * (1.0 + f(1.702) * x * (1.0 - s))
-    quick = x * s
-    z = x.abs() * f(0.70710678118654752)
-    t = rcp(1.0 + f(0.3275911) * z)
-    poly = t * (f(0.254829592) + t * (f(-0.284496736) + t * (f(1.421413741) + t * (f(-1.453152027) + t * f(1.061405429)))))
-    e = exp2(f(-1.4426950408889634) * z * z)
-    erf_abs = 1.0 - poly * e
-    cdf = 0.5 * (1.0 + torch.copysign(erf_abs, x))
-    dgelu = cdf + x * f(0.3989422804014327) * e
-    gelu = 0.5 * x * (1.0 + torch.copysign(erf_abs, x))
-    return dquick, dgelu, quick, gelu
-
-
-_DELTAS = {}
-
-
-def _deltas():
-    """{'dquick', 'dgelu'} over every bf16 |x| <= 1e4, {'quick', 'gelu'} over every bf16 |x| <= 256"""
-    if not _DELTAS:
-        bits = torch.arange(-32768, 32768, dtype=torch.int32).to(torch.int16)
-        x = bits.view(torch.bfloat16).float()
-        x = x[torch.isfinite(x) & (x.abs() <= 1e4)]
-        exact = [f(x.double()) for f in (_dquick, _dgelu, _quick, _gelu)]
-        worst = [0.0] * 4
-        got = _kernel_formulas(x)
-        for i in range(4):
-            sel = slice(None) if i < 2 else (x.abs() <= 256)
-            worst[i] = float((got[i].double() - exact[i])[sel].abs().max())
-        _DELTAS.update(dquick=worst[0], dgelu=worst[1], quick=worst[2], gelu=worst[3])
-        print("deltas (fp32 formulas vs fp64): " + ", ".join(f"{k} {v:.2e}" for k, v in _DELTAS.items()))
-    return _DELTAS
-
-
 def _ratio(got, want, bound, what):
     got = got.double()
     assert bool(torch.isfinite(got).all()), f"{what}: non-finite values"
@@ -128,22 +71,7 @@ def _ratio(got, want, bound, what):
 
 
 def _operands(M, N, K, seed):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Mp = (M + 255) // 256 * 256
-    X = torch.zeros(Mp, K, dtype=torch.bfloat16, device="cuda")
-    X[:M] = torch.randn(M, K, generator=g, device="cuda").to(torch.bfloat16)
-    W = (torch.randn(N, K, generator=g, device="cuda") * K ** -0.5).to(torch.bfloat16)
-    bias = torch.randn(N, generator=g, device="cuda")
-    return g, Mp, X, W, bias
-
-
-def _sentinel(rows, ld):
-    return torch.full((rows, ld), SENT16, dtype=torch.int16, device="cuda")
-
-
-def _untouched(buf, M, N):
-    """rows >= M and the gap columns >= N of a sentinel-filled [rows, ld] bf16 buffer"""
-    return bool((buf[M:] == SENT16).all()) and bool((buf[:M, N:] == SENT16).all())
+    return operands(M, N, K, seed, "cuda")
 
 
 def _train(lib, variant, X, W, bias, M, epi, out, ldo, aux=None, scale=None, stats=None, fold_c=None, eps=1e-5, hb=None, ld_hb=0):
@@ -216,33 +144,20 @@ def test_derivative_epilogue_refuses_aliased_aux(lib):
 # ---- ACT2 ------------------------------------------------------------------------------------------------------------------------
 def _fold_case(M, N, K):
     """The LayerNorm-folded operands of tests/test_gemm_gpu.py::test_layernorm_folded_consumers"""
-    g = torch.Generator(device="cuda").manual_seed(5)
-    Mp = (M + 255) // 256 * 256
-    x = torch.randn(M, K, generator=g, device="cuda") * (0.5 + 3 * torch.rand(M, 1, generator=g, device="cuda")) \
-        + 2 * torch.randn(M, 1, generator=g, device="cuda")
-    x[:, 5] *= 20
-    X = torch.zeros(Mp, K, dtype=torch.bfloat16, device="cuda")
-    X[:M] = x.to(torch.bfloat16)
-    W32 = torch.randn(N, K, generator=g, device="cuda") * K ** -0.5
-    gam = 1 + 0.3 * torch.randn(K, generator=g, device="cuda")
-    beta = 0.2 * torch.randn(K, generator=g, device="cuda")
-    b = torch.randn(N, generator=g, device="cuda")
-    Wf = (W32 * gam).to(torch.bfloat16)
-    c = Wf.float().sum(1)
-    d = b + W32 @ beta
-    stats = torch.zeros(Mp, K // 64, 2, device="cuda")
-    xs = X[:M].double().view(M, -1, 64)
-    stats[:M] = torch.stack([xs.sum(-1), (xs * xs).sum(-1)], dim=-1).float()
-    xn = torch.nn.functional.layer_norm(X[:M].double(), (K,), gam.double(), beta.double(), 1e-5)
-    pre = xn @ W32.double().t() + b.double()
-    assert float(pre.abs().max()) < 256.0                                   # the range delta_act was measured over
-    return X, Wf, d, c, stats, pre
+    return fold_operands(M, N, K, "cuda")
+
+
+def _fold_first_output(X, Wf, d, c, stats, M):
+    """(want, bound) of the first output by tests/gemm_ref.py: the exact function of these operands, the fp32 partials included"""
+    eps = float(torch.tensor(1e-5, dtype=torch.float32))
+    return out_ref(8, Ops(X[:M], Wf, d, stats=stats[:M], fold_c=c, eps=eps))
 
 
 @pytest.mark.parametrize("N,K", SHAPES)
 def test_two_output_epilogues(lib, N, K):
     for M in MS:
         X, Wf, d, c, stats, pre = _fold_case(M, N, K)
+        want1, bound1 = _fold_first_output(X, Wf, d, c, stats, M)
         for ldo, ld_hb in ((N, N + 64), (N + 64, N + 128)):
             for variant in VARIANTS:
                 for epi in (ACT2_QUICK, ACT2_GELU):
@@ -260,6 +175,7 @@ def test_two_output_epilogues(lib, N, K):
                     print(f"{what}: first output max err {float(err.max()):.3e} rms {float(err.pow(2).mean().sqrt()):.3e}")
                     assert torch.allclose(got, pre.float(), atol=3e-2, rtol=2 ** -7), (what, float(err.max()))
                     assert float(err.pow(2).mean().sqrt()) < 6e-3, what
+                    _ratio(got, want1, bound1, what + " first output")
                     quick = epi == ACT2_QUICK
                     act = (_quick if quick else _gelu)(got.double())
                     bound = U * act.abs() + _deltas()["quick" if quick else "gelu"]
@@ -283,6 +199,7 @@ def test_smallest_m_the_dispatcher_sends_to_the_256x256_kernel(lib):
         c2 = count()
         assert c2[0] - c1[0] == 1 and c2[1] == c1[1], "10752 rows should stay on the 128x128 path"
     X, Wf, d, c, stats, pre = _fold_case(M, N, K)
+    want1, bound1 = _fold_first_output(X, Wf, d, c, stats, M)
     for epi in (ACT2_QUICK, ACT2_GELU):
         out, hb = _sentinel(X.shape[0], N + 64), _sentinel(X.shape[0], N + 128)
         c0 = count()
@@ -292,6 +209,7 @@ def test_smallest_m_the_dispatcher_sends_to_the_256x256_kernel(lib):
         got = out.view(torch.bfloat16)[:M, :N].float()
         assert torch.allclose(got, pre.float(), atol=3e-2, rtol=2 ** -7)
         assert float((got - pre.float()).pow(2).mean().sqrt()) < 6e-3
+        _ratio(got, want1, bound1, f"act2 epi {epi} dispatcher M {M} first output")
         quick = epi == ACT2_QUICK
         act = (_quick if quick else _gelu)(got.double())
         _ratio(hb.view(torch.bfloat16)[:M, :N], act, U * act.abs() + _deltas()["quick" if quick else "gelu"], f"act2 epi {epi} dispatcher M {M}")
