@@ -1,10 +1,9 @@
 // Streaming multi-head self-attention, forward and backward, for sequences past the 288 tokens that the LDS-resident kernels
 // (attention.hip, attention_bwd.hip) hold: head_dim 64, no mask, up to CH_ATTN_MAX_TOKENS tokens (a 32 x 32 patch grid).
 //
-// Same arithmetic (HF CLIPAttention eager path, softmax(q k^T / sqrt(d)) v), same MFMA forms, same LDS image -- rows of 128 B, the
-// 16-B chunk index XOR (row & 7) applied on the per-lane SOURCE address of the LDS-DMA, K fragments by ds_read_b128, V^T / K^T /
-// Q^T / dO^T through the hardware transpose read ds_read_b64_tr_b16 -- but the sequence is walked in blocks of BK = 64 rows that
-// are staged into a two-deep LDS ring: the block after the one being computed is in flight (global_load_lds_dwordx4) while the
+// Same arithmetic (HF CLIPAttention eager path, softmax(q k^T / sqrt(d)) v) and the same tile vocabulary as the resident kernels
+// (attention_tile.h: LDS image, lane geometry, staging, tile primitives) -- only the walk differs: the sequence is taken in blocks
+// of BK = 64 rows that are staged into a two-deep LDS ring: the block after the one being computed is in flight (LDS-DMA) while the
 // MFMAs run, and one barrier per block both publishes the landed block and frees the buffer the next one goes into.  41 KB of LDS
 // at 1,029 tokens for the backward, 32 KB for the forward, at any length.
 //
@@ -24,46 +23,22 @@
 //     walk 2: P = exp2(s c - lse), dS = 0.125 P (dP - D_q) as the bf16 B operand, dQ^T += K^T dS^T.
 //   Phase B, per chunk of 128 keys (a wave owns a 16-key tile, its K / V fragments from global memory), one walk over the query
 //     blocks (Q and dO staged): S and dP in the transposed lane layout, P and dS rebuilt from the statistics in LDS,
-//     dV^T += dO^T P, dK^T += Q^T dS by v_mfma_f32_16x16x16_bf16 -- the resident kernel's phase B, block by block.
-#include "ch_common.h"
+//     dV^T += dO^T P, dK^T += Q^T dS by the 16x16x16 bf16 MFMA -- the resident kernel's phase B, block by block.
+#include "attention_tile.h"
 #include "kernels.h"
 
 namespace {
 
-constexpr int HD = 64;
-constexpr int NW = 8;                        // waves per workgroup
 constexpr int BK = 64;                       // rows (keys, or queries in the backward's phase B) per staged block: one LDS-DMA pair per wave
 constexpr int BT = BK / 16;                  // 16-row tiles per block
 constexpr int BU = BK / 32;                  // 32-key units (one PV MFMA's reduction depth) per block
 constexpr int STAGE_BYTES = 2 * BK * 128;    // two matrices per stage
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// rows [r0, r0 + BK) of two row-major [*, 64] bf16 matrices -> buf (first matrix) and buf + BK * 128 (second); instruction i
-// covers rows 8i .. 8i + 7 (1 KB); rows past the sequence re-read the last row (finite data; masked / zero weight downstream)
+// rows [r0, r0 + BK) of two column blocks -> buf (first) and buf + BK * 128 (second)
 __device__ __forceinline__ void stage_block(const bf16_t *a, size_t lda, const bf16_t *b, size_t ldb, int r0, int ntok, char *buf, int wid,
                                             int lane) {
-    const int lrow = lane >> 3;
-    const int src_chunk = (lane & 7) ^ lrow;
-    for (int i = wid; i < BK / 8; i += NW) {
-        int row = r0 + i * 8 + lrow;
-        row = row < ntok ? row : ntok - 1;
-        __builtin_amdgcn_global_load_lds((gbl_void_t *)(a + (size_t)row * lda + src_chunk * 8), (lds_void_t *)(buf + i * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gbl_void_t *)(b + (size_t)row * ldb + src_chunk * 8), (lds_void_t *)(buf + BK * 128 + i * 1024), 16, 0, 0);
-    }
+    stage_rows(a, lda, 0, b, ldb, 0, r0, BK, ntok, buf, buf + BK * 128, wid, lane);
 }
-
-union VF {
-    bf16x8 v;
-    v4s h[2];
-};
-union PF {
-    bf16x8 v;
-    uint32_t u[4];
-};
 
 // TAP: write the concept-token attention rows; COMPACT: only CLS and the `ncon` concept tokens are queries, out is [B * (1 + ncon), D]
 template <bool TAP, bool COMPACT>
@@ -89,24 +64,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_stream_kernel(const bf16
     // query slot j of this image -> (token row, valid), as attention.hip
     const int qslot = qt * 16 + fr;
     bool qvalid;
-    int q;
-    if constexpr (COMPACT) {
-        qvalid = qslot < nqc;
-        q = !qvalid ? ntok - 1 : (qslot == 0 ? 0 : ntok - ncon + qslot - 1);
-    } else {
-        qvalid = qslot < ntok;
-        q = qvalid ? qslot : ntok - 1;
-    }
-    const bf16x8 qf0 = *(const bf16x8 *)(base + (size_t)q * ld + fq * 8);
-    const bf16x8 qf1 = *(const bf16x8 *)(base + (size_t)q * ld + fq * 8 + 32);
-
-    // transpose-read addressing (attention.hip): lane 4*tq + tp of group fq supplies row 4*fq + tq of a 16-row tile
-    const int tq = fr >> 2, tp = fr & 3;
-    const int trow7 = ((fq & 1) << 2) | tq;
-    int voff[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) voff[dt] = (fq * 4 + tq) * 128 + (((dt * 2 + (tp >> 1)) ^ trow7) << 4) + (tp & 1) * 8;
-    const int koff0 = fr * 128 + ((fq ^ (fr & 7)) << 4), koff1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);
+    const int q = query_slot<COMPACT>(qslot, ntok, ncon, nqc, qvalid);
+    const Frag2 qf = ld_frag(base, ld, q, fq);
+    const Lane g(lane);
 
     float m = -1e30f, l = 0.f;   // running maximum (raw score units) and this lane's share of the running sum
     f32x4 o[4];
@@ -121,27 +81,17 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_stream_kernel(const bf16
         const char *Ks = smem + (j & 1) * STAGE_BYTES, *Vs = Ks + BK * 128;
         f32x4 st[BT];   // S^T[key = j*BK + t*16 + 4*fq + r][query fr]
 #pragma unroll
-        for (int t = 0; t < BT; ++t) {
-            const bf16x8 k0 = *(const bf16x8 *)(Ks + t * 2048 + koff0), k1 = *(const bf16x8 *)(Ks + t * 2048 + koff1);
-            f32x4 a = {0.f, 0.f, 0.f, 0.f};
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf0, a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf1, a, 0, 0, 0);
-            st[t] = a;
-        }
+        for (int t = 0; t < BT; ++t) st[t] = tile_mma(Ks, t, g.off0, g.off1, qf);
         if (j * BK + BK > ntok) {   // only the last block has keys past the sequence (wave-uniform test)
 #pragma unroll
-            for (int t = 0; t < BT; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (j * BK + t * 16 + fq * 4 + r >= ntok) st[t][r] = -1e30f;
+            for (int t = 0; t < BT; ++t) st[t] = mask_tail(st[t], j * BK + t * 16, ntok, fq);
         }
         float bm = -1e30f;
 #pragma unroll
         for (int t = 0; t < BT; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) bm = fmaxf(bm, st[t][r]);
-        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+        bm = quad_max(bm);
         const float mn = fmaxf(m, bm);   // every block holds at least one real key: finite from the first block on
         const float alpha = __builtin_amdgcn_exp2f((m - mn) * scale_log2e);   // first block: exp2(-huge) = 0 on O = 0, l = 0
         const float mns = mn * scale_log2e;
@@ -162,23 +112,12 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_stream_kernel(const bf16
 #pragma unroll
         for (int u = 0; u < BU; ++u) {
             VF vf[4];
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                vf[dt].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Vs + u * 4096 + voff[dt]));
-                vf[dt].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Vs + u * 4096 + 2048 + voff[dt]));
-            }
-            PF pf;
-            pf.u[0] = pack_bf16x2(st[2 * u][0], st[2 * u][1]);
-            pf.u[1] = pack_bf16x2(st[2 * u][2], st[2 * u][3]);
-            pf.u[2] = pack_bf16x2(st[2 * u + 1][0], st[2 * u + 1][1]);
-            pf.u[3] = pack_bf16x2(st[2 * u + 1][2], st[2 * u + 1][3]);
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[dt].v, pf.v, o[dt], 0, 0, 0);
+            tr_unit(Vs, u, g.toff, vf);
+            unit_mma(o, vf, pack8(st[2 * u], st[2 * u + 1]));
         }
     }
     if (!active) return;   // no barrier below
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
+    l = quad_sum(l);
     const float inv = 1.0f / l;
     if constexpr (TAP) {
         // second pass for the tiles that hold concept tokens: their rows over the patch tokens with the final statistics
@@ -190,12 +129,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_stream_kernel(const bf16
             const float ms = m * scale_log2e;
             const int KT = (ntok + 15) >> 4;
             for (int kt = 0; kt < KT; ++kt) {
-                const int kr = min(kt * 16 + fr, ntok - 1);
-                const bf16x8 k0 = *(const bf16x8 *)(base + D + (size_t)kr * ld + fq * 8);
-                const bf16x8 k1 = *(const bf16x8 *)(base + D + (size_t)kr * ld + fq * 8 + 32);
-                f32x4 a = {0.f, 0.f, 0.f, 0.f};
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf0, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf1, a, 0, 0, 0);
+                const f32x4 a = mma2(row_frag(base + D, ld, kt * 16 + fr, ntok, fq), qf);
                 if (crow) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -206,16 +140,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_stream_kernel(const bf16
             }
         }
     }
-    if (qvalid) {
-        bf16_t *op = out + (COMPACT ? (size_t)b * nqc + qslot : (size_t)b * ntok + q) * D + h * HD + fq * 4;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            uint2 w;
-            w.x = pack_bf16x2(o[dt][0] * inv, o[dt][1] * inv);
-            w.y = pack_bf16x2(o[dt][2] * inv, o[dt][3] * inv);
-            *(uint2 *)(op + dt * 16) = w;
-        }
-    }
+    if (qvalid) store_o(out + (COMPACT ? (size_t)b * nqc + qslot : (size_t)b * ntok + q) * D + h * HD + fq * 4, o, inv);
 }
 
 // EXT: dpext [B, heads, ncon, ntok - ncon - 1] fp32, the cotangent of the tapped probability rows, is added to dP on those
@@ -246,12 +171,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
     const int fr = lane & 15, fq = lane >> 4;
     const int npatch = ntok - ncon - 1, q_con0 = ntok - ncon;   // EXT: keys 1 .. npatch, queries q_con0 .. ntok - 1
     const float *ext = EXT ? dpext + (size_t)blockIdx.x * ncon * npatch : nullptr;
-    const int off0 = fr * 128 + ((fq ^ (fr & 7)) << 4), off1 = fr * 128 + (((4 + fq) ^ (fr & 7)) << 4);
-    const int tq = fr >> 2, tp = fr & 3;
-    const int trow7 = ((fq & 1) << 2) | tq;
-    int toff[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) toff[dt] = (fq * 4 + tq) * 128 + (((dt * 2 + (tp >> 1)) ^ trow7) << 4) + (tp & 1) * 8;
+    const Lane g(lane);
+    const int off0 = g.off0, off1 = g.off1;
+    const int (&toff)[4] = g.toff;
     // fragments of one 16-row tile straight from global memory (rows past the sequence re-read the last row)
     auto row_frag = [&](const bf16_t *mat, size_t ldm, int tile, bf16x8 &f0, bf16x8 &f1) {
         const int r = min(tile * 16 + fr, ntok - 1);
@@ -304,13 +226,9 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
             f32x4 st[BT], dp[BT];   // S^T and dP^T [key = j*BK + t*16 + 4*fq + r][query fr]
 #pragma unroll
             for (int t = 0; t < BT; ++t) {
-                const bf16x8 k0 = *(const bf16x8 *)(Ks + t * 2048 + off0), k1 = *(const bf16x8 *)(Ks + t * 2048 + off1);
-                const bf16x8 v0 = *(const bf16x8 *)(Vs + t * 2048 + off0), v1 = *(const bf16x8 *)(Vs + t * 2048 + off1);
-                f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf0, a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf1, a, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, gf0, c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, gf1, c, 0, 0, 0);
+                const Frag2 kt2 = tile_frag(Ks, t, off0, off1), vt2 = tile_frag(Vs, t, off0, off1);
+                const f32x4 a = mma2(kt2, Frag2{qf0, qf1});
+                f32x4 c = mma2(vt2, Frag2{gf0, gf1});
                 if constexpr (EXT) {
                     if (ext_row) {
 #pragma unroll
@@ -336,8 +254,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
                 for (int t = 0; t < BT; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) bm = fmaxf(bm, st[t][r]);
-                bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
-                bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+                bm = quad_max(bm);
                 const float mn = fmaxf(m, bm);
                 const float alpha = __builtin_amdgcn_exp2f((m - mn) * scale_log2e);
                 const float mns = mn * scale_log2e;
@@ -354,10 +271,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
                 l = l * alpha + bs;
                 pd = pd * alpha + bp;
                 if (j == NB - 1) {
-                    l += __shfl_xor(l, 16, 64);
-                    l += __shfl_xor(l, 32, 64);
-                    pd += __shfl_xor(pd, 16, 64);
-                    pd += __shfl_xor(pd, 32, 64);
+                    l = quad_sum(l);
+                    pd = quad_sum(pd);
                     // lse = m c + log2(l) so that P = exp2(s c - lse) needs no multiply by 1/l; D_q / 8 for phase B (attention_bwd.hip)
                     lse = m * scale_log2e + __builtin_amdgcn_logf(l);
                     Dq = pd / l;
@@ -382,11 +297,11 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
                     VF kf[4];
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) {
-                        kf[dt].h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Ks + u * 4096 + toff[dt]));
-                        kf[dt].h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Ks + u * 4096 + 2048 + toff[dt]));
+                        kf[dt].h[0] = tr_read(Ks + u * 4096 + toff[dt]);
+                        kf[dt].h[1] = tr_read(Ks + u * 4096 + 2048 + toff[dt]);
                     }
 #pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[dt].v, pf.v, o[dt], 0, 0, 0);
+                    for (int dt = 0; dt < 4; ++dt) o[dt] = mma_acc(kf[dt], pf, o[dt]);
                 }
                 if (j == NB - 1 && qvalid) {
                     bf16_t *op = obase + (size_t)q * ld + fq * 4;   // dQ[q][dt*16 + 4*fq + r]
@@ -440,6 +355,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
 #pragma unroll
             for (int t = 0; t < BT; ++t) {
                 const int qt = cj * BT + t;
+                // bwd_key_tile_step of attention_tile.h (the resident kernel's call), written out: through the helper the EXT instance's
+                // spill deepens from 24 to 28 bytes per lane (profiles/attention_tile_registers.txt)
                 if (qt < QT) {   // wave-uniform: tiles past the sequence carry no weight
                     const bf16x8 qf0 = *(const bf16x8 *)(Qs + t * 2048 + off0), qf1 = *(const bf16x8 *)(Qs + t * 2048 + off1);
                     const bf16x8 gf0 = *(const bf16x8 *)(Gs + t * 2048 + off0), gf1 = *(const bf16x8 *)(Gs + t * 2048 + off1);
@@ -476,8 +393,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
                     sb.u[1] = pack_bf16x2(ds[2], ds[3]);
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) {
-                        const v4s gt = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Gs + t * 2048 + toff[dt]));  // dO^T[d][q]
-                        const v4s qT = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s *)(Qs + t * 2048 + toff[dt]));  // Q^T[d][q]
+                        const v4s gt = tr_read(Gs + t * 2048 + toff[dt]);  // dO^T[d][q]
+                        const v4s qT = tr_read(Qs + t * 2048 + toff[dt]);  // Q^T[d][q]
                         dvt[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(gt, pb.v, dvt[dt], 0, 0, 0);
                         dkt[dt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(qT, sb.v, dkt[dt], 0, 0, 0);
                     }
@@ -503,9 +420,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attention_bwd_stream_kernel(const 
 template <bool TAP, bool COMPACT>
 int launch_fwd(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *out, float *cattn, int ncon, int rev, hipStream_t s) {
     const int QT = COMPACT ? (1 + ncon + 15) / 16 : (ntok + 15) / 16;
-    const float scale_log2e = 0.125f * 1.4426950408889634f;  // head_dim^-0.5 * log2(e), head_dim = 64
     CH_LAUNCH((attention_stream_kernel<TAP, COMPACT>), dim3(B * heads, (QT + NW - 1) / NW), dim3(NW * 64), (size_t)2 * STAGE_BYTES, s, qkv, ntok,
-              heads, scale_log2e, out, cattn, ncon, rev);
+              heads, ATTN_SCALE_LOG2E, out, cattn, ncon, rev);
     CH_LAUNCH_CHECK();
     return 0;
 }
@@ -525,11 +441,9 @@ int ch_attention_stream(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *o
     CH_REQUIRE((int64_t)B * heads <= 0x7fffffff, "attention: batch too large");
     CH_REQUIRE(!cattn || (ncon >= 1 && ncon < ntok - 1), "attention: the concept-attention tap needs 1 <= ncon < ntok - 1");
     const int r = rev ? 1 : 0;
-    if (compact)
-        return cattn ? launch_fwd<true, true>(qkv, B, ntok, heads, out, cattn, ncon, r, s)
-                     : launch_fwd<false, true>(qkv, B, ntok, heads, out, cattn, ncon, r, s);
-    return cattn ? launch_fwd<true, false>(qkv, B, ntok, heads, out, cattn, ncon, r, s)
-                 : launch_fwd<false, false>(qkv, B, ntok, heads, out, cattn, ncon, r, s);
+    return ch_attn_pick_mode(cattn != nullptr, compact, [&](auto tap, auto cmp) {
+        return launch_fwd<decltype(tap)::value, decltype(cmp)::value>(qkv, B, ntok, heads, out, cattn, ncon, r, s);
+    });
 }
 
 int ch_attention_bwd_stream(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, bf16_t *dqkv, hipStream_t s, const float *dpext,
@@ -537,12 +451,11 @@ int ch_attention_bwd_stream(const bf16_t *qkv, const bf16_t *dO, int B, int ntok
     CH_REQUIRE(ntok <= CH_ATTN_MAX_TOKENS, "attention backward: more than 1089 tokens per image (a 32 x 32 patch grid) is not supported");
     const int NB = (ntok + BK - 1) / BK;
     const size_t lds = (size_t)2 * STAGE_BYTES + (size_t)NB * BK * sizeof(f32x2);   // <= 41.5 KB: under the 64 KB a launch gets unasked
-    const float scale_log2e = 0.125f * 1.4426950408889634f;
     if (dpext)
-        hipLaunchKernelGGL((attention_bwd_stream_kernel<true>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, dO, ntok, heads, scale_log2e, dqkv,
+        hipLaunchKernelGGL((attention_bwd_stream_kernel<true>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, dO, ntok, heads, ATTN_SCALE_LOG2E, dqkv,
                            dpext, ncon);
     else
-        hipLaunchKernelGGL((attention_bwd_stream_kernel<false>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, dO, ntok, heads, scale_log2e, dqkv,
+        hipLaunchKernelGGL((attention_bwd_stream_kernel<false>), dim3(B * heads), dim3(NW * 64), lds, s, qkv, dO, ntok, heads, ATTN_SCALE_LOG2E, dqkv,
                            (const float *)nullptr, 0);
     CH_LAUNCH_CHECK();
     return 0;

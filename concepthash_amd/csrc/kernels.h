@@ -1,5 +1,6 @@
 // Internal launcher declarations shared by the .hip translation units of libconcepthash_hip.
 #pragma once
+#include <type_traits>
 #include "ch_common.h"
 #include "layer_types.h"   // GemmEpilogue (EPI_*), AdapterW, LayerW
 
@@ -161,6 +162,28 @@ int ch_attention_stream(const bf16_t *qkv, int B, int ntok, int heads, bf16_t *o
 int ch_attention_bwd_stream(const bf16_t *qkv, const bf16_t *dO, int B, int ntok, int heads, bf16_t *dqkv, hipStream_t s, const float *dpext,
                             int ncon);
 void ch_attention_count_launch(int which);   // 0 forward resident, 1 forward streaming, 2 backward resident, 3 backward streaming
+// runtime -> template arguments of the attention launchers: f(std::integral_constant<int, KB>) for the resident kernels'
+// 1 <= KB <= 9 blocks of 32 keys (-1 outside that range), f(tap, compact) as std::bool_constant for the forward kernels' mode
+template <typename F>
+int ch_attn_dispatch_kb(int KB, F &&f) {
+    switch (KB) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 9: return f(std::integral_constant<int, 9>{});
+    }
+    return -1;
+}
+template <typename F>
+int ch_attn_pick_mode(bool tap, bool compact, F &&f) {
+    if (compact) return tap ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+    return tap ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+}
 
 // ---- head.hip ------------------------------------------------------------------------------------------------
 struct HeadParams {
