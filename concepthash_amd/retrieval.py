@@ -1654,3 +1654,147 @@ def evaluate_reranked(q_codes, g_codes, q_labels: torch.Tensor, g_labels: torch.
             shares.append((found / (want >= 0).sum(1).clamp_min(1).double()).mean())
         out["agreement"] = dict(zip(deep, torch.stack(shares).tolist()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# learned rotation: iterative quantisation of the real-valued codes ("learned rotation"; csrc/itq.hip)
+# ---------------------------------------------------------------------------------------------------------------
+ITQ_MAX_DIM = 256
+ITQ_MAX_SEG = 4096
+
+
+def check_blocks(n: int, blocks) -> int:
+    """`blocks` of a block-diagonal rotation of n-dimensional codes: an int >= 1 that divides n (ValueError otherwise) -> block size s"""
+    if isinstance(blocks, bool) or not isinstance(blocks, int):
+        raise ValueError(f"blocks must be an int, got {blocks!r}")
+    if blocks < 1 or n % blocks:
+        raise ValueError(f"blocks = {blocks} does not divide the {n} dimensions of the codes (a rotation has n / blocks columns per block)")
+    return n // blocks
+
+
+def compact_rotation(R: torch.Tensor, blocks: int) -> torch.Tensor:
+    """[n, n] block-diagonal -> [n, s], s = n / blocks: row b s + l holds R_b[l, :] (the form the kernels take).  An entry outside the
+    blocks that is not zero is a ValueError."""
+    n = R.shape[0]
+    s = check_blocks(n, blocks)
+    if tuple(R.shape) != (n, n):
+        raise ValueError(f"a full rotation must be square, got {tuple(R.shape)}")
+    diag = torch.arange(blocks, device=R.device)
+    out = R.reshape(blocks, s, blocks, s)[diag, :, diag, :].reshape(n, s).contiguous()      # [blocks, s, s]
+    if not torch.equal(full_rotation(out, blocks), R):
+        raise ValueError(f"R is not block-diagonal under blocks = {blocks}: an entry outside the blocks is not zero")
+    return out
+
+
+def full_rotation(Rc: torch.Tensor, blocks: int) -> torch.Tensor:
+    """[n, s] compact -> [n, n] block-diagonal"""
+    n, s = Rc.shape
+    return torch.block_diag(*Rc.reshape(blocks, s, s).unbind(0)).contiguous()
+
+
+def _check_itq(codes, R, blocks):
+    """The argument checks of itq_step / rotate_codes, all in front of the first launch -> (codes, compact R, n, s)"""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.float32:
+        raise TypeError(f"codes must be a float32 tensor, got {getattr(codes, 'dtype', type(codes))}")
+    if codes.dim() != 2:
+        raise ValueError(f"codes must be 2-D [rows, n] real-valued codes, got {tuple(codes.shape)}")
+    n = codes.shape[1]
+    if not 1 <= n <= ITQ_MAX_DIM:
+        raise ValueError(f"codes have {n} dimensions; a learned rotation takes 1 .. {ITQ_MAX_DIM}")
+    s = check_blocks(n, blocks)
+    if R is not None:
+        if not isinstance(R, torch.Tensor) or R.dtype != torch.float32:
+            raise TypeError(f"R must be a float32 tensor, got {getattr(R, 'dtype', type(R))}")
+        if R.dim() != 2 or tuple(R.shape) not in ((n, n), (n, s)):
+            raise ValueError(f"R must be [{n}, {n}] (block-diagonal) or [{n}, {s}] (compact) for blocks = {blocks}, got {tuple(R.shape)}")
+        if R.device != codes.device:
+            raise ValueError("R and the codes must be on the same device")
+        if not bool(torch.isfinite(R).all()):
+            raise ValueError("R holds NaN or infinite entries")
+        if tuple(R.shape) != (n, s):
+            R = compact_rotation(R, blocks)
+        R = R.contiguous()
+    if codes.numel() and not bool(torch.isfinite(codes).all()):
+        raise ValueError("codes hold NaN or infinite entries: a rotation is fitted on finite codes")
+    return codes.contiguous(), R, n, s
+
+
+def itq_step(codes: torch.Tensor, R: torch.Tensor, blocks: int, seg_rows: Optional[int] = None, stream=None):
+    """One pass of iterative quantisation under the rotation R ([n, n] block-diagonal or [n, n / blocks] compact), the kernels' own
+    fmaf chain and sign rule -> (M [n, s] float64: row j = sum_i sign(z_ij) codes[i, block of j], l1 = sum |z|, qerr = mean_i (1 -
+    |z_i|_1 / (sqrt(n) |z_i|_2)), a zero row counting 1).  seg_rows (1 .. 4096; tests): rows whose M is accumulated in fp32 before the
+    fp64 sum over segments.  No rows: zeros, l1 = 0, qerr = 0."""
+    codes, Rc, n, s = _check_itq(codes, R, blocks)
+    if R is None:
+        raise TypeError("R must be a float32 tensor, got None")
+    seg = 0 if seg_rows is None else int(seg_rows)
+    if not 0 <= seg <= ITQ_MAX_SEG or (seg_rows is not None and seg < 1):
+        raise ValueError(f"seg_rows must be in [1, {ITQ_MAX_SEG}], got {seg_rows!r}")
+    return _itq_step(codes, Rc, n, s, seg, stream)
+
+
+def _itq_step(codes, Rc, n: int, s: int, seg: int, stream=None):
+    """`itq_step` behind its argument checks"""
+    guard = _dev_guard(codes)
+    lib = _lib.load()
+    rows = codes.shape[0]
+    M = torch.zeros(n, s, dtype=torch.float64, device=codes.device)
+    if rows == 0:
+        return M, 0.0, 0.0
+    stats = torch.zeros(2, dtype=torch.float64, device=codes.device)
+    wsb = int(lib.ch_itq_step_workspace(rows, n, s, seg))
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=codes.device)
+    with guard:
+        _lib.check(lib.ch_itq_step(_lib.ptr(codes), rows, n, _lib.ptr(Rc), s, seg, _lib.ptr(M), _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 8,
+                                   _lib.stream_ptr(stream)), "ch_itq_step")
+    l1, cs = stats.tolist()
+    return M, l1, 1.0 - cs / rows
+
+
+def rotate_codes(codes: torch.Tensor, R: torch.Tensor, blocks: int, stream=None) -> torch.Tensor:
+    """[rows, n] fp32 -> codes R, entry by entry the fmaf chain of `itq_step` (a row rotates to the same bits alone or in a batch)"""
+    codes, Rc, n, s = _check_itq(codes, R, blocks)
+    if R is None:
+        raise TypeError("R must be a float32 tensor, got None")
+    guard = _dev_guard(codes)
+    lib = _lib.load()
+    out = torch.empty_like(codes)
+    if codes.shape[0]:
+        with guard:
+            _lib.check(lib.ch_itq_rotate(_lib.ptr(codes), codes.shape[0], n, _lib.ptr(Rc), s, _lib.ptr(out), _lib.stream_ptr(stream)),
+                       "ch_itq_rotate")
+    return out
+
+
+def procrustes_update(M: torch.Tensor, blocks: int) -> torch.Tensor:
+    """M [n, s] float64 (`itq_step`) -> the next rotation, compact [n, s] float64: per block M_b = U S W^T (fp64 SVD on the host) and
+    R_b = W U^T, the maximiser of tr(R_b M_b) over orthogonal matrices -- the orthogonal Procrustes solution."""
+    n, s = M.shape
+    U, _, Wh = torch.linalg.svd(M.detach().to("cpu", torch.float64).reshape(blocks, s, s))
+    return (U @ Wh).transpose(1, 2).reshape(n, s)
+
+
+def fit_rotation(codes: torch.Tensor, blocks: int, iters: int = 50, tol: float = 1e-6) -> dict:
+    """Fit a block-diagonal rotation to `codes` [G, n] fp32 by iterative quantisation from R_0 = I: pass t scores R_t (`itq_step`) and,
+    unless it is the last, builds R_{t+1} (`procrustes_update`); at most `iters` updates, and none after a pass whose gain
+    l1_t - l1_{t-1} is <= tol l1_{t-1}.  -> dict(R [n, n] fp32 block-diagonal: the R_t with the largest l1, the earliest of equals;
+    blocks; iters_run: that t; l1: [l1_0, l1_1, ...] of every pass; qerr_before: qerr of R_0; qerr_after: of the returned R)."""
+    codes, _, n, s = _check_itq(codes, None, blocks)
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"iters must be an int >= 0, got {iters!r}")
+    if not (isinstance(tol, (int, float)) and tol >= 0):
+        raise ValueError(f"tol must be a number >= 0, got {tol!r}")
+    _dev_guard(codes)
+    R = torch.eye(s, dtype=torch.float32).repeat(blocks, 1)
+    l1s, best, before = [], None, None
+    for t in range(iters + 1):
+        Rd = R.to(codes.device).contiguous()
+        M, l1, qerr = _itq_step(codes, Rd, n, s, 0)              # the codes were checked above, once
+        l1s.append(l1)
+        before = qerr if t == 0 else before
+        if best is None or l1 > best[0]:
+            best = (l1, Rd, t, qerr)
+        if t == iters or (t >= 1 and l1 - l1s[-2] <= tol * l1s[-2]):
+            break
+        R = procrustes_update(M, blocks).to(torch.float32)
+    return dict(R=full_rotation(best[1], blocks), blocks=blocks, iters_run=best[2], l1=l1s, qerr_before=before, qerr_after=best[3])

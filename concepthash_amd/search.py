@@ -43,12 +43,16 @@ class GalleryIndex:
     real: None, or the plane [G, nbit] fp32 of the real-valued codes that were packed (after the mean shift, where there is one) -- what
     rank="cosine" | "euclidean" | "dot" need; optional in the same way.
     groups: None, or the plane [G] int32 (values >= 0, checked here, once) of the group every row belongs to -- its album, video or
-    source -- what `search(query_group=..., group_by="groups")` filters by; optional in the same way."""
+    source -- what `search(query_group=..., group_by="groups")` filters by; optional in the same way.
+    rotation: None, or the learned rotation [nbit, nbit] fp32 (`fit_rotation`; DESIGN.md section 2.0, "learned rotation"), block-diagonal
+    with `rotation_blocks` blocks, that the real codes went through before they were packed: every query goes through it too.
+    rotation_info: what the fit reported ({"method", "blocks", "iters_run", "qerr_before", "qerr_after"}), kept with the rotation."""
 
     def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
                  paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
                  transform: Optional[dict] = None, fingerprint: Optional[dict] = None, mask: Optional[torch.Tensor] = None,
-                 margin: Optional[float] = None, real: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None):
+                 margin: Optional[float] = None, real: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None,
+                 rotation: Optional[torch.Tensor] = None, rotation_blocks: Optional[int] = None, rotation_info: Optional[dict] = None):
         nbit, ncontext = int(nbit), int(ncontext)
         if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
             raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
@@ -80,6 +84,16 @@ class GalleryIndex:
             if G and int(groups.min()) < 0:
                 raise ValueError(f"groups must be >= 0 (a query's -1 means no group filter), got {int(groups.min())}")
             groups = groups.contiguous()
+        if rotation is not None:
+            if rotation.dtype != torch.float32 or tuple(rotation.shape) != (nbit, nbit) or rotation.device != codes.device:
+                raise ValueError(f"rotation must be the float32 matrix [{nbit}, {nbit}] on the codes' device, got {rotation.dtype} "
+                                 f"{tuple(rotation.shape)} on {rotation.device}")
+            rt.check_blocks(nbit, rotation_blocks)
+            rotation = rotation.contiguous()
+        elif rotation_blocks is not None or rotation_info is not None:
+            raise ValueError("rotation_blocks / rotation_info without a rotation")
+        self.rotation, self.rotation_blocks = rotation, (int(rotation_blocks) if rotation is not None else None)
+        self.rotation_info = dict(rotation_info or {}) if rotation is not None else None
         self.real, self.groups = real, groups
         self.codes, self.nbit, self.ncontext = codes.contiguous(), nbit, ncontext
         self.mask, self.margin = (mask.contiguous() if mask is not None else None), margin
@@ -100,7 +114,8 @@ class GalleryIndex:
     def to(self, device) -> "GalleryIndex":
         mv = lambda t: t.to(device) if t is not None else None
         return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
-                            self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real), mv(self.groups))
+                            self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real), mv(self.groups),
+                            mv(self.rotation), self.rotation_blocks, self.rotation_info)
 
     # ---- file --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -117,6 +132,8 @@ class GalleryIndex:
             d.update(real=cpu(self.real))
         if self.groups is not None:
             d.update(groups=cpu(self.groups))
+        if self.rotation is not None:
+            d.update(rotation=cpu(self.rotation), rotation_blocks=self.rotation_blocks, rotation_info=self.rotation_info)
         torch.save(d, tmp)
         os.replace(tmp, path)
 
@@ -139,9 +156,36 @@ class GalleryIndex:
         if not isinstance(d, dict) or d.get("format") != FORMAT:
             raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
         index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
-                    d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"), d.get("groups"))
+                    d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"), d.get("groups"), d.get("rotation"),
+                    d.get("rotation_blocks"), d.get("rotation_info"))
         index.check(fingerprint, nbit, source=path)
         return index
+
+    # ---- learned rotation --------------------------------------------------------------------------------------------------------
+    @property
+    def keeps_concepts(self) -> bool:
+        """whether `concepts=`, concept_dist and the per-concept evaluation still mean the concepts: no rotation, or one whose blocks
+        lie inside the sub-codes"""
+        return self.rotation is None or self.rotation_blocks % self.ncontext == 0
+
+    def fit_rotation(self, blocks: Optional[int] = None, iters: int = 50) -> "GalleryIndex":
+        """The index under a rotation fitted to its real plane (`retrieval.fit_rotation`; blocks=None: one block per concept): its real
+        plane holds the rotated codes, its packed codes their signs, its mask plane -- where the index has one -- is rebuilt from them
+        under the same margin, and every query is rotated in `search`.  An index without the real plane, or one that is rotated
+        already, raises ValueError."""
+        if self.real is None:
+            raise ValueError("fit_rotation needs the index's real plane, which this index was built without: rebuild it "
+                             "(exp=search rotate=itq rebuilds it by itself; rebuild_index=true forces it)")
+        if self.rotation is not None:
+            raise ValueError("this index is rotated already: fit a rotation on the index as it was built")
+        blocks = self.ncontext if blocks is None else blocks
+        rt.check_blocks(self.nbit, blocks)
+        fit = rt.fit_rotation(self.real, blocks, iters)
+        real = rt.rotate_codes(self.real, fit["R"], blocks)
+        info = dict(method="itq", blocks=blocks, iters_run=fit["iters_run"], qerr_before=fit["qerr_before"], qerr_after=fit["qerr_after"])
+        return GalleryIndex(rt.pack_sign(real), self.nbit, self.ncontext, self.labels, self.paths, self.data_root, self.mean, self.transform,
+                            self.fingerprint, rt.confidence_mask(real, self.margin) if self.mask is not None else None, self.margin, real,
+                            self.groups, fit["R"], blocks, info)
 
     # ---- search ------------------------------------------------------------------------------------------------------------------
     def resolve(self, rel: Optional[str]) -> Optional[str]:
@@ -162,7 +206,8 @@ class GalleryIndex:
                labels_out: Optional[Sequence[int]] = None, query_group: Optional[torch.Tensor] = None, group_mode: str = "only",
                group_by: str = "groups") -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here;
-        mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0).
+        mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0;
+        a rotated index then rotates them, shifted or not, before anything else reads them).
         Ranks the database by ascending (distance, index) and returns
           idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
           concept_dist [Qn, k, ncontext] int32: the UNMASKED distance inside every concept's sub-code (they sum to the whole-code
@@ -209,6 +254,9 @@ class GalleryIndex:
         short list explains itself."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+        if concepts is not None and not self.keeps_concepts:
+            raise ValueError(f"concepts with a rotation of {self.rotation_blocks} blocks is not built: a block would straddle the sub-codes "
+                             f"of the {self.ncontext} concepts (fit it with blocks a multiple of {self.ncontext})")
         if shortlist is not None and rank not in rt.DENSE_METRICS:
             raise ValueError(f"shortlist with rank='{rank}' is not built: a shortlist is reranked by a dense rank, one of {rt.DENSE_METRICS}")
         filtered = any(v is not None for v in (rows, labels_in, labels_out, query_group))
@@ -311,6 +359,8 @@ class GalleryIndex:
         if self.mean is not None and mean_shift:
             codes = codes - self.mean[None, :]
         checked = None if refuse is None else refuse(codes.shape[0])
+        if self.rotation is not None:
+            codes = rt.rotate_codes(codes.contiguous(), self.rotation, self.rotation_blocks)
         return codes, rt.pack_sign(codes), checked
 
     # the list of one rank at k <= TOPK_MAX; flt: None, or the arguments of `_filter`

@@ -12,13 +12,14 @@ import experiments.test_hashing as base
 import utils.hashing
 
 
-def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str, keys, on_call=None, finish=None) -> dict:
+def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str, keys, on_call=None, finish=None, recode=None) -> dict:
     """`run()` -- the main() of the class that the calling class extends -- with every whole-code `calculate_mAP` call of the evaluator
     followed by the same call with the keyword arguments `again` (rank=..., and what goes with it) in place of those named in `drop`,
     on the codes the evaluator hands over.  The triple of a repeated call is printed under `label` (mAP) and `short` (P@k, R@k) and stored
     under `keys` + the postfix of the call's own "mAP" key; `on_call(db_codes, test_codes)` sees every repeated call's codes;
     `finish(res, calls)`, calls = [(the call's own mAP, postfix, its triple under the rank)], adds the class's extra results before
-    `history.json` is written again.  `who` (the config key) opens the error messages.
+    `history.json` is written again.  `who` (the config key) opens the error messages.  `recode(db_codes, db_labels, test_codes,
+    test_labels) -> (db_codes, test_codes)`, where given, makes the codes of the repeated call from the evaluator's (the learned rotation).
     Passed through, scored once: a call under another rank (an evaluator further out repeating its own), the concepts' column slices
     -- under concept_eval the metric is reached Q times on them in front of the call on the whole code (experiments/concept_eval.py) --
     and the text evaluator's call on its prompts."""
@@ -43,7 +44,8 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
         slices.clear()
         # the bracket and the lookup the Hamming call left behind are read by the evaluators around this one after it returns
         left = utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected
-        other = metric(db_codes, db_labels, test_codes, test_labels, R, **again, **{key: v for key, v in k.items() if key not in drop})
+        db_again, test_again = (db_codes, test_codes) if recode is None else recode(db_codes, db_labels, test_codes, test_labels)
+        other = metric(db_again, db_labels, test_again, test_labels, R, **again, **{key: v for key, v in k.items() if key not in drop})
         utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected = left
         calls.append((out[0], other))
         if on_call is not None:

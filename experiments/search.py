@@ -4,6 +4,11 @@
         [query_margin=0.0] [rank=hamming|asymmetric|ternary|cosine|euclidean|dot] [shortlist=1000] [weight_bits=8] [index=<file>] [rebuild_index=false] [save_attention=false]
         [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
         [only_classes=[3,"Painted Bunting"]] [exclude_classes=[...]] [exclude_self=true] [same_class=only|exclude]
+        [rotate=itq] [rotate_blocks=<int>] [rotate_iters=50]
+
+Learned rotation ("learned rotation"): `rotate=itq` fits a block-diagonal rotation to the database's real-valued
+codes once (`GalleryIndex.fit_rotation`; `rotate_blocks` blocks, the run's ncontext by default, at most `rotate_iters` updates), keeps it in
+the index and rotates every query; an index built under another `rotate` setting is stale.  `results.json` records it under "rotation".
 
 Filtered search ("filtered search"; rank hamming, asymmetric or ternary, k <= 128): `only_classes` / `exclude_classes`
 admit only database rows of (not of) these classes -- ids, or names of the dataset's class_names.txt; `exclude_self=true` keeps an image
@@ -137,6 +142,27 @@ def filter_request(config):
             "exclude_self": self_, "same_class": str(same) if same is not None else None}
 
 
+def rotation_request(config):
+    """The learned rotation of an invocation, from its config alone (no model, no GPU): None without `rotate`, else a dict with `method`
+    ("itq"), `blocks` (rotate_blocks, or the run's ncontext) and `iters`.  An error names the key."""
+    method, blocks, iters = config.get("rotate"), config.get("rotate_blocks"), config.get("rotate_iters")
+    if method is None or str(method) in ("", "none", "None"):
+        if blocks is not None:
+            raise ValueError(f"rotate_blocks={blocks!r} without rotate=itq")
+        return None
+    if str(method) != "itq":
+        raise ValueError(f"rotate must be itq (or left out), got {method!r}")
+    nbit, ncontext = int(config.model.nbit), int(config.model.ncontext)
+    if blocks is None:
+        blocks = ncontext
+    if isinstance(blocks, bool) or not isinstance(blocks, int) or blocks < 1 or nbit % blocks:
+        raise ValueError(f"rotate_blocks must be an int >= 1 that divides nbit = {nbit}, got {blocks!r}")
+    iters = 50 if iters is None else iters
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError(f"rotate_iters must be an int >= 1, got {iters!r}")
+    return {"method": "itq", "blocks": blocks, "iters": iters}
+
+
 class SearchExperiment:
     def __init__(self, config: DictConfig):
         import torch.distributed as dist
@@ -148,6 +174,7 @@ class SearchExperiment:
         self.query = str(config.get("query", "test") or "test")
         self.text = text_request(config)              # None: image queries.  Argument errors surface here, before anything is loaded
         self.filter = filter_request(config)          # None: every row may be a hit
+        self.rotation = rotation_request(config)      # None: the codes are searched as the model gives them
         if self.filter is not None and self.filter["exclude_self"] and self.text is not None:
             raise ValueError("exclude_self=true needs image queries: a text query is no database row")
         engine.seeding(config["seed"])
@@ -165,6 +192,7 @@ class SearchExperiment:
         self.ternary = str(config.get("rank", "hamming") or "hamming") == "ternary"
         self.index_margin = rt.check_margin(config.get("index_margin", 0.0) or 0.0, "index_margin") if self.ternary else None
         # rank=cosine | euclidean | dot rank the real-valued codes themselves: the index then carries them as its real plane
+        # (so does rotate=itq: the rotation is fitted to them)
         self.dense = str(config.get("rank", "hamming") or "hamming") in rt.DENSE_METRICS
 
         # the index first: whether the database split has to be encoded decides what is loaded
@@ -217,6 +245,11 @@ class SearchExperiment:
         if self.dense and index.real is None:
             raise StaleIndexError(f"{self.index_path} holds no real plane; rank={self.config.get('rank')} ranks the real-valued codes and "
                                   f"needs it: rebuild the index (rebuild_index=true)")
+        have = None if index.rotation is None else (index.rotation_info.get("method"), index.rotation_blocks)
+        want = None if self.rotation is None else (self.rotation["method"], self.rotation["blocks"])
+        if have != want:
+            raise StaleIndexError(f"{self.index_path} was built under rotate = {have}; this run asks for {want} ((method, blocks); None: no "
+                                  f"rotation): rebuild the index (rebuild_index=true)")
 
     def _build_index(self) -> GalleryIndex:
         _, out = self._phase("encode_db", self.trainer.inference_one_epoch, "db", True)
@@ -234,7 +267,9 @@ class SearchExperiment:
                              paths=[p for p, _ in items] if items is not None else None,
                              data_root=getattr(ds, "root", None) if items is not None else None, mean=mean,
                              transform=self._transform_settings(), fingerprint=self.fingerprint, mask=mask, margin=self.index_margin,
-                             real=codes if self.dense else None)
+                             real=codes if self.dense or self.rotation is not None else None)
+        if self.rotation is not None:
+            index = self._phase("fit_rotation", index.fit_rotation, self.rotation["blocks"], self.rotation["iters"])
         self._phase("index_save", index.save, self.index_path)
         return index
 
@@ -410,6 +445,7 @@ class SearchExperiment:
                "query": self.query if self.text is None else list(self.text["prompts"]),
                "prefix": None if self.text is None else self.text["prefix"], "text_model": None if self.text is None else self.text["text_model"],
                "filter": None if self.filter is None else dict(self.filter, rows_admitted=int(res["rows_admitted"])),
+               "rotation": None if index.rotation is None else dict(index.rotation_info, keeps_concepts=index.keeps_concepts),
                "center_agreement": agreement, "mean_shift": self.text is None and index.mean is not None, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
         with open(os.path.join(self.search_logdir, "results.json"), "w") as f:

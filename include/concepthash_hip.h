@@ -644,6 +644,22 @@ int ch_dense_rank_count(const float *q, int64_t Qn, const float *g, int64_t G, i
 int ch_dense_rerank(const float *q, int64_t Qn, const float *g, int64_t G, int32_t n, int32_t metric, const int64_t *cand, int32_t m,
                     int32_t k, int64_t g_index_base, int64_t *out_idx, float *out_dist, void *stream);
 
+/* Learned rotation ("learned rotation"): iterative quantisation of real-valued codes.  codes [rows,n] fp32
+ * row-major, 1 <= n <= 256.  R is block-diagonal with blocks of `block` = s columns (s divides n) and is passed compact, [n,s] fp32
+ * row-major: row b s + l holds R_b[l, :] (off-block entries do not exist).  The rotated entry of row i and output j of block b is the
+ * chain acc = 0; for l = 0 .. s-1: acc = fmaf(codes[i, b s + l], R_b[l, j - b s], acc), in this order, in both entries: a row rotates
+ * to the same bits alone or in a batch, in the step or in the rotate.  Sign: B = +1 where z > 0, else -1 (ch_pack_sign's rule).
+ * ch_itq_step: ONE launch over the codes.  out_M [n,s] fp64, row j = sum_i B_ij codes[i, b s + .]; out_stats [2] fp64 =
+ * {sum_ij |z_ij|, sum_i |z_i|_1 / (sqrt(n) |z_i|_2)} (a zero row adds 0 to the second).  Both WRITTEN.  Nothing of size rows x n is
+ * written.  M is accumulated in fp32 inside a segment of seg_rows rows (1 .. 4096; 0: chosen here) in row order, the segments'
+ * partials are added in fp64 in segment order; no atomics, so two calls on the same inputs give the same bits.  workspace:
+ * ch_itq_step_workspace bytes, 8-byte aligned (as out_M and out_stats).  rows == 0: status 0, nothing launched, nothing written. */
+size_t ch_itq_step_workspace(int64_t rows, int32_t n, int32_t block, int32_t seg_rows);
+int ch_itq_step(const float *codes, int64_t rows, int32_t n, const float *R, int32_t block, int32_t seg_rows, double *out_M,
+                double *out_stats, void *workspace, size_t workspace_bytes, void *stream);
+/* out [rows,n] fp32 = the chain above. */
+int ch_itq_rotate(const float *codes, int64_t rows, int32_t n, const float *R, int32_t block, float *out, void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the
