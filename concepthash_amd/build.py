@@ -18,7 +18,7 @@ HOST_SOURCES = ["jpeg_host.cpp", "errors.cpp"]
 # only into an experiments build (CH_BUILD_EXPERIMENTS=1), never into the product library
 EXPERIMENT_SOURCES = [os.path.join("experiments", f) for f in ("gemm_pq.hip", "gemm_ppp.hip", "gemm_dp.hip",
                                                                 "adapter_fused.hip", "gemm_rows.hip", "gemm_wide.hip")]
-HEADERS = ["ch_common.h", "ch_host.h", "kernels.h", "gemm_epilogue.h", "model_internal.h", "layer_types.h", "layer_forward.h", "weight_builder.h", "device_owner.h", "hamming_shared.h", "attention_tile.h", os.path.join("..", "..", "include", "concepthash_hip.h"),
+HEADERS = ["ch_common.h", "ch_host.h", "kernels.h", "gemm_epilogue.h", "model_internal.h", "layer_types.h", "layer_forward.h", "weight_builder.h", "device_owner.h", "hamming_shared.h", "attention_tile.h", "gemm_tile.h", "gemm_tile_walk.h", os.path.join("..", "..", "include", "concepthash_hip.h"),
            os.path.join("..", "..", "include", "concepthash_hip_debug.h")]
 # attention post-processes every MFMA result on the VALU: keep accumulators in VGPRs (no v_accvgpr_read round trips)
 # preprocess / augment reproduce Pillow's double-precision filter coefficients (and its samplers) bit for bit: no fused multiply-adds there

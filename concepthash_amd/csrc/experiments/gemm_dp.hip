@@ -19,6 +19,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -28,15 +29,6 @@ constexpr int NSTAGE = 3;
 constexpr int NTHREADS = 256;
 constexpr int LDS_BYTES = NSTAGE * STAGE_BYTES;  // 72 KiB (the epilogue reuses the first 64 KiB)
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
-
 template <int EPI>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_dp_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -45,14 +37,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_dp_kernel(GemmParams p) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 1, wc = wid & 1;
 
-    const int tiles_n = p.N / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
-    const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    const int per_group = tiles_m * p.group_n;
-    const int g = wg / per_group, rem = wg - g * per_group;
-    const int gn = min(p.group_n, tiles_n - g * p.group_n);
-    const int tm = rem / gn, tn = g * p.group_n + (rem - tm * gn);
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileIndex t = tile_walk(blockIdx.x, (p.M + BM - 1) / BM, p.N / BN, p.group_n, 0);   // this kernel does not read p.rev
+    const int m0 = t.tm * BM, n0 = t.tn * BN;
 
     // ---- staging: the stage image is 384 rows x 64 B = 24 wave-instructions of 16 rows; wave w issues i = 6w .. 6w+5.
     // lane l -> row 16i + (l >> 2), LDS chunk (l & 3) <- source chunk (l & 3) ^ (((row >> 3) & 1) << 1), (row>>3)&1 == (l>>5)&1
@@ -85,10 +71,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_dp_kernel(GemmParams p) {
     const int wrow = BM * 64 + (wc * 64 + fr) * 64 + fsw;  // + nt*1024
 
     f32x4 acc[4][8];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     const int nk = p.K / BK;
     stage(0, 0);
@@ -150,18 +133,11 @@ bool ch_gemm_dp_supported(const GemmParams &p) {
            (size_t)round_up64(p.M, BM) * p.K * 2 < (1ull << 32) && (size_t)p.N * p.K * 2 < (1ull << 32);
 }
 
+// the forward epilogues without a LayerNorm fold on either side
+constexpr bool dp_epi(int e) { return ch_epi::is_forward(e) && !ch_epi::is_stats(e) && !ch_epi::is_fold(e); }
+
 int ch_gemm_bf16_dp(const GemmParams &p, int epi, hipStream_t s) {
-    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    if (int e = ch_gemm_check_common(p, epi)) return e;
     CH_REQUIRE(ch_gemm_dp_supported(p), "gemm_dp: needs N % 128 == 0, K % 32 == 0, X padded to 256 rows, operands < 4 GiB");
-    switch (epi) {
-        case EPI_BIAS: return launch_dp<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_dp<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch_dp<EPI_BIAS_GELU>(p, s);
-        case EPI_BIAS_RESID: return launch_dp<EPI_BIAS_RESID>(p, s);
-        case EPI_SCALE_RESID: return launch_dp<EPI_SCALE_RESID>(p, s);
-        case EPI_PATCH: return launch_dp<EPI_PATCH>(p, s);
-    }
-    ch_set_error("gemm: unknown epilogue");
-    return 2;
+    return ch_epi_dispatch<dp_epi>(epi, [&](auto e) { return launch_dp<e()>(p, s); });
 }

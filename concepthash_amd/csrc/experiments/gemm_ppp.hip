@@ -17,6 +17,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -26,15 +27,6 @@ constexpr int BUF_BYTES = 4 * HALF_BYTES;  // 64 KiB: [X_h0][X_h1][W_h0][W_h1]
 constexpr int STAGE_OFF = 2 * BUF_BYTES;   // epilogue staging: 8 waves x 4 KiB
 constexpr int LDS_BYTES = STAGE_OFF + 8 * 4096;  // 160 KiB
 constexpr int NTHREADS = 512;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
 
 #define PP_BARRIER()                       \
     do {                                   \
@@ -83,6 +75,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_ppp_kernel(GemmParams p, int
         }
     }
     auto tile_offsets = [&](int v, TileOff &t) {
+        // gemm_tile_walk.h's order without rev, written out: through tile_walk (which multiplies tiles_m * tiles_n instead of reading
+        // the argument ntiles) an s_waitcnt of the tile loop moves (profiles/gemm_tile_registers.txt)
         const int wg = xcd_remap(v, ntiles);
         const int per_group = tiles_m * p.group_n;
         const int g = wg / per_group, rem = wg - g * per_group;
@@ -182,10 +176,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_ppp_kernel(GemmParams p, int
             for (int nt = 0; nt < 4; ++nt)
                 *(f32x4 *)(park + nt * 16) = *(const f32x4 *)(p.bias + cur.n0 + wc * 64 + nt * 16 + fq * 4);
         }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         for (int j = 0; j < J; ++j) {
             const bool last = (j + 1 == J);
@@ -308,17 +299,14 @@ int launch_ppp(const GemmParams &p0, hipStream_t s) {
 
 }  // namespace
 
-bool ch_gemm_ppp_supported(const GemmParams &p, int epi) {
-    return (epi == EPI_BIAS || epi == EPI_BIAS_QUICKGELU || epi == EPI_BIAS_GELU) && ch_gemm_pp_supported(p);
-}
+// bias, bias + quick_gelu, bias + gelu
+constexpr bool ppp_epi(int e) { return ch_epi::is_forward(e) && ch_epi::is_bf16_only(e) && !ch_epi::is_stats(e) && !ch_epi::is_fold(e); }
+
+bool ch_gemm_ppp_supported(const GemmParams &p, int epi) { return ppp_epi(epi) && ch_gemm_pp_supported(p); }
 
 int ch_gemm_bf16_ppp(const GemmParams &p, int epi, hipStream_t s) {
     CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
     CH_REQUIRE(p.bias != nullptr, "gemm: bias is required");
     CH_REQUIRE(ch_gemm_ppp_supported(p, epi), "gemm_ppp: bf16-output epilogues only; N % 256 == 0, K % 128 == 0, X padded to 256 rows");
-    switch (epi) {
-        case EPI_BIAS: return launch_ppp<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_ppp<EPI_BIAS_QUICKGELU>(p, s);
-        default: return launch_ppp<EPI_BIAS_GELU>(p, s);
-    }
+    return ch_epi_dispatch<ppp_epi>(epi, [&](auto e) { return launch_ppp<e()>(p, s); });
 }

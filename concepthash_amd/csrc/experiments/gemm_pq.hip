@@ -29,6 +29,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -37,15 +38,6 @@ constexpr int UNIT_BYTES = 128 * BK * 2;   // 16 KiB
 constexpr int BUF_BYTES = 3 * UNIT_BYTES;  // 48 KiB: [X_a][X_b][W]
 constexpr int STAGE_BYTES = 8 * 16384;     // epilogue staging: 16 KB per wave (re-uses the operand buffers)
 constexpr int NTHREADS = 512;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
 
 #define PQ_BARRIER()                       \
     do {                                   \
@@ -73,15 +65,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_pq_kernel(GemmParams p) {
     const int wr = wid >> 1, wc = wid & 1;  // 4 x 2 waves
     const int grp = wid >> 2;               // stagger group: waves 4-7 run one barrier behind waves 0-3
 
-    const int tiles_n = p.N / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
-    const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    // tile order inside an XCD's contiguous chunk: see gemm_bf16.hip (n-tile groups with L2-resident weight panels)
-    const int per_group = tiles_m * p.group_n;
-    const int g = wg / per_group, rem = wg - g * per_group;
-    const int gn = min(p.group_n, tiles_n - g * p.group_n);
-    const int tm = rem / gn, tn = g * p.group_n + (rem - tm * gn);
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileIndex t = tile_walk(blockIdx.x, (p.M + BM - 1) / BM, p.N / BN, p.group_n, 0);   // this kernel does not read p.rev
+    const int m0 = t.tm * BM, n0 = t.tn * BN;
 
     // ---- prefetch addressing.  A unit = 16 wave-instructions of 8 rows; wave w issues instructions 2w, 2w+1:
     // lane l -> unit row lr = 16w + 8j + (l>>3), LDS chunk (l&7) <- source chunk (l&7)^(lr&7) = (l&7)^(l>>3).
@@ -115,10 +100,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_pq_kernel(GemmParams p) {
     const int wbase = 2 * UNIT_BYTES + (wc * 64 + fr) * 128;                // + nt*2048
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     bf16x8 Wf[2][2] = {}, Xf[4][2] = {};  // [tile][kk]
 
     auto read_w = [&](int buf, int h) {
@@ -238,22 +220,7 @@ bool ch_gemm_pq_supported(const GemmParams &p) {
 }
 
 int ch_gemm_bf16_pq(const GemmParams &p, int epi, hipStream_t s) {
-    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    if (int e = ch_gemm_check_common(p, epi)) return e;
     CH_REQUIRE(ch_gemm_pq_supported(p), "gemm_pq: needs N % 128 == 0, K % 128 == 0, X padded to 256 rows, operands < 4 GiB");
-    switch (epi) {
-        case EPI_BIAS: return launch_pq<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_pq<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch_pq<EPI_BIAS_GELU>(p, s);
-        case EPI_BIAS_RESID: return launch_pq<EPI_BIAS_RESID>(p, s);
-        case EPI_SCALE_RESID: return launch_pq<EPI_SCALE_RESID>(p, s);
-        case EPI_PATCH: return launch_pq<EPI_PATCH>(p, s);
-        case EPI_BIAS_STATS: return launch_pq<EPI_BIAS_STATS>(p, s);
-        case EPI_SCALE_RESID_STATS: return launch_pq<EPI_SCALE_RESID_STATS>(p, s);
-        case EPI_FOLD_BIAS: return launch_pq<EPI_FOLD_BIAS>(p, s);
-        case EPI_FOLD_QUICKGELU: return launch_pq<EPI_FOLD_QUICKGELU>(p, s);
-        case EPI_FOLD_GELU: return launch_pq<EPI_FOLD_GELU>(p, s);
-    }
-    ch_set_error("gemm: unknown epilogue");
-    return 2;
+    return ch_epi_dispatch<ch_epi::is_forward>(epi, [&](auto e) { return launch_pq<e()>(p, s); });
 }

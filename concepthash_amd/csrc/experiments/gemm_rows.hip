@@ -23,6 +23,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -31,9 +32,6 @@ constexpr int NT = BN / 16;                     // 24 n-tiles per wave
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 32 KiB
 constexpr int NTHREADS = 256;
 constexpr int LDS_BYTES = 2 * STAGE_BYTES + CH_FOLD_LDS_BYTES;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
 
 template <int EPI>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_rows_kernel(GemmParams p) {
@@ -141,24 +139,16 @@ int launch_rows(const GemmParams &p, hipStream_t s) {
 
 }  // namespace
 
+// the bf16-output forward epilogues that write no statistics
+constexpr bool rows_epi(int e) { return ch_epi::is_forward(e) && ch_epi::is_bf16_only(e) && !ch_epi::is_stats(e); }
+
 bool ch_gemm_rows_supported(const GemmParams &p, int epi) {
-    const bool epi_ok = epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_QUICKGELU || epi == EPI_FOLD_GELU ||
-                        epi == EPI_FOLD_QUICKGELU || epi == EPI_FOLD_BIAS;
-    return epi_ok && p.N == BN && p.K % BK == 0 && p.K >= 2 * BK && p.X_rows_alloc >= round_up64(p.M, BM) &&
+    return rows_epi(epi) && p.N == BN && p.K % BK == 0 && p.K >= 2 * BK && p.X_rows_alloc >= round_up64(p.M, BM) &&
            (size_t)round_up64(p.M, BM) * p.K * 2 < (1ull << 32);
 }
 
 int ch_gemm_bf16_rows(const GemmParams &p, int epi, hipStream_t s) {
     CH_REQUIRE(p.M > 0 && p.bias != nullptr, "gemm_rows: empty problem or missing bias");
     CH_REQUIRE(ch_gemm_rows_supported(p, epi), "gemm_rows: needs N == 384, K % 32 == 0, X padded to 128 rows, a bf16-output epilogue");
-    switch (epi) {
-        case EPI_BIAS: return launch_rows<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_rows<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch_rows<EPI_BIAS_GELU>(p, s);
-        case EPI_FOLD_BIAS: return launch_rows<EPI_FOLD_BIAS>(p, s);
-        case EPI_FOLD_QUICKGELU: return launch_rows<EPI_FOLD_QUICKGELU>(p, s);
-        case EPI_FOLD_GELU: return launch_rows<EPI_FOLD_GELU>(p, s);
-    }
-    ch_set_error("gemm_rows: unsupported epilogue");
-    return 2;
+    return ch_epi_dispatch<rows_epi>(epi, [&](auto e) { return launch_rows<e()>(p, s); });
 }

@@ -31,6 +31,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -42,15 +43,6 @@ constexpr int NSTAGE = 3;
 constexpr int NTHREADS = 512;
 constexpr int FOLD_OFF = NSTAGE * STAGE_BYTES;   // (rstd, mean) table of the block's 256 rows
 constexpr int WIDE_LDS_BYTES = FOLD_OFF + CH_FOLD_LDS_BYTES;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
 
 #define WD_BARRIER()                       \
     do {                                   \
@@ -127,10 +119,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_wide_kernel(GemmParams p) {
     const int wrow = X_BYTES + (wc * 96 + fr) * 64 + fsw;               // + h * WH_BYTES + nt * 1024
 
     f32x4 acc[12][4];
-#pragma unroll
-    for (int a = 0; a < 12; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     bf16x8 Xf[4] = {}, Wf[6] = {};
 
     auto read_x = [&](int st) {
@@ -235,9 +224,11 @@ int launch_wide(const GemmParams &p, hipStream_t s) {
 
 }  // namespace
 
+// what the adapter's two projections use, forward and backward
+constexpr bool wide_epi(int e) { return e == EPI_BIAS || e == EPI_BIAS_GELU || e == EPI_FOLD_GELU || e == EPI_FOLD_ACT2_GELU || e == EPI_BIAS_DACT_GELU; }
+
 bool ch_gemm_wide_supported(const GemmParams &p, int epi) {
-    const bool epi_ok = epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_FOLD_GELU || epi == EPI_FOLD_ACT2_GELU || epi == EPI_BIAS_DACT_GELU;
-    return epi_ok && p.N % BN == 0 && p.K % BK == 0 && p.K >= 2 * BK && p.X_rows_alloc >= round_up64(p.M, BM) &&
+    return wide_epi(epi) && p.N % BN == 0 && p.K % BK == 0 && p.K >= 2 * BK && p.X_rows_alloc >= round_up64(p.M, BM) &&
            (size_t)round_up64(p.M, BM) * p.K * 2 < (1ull << 32) && (size_t)p.N * p.K * 2 < (1ull << 32);
 }
 
@@ -268,13 +259,5 @@ int ch_gemm_bf16_wide(const GemmParams &p, int epi, hipStream_t s) {
     CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
     CH_REQUIRE(p.bias != nullptr, "gemm: bias is required");
     CH_REQUIRE(ch_gemm_wide_supported(p, epi), "gemm_wide: needs N % 384 == 0, K % 32 == 0, K >= 64, X padded to 256 rows, a bf16-output epilogue");
-    switch (epi) {
-        case EPI_BIAS: return launch_wide<EPI_BIAS>(p, s);
-        case EPI_BIAS_GELU: return launch_wide<EPI_BIAS_GELU>(p, s);
-        case EPI_FOLD_GELU: return launch_wide<EPI_FOLD_GELU>(p, s);
-        case EPI_FOLD_ACT2_GELU: return launch_wide<EPI_FOLD_ACT2_GELU>(p, s);
-        case EPI_BIAS_DACT_GELU: return launch_wide<EPI_BIAS_DACT_GELU>(p, s);
-    }
-    ch_set_error("gemm_wide: unsupported epilogue");
-    return 2;
+    return ch_epi_dispatch<wide_epi>(epi, [&](auto e) { return launch_wide<e()>(p, s); });
 }

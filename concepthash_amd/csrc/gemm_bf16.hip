@@ -18,23 +18,13 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 32 KiB
 constexpr int NTHREADS = 256;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-
-// XCD-aware, bijective block remap: blocks b and b+8 share an XCD (observed round-robin dispatch; speed only).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
 
 // NT: the scale+residual epilogues' read-modify-write of the fp32 residual is non-temporal (gemm_epilogue.h: ld_resid).  A parameter of
 // the KERNEL template on purpose: wrapping the body in an inlined function shared by two __global__ symbols changed the compiler's
@@ -48,18 +38,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(GemmParams p) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid & 1, wn = wid >> 1;
 
-    const int tiles_n = p.N / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
-    const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    // tile order inside an XCD's contiguous chunk: n-tiles are taken in groups of p.group_n whose weight panels stay
-    // L2-resident (<= ~2.0 MB) while the m-tiles sweep past; inside a group n is fastest so the co-resident workgroups of
-    // an XCD share activation panels too.  (host: gemm_group_n)
-    const int per_group = tiles_m * p.group_n;
-    const int g = wg / per_group, rem = wg - g * per_group;
-    const int gn = min(p.group_n, tiles_n - g * p.group_n);
-    const int tm_fwd = rem / gn, tn = g * p.group_n + (rem - tm_fwd * gn);
-    const int tm = p.rev ? tiles_m - 1 - tm_fwd : tm_fwd;
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileOrigin org = tile_origin<BM, BN>(p, blockIdx.x);
+    const int m0 = org.m0, n0 = org.n0;
 
     // ---- staging addresses: the stage image is [X rows 0..127 ; W rows 0..127] x 128 B, 8 rows per wave-instruction.
     // wave w issues instructions i = 8w .. 8w+7; lane l -> row 8i + (l>>3), LDS chunk (l&7) holding source chunk
@@ -82,10 +62,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(GemmParams p) {
     };
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // fragment read offsets (bytes) inside a stage: row = sub*16 + (lane&15), chunk = (kk*4 + (lane>>4)) ^ (row&7)
     const int frow = lane & 15, fq = lane >> 4;
@@ -139,53 +116,26 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_kernel(GemmParams p) {
 template <int EPI>
 int launch(const GemmParams &p0, hipStream_t s) {
     GemmParams p = p0;
-    p.group_n = ch_gemm_group_n(p.M, p.N, p.K, BM, BN, p.group_n_opt);
-    const int tiles = ((p.M + BM - 1) / BM) * (p.N / BN);
-    constexpr int lds = 2 * STAGE_BYTES + (ch_epi::traits<EPI>::fold ? CH_FOLD_LDS_BYTES : 0);
-    static ch_once_per_device lds_once;
-    if (int e = ch_func_max_lds((const void *)gemm_bf16_kernel<EPI>, lds, lds_once)) return e;
-    if constexpr (ch_epi::traits<EPI>::scale_resid) {
+    const dim3 grid(ch_gemm_plan_tiles(p, BM, BN));
+    constexpr int lds = 2 * STAGE_BYTES + (ch_epi::is_fold(EPI) ? CH_FOLD_LDS_BYTES : 0);
+    if constexpr (ch_epi::is_scale_resid(EPI)) {
         if (p.nt_resid) {
-            static ch_once_per_device lds_once_nt;
-            if (int e = ch_func_max_lds((const void *)gemm_bf16_kernel<EPI, true>, lds, lds_once_nt)) return e;
-            CH_LAUNCH((gemm_bf16_kernel<EPI, true>), dim3(tiles), dim3(NTHREADS), lds, s, p);
-            CH_LAUNCH_CHECK();
+            if (int e = ch_gemm_launch<gemm_bf16_kernel<EPI, true>>(grid, NTHREADS, lds, s, p)) return e;
             ch_gemm_count_nt_launch(0);
             return 0;
         }
     }
-    CH_LAUNCH(gemm_bf16_kernel<EPI>, dim3(tiles), dim3(NTHREADS), lds, s, p);
-    CH_LAUNCH_CHECK();
-    return 0;
+    return ch_gemm_launch<gemm_bf16_kernel<EPI>>(grid, NTHREADS, lds, s, p);
 }
 
 }  // namespace
 
 int ch_gemm_bf16_v1(const GemmParams &p, int epi, hipStream_t s) {
-    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    if (int e = ch_gemm_check_common(p, epi)) return e;
     CH_REQUIRE(p.N % BN == 0, "gemm: N must be a multiple of 128");
     CH_REQUIRE(p.K % BK == 0, "gemm: K must be a multiple of 64");
     CH_REQUIRE(p.X_rows_alloc >= round_up64(p.M, BM), "gemm: X must be allocated for M rounded up to 128 rows");
-    switch (epi) {
-        case EPI_BIAS: return launch<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch<EPI_BIAS_GELU>(p, s);
-        case EPI_BIAS_RESID: return launch<EPI_BIAS_RESID>(p, s);
-        case EPI_SCALE_RESID: return launch<EPI_SCALE_RESID>(p, s);
-        case EPI_PATCH: return launch<EPI_PATCH>(p, s);
-        case EPI_BIAS_STATS: return launch<EPI_BIAS_STATS>(p, s);
-        case EPI_SCALE_RESID_STATS: return launch<EPI_SCALE_RESID_STATS>(p, s);
-        case EPI_FOLD_BIAS: return launch<EPI_FOLD_BIAS>(p, s);
-        case EPI_FOLD_QUICKGELU: return launch<EPI_FOLD_QUICKGELU>(p, s);
-        case EPI_FOLD_GELU: return launch<EPI_FOLD_GELU>(p, s);
-        case EPI_BIAS_DACT_QUICK: return launch<EPI_BIAS_DACT_QUICK>(p, s);
-        case EPI_BIAS_DACT_GELU: return launch<EPI_BIAS_DACT_GELU>(p, s);
-        case EPI_FOLD_ACT2_QUICK: return launch<EPI_FOLD_ACT2_QUICK>(p, s);
-        case EPI_FOLD_ACT2_GELU: return launch<EPI_FOLD_ACT2_GELU>(p, s);
-    }
-    ch_set_error("gemm: unknown epilogue");
-    return 2;
+    return ch_epi_dispatch(epi, [&](auto e) { return launch<e()>(p, s); });
 }
 
 // Estimated beyond-L2 read traffic for n-groups of gn tiles: every group re-streams X once; a group's weight panels are
@@ -215,7 +165,7 @@ void ch_gemm_count_nt_launch(int kind) { g_dispatch_count[2 + (kind != 0)].fetch
 // residual tensors from this size up are streamed past the caches by the scale+residual epilogues (gemm_epilogue.h: ld_resid);
 // the model option "resid_nt" (1 / -1) forces the choice
 static int resid_nt_choice(const GemmParams &p, int epi) {
-    if (epi != EPI_SCALE_RESID && epi != EPI_SCALE_RESID_STATS) return 0;
+    if (!ch_epi::is_scale_resid(epi)) return 0;
     if (p.nt_resid_opt) return p.nt_resid_opt > 0;
     return std::max<int64_t>(p.M, p.footprint_rows) * p.N * 4 >= (48ll << 20);
 }
@@ -223,9 +173,7 @@ static int resid_nt_choice(const GemmParams &p, int epi) {
 // next kernel, out of HBM whatever the policy) are stored non-temporally by the 256x256 kernel, which leaves the caches to the
 // operands: 12.15 -> 11.99 ms per encode step (profiles/r03_cache_policy_ab.txt).  The model option "nt_out" (1 / -1) forces the choice.
 static int out_nt_choice(const GemmParams &p, int epi) {
-    if (epi != EPI_BIAS && epi != EPI_FOLD_BIAS && epi != EPI_FOLD_QUICKGELU && epi != EPI_FOLD_GELU && epi != EPI_FOLD_ACT2_QUICK &&
-        epi != EPI_FOLD_ACT2_GELU && epi != EPI_BIAS_DACT_QUICK && epi != EPI_BIAS_DACT_GELU)
-        return 0;
+    if (!ch_epi::may_nt_out(epi)) return 0;
     if (p.nt_out_opt) return p.nt_out_opt > 0;
     return std::max<int64_t>(p.M, p.footprint_rows) * p.N * 2 >= (128ll << 20);
 }
@@ -259,13 +207,13 @@ int ch_gemm_bf16(const GemmParams &p0, int epi, hipStream_t s, int variant) {
     GemmParams p = p0;
     p.nt_resid = resid_nt_choice(p, epi);
     p.nt_out = out_nt_choice(p, epi);
-    if (epi == EPI_BIAS_DACT_QUICK || epi == EPI_BIAS_DACT_GELU) CH_REQUIRE(p.aux != nullptr, "gemm: derivative epilogue needs aux (the pre-activation)");
-    if (epi == EPI_FOLD_ACT2_QUICK || epi == EPI_FOLD_ACT2_GELU) CH_REQUIRE(p.hb_out != nullptr, "gemm: two-output epilogue needs hb_out");
-    if (epi == EPI_FOLD_BIAS || epi == EPI_FOLD_QUICKGELU || epi == EPI_FOLD_GELU || epi == EPI_FOLD_ACT2_QUICK || epi == EPI_FOLD_ACT2_GELU)
+    if (ch_epi::is_dact(epi)) CH_REQUIRE(p.aux != nullptr, "gemm: derivative epilogue needs aux (the pre-activation)");
+    if (ch_epi::is_act2(epi)) CH_REQUIRE(p.hb_out != nullptr, "gemm: two-output epilogue needs hb_out");
+    if (ch_epi::is_fold(epi))
         CH_REQUIRE(p.stats_in && p.fold_c && p.K % 128 == 0 && p.K <= 1280 && p.ln_eps > 0.f,
                    "gemm: LN-folded epilogue needs stats_in, fold_c, ln_eps and K % 128 == 0, K <= 1280");
-    if (epi == EPI_BIAS_STATS || epi == EPI_SCALE_RESID_STATS)
-        CH_REQUIRE(p.stats_out && (epi == EPI_BIAS_STATS || p.hb_out), "gemm: statistics epilogue needs stats_out (and hb_out)");
+    if (ch_epi::is_stats(epi))
+        CH_REQUIRE(p.stats_out && (!ch_epi::is_scale_resid(epi) || p.hb_out), "gemm: statistics epilogue needs stats_out (and hb_out)");
     if (variant != 0 && variant != 7) return ch_gemm_launch_variant(variant, p, epi, s);
     // Short-K GEMMs (the adapter up-projection, K = 384) are epilogue/HBM bound: two 128x128 workgroups per CU overlap one's
     // read-modify-write epilogue with the other's K loop and win there (measured: 152 -> 97 us per launch in the pipeline);

@@ -67,15 +67,9 @@ __device__ __forceinline__ float dgelu_erf_f(float x) {
 }
 
 template <int EPI>
-struct traits {
-    static constexpr bool dact = (EPI == EPI_BIAS_DACT_QUICK || EPI == EPI_BIAS_DACT_GELU);
-    static constexpr bool act2 = (EPI == EPI_FOLD_ACT2_QUICK || EPI == EPI_FOLD_ACT2_GELU);
-    static constexpr bool fold = (EPI == EPI_FOLD_BIAS || EPI == EPI_FOLD_QUICKGELU || EPI == EPI_FOLD_GELU || act2);
-    static constexpr bool quick = (EPI == EPI_BIAS_QUICKGELU || EPI == EPI_FOLD_QUICKGELU);
-    static constexpr bool erf = (EPI == EPI_BIAS_GELU || EPI == EPI_FOLD_GELU);
-    static constexpr bool bf16_only = (EPI == EPI_BIAS || EPI == EPI_BIAS_STATS || quick || erf || fold || dact);
-    static constexpr bool scale_resid = (EPI == EPI_SCALE_RESID || EPI == EPI_SCALE_RESID_STATS);
-    static constexpr bool stats = (EPI == EPI_BIAS_STATS || EPI == EPI_SCALE_RESID_STATS);
+struct traits {   // the epilogue table of kernels.h as compile-time members
+    static constexpr bool dact = is_dact(EPI), act2 = is_act2(EPI), fold = is_fold(EPI), quick = is_quick(EPI), erf = is_erf(EPI);
+    static constexpr bool bf16_only = is_bf16_only(EPI), scale_resid = is_scale_resid(EPI), stats = is_stats(EPI);
 };
 
 template <int EPI>

@@ -26,6 +26,7 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
@@ -34,16 +35,6 @@ constexpr int HALF_BYTES = 128 * BK * 2;       // 16 KiB
 constexpr int BUF_BYTES = 4 * HALF_BYTES;      // 64 KiB: [X_h0][X_h1][W_h0][W_h1]
 constexpr int NTHREADS = 512;
 constexpr int PP_LDS_BYTES = 2 * BUF_BYTES + CH_FOLD_LDS_BYTES + 16;  // operands + (mean, rstd) table + split-K ticket
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
 
 #define PP_BARRIER()                       \
     do {                                   \
@@ -90,24 +81,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_pp_kernel(GemmParams p) {
         stamp[1] = __builtin_amdgcn_s_memtime();
     }
 
-    const int tiles_n = p.N / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
     // blocks [0, split_full) own one tile each; the tiles of the last, partial round are cut along K into split_s slices
     // (blocks split_full + tile * split_s + slice) whose fp32 partial tiles the last arriver sums -- see the split-K block
     // after the K loop.  Without a split split_full = tiles and split_s = 1.
     const bool split = (int)blockIdx.x >= p.split_full;  // workgroup-uniform
     const int unit = (int)blockIdx.x - p.split_full;
     const int split_tile = split ? unit / p.split_s : 0, slice = split ? unit - split_tile * p.split_s : 0;
-    const int wg = xcd_remap(split ? p.split_full + split_tile : (int)blockIdx.x, tiles_m * tiles_n);
-    // tile order inside an XCD's contiguous chunk: n-tiles are taken in groups of p.group_n whose weight panels stay
-    // L2-resident (<= ~2.0 MB) while the m-tiles sweep past; inside a group n is fastest so the co-resident workgroups of
-    // an XCD share activation panels too.  (host: gemm_group_n)
-    const int per_group = tiles_m * p.group_n;
-    const int g = wg / per_group, rem = wg - g * per_group;
-    const int gn = min(p.group_n, tiles_n - g * p.group_n);
-    const int tm_fwd = rem / gn, tn = g * p.group_n + (rem - tm_fwd * gn);
-    const int tm = p.rev ? tiles_m - 1 - tm_fwd : tm_fwd;
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileOrigin org = tile_origin<BM, BN>(p, split ? p.split_full + split_tile : (int)blockIdx.x);
+    const int m0 = org.m0, n0 = org.n0;
 
     // ---- prefetch addressing.  A half-tile = 16 wave-instructions of 8 local rows; wave w issues instructions 2w, 2w+1:
     // lane l -> local row lr = 16w + 8j + (l>>3), LDS chunk (l&7) <- source chunk (l&7)^(lr&7) = (l&7)^(l>>3).
@@ -149,10 +130,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_pp_kernel(GemmParams p) {
     const int wrow = (wc * 32 + fr) * 128;            // + nt*2048
 
     f32x4 acc[4][8];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     bf16x8 Wa[2][2] = {}, Wbf[2][2] = {}, Xf[4][2] = {};  // [tile][kk]
 
     auto read_w = [&](bf16x8 (&dst)[2][2], int buf, int h) {
@@ -405,10 +383,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_pp_kernel(GemmParams p) {
         if (tid == 0)  // ready for the next launch
             __hip_atomic_store(p.splitk_cnt + split_tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no instruction: keeps the slab loads below the ticket
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         for (int sl = 0; sl < p.split_s; ++sl) {
             const unsigned base = tile_off + (unsigned)sl * SLAB_BYTES + lane_off;
 #pragma unroll
@@ -497,37 +472,23 @@ int launch_pp_sched(GemmParams &p, int tiles, hipStream_t s) {
     constexpr int lds = PP_LDS_BYTES;
     const dim3 grid(p.split_full + (tiles - p.split_full) * p.split_s);
     if constexpr (EPI == EPI_BIAS_STATS && SCHED == 0) {
-        if (p.tag == 1) {  // same code under a second name (fc2 of the encoder chain): see TAG above
-            static ch_once_per_device lds_once_t;
-            if (int e = ch_func_max_lds((const void *)gemm_pp_kernel<EPI, 0, SCHED, 1>, lds, lds_once_t)) return e;
-            CH_LAUNCH((gemm_pp_kernel<EPI, 0, SCHED, 1>), grid, dim3(NTHREADS), lds, s, p);
-            CH_LAUNCH_CHECK();
-            return 0;
-        }
+        if (p.tag == 1)  // same code under a second name (fc2 of the encoder chain): see TAG above
+            return ch_gemm_launch<gemm_pp_kernel<EPI, 0, SCHED, 1>>(grid, NTHREADS, lds, s, p);
     }
-    if constexpr ((EPI == EPI_BIAS || EPI == EPI_FOLD_BIAS || EPI == EPI_FOLD_QUICKGELU || EPI == EPI_FOLD_GELU || EPI == EPI_FOLD_ACT2_QUICK ||
-                   EPI == EPI_FOLD_ACT2_GELU || EPI == EPI_BIAS_DACT_QUICK || EPI == EPI_BIAS_DACT_GELU) && SCHED == 0) {
+    if constexpr (ch_epi::may_nt_out(EPI) && SCHED == 0) {
         if (p.nt_out) {  // TAG 2: out_bf16 stored non-temporally (an output larger than the caches that is read once)
-            static ch_once_per_device lds_once_n;
-            if (int e = ch_func_max_lds((const void *)gemm_pp_kernel<EPI, 0, SCHED, 2>, lds, lds_once_n)) return e;
-            CH_LAUNCH((gemm_pp_kernel<EPI, 0, SCHED, 2>), grid, dim3(NTHREADS), lds, s, p);
-            CH_LAUNCH_CHECK();
+            if (int e = ch_gemm_launch<gemm_pp_kernel<EPI, 0, SCHED, 2>>(grid, NTHREADS, lds, s, p)) return e;
             ch_gemm_count_nt_launch(1);
             return 0;
         }
     }
-    static ch_once_per_device lds_once;
-    if (int e = ch_func_max_lds((const void *)gemm_pp_kernel<EPI, 0, SCHED>, lds, lds_once)) return e;
-    CH_LAUNCH((gemm_pp_kernel<EPI, 0, SCHED>), grid, dim3(NTHREADS), lds, s, p);
-    CH_LAUNCH_CHECK();
-    return 0;
+    return ch_gemm_launch<gemm_pp_kernel<EPI, 0, SCHED>>(grid, NTHREADS, lds, s, p);
 }
 
 template <int EPI>
 int launch_pp(const GemmParams &p0, hipStream_t s) {
     GemmParams p = p0;
-    p.group_n = ch_gemm_group_n(p.M, p.N, p.K, BM, BN, p.group_n_opt);
-    const int tiles = ((p.M + BM - 1) / BM) * (p.N / BN);
+    const int tiles = ch_gemm_plan_tiles(p, BM, BN);
     if (p.pp_sched == 1) {  // coarse schedule (experiment, DESIGN.md section 3.8: bit-identical, no faster): no split-K
 #ifdef CH_EXPERIMENTS
         p.split_full = tiles;
@@ -598,26 +559,7 @@ int ch_gemm_bf16_pp_dbg(const GemmParams &p0, int dbg, hipStream_t s) {
 }
 
 int ch_gemm_bf16_pp(const GemmParams &p, int epi, hipStream_t s) {
-    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    if (int e = ch_gemm_check_common(p, epi)) return e;
     CH_REQUIRE(ch_gemm_pp_supported(p), "gemm_pp: needs N % 256 == 0, K % 128 == 0, X padded to 256 rows, operands < 4 GiB");
-    switch (epi) {
-        case EPI_BIAS: return launch_pp<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_pp<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch_pp<EPI_BIAS_GELU>(p, s);
-        case EPI_BIAS_RESID: return launch_pp<EPI_BIAS_RESID>(p, s);
-        case EPI_SCALE_RESID: return launch_pp<EPI_SCALE_RESID>(p, s);
-        case EPI_PATCH: return launch_pp<EPI_PATCH>(p, s);
-        case EPI_BIAS_STATS: return launch_pp<EPI_BIAS_STATS>(p, s);
-        case EPI_SCALE_RESID_STATS: return launch_pp<EPI_SCALE_RESID_STATS>(p, s);
-        case EPI_FOLD_BIAS: return launch_pp<EPI_FOLD_BIAS>(p, s);
-        case EPI_FOLD_QUICKGELU: return launch_pp<EPI_FOLD_QUICKGELU>(p, s);
-        case EPI_FOLD_GELU: return launch_pp<EPI_FOLD_GELU>(p, s);
-        case EPI_BIAS_DACT_QUICK: return launch_pp<EPI_BIAS_DACT_QUICK>(p, s);
-        case EPI_BIAS_DACT_GELU: return launch_pp<EPI_BIAS_DACT_GELU>(p, s);
-        case EPI_FOLD_ACT2_QUICK: return launch_pp<EPI_FOLD_ACT2_QUICK>(p, s);
-        case EPI_FOLD_ACT2_GELU: return launch_pp<EPI_FOLD_ACT2_GELU>(p, s);
-    }
-    ch_set_error("gemm: unknown epilogue");
-    return 2;
+    return ch_epi_dispatch(epi, [&](auto e) { return launch_pp<e()>(p, s); });
 }

@@ -28,42 +28,25 @@
 #include "ch_common.h"
 #include "kernels.h"
 #include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace {
 
 constexpr int BM = 128, BN = 128, BK = 32;
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 16 KiB
-// NS (template): 4 = the ring above (64 KB, two workgroups per CU); 2 = one K-step in flight, 32 KB of LDS and <= 128 VGPRs so that FOUR
-// workgroups share a CU (bf16-output epilogues only: their staging is 8 KB per wave) -- the occupancy experiment of round 3
-// (not instantiated any more; the bandwidth-bound adapter launches lose 24-34 % when a CU holds one workgroup instead of two).
 constexpr int NTHREADS = 256;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, local = bid >> 3;
-    const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + local;
-}
-
 template <int EPI, int NSTAGE>
-__global__ __launch_bounds__(NTHREADS, NSTAGE == 2 ? 4 : 2) void gemm_r4_kernel(GemmParams p) {
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_r4_kernel(GemmParams p) {
+    static_assert(NSTAGE == 4, "the ring has four stages (64 KB, two workgroups per CU)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid & 1, wn = wid >> 1;
 
-    const int tiles_n = p.N / BN;
-    const int tiles_m = (p.M + BM - 1) / BM;
-    const int wg = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    const int per_group = tiles_m * p.group_n;
-    const int g = wg / per_group, rem = wg - g * per_group;
-    const int gn = min(p.group_n, tiles_n - g * p.group_n);
-    const int tm_fwd = rem / gn, tn = g * p.group_n + (rem - tm_fwd * gn);
-    const int tm = p.rev ? tiles_m - 1 - tm_fwd : tm_fwd;
-    const int m0 = tm * BM, n0 = tn * BN;
+    const TileOrigin org = tile_origin<BM, BN>(p, blockIdx.x);
+    const int m0 = org.m0, n0 = org.n0;
 
     // ---- staging: 256 rows x 64 B = 16 wave-instructions of 16 rows; lane l -> row 16i + (l >> 2), LDS chunk (l & 3) holding
     // source chunk (l & 3) ^ (((row >> 3) & 1) << 1), and (row >> 3) & 1 == (l >> 5) & 1
@@ -83,10 +66,7 @@ __global__ __launch_bounds__(NTHREADS, NSTAGE == 2 ? 4 : 2) void gemm_r4_kernel(
     };
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // fragment addressing: row = base + t*16 + (lane & 15) with base a multiple of 16, chunk = (lane >> 4) ^ (((row >> 3) & 1) << 1)
     const int fr = lane & 15, fq = lane >> 4;
@@ -101,14 +81,12 @@ __global__ __launch_bounds__(NTHREADS, NSTAGE == 2 ? 4 : 2) void gemm_r4_kernel(
     ch_epi::ResidPrefetch rp;
     if constexpr (PREF) ch_epi::resid_prefetch<EPI>(p, m0 + wm * 64, n0 + wn * 64, lane, rp);  // arrives under the K loop
     stage(0, 0);
-    if (NSTAGE > 2 && nk > 1) stage(1, 1);
-    if (NSTAGE > 2 && nk > 2) stage(2, 2);
+    if (nk > 1) stage(1, 1);
+    if (nk > 2) stage(2, 2);
     if constexpr (ch_epi::traits<EPI>::fold) {
         // the statistics loads are older than the stages: retire them (and nothing else) with a counted wait
-        if (NSTAGE > 2 && nk > 2)
+        if (nk > 2)
             asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (NSTAGE == 2)
-            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -118,9 +96,9 @@ __global__ __launch_bounds__(NTHREADS, NSTAGE == 2 ? 4 : 2) void gemm_r4_kernel(
     int buf = 0;
     for (int kt = 0; kt < nk; ++kt) {
         const int ahead = nk - 1 - kt;  // stages issued after stage kt that may still be in flight: min(NSTAGE - 2, ahead)
-        if (NSTAGE > 2 && ahead >= 2)
+        if (ahead >= 2)
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (NSTAGE > 2 && ahead == 1)
+        else if (ahead == 1)
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -148,46 +126,26 @@ __global__ __launch_bounds__(NTHREADS, NSTAGE == 2 ? 4 : 2) void gemm_r4_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    ch_epi::store_tile<EPI, 4, PREF>(p, acc, smem + wid * (NSTAGE == 2 ? 8192 : 16384), m0 + wm * 64, n0 + wn * 64, lane,
+    ch_epi::store_tile<EPI, 4, PREF>(p, acc, smem + wid * 16384, m0 + wm * 64, n0 + wn * 64, lane,
                                      (const float *)(smem + NSTAGE * STAGE_BYTES) + 2 * (wm * 64), &rp);
 }
 
-template <int EPI, int NSTAGE = 4>
+template <int EPI>
 int launch_r4(const GemmParams &p0, hipStream_t s) {
     GemmParams p = p0;
-    p.group_n = ch_gemm_group_n(p.M, p.N, p.K, BM, BN);
-    const int tiles = ((p.M + BM - 1) / BM) * (p.N / BN);
-    constexpr int lds = NSTAGE * STAGE_BYTES + (ch_epi::traits<EPI>::fold ? CH_FOLD_LDS_BYTES : 0);
-    static ch_once_per_device lds_once;
-    if (int e = ch_func_max_lds((const void *)gemm_r4_kernel<EPI, NSTAGE>, lds, lds_once)) return e;
-    hipLaunchKernelGGL((gemm_r4_kernel<EPI, NSTAGE>), dim3(tiles), dim3(NTHREADS), lds, s, p);
-    CH_LAUNCH_CHECK();
-    return 0;
+    const dim3 grid(ch_gemm_plan_tiles(p, BM, BN));
+    constexpr int lds = 4 * STAGE_BYTES + (ch_epi::is_fold(EPI) ? CH_FOLD_LDS_BYTES : 0);
+    return ch_gemm_launch<gemm_r4_kernel<EPI, 4>>(grid, NTHREADS, lds, s, p);
 }
 
 }  // namespace
 
 bool ch_gemm_r4_supported(const GemmParams &p, int epi) {   // the forward epilogues (the training-only ones stay with gemm_bf16.hip)
-    return epi >= EPI_BIAS && epi <= EPI_FOLD_GELU && p.N % BN == 0 && p.K % BK == 0 && p.K >= 3 * BK && p.X_rows_alloc >= round_up64(p.M, BM);
+    return ch_epi::is_forward(epi) && p.N % BN == 0 && p.K % BK == 0 && p.K >= 3 * BK && p.X_rows_alloc >= round_up64(p.M, BM);
 }
 
 int ch_gemm_bf16_r4(const GemmParams &p, int epi, hipStream_t s) {
-    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
-    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    if (int e = ch_gemm_check_common(p, epi)) return e;
     CH_REQUIRE(ch_gemm_r4_supported(p, epi), "gemm_r4: needs a forward epilogue, N % 128 == 0, K % 32 == 0, K >= 96, X padded to 128 rows");
-    switch (epi) {
-        case EPI_BIAS: return launch_r4<EPI_BIAS>(p, s);
-        case EPI_BIAS_QUICKGELU: return launch_r4<EPI_BIAS_QUICKGELU>(p, s);
-        case EPI_BIAS_GELU: return launch_r4<EPI_BIAS_GELU>(p, s);
-        case EPI_BIAS_RESID: return launch_r4<EPI_BIAS_RESID>(p, s);
-        case EPI_SCALE_RESID: return launch_r4<EPI_SCALE_RESID>(p, s);
-        case EPI_PATCH: return launch_r4<EPI_PATCH>(p, s);
-        case EPI_BIAS_STATS: return launch_r4<EPI_BIAS_STATS>(p, s);
-        case EPI_SCALE_RESID_STATS: return launch_r4<EPI_SCALE_RESID_STATS>(p, s);
-        case EPI_FOLD_BIAS: return launch_r4<EPI_FOLD_BIAS>(p, s);
-        case EPI_FOLD_QUICKGELU: return launch_r4<EPI_FOLD_QUICKGELU>(p, s);
-        case EPI_FOLD_GELU: return launch_r4<EPI_FOLD_GELU>(p, s);
-    }
-    ch_set_error("gemm: unknown epilogue");
-    return 2;
+    return ch_epi_dispatch<ch_epi::is_forward>(epi, [&](auto e) { return launch_r4<e()>(p, s); });
 }

@@ -98,6 +98,76 @@ void ch_gemm_count_nt_launch(int kind);  // test tap counters: 0 = non-temporal 
 // n-tiles per weight group for a block tile of bn columns: minimises X re-fetches + W re-fetches
 int ch_gemm_group_n(int M, int N, int K, int bm, int bn, int forced = 0);
 
+// ---- the one epilogue table: the classes of GemmEpilogue as functions of the number.  ch_epi::traits<EPI> (gemm_epilogue.h) is
+// defined from them and the host code (dispatcher, launchers, argument checks) asks the same functions.
+namespace ch_epi {
+constexpr bool is_dact(int e) { return e == EPI_BIAS_DACT_QUICK || e == EPI_BIAS_DACT_GELU; }
+constexpr bool is_act2(int e) { return e == EPI_FOLD_ACT2_QUICK || e == EPI_FOLD_ACT2_GELU; }
+constexpr bool is_fold(int e) { return e == EPI_FOLD_BIAS || e == EPI_FOLD_QUICKGELU || e == EPI_FOLD_GELU || is_act2(e); }
+constexpr bool is_quick(int e) { return e == EPI_BIAS_QUICKGELU || e == EPI_FOLD_QUICKGELU; }
+constexpr bool is_erf(int e) { return e == EPI_BIAS_GELU || e == EPI_FOLD_GELU; }
+constexpr bool is_scale_resid(int e) { return e == EPI_SCALE_RESID || e == EPI_SCALE_RESID_STATS; }
+constexpr bool is_stats(int e) { return e == EPI_BIAS_STATS || e == EPI_SCALE_RESID_STATS; }
+constexpr bool is_bf16_only(int e) { return e == EPI_BIAS || e == EPI_BIAS_STATS || is_quick(e) || is_erf(e) || is_fold(e) || is_dact(e); }
+constexpr bool may_nt_out(int e) { return e == EPI_BIAS || is_fold(e) || is_dact(e); }   // has an instance that stores out_bf16 non-temporally
+constexpr bool is_forward(int e) { return e >= EPI_BIAS && e <= EPI_FOLD_GELU; }         // the encode step's epilogues: what the ring is built for
+constexpr bool is_any(int e) { return e >= 0 && e < EPI_COUNT; }
+}  // namespace ch_epi
+static inline int ch_epi_unknown() {
+    ch_set_error("gemm: unknown epilogue");
+    return 2;
+}
+template <bool (*OK)(int), int EPI, typename F>
+int ch_epi_call(F &f) {
+    if constexpr (OK(EPI)) return f(std::integral_constant<int, EPI>{});
+    else return ch_epi_unknown();
+}
+// run-time epilogue -> template argument: f(std::integral_constant<int, EPI>) for the epilogues that OK admits (only those are instantiated)
+template <bool (*OK)(int) = ch_epi::is_any, typename F>
+int ch_epi_dispatch(int epi, F &&f) {
+    switch (epi) {
+        case EPI_BIAS: return ch_epi_call<OK, EPI_BIAS>(f);
+        case EPI_BIAS_QUICKGELU: return ch_epi_call<OK, EPI_BIAS_QUICKGELU>(f);
+        case EPI_BIAS_GELU: return ch_epi_call<OK, EPI_BIAS_GELU>(f);
+        case EPI_BIAS_RESID: return ch_epi_call<OK, EPI_BIAS_RESID>(f);
+        case EPI_SCALE_RESID: return ch_epi_call<OK, EPI_SCALE_RESID>(f);
+        case EPI_PATCH: return ch_epi_call<OK, EPI_PATCH>(f);
+        case EPI_BIAS_STATS: return ch_epi_call<OK, EPI_BIAS_STATS>(f);
+        case EPI_SCALE_RESID_STATS: return ch_epi_call<OK, EPI_SCALE_RESID_STATS>(f);
+        case EPI_FOLD_BIAS: return ch_epi_call<OK, EPI_FOLD_BIAS>(f);
+        case EPI_FOLD_QUICKGELU: return ch_epi_call<OK, EPI_FOLD_QUICKGELU>(f);
+        case EPI_FOLD_GELU: return ch_epi_call<OK, EPI_FOLD_GELU>(f);
+        case EPI_BIAS_DACT_QUICK: return ch_epi_call<OK, EPI_BIAS_DACT_QUICK>(f);
+        case EPI_BIAS_DACT_GELU: return ch_epi_call<OK, EPI_BIAS_DACT_GELU>(f);
+        case EPI_FOLD_ACT2_QUICK: return ch_epi_call<OK, EPI_FOLD_ACT2_QUICK>(f);
+        case EPI_FOLD_ACT2_GELU: return ch_epi_call<OK, EPI_FOLD_ACT2_GELU>(f);
+    }
+    return ch_epi_unknown();
+}
+
+// ---- the one launch path of the GEMM kernels
+// the checks every entry opens with
+static inline int ch_gemm_check_common(const GemmParams &p, int epi) {
+    CH_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem");
+    CH_REQUIRE(epi == EPI_PATCH || p.bias != nullptr, "gemm: bias is required");
+    return 0;
+}
+// sets the tile order of a launch of bm x bn tiles (always with the model option "group_n") and returns the number of tiles
+static inline int ch_gemm_plan_tiles(GemmParams &p, int bm, int bn) {
+    p.group_n = ch_gemm_group_n(p.M, p.N, p.K, bm, bn, p.group_n_opt);
+    return (int)ceil_div64(p.M, bm) * (p.N / bn);
+}
+// LDS attribute once per device and kernel instance (the static is per Kernel), launch through CH_LAUNCH (so that a profiled
+// encode's event pair rides on it), check
+template <auto Kernel, typename... Args>
+int ch_gemm_launch(dim3 grid, int nthreads, int lds, hipStream_t s, const Args &...args) {
+    static ch_once_per_device lds_once;
+    if (int e = ch_func_max_lds((const void *)Kernel, lds, lds_once)) return e;
+    CH_LAUNCH(Kernel, grid, dim3(nthreads), lds, s, args...);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
 // ---- adapter_fused.hip --------------------------------------------------------------------------------------------
 struct AdapterParams {
     const bf16_t *A;      // sub-block output a [M, D] bf16 (read twice: statistics + MFMA operand, and as the residual addend)

@@ -348,9 +348,9 @@ def test_tile_order_options_do_not_change_a_byte(lib):
         if variant == 4 and not _experiments(lib):
             continue
         tiles_n = N // (256 if variant in (2, 4) else 128)
-        options = [dict(rev=1)]
-        if variant != 7:                                                      # the ring does not read group_n_opt
-            options += [dict(group_n=g) for g in (1, 2, tiles_n)] + [dict(rev=1, group_n=2)]
+        options = [dict(rev=1)] + [dict(group_n=g) for g in (1, 2, tiles_n)] + [dict(rev=1, group_n=2)]
+        if variant in (1, 7):                                                 # six n-tiles: a group of four and a partial group of two
+            options += [dict(group_n=4)]
         for epi in (0, 7):
             base = _check(lib, dv, epi, variant, wide=True)                   # sentinel payloads: no tile was skipped
             for opt in options:
