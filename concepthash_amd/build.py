@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libconcepthash_hip.so")
-SOURCES = ["model.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_r4.hip", "attention.hip", "rowops.hip", "head.hip", "small_f32.hip", "hamming.hip", "hamming_tie_expected.hip", "hamming_topk.hip", "hamming_rank.hip", "hamming_rankcount.hip", "hamming_ternary.hip", "dense_rank.hip", "itq.hip",
+SOURCES = ["model.hip", "gemm_bf16.hip", "gemm_pp.hip", "gemm_r4.hip", "attention.hip", "rowops.hip", "head.hip", "small_f32.hip", "hamming.hip", "hamming_tie_expected.hip", "hamming_topk.hip", "hamming_rank.hip", "hamming_rankcount.hip", "hamming_ternary.hip", "dense_rank.hip", "itq.hip", "pca.hip",
            "preprocess.hip", "augment.hip", "train_kernels.hip", "attention_bwd.hip", "attention_stream.hip", "train.hip", "text_model.hip", "debug_taps.hip", "jpeg.hip", "jpeg_host.cpp", "errors.cpp"]
 # plain C++ sources (no HIP): compiled by the same driver as host code; tests/test_jpeg.py also builds them with g++ -fsanitize=address,undefined
 HOST_SOURCES = ["jpeg_host.cpp", "errors.cpp"]
@@ -28,6 +28,8 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "attention
                "dense_rank.hip": ["-ffp-contract=off"],
                # itq spells out the fmaf chain of the rotation: the step and the rotate must give the same bits
                "itq.hip": ["-ffp-contract=off"],
+               # pca spells out the fmaf chains of the Gram and of the projection: database and query must give the same bits
+               "pca.hip": ["-ffp-contract=off"],
                # the tie expectation's fp64 error bound counts one rounding per operation written in the source
                "hamming_tie_expected.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -1798,3 +1798,192 @@ def fit_rotation(codes: torch.Tensor, blocks: int, iters: int = 50, tol: float =
             break
         R = procrustes_update(M, blocks).to(torch.float32)
     return dict(R=full_rotation(best[1], blocks), blocks=blocks, iters_run=best[2], l1=l1s, qerr_before=before, qerr_after=best[3])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# reduction: PCA (and PCA-ITQ) of the real-valued codes to any code length (DESIGN.md section 2.0, "reduction"; csrc/pca.hip)
+# ---------------------------------------------------------------------------------------------------------------
+REDUCE_METHODS = ("pca-itq", "pca")
+
+
+def compact_projection(A: torch.Tensor, blocks: int) -> torch.Tensor:
+    """[n, bits] block-structured (rows b s .. of block b are zero outside columns b t ..) -> [n, t], t = bits / blocks: row b s + l
+    holds A_b[l, :] (the form the kernel takes).  An entry outside the blocks that is not zero is a ValueError."""
+    n, bits = A.shape
+    s = check_blocks(n, blocks)
+    if bits % blocks or not blocks <= bits <= n:
+        raise ValueError(f"a projection of {n} dimensions in {blocks} blocks has blocks .. n columns, a multiple of blocks; got {bits}")
+    t = bits // blocks
+    diag = torch.arange(blocks, device=A.device)
+    out = A.reshape(blocks, s, blocks, t)[diag, :, diag, :].reshape(n, t).contiguous()
+    if not torch.equal(full_projection(out, blocks), A):
+        raise ValueError(f"A is not block-structured under blocks = {blocks}: an entry outside the blocks is not zero")
+    return out
+
+
+def full_projection(Ac: torch.Tensor, blocks: int) -> torch.Tensor:
+    """[n, t] compact -> [n, blocks t] block-structured"""
+    n, t = Ac.shape
+    return torch.block_diag(*Ac.reshape(blocks, n // blocks, t).unbind(0)).contiguous()
+
+
+def _check_pca(codes, blocks, shift=None, who="shift"):
+    """The argument checks the reduction's functions share, all in front of the first launch -> (codes, shift, n, s)"""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.float32:
+        raise TypeError(f"codes must be a float32 tensor, got {getattr(codes, 'dtype', type(codes))}")
+    if codes.dim() != 2:
+        raise ValueError(f"codes must be 2-D [rows, n] real-valued codes, got {tuple(codes.shape)}")
+    n = codes.shape[1]
+    if not 1 <= n <= ITQ_MAX_DIM:
+        raise ValueError(f"codes have {n} dimensions; a reduction takes 1 .. {ITQ_MAX_DIM}")
+    s = check_blocks(n, blocks)
+    if shift is not None:
+        if not isinstance(shift, torch.Tensor) or shift.dtype != torch.float32 or tuple(shift.shape) != (n,):
+            raise ValueError(f"{who} must be a float32 tensor [{n}], got {getattr(shift, 'dtype', type(shift))} "
+                             f"{tuple(getattr(shift, 'shape', ()))}")
+        if shift.device != codes.device:
+            raise ValueError(f"{who} and the codes must be on the same device")
+        if not bool(torch.isfinite(shift).all()):
+            raise ValueError(f"{who} holds NaN or infinite entries")
+        shift = shift.contiguous()
+    if codes.numel() and not bool(torch.isfinite(codes).all()):
+        raise ValueError("codes hold NaN or infinite entries: a reduction is fitted on, and applied to, finite codes")
+    return codes.contiguous(), shift, n, s
+
+
+def pca_moments(codes: torch.Tensor, blocks: int, shift: Optional[torch.Tensor] = None, seg_rows: Optional[int] = None, stream=None):
+    """The first and second moments of y = fl32(codes - shift) (y = codes without a shift) -> (sum [n] float64, gram [n, s] float64:
+    gram[b s + a, c] = sum_i y[i, b s + a] y[i, b s + c], s = n / blocks).  Inside a segment of seg_rows rows (1 .. 4096; None: chosen
+    by the library) every entry is accumulated in fp32 -- a gram entry as one fmaf chain in row order --, the segments in fp64 in
+    segment order: no atomics, the same bits on every call, gram exactly symmetric inside a block.  No rows: zeros."""
+    codes, shift, n, s = _check_pca(codes, blocks, shift)
+    seg = 0 if seg_rows is None else int(seg_rows)
+    if not 0 <= seg <= ITQ_MAX_SEG or (seg_rows is not None and seg < 1):
+        raise ValueError(f"seg_rows must be in [1, {ITQ_MAX_SEG}], got {seg_rows!r}")
+    return _pca_moments(codes, n, s, shift, seg, True, stream)
+
+
+def _pca_moments(codes, n: int, s: int, shift, seg: int, with_gram: bool, stream=None):
+    """`pca_moments` behind its argument checks; with_gram=False: (sum, None)"""
+    guard = _dev_guard(codes)
+    lib = _lib.load()
+    rows = codes.shape[0]
+    total = torch.zeros(n, dtype=torch.float64, device=codes.device)
+    gram = torch.zeros(n, s, dtype=torch.float64, device=codes.device) if with_gram else None
+    if rows == 0:
+        return total, gram
+    wsb = int(lib.ch_pca_moments_workspace(rows, n, s, seg, int(with_gram)))
+    ws = torch.empty((wsb + 7) // 8, dtype=torch.int64, device=codes.device)
+    with guard:
+        _lib.check(lib.ch_pca_moments(_lib.ptr(codes), rows, n, s, _lib.ptr(shift) if shift is not None else None, seg, _lib.ptr(total),
+                                      _lib.ptr(gram) if with_gram else None, _lib.ptr(ws), ws.numel() * 8, _lib.stream_ptr(stream)),
+                   "ch_pca_moments")
+    return total, gram
+
+
+def pca_components(cov_blocks: torch.Tensor, t: int):
+    """cov_blocks [blocks, s, s] float64, symmetric -> (P [blocks, s, t] float64: per block the eigenvectors of the t largest
+    eigenvalues as columns, eigenvalues [blocks, s] float64, descending).  Each component is signed so that its entry of largest
+    magnitude is positive (the lowest index among equals).  A pure host function: `torch.linalg.eigh` in fp64 on the CPU."""
+    if not isinstance(cov_blocks, torch.Tensor) or cov_blocks.dtype != torch.float64:
+        raise TypeError(f"cov_blocks must be a float64 tensor, got {getattr(cov_blocks, 'dtype', type(cov_blocks))}")
+    if cov_blocks.dim() != 3 or cov_blocks.shape[1] != cov_blocks.shape[2] or cov_blocks.shape[1] < 1:
+        raise ValueError(f"cov_blocks must be [blocks, s, s], got {tuple(cov_blocks.shape)}")
+    s = cov_blocks.shape[1]
+    if isinstance(t, bool) or not isinstance(t, int) or not 1 <= t <= s:
+        raise ValueError(f"t must be an int in [1, {s}], got {t!r}")
+    C = cov_blocks.detach().to("cpu")
+    if not bool(torch.isfinite(C).all()):
+        raise ValueError("cov_blocks hold NaN or infinite entries")
+    lam, vec = torch.linalg.eigh(C)                                  # ascending
+    lam, vec = lam.flip(-1), vec.flip(-1)
+    P = vec[:, :, :t].contiguous()
+    lead = P.abs().argmax(dim=1, keepdim=True)                       # the first of equals
+    sign = torch.where(P.gather(1, lead) < 0, -1.0, 1.0).to(torch.float64)
+    return P * sign, lam.contiguous()
+
+
+def project_codes(codes: torch.Tensor, mean: Optional[torch.Tensor], A: torch.Tensor, blocks: int, compact: bool = False,
+                  stream=None) -> torch.Tensor:
+    """[rows, n] fp32 -> [rows, bits] fp32: out[i, b t + j] = the chain acc = 0; for l = 0 .. s-1: acc = fmaf(fl32(codes[i, b s + l] -
+    mean[b s + l]), A_b[l, j], acc) (mean=None: no subtraction).  A: [n, bits] block-structured as `fit_reduction` returns it, or with
+    compact=True [n, t] (`compact_projection`).  A row projects to the same bits alone or in a batch; with t = s and no mean it is
+    `rotate_codes`."""
+    codes, mean, n, s = _check_pca(codes, blocks, mean, "mean")
+    if not isinstance(A, torch.Tensor) or A.dtype != torch.float32 or A.dim() != 2 or A.shape[0] != n:
+        raise ValueError(f"A must be a float32 tensor with {n} rows, got {getattr(A, 'dtype', type(A))} {tuple(getattr(A, 'shape', ()))}")
+    if A.device != codes.device:
+        raise ValueError("A and the codes must be on the same device")
+    if not bool(torch.isfinite(A).all()):
+        raise ValueError("A holds NaN or infinite entries")
+    Ac = A.contiguous() if compact else compact_projection(A, blocks)
+    if not 1 <= Ac.shape[1] <= s:
+        raise ValueError(f"a block of {s} dimensions projects to 1 .. {s} columns, got {Ac.shape[1]}")
+    return _project_codes(codes, mean, Ac, n, s, stream)
+
+
+def _project_codes(codes, mean, Ac, n: int, s: int, stream=None):
+    """`project_codes` behind its argument checks; Ac compact [n, t]"""
+    guard = _dev_guard(codes)
+    lib = _lib.load()
+    t = Ac.shape[1]
+    out = torch.empty(codes.shape[0], n // s * t, dtype=torch.float32, device=codes.device)
+    if codes.shape[0]:
+        with guard:
+            _lib.check(lib.ch_pca_project(_lib.ptr(codes), codes.shape[0], n, s, _lib.ptr(mean) if mean is not None else None, _lib.ptr(Ac),
+                                          t, _lib.ptr(out), _lib.stream_ptr(stream)), "ch_pca_project")
+    return out
+
+
+def check_reduction(n: int, bits, blocks, method="pca-itq") -> int:
+    """(`bits`, `blocks`, `method`) of a reduction of n-dimensional codes (ValueError otherwise) -> t = bits / blocks"""
+    check_blocks(n, blocks)
+    if isinstance(bits, bool) or not isinstance(bits, int) or not blocks <= bits <= n or bits % blocks:
+        raise ValueError(f"bits must be an int in [blocks, n] = [{blocks}, {n}] and a multiple of blocks = {blocks}, got {bits!r}")
+    if method not in REDUCE_METHODS:
+        raise ValueError(f"method must be one of {REDUCE_METHODS}, got {method!r}")
+    return bits // blocks
+
+
+def fit_reduction(codes: torch.Tensor, bits: int, blocks: int, iters: int = 50, method: str = "pca-itq") -> dict:
+    """Fit a reduction of `codes` [N, n] fp32 to `bits` dimensions, block by block (s = n / blocks in, t = bits / blocks out):
+      1. mu = fp32(sum / N) from `pca_moments` without a shift;  2. the moments of y = fl32(x - mu), C_b = (gram_b - sum_b sum_b^T / N) /
+      (N - 1) in fp64;  3. P = `pca_components(C, t)`;  4. V = `project_codes(codes, mu, P)`;  5. method "pca-itq": R =
+      `fit_rotation(V, blocks, iters)` and A_b = fp32(P_b R_b), the product in fp64; "pca": A = fp32(P).
+    The reduced codes of a row, database or query, are `project_codes(row, mean, A, blocks)`: ONE chain, not project-then-rotate.
+    -> dict(mean [n] fp32, A [n, bits] fp32 block-structured, blocks, bits, method, iters_run, explained_share: the kept eigenvalues'
+    share of tr(C) (0.0 where tr(C) = 0), eigenvalues [blocks, s] (descending; a zero is a direction without variance), qerr_pca /
+    qerr_after: `itq_step`'s qerr at R = I on V / on the final codes).  ValueError: bits outside [blocks, n] or no multiple of blocks,
+    fewer than 2 rows, codes that are not finite."""
+    codes, _, n, s = _check_pca(codes, blocks)
+    t = check_reduction(n, bits, blocks, method)
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 0:
+        raise ValueError(f"iters must be an int >= 0, got {iters!r}")
+    N = codes.shape[0]
+    if N < 2:
+        raise ValueError(f"a reduction is fitted on at least 2 rows (the covariance divides by N - 1), got {N}")
+    _dev_guard(codes)
+    dev = codes.device
+    total, _ = _pca_moments(codes, n, s, None, 0, False)
+    mean = (total / N).to(torch.float32)
+    total, gram = _pca_moments(codes, n, s, mean, 0, True)
+    sb = total.cpu().reshape(blocks, s)
+    C = (gram.cpu().reshape(blocks, s, s) - sb[:, :, None] * sb[:, None, :] / N) / (N - 1)
+    P, lam = pca_components(C, t)
+    trace = float(C.diagonal(dim1=1, dim2=2).sum())
+    share = float(lam[:, :t].sum()) / trace if trace > 0 else 0.0
+    Pc = P.reshape(n, t).to(torch.float32).to(dev).contiguous()
+    V = _project_codes(codes, mean, Pc, n, s)
+    eye = torch.eye(t, dtype=torch.float32, device=dev).repeat(blocks, 1)
+    if method == "pca-itq":
+        fit = fit_rotation(V, blocks, iters)
+        R = compact_rotation(fit["R"], blocks).cpu().to(torch.float64).reshape(blocks, t, t)
+        Ac = (P @ R).reshape(n, t).to(torch.float32).to(dev).contiguous()
+        iters_run, qerr_pca = fit["iters_run"], fit["qerr_before"]
+        _, _, qerr_after = _itq_step(_project_codes(codes, mean, Ac, n, s), eye, bits, t, 0)
+    else:
+        Ac, iters_run = Pc, 0
+        _, _, qerr_pca = _itq_step(V, eye, bits, t, 0)
+        qerr_after = qerr_pca
+    return dict(mean=mean, A=full_projection(Ac, blocks), blocks=blocks, bits=bits, method=method, iters_run=iters_run,
+                explained_share=share, eigenvalues=lam.tolist(), qerr_pca=qerr_pca, qerr_after=qerr_after)

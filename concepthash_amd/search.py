@@ -46,13 +46,20 @@ class GalleryIndex:
     source -- what `search(query_group=..., group_by="groups")` filters by; optional in the same way.
     rotation: None, or the learned rotation [nbit, nbit] fp32 (`fit_rotation`; DESIGN.md section 2.0, "learned rotation"), block-diagonal
     with `rotation_blocks` blocks, that the real codes went through before they were packed: every query goes through it too.
-    rotation_info: what the fit reported ({"method", "blocks", "iters_run", "qerr_before", "qerr_after"}), kept with the rotation."""
+    rotation_info: what the fit reported ({"method", "blocks", "iters_run", "qerr_before", "qerr_after"}), kept with the rotation.
+    reduce_mean [nbit_in], reduce_A [nbit_in, nbit], reduce_blocks, reduce_info: None, or the reduction (`fit_reduction`; DESIGN.md
+    section 2.0, "reduction") that took the real codes of the model's width `nbit_in` to the `nbit` dimensions the index holds: its
+    centre, its block-structured fp32 matrix, its number of blocks and what the fit reported.  Every query arrives `nbit_in` wide and
+    goes through `retrieval.project_codes(q, reduce_mean, reduce_A, reduce_blocks)`, the chain the database went through; `mean` is
+    then [nbit_in] too.  Without a reduction nbit_in == nbit."""
 
     def __init__(self, codes: torch.Tensor, nbit: int, ncontext: int, labels: Optional[torch.Tensor] = None,
                  paths: Optional[Sequence[str]] = None, data_root: Optional[str] = None, mean: Optional[torch.Tensor] = None,
                  transform: Optional[dict] = None, fingerprint: Optional[dict] = None, mask: Optional[torch.Tensor] = None,
                  margin: Optional[float] = None, real: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None,
-                 rotation: Optional[torch.Tensor] = None, rotation_blocks: Optional[int] = None, rotation_info: Optional[dict] = None):
+                 rotation: Optional[torch.Tensor] = None, rotation_blocks: Optional[int] = None, rotation_info: Optional[dict] = None,
+                 reduce_mean: Optional[torch.Tensor] = None, reduce_A: Optional[torch.Tensor] = None, reduce_blocks: Optional[int] = None,
+                 reduce_info: Optional[dict] = None):
         nbit, ncontext = int(nbit), int(ncontext)
         if codes.dtype != torch.int64 or codes.dim() != 2 or codes.shape[1] != (nbit + 63) // 64:
             raise ValueError(f"codes must be packed int64 [G, {(nbit + 63) // 64}] for nbit = {nbit}, got {codes.dtype} {tuple(codes.shape)}")
@@ -63,8 +70,27 @@ class GalleryIndex:
             raise ValueError(f"{labels.shape[0]} labels for {G} codes")
         if paths is not None and len(paths) != G:
             raise ValueError(f"{len(paths)} paths for {G} codes")
-        if mean is not None and tuple(mean.shape) != (nbit,):
-            raise ValueError(f"mean must be [{nbit}], got {tuple(mean.shape)}")
+        if reduce_A is not None:
+            if reduce_A.dtype != torch.float32 or reduce_A.dim() != 2 or reduce_A.shape[1] != nbit or reduce_A.device != codes.device:
+                raise ValueError(f"reduce_A must be a float32 matrix [nbit_in, {nbit}] on the codes' device, got {reduce_A.dtype} "
+                                 f"{tuple(reduce_A.shape)} on {reduce_A.device}")
+            nbit_in = int(reduce_A.shape[0])
+            rt.check_reduction(nbit_in, nbit, reduce_blocks, (reduce_info or {}).get("method", "pca-itq"))
+            if reduce_mean is None or reduce_mean.dtype != torch.float32 or tuple(reduce_mean.shape) != (nbit_in,) or \
+                    reduce_mean.device != codes.device:
+                raise ValueError(f"reduce_mean must be the float32 centre [{nbit_in}] of the reduction on the codes' device")
+            self._reduce_Ac = rt.compact_projection(reduce_A.contiguous(), reduce_blocks)    # the form the kernel takes, made once
+            reduce_A, reduce_mean = reduce_A.contiguous(), reduce_mean.contiguous()
+        elif reduce_mean is not None or reduce_blocks is not None or reduce_info is not None:
+            raise ValueError("reduce_mean / reduce_blocks / reduce_info without reduce_A")
+        else:
+            nbit_in, self._reduce_Ac = nbit, None
+        self.reduce_mean, self.reduce_A = reduce_mean, reduce_A
+        self.reduce_blocks = int(reduce_blocks) if reduce_A is not None else None
+        self.reduce_info = dict(reduce_info or {}) if reduce_A is not None else None
+        self._nbit_in = nbit_in
+        if mean is not None and tuple(mean.shape) != (nbit_in,):
+            raise ValueError(f"mean must be [{nbit_in}], got {tuple(mean.shape)}")
         if mask is not None:
             if mask.dtype != torch.int64 or tuple(mask.shape) != tuple(codes.shape) or mask.device != codes.device:
                 raise ValueError(f"mask must be an int64 plane {tuple(codes.shape)} on the codes' device, got {mask.dtype} {tuple(mask.shape)} "
@@ -111,11 +137,17 @@ class GalleryIndex:
     def device(self):
         return self.codes.device
 
+    @property
+    def nbit_in(self) -> int:
+        """the width of the codes a query arrives with: the model's; nbit unless the index holds a reduction"""
+        return self._nbit_in
+
     def to(self, device) -> "GalleryIndex":
         mv = lambda t: t.to(device) if t is not None else None
         return GalleryIndex(mv(self.codes), self.nbit, self.ncontext, mv(self.labels), self.paths, self.data_root, mv(self.mean),
                             self.transform, self.fingerprint, mv(self.mask), self.margin, mv(self.real), mv(self.groups),
-                            mv(self.rotation), self.rotation_blocks, self.rotation_info)
+                            mv(self.rotation), self.rotation_blocks, self.rotation_info, mv(self.reduce_mean), mv(self.reduce_A),
+                            self.reduce_blocks, self.reduce_info)
 
     # ---- file --------------------------------------------------------------------------------------------------------------------
     def save(self, path: str) -> None:
@@ -134,13 +166,17 @@ class GalleryIndex:
             d.update(groups=cpu(self.groups))
         if self.rotation is not None:
             d.update(rotation=cpu(self.rotation), rotation_blocks=self.rotation_blocks, rotation_info=self.rotation_info)
+        if self.reduce_A is not None:
+            d.update(reduce_mean=cpu(self.reduce_mean), reduce_A=cpu(self.reduce_A), reduce_blocks=self.reduce_blocks,
+                     reduce_info=self.reduce_info)
         torch.save(d, tmp)
         os.replace(tmp, path)
 
     def check(self, fingerprint: Optional[dict] = None, nbit: Optional[int] = None, source: str = "the index") -> None:
-        """Raises StaleIndexError unless the index was encoded with the checkpoint `fingerprint` and holds `nbit`-bit codes."""
-        if nbit is not None and int(nbit) != self.nbit:
-            raise StaleIndexError(f"{source} holds {self.nbit}-bit codes but the model produces {int(nbit)}-bit codes: rebuild the index "
+        """Raises StaleIndexError unless the index was encoded with the checkpoint `fingerprint` and holds codes of a model of `nbit`
+        bits (`nbit_in`: a reduced index holds fewer)."""
+        if nbit is not None and int(nbit) != self.nbit_in:
+            raise StaleIndexError(f"{source} holds {self.nbit_in}-bit codes but the model produces {int(nbit)}-bit codes: rebuild the index "
                                   f"(rebuild_index=true)")
         if fingerprint is not None:
             mine = {k: self.fingerprint.get(k) for k in ("size", "sha256")}
@@ -157,7 +193,8 @@ class GalleryIndex:
             raise StaleIndexError(f"{path} is not a gallery index of format {FORMAT}: rebuild the index (rebuild_index=true)")
         index = cls(d["codes"], d["nbit"], d["ncontext"], d["labels"], d["paths"], d["data_root"], d["mean"], d["transform"],
                     d["fingerprint"], d.get("mask"), d.get("margin"), d.get("real"), d.get("groups"), d.get("rotation"),
-                    d.get("rotation_blocks"), d.get("rotation_info"))
+                    d.get("rotation_blocks"), d.get("rotation_info"), d.get("reduce_mean"), d.get("reduce_A"), d.get("reduce_blocks"),
+                    d.get("reduce_info"))
         index.check(fingerprint, nbit, source=path)
         return index
 
@@ -166,7 +203,8 @@ class GalleryIndex:
     def keeps_concepts(self) -> bool:
         """whether `concepts=`, concept_dist and the per-concept evaluation still mean the concepts: no rotation, or one whose blocks
         lie inside the sub-codes"""
-        return self.rotation is None or self.rotation_blocks % self.ncontext == 0
+        return (self.rotation is None or self.rotation_blocks % self.ncontext == 0) and \
+            (self.reduce_A is None or self.reduce_blocks % self.ncontext == 0)
 
     def fit_rotation(self, blocks: Optional[int] = None, iters: int = 50) -> "GalleryIndex":
         """The index under a rotation fitted to its real plane (`retrieval.fit_rotation`; blocks=None: one block per concept): its real
@@ -185,7 +223,33 @@ class GalleryIndex:
         info = dict(method="itq", blocks=blocks, iters_run=fit["iters_run"], qerr_before=fit["qerr_before"], qerr_after=fit["qerr_after"])
         return GalleryIndex(rt.pack_sign(real), self.nbit, self.ncontext, self.labels, self.paths, self.data_root, self.mean, self.transform,
                             self.fingerprint, rt.confidence_mask(real, self.margin) if self.mask is not None else None, self.margin, real,
-                            self.groups, fit["R"], blocks, info)
+                            self.groups, fit["R"], blocks, info, self.reduce_mean, self.reduce_A, self.reduce_blocks, self.reduce_info)
+
+    # ---- reduction ---------------------------------------------------------------------------------------------------------------
+    def fit_reduction(self, bits: int, blocks: Optional[int] = None, iters: int = 50, method: str = "pca-itq") -> "GalleryIndex":
+        """A NEW index of `bits`-bit codes under a reduction fitted to this index's real plane (`retrieval.fit_reduction`; blocks=None:
+        one block per concept): nbit = bits, its real plane holds the reduced codes, its packed codes their signs, its mask plane --
+        where the index has one -- is rebuilt from them under the same margin, and every query (nbit_in wide) is reduced in `search`.
+        With blocks a multiple of ncontext, `concepts=[...]` addresses sub-codes of bits / ncontext bits.  An index without the real
+        plane, one that is rotated already or one that is reduced already raises ValueError."""
+        if self.real is None:
+            raise ValueError("fit_reduction needs the index's real plane, which this index was built without: rebuild it "
+                             "(exp=search reduce=pca-itq rebuilds it by itself; rebuild_index=true forces it)")
+        if self.rotation is not None:
+            raise ValueError("this index is rotated already: fit a reduction on the index as it was built")
+        if self.reduce_A is not None:
+            raise ValueError("this index is reduced already: fit a reduction on the index as it was built")
+        blocks = self.ncontext if blocks is None else blocks
+        rt.check_reduction(self.nbit, bits, blocks, method)
+        if bits % self.ncontext:
+            raise ValueError(f"bits = {bits} is not a multiple of ncontext = {self.ncontext}: the reduced code keeps ncontext sub-codes")
+        fit = rt.fit_reduction(self.real, bits, blocks, iters, method)
+        real = rt.project_codes(self.real, fit["mean"], fit["A"], blocks)
+        info = {k: fit[k] for k in ("method", "bits", "blocks", "iters_run", "explained_share", "qerr_pca", "qerr_after")}
+        info["bits_in"] = self.nbit
+        return GalleryIndex(rt.pack_sign(real), bits, self.ncontext, self.labels, self.paths, self.data_root, self.mean, self.transform,
+                            self.fingerprint, rt.confidence_mask(real, self.margin) if self.mask is not None else None, self.margin, real,
+                            self.groups, None, None, None, fit["mean"], fit["A"], blocks, info)
 
     # ---- search ------------------------------------------------------------------------------------------------------------------
     def resolve(self, rel: Optional[str]) -> Optional[str]:
@@ -207,7 +271,8 @@ class GalleryIndex:
                group_by: str = "groups") -> dict:
         """query_codes: [Qn, nbit] fp32 as the model returns them (the database mean, if the index holds one, is subtracted here;
         mean_shift=False leaves them as they are -- text queries, whose codes are centre-side and never shifted: DESIGN.md section 2.0;
-        a rotated index then rotates them, shifted or not, before anything else reads them).
+        a rotated index then rotates them, shifted or not, before anything else reads them; a reduced index takes them [Qn, nbit_in]
+        wide and reduces them first, in the same place).
         Ranks the database by ascending (distance, index) and returns
           idx [Qn, k] int64 (-1 past the end of the database), dist [Qn, k] int32: the ranking distance, popcount((q ^ g) & mask);
           concept_dist [Qn, k, ncontext] int32: the UNMASKED distance inside every concept's sub-code (they sum to the whole-code
@@ -254,6 +319,9 @@ class GalleryIndex:
         short list explains itself."""
         if rank not in RANKS:
             raise ValueError(f"rank must be one of {RANKS}, got {rank!r}")
+        if concepts is not None and self.reduce_A is not None and self.reduce_blocks % self.ncontext:
+            raise ValueError(f"concepts with a reduction of {self.reduce_blocks} blocks is not built: a block would straddle the sub-codes "
+                             f"of the {self.ncontext} concepts (fit it with blocks a multiple of {self.ncontext})")
         if concepts is not None and not self.keeps_concepts:
             raise ValueError(f"concepts with a rotation of {self.rotation_blocks} blocks is not built: a block would straddle the sub-codes "
                              f"of the {self.ncontext} concepts (fit it with blocks a multiple of {self.ncontext})")
@@ -351,14 +419,16 @@ class GalleryIndex:
         anything is launched), minus the database mean where there is one and mean_shift asks for it -> (codes, their packed signs,
         refuse(Qn) or None).  refuse: the caller's checks that need the number of queries (the filter); they raise behind the checks
         of the codes and in front of the first kernel."""
-        if query_codes.dim() != 2 or query_codes.shape[1] != self.nbit:
-            raise ValueError(f"query codes must be [Qn, {self.nbit}], got {tuple(query_codes.shape)}")
+        if query_codes.dim() != 2 or query_codes.shape[1] != self.nbit_in:
+            raise ValueError(f"query codes must be [Qn, {self.nbit_in}], got {tuple(query_codes.shape)}")
         if dense:
             query_codes = rt.check_dense_codes(query_codes, "query codes")
         codes = query_codes.to(self.device, torch.float32)
         if self.mean is not None and mean_shift:
             codes = codes - self.mean[None, :]
         checked = None if refuse is None else refuse(codes.shape[0])
+        if self.reduce_A is not None:           # every query, shifted or not: the chain the database went through, its centre included
+            codes = rt.project_codes(codes.contiguous(), self.reduce_mean, self._reduce_Ac, self.reduce_blocks, compact=True)
         if self.rotation is not None:
             codes = rt.rotate_codes(codes.contiguous(), self.rotation, self.rotation_blocks)
         return codes, rt.pack_sign(codes), checked

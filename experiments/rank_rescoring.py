@@ -12,7 +12,7 @@ import experiments.test_hashing as base
 import utils.hashing
 
 
-def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str, keys, on_call=None, finish=None, recode=None) -> dict:
+def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str, keys, on_call=None, finish=None, recode=None, also=()) -> dict:
     """`run()` -- the main() of the class that the calling class extends -- with every whole-code `calculate_mAP` call of the evaluator
     followed by the same call with the keyword arguments `again` (rank=..., and what goes with it) in place of those named in `drop`,
     on the codes the evaluator hands over.  The triple of a repeated call is printed under `label` (mAP) and `short` (P@k, R@k) and stored
@@ -20,6 +20,8 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
     `finish(res, calls)`, calls = [(the call's own mAP, postfix, its triple under the rank)], adds the class's extra results before
     `history.json` is written again.  `who` (the config key) opens the error messages.  `recode(db_codes, db_labels, test_codes,
     test_labels) -> (db_codes, test_codes)`, where given, makes the codes of the repeated call from the evaluator's (the learned rotation).
+    `also`: further repeated calls of the same kind, each (its keys, its recode, its label) -- the reduction's truncation baseline; their
+    triples are stored under their keys + the postfix, printed under their label, and not handed to `finish`.
     Passed through, scored once: a call under another rank (an evaluator further out repeating its own), the concepts' column slices
     -- under concept_eval the metric is reached Q times on them in front of the call on the whole code (experiments/concept_eval.py) --
     and the text evaluator's call on its prompts."""
@@ -47,7 +49,11 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
         db_again, test_again = (db_codes, test_codes) if recode is None else recode(db_codes, db_labels, test_codes, test_labels)
         other = metric(db_again, db_labels, test_again, test_labels, R, **again, **{key: v for key, v in k.items() if key not in drop})
         utils.hashing.last_tie_bracket, utils.hashing.last_hash_lookup, utils.hashing.last_tie_expected = left
-        calls.append((out[0], other))
+        more = []
+        for _, rc, _ in also:
+            db_more, test_more = rc(db_codes, db_labels, test_codes, test_labels)
+            more.append(metric(db_more, db_labels, test_more, test_labels, R, **again, **{key: v for key, v in k.items() if key not in drop}))
+        calls.append((out[0], other, more))
         if on_call is not None:
             on_call(db_codes, test_codes)
         many = isinstance(other[0], list)
@@ -55,6 +61,9 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
             print(f"mAP@{r_} ({label}): {m:.4f}")
         for kk, r, p in zip(k.get("PRs") or [], other[1], other[2]):
             print(f"P@{kk} ({short}): {p:.4f}; R@{kk} ({short}): {r:.4f}")
+        for (_, _, label_more), triple in zip(also, more):
+            for r_, m in (zip(R, triple[0]) if many else [(R, triple[0])]):
+                print(f"mAP@{r_} ({label_more}): {m:.4f}")
         return out
     # This wrapper stands where the metric itself stood, under both names it is reached by: the evaluator calls `calculate_mAP` of its
     # own module, and the evaluators the calling class extends rebind that name (or utils.hashing's) for their run on top of it and end
@@ -79,13 +88,16 @@ def main_under_rank(ev, run, who: str, again: dict, drop, label: str, short: str
             ev._phase = phase
     # the evaluator stored each call's mAP object under "mAP" + postfix: find it by identity, not by position or key order
     stored = []
-    for mAP, other in calls:
+    for mAP, other, more in calls:
         found = [k for k, v in res.items() if v is mAP and k.startswith("mAP")]
         if len(found) != 1:
             raise RuntimeError(f"{who}: a calculate_mAP result is stored under {found} in the results, expected one key")
         postfix = found[0][len("mAP"):]
         for key, v in zip(keys, other):
             res[key + postfix] = v
+        for (keys_more, _, _), triple in zip(also, more):
+            for key, v in zip(keys_more, triple):
+                res[key + postfix] = v
         stored.append((mAP, postfix, other))
     if finish is not None:
         finish(res, stored)

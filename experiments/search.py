@@ -5,6 +5,12 @@
         [query_text="painted bunting" | query_text=[...] | query_text_file=<file> | query=classes] [prompt_prefix=...] [text_model=<dir>]
         [only_classes=[3,"Painted Bunting"]] [exclude_classes=[...]] [exclude_self=true] [same_class=only|exclude]
         [rotate=itq] [rotate_blocks=<int>] [rotate_iters=50]
+        [reduce=pca-itq|pca reduce_bits=<m>] [reduce_blocks=<int>] [reduce_iters=50]
+
+Reduction ("reduction"): `reduce=pca-itq reduce_bits=<m>` fits a block-wise PCA of the database's real-valued codes
+to `m` dimensions, and behind it a rotation (`reduce=pca`: none), once (`GalleryIndex.fit_reduction`; `reduce_blocks` blocks, the run's
+ncontext by default), keeps it in the index -- then an ordinary index of `m` bits -- and reduces every query; an index built under another
+`reduce` setting is stale, and `reduce` together with `rotate` is a ValueError.  `results.json` records it under "reduction".
 
 Learned rotation ("learned rotation"): `rotate=itq` fits a block-diagonal rotation to the database's real-valued
 codes once (`GalleryIndex.fit_rotation`; `rotate_blocks` blocks, the run's ncontext by default, at most `rotate_iters` updates), keeps it in
@@ -163,6 +169,37 @@ def rotation_request(config):
     return {"method": "itq", "blocks": blocks, "iters": iters}
 
 
+def reduction_request(config):
+    """The reduction of an invocation, from its config alone (no model, no GPU): None without `reduce`, else a dict with `method`
+    ("pca-itq" | "pca"), `bits` (reduce_bits: required), `blocks` (reduce_blocks, or the run's ncontext) and `iters`.  An error names
+    the key; `reduce` beside `rotate` is refused."""
+    method, bits = config.get("reduce"), config.get("reduce_bits")
+    blocks, iters = config.get("reduce_blocks"), config.get("reduce_iters")
+    if method is None or str(method) in ("", "none", "None"):
+        if bits is not None or blocks is not None:
+            raise ValueError(f"reduce_bits={bits!r} / reduce_blocks={blocks!r} without reduce=pca-itq|pca")
+        return None
+    if str(method) not in rt.REDUCE_METHODS:
+        raise ValueError(f"reduce must be one of {rt.REDUCE_METHODS} (or left out), got {method!r}")
+    rotate = config.get("rotate")
+    if rotate is not None and str(rotate) not in ("", "none", "None"):
+        raise ValueError(f"reduce={method} together with rotate={rotate} is not built: reduce=pca-itq holds its own rotation")
+    if bits is None:
+        raise ValueError(f"reduce={method} needs reduce_bits=<m>, the code length to reduce to (no default)")
+    nbit, ncontext = int(config.model.nbit), int(config.model.ncontext)
+    if blocks is None:
+        blocks = ncontext
+    if isinstance(blocks, bool) or not isinstance(blocks, int) or blocks < 1 or nbit % blocks:
+        raise ValueError(f"reduce_blocks must be an int >= 1 that divides nbit = {nbit}, got {blocks!r}")
+    if isinstance(bits, bool) or not isinstance(bits, int) or not blocks <= bits <= nbit or bits % blocks or bits % ncontext:
+        raise ValueError(f"reduce_bits must be an int in [reduce_blocks, nbit] = [{blocks}, {nbit}], a multiple of reduce_blocks = {blocks} "
+                         f"and of ncontext = {ncontext}, got {bits!r}")
+    iters = 50 if iters is None else iters
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError(f"reduce_iters must be an int >= 1, got {iters!r}")
+    return {"method": str(method), "bits": bits, "blocks": blocks, "iters": iters}
+
+
 class SearchExperiment:
     def __init__(self, config: DictConfig):
         import torch.distributed as dist
@@ -175,6 +212,7 @@ class SearchExperiment:
         self.text = text_request(config)              # None: image queries.  Argument errors surface here, before anything is loaded
         self.filter = filter_request(config)          # None: every row may be a hit
         self.rotation = rotation_request(config)      # None: the codes are searched as the model gives them
+        self.reduction = reduction_request(config)    # None: at the length the model gives them
         if self.filter is not None and self.filter["exclude_self"] and self.text is not None:
             raise ValueError("exclude_self=true needs image queries: a text query is no database row")
         engine.seeding(config["seed"])
@@ -192,7 +230,7 @@ class SearchExperiment:
         self.ternary = str(config.get("rank", "hamming") or "hamming") == "ternary"
         self.index_margin = rt.check_margin(config.get("index_margin", 0.0) or 0.0, "index_margin") if self.ternary else None
         # rank=cosine | euclidean | dot rank the real-valued codes themselves: the index then carries them as its real plane
-        # (so does rotate=itq: the rotation is fitted to them)
+        # (so do rotate=itq and reduce=...: they are fitted to them)
         self.dense = str(config.get("rank", "hamming") or "hamming") in rt.DENSE_METRICS
 
         # the index first: whether the database split has to be encoded decides what is loaded
@@ -250,6 +288,11 @@ class SearchExperiment:
         if have != want:
             raise StaleIndexError(f"{self.index_path} was built under rotate = {have}; this run asks for {want} ((method, blocks); None: no "
                                   f"rotation): rebuild the index (rebuild_index=true)")
+        have = None if index.reduce_A is None else (index.reduce_info.get("method"), index.nbit, index.reduce_blocks)
+        want = None if self.reduction is None else (self.reduction["method"], self.reduction["bits"], self.reduction["blocks"])
+        if have != want:
+            raise StaleIndexError(f"{self.index_path} was built under reduce = {have}; this run asks for {want} ((method, bits, blocks); "
+                                  f"None: no reduction): rebuild the index (rebuild_index=true)")
 
     def _build_index(self) -> GalleryIndex:
         _, out = self._phase("encode_db", self.trainer.inference_one_epoch, "db", True)
@@ -267,7 +310,10 @@ class SearchExperiment:
                              paths=[p for p, _ in items] if items is not None else None,
                              data_root=getattr(ds, "root", None) if items is not None else None, mean=mean,
                              transform=self._transform_settings(), fingerprint=self.fingerprint, mask=mask, margin=self.index_margin,
-                             real=codes if self.dense or self.rotation is not None else None)
+                             real=codes if self.dense or self.rotation is not None or self.reduction is not None else None)
+        if self.reduction is not None:
+            red = self.reduction
+            index = self._phase("fit_reduction", index.fit_reduction, red["bits"], red["blocks"], red["iters"], red["method"])
         if self.rotation is not None:
             index = self._phase("fit_rotation", index.fit_rotation, self.rotation["blocks"], self.rotation["iters"])
         self._phase("index_save", index.save, self.index_path)
@@ -446,6 +492,7 @@ class SearchExperiment:
                "prefix": None if self.text is None else self.text["prefix"], "text_model": None if self.text is None else self.text["text_model"],
                "filter": None if self.filter is None else dict(self.filter, rows_admitted=int(res["rows_admitted"])),
                "rotation": None if index.rotation is None else dict(index.rotation_info, keeps_concepts=index.keeps_concepts),
+               "reduction": None if index.reduce_A is None else dict(index.reduce_info, keeps_concepts=index.keeps_concepts),
                "center_agreement": agreement, "mean_shift": self.text is None and index.mean is not None, "queries": queries,
                "timing_s": dict(self.timing, since_start=round(time.time() - self.start_time, 3))}
         with open(os.path.join(self.search_logdir, "results.json"), "w") as f:

@@ -660,6 +660,25 @@ int ch_itq_step(const float *codes, int64_t rows, int32_t n, const float *R, int
 /* out [rows,n] fp32 = the chain above. */
 int ch_itq_rotate(const float *codes, int64_t rows, int32_t n, const float *R, int32_t block, float *out, void *stream);
 
+/* Reduction ("reduction"): the moments a PCA of real-valued codes is fitted on, and the projection that applies
+ * it.  codes [rows,n] fp32 row-major, 1 <= n <= 256; blocks of `block` = s columns (s divides n).  shift: fp32 [n] or NULL;
+ * y = fl32(x - shift), one rounding (y = x under NULL).
+ * ch_pca_moments: out_sum [n] fp64, sum[j] = sum_i y_ij; out_gram [n,s] fp64 or NULL (only the sums are wanted),
+ * gram[b s + a, c] = sum_i y_{i, b s + a} y_{i, b s + c}.  Both WRITTEN.  Inside a segment of seg_rows rows (1 .. 4096; 0: chosen
+ * here) every entry of gram is one fp32 chain in row order, acc = fmaf(y_a, y_c, acc), and a sum is a fixed tree of plain fp32 adds
+ * (P = max(1, 256 / n) interleaved row-order chains, added in the order 0 .. P-1); the segments' partials are added in fp64 in segment
+ * order.  No atomics: two calls on the same inputs give the same bits, and gram is exactly symmetric inside a block.  workspace:
+ * ch_pca_moments_workspace bytes (with_gram: whether out_gram is given), 8-byte aligned (as out_sum and out_gram).  rows == 0:
+ * status 0, nothing launched, nothing written. */
+size_t ch_pca_moments_workspace(int64_t rows, int32_t n, int32_t block, int32_t seg_rows, int32_t with_gram);
+int ch_pca_moments(const float *codes, int64_t rows, int32_t n, int32_t block, const float *shift, int32_t seg_rows, double *out_sum,
+                   double *out_gram, void *workspace, size_t workspace_bytes, void *stream);
+/* out [rows, blocks t] fp32, 1 <= t <= s.  A is block-structured and passed compact, [n,t] fp32 row-major: row b s + l holds A_b[l, :].
+ * out[i, b t + j] is the chain acc = 0; for l = 0 .. s-1: acc = fmaf(fl32(codes[i, b s + l] - shift[b s + l]), A_b[l, j], acc), in
+ * this order: a row projects to the same bits alone or in a batch, and with t == s and shift == NULL it is ch_itq_rotate's chain. */
+int ch_pca_project(const float *codes, int64_t rows, int32_t n, int32_t block, const float *shift, const float *A, int32_t t, float *out,
+                   void *stream);
+
 /* Tie bracket: for every query and rank limit the smallest and the largest AP@R that ANY order of the rows sharing a Hamming distance
  * can give (the ranking of the passes above breaks such ties by gallery index; another implementation's sort need not).
  * bucket_counts [Qn, nb, 2] uint32, nb = 64 W + 1: rows / relevant rows of each query at each distance over the WHOLE gallery -- the

@@ -3,7 +3,7 @@
 
     python main_v2.py --config-name val.yaml logdir=<run dir> dataset=cub200 [R=-1] [PRs=[1,5,10]] [batch_size=64] ...
     python main_v2.py exp=extract model=concept_hash_final_v1_nosa_apt dataset=synthetic_cub200 ...
-    python main_v2.py --config-name search.yaml logdir=<run dir> dataset=cub200 [query=test] [k=10] [radius=2] [concepts=[0,2]] [rotate=itq] ...
+    python main_v2.py --config-name search.yaml logdir=<run dir> dataset=cub200 [query=test] [k=10] [radius=2] [concepts=[0,2]] [rotate=itq] [reduce=pca-itq reduce_bits=32] ...
 
 `exp` dispatch: hashing -> RetrievalExperiment (train the adapters + hashing head, frozen backbone); validation -> load
 <logdir>/config.yaml, overlay the evaluation knobs, RetrievalEvaluation; search -> the same run config, SearchExperiment (ranked hits of
@@ -32,12 +32,13 @@ EVAL_KEYS = ("dataset", "data_dir", "work_dir", "eval_logdir", "R", "PRs", "use_
 # knobs of this implementation's evaluation loop (configs/val.yaml), overlaid the same way
 LOOP_KEYS = ("eval_batch_min", "meter_stream", "tie_bracket", "tie_expected", "concept_eval", "hash_lookup_radii", "asymmetric_eval", "weight_bits", "text_eval",
              "prompt_prefix", "text_model", "ternary_eval", "ternary_margin", "dense_eval", "dense_metric", "rerank_eval", "rerank_metric",
-             "rerank_shortlist", "itq_eval", "itq_blocks", "itq_iters")
+             "rerank_shortlist", "itq_eval", "itq_blocks", "itq_iters", "reduce_eval", "reduce_bits", "reduce_method", "reduce_blocks",
+             "reduce_iters")
 # exp=search (configs/search.yaml, experiments/search.py): what it takes from the command line over the run's own config
 SEARCH_KEYS = ("dataset", "data_dir", "work_dir", "search_logdir", "use_last", "batch_size", "zero_mean_eval", "query", "k", "concepts",
                "query_margin", "index", "rebuild_index", "save_attention", "rank", "index_margin", "weight_bits", "radius", "query_text", "query_text_file",
                "prompt_prefix", "text_model", "shortlist", "only_classes", "exclude_classes", "exclude_self", "same_class", "rotate",
-               "rotate_blocks", "rotate_iters")
+               "rotate_blocks", "rotate_iters", "reduce", "reduce_bits", "reduce_blocks", "reduce_iters")
 
 
 def _run_config(config, exp, keys):
@@ -86,6 +87,8 @@ def run(config):
             from experiments.rerank_eval import RerankEvaluation as RetrievalEvaluation
         if load_config.get("itq_eval"):         # ... + the Hamming ranking once more after a rotation fitted to the database codes (it extends all eight)
             from experiments.itq_eval import ItqEvaluation as RetrievalEvaluation
+        if load_config.get("reduce_eval"):      # ... + the Hamming ranking once more at reduce_bits bits, PCA(-ITQ) beside dropping bits (it extends all nine)
+            from experiments.reduce_eval import ReduceEvaluation as RetrievalEvaluation
         experiment = RetrievalEvaluation(load_config)
     elif config.exp == "search":
         from experiments.search import SearchExperiment
