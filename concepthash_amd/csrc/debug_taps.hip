@@ -197,6 +197,19 @@ extern "C" int ch_debug_attention_causal(const void *qkv, int32_t B, int32_t nto
     return ch_attention_causal((const bf16_t *)qkv, B, ntok, heads, (bf16_t *)out, (hipStream_t)stream);
 }
 
+// ---- the text tower's own two kernels (text_model.hip), each launcher by itself on caller buffers (tests/test_text_chain_gpu.py).
+// Device pointers only: ids and eos are NOT range-checked here (ch_text_encode checks its host arrays; the test supplies valid ones).
+extern "C" int ch_debug_text_embed(const int32_t *ids, int32_t rows, int32_t T, int32_t D, const float *tok, const float *pos, float *H,
+                                   void *stream) {
+    CH_REQUIRE(ids && tok && pos && H, "debug_text_embed: null argument");
+    return ch_text_embed(ids, rows, T, D, tok, pos, H, (hipStream_t)stream);
+}
+extern "C" int ch_debug_text_pool(const float *H, const int32_t *eos, int32_t nrows, int32_t T, int32_t D, const float *w, const float *b,
+                                  float eps, float *out, void *stream) {
+    CH_REQUIRE(H && w && b && out, "debug_text_pool: null argument");
+    return ch_text_pool(H, eos, nrows, T, D, w, b, eps, out, (hipStream_t)stream);
+}
+
 extern "C" int ch_debug_adapter(const void *A, float *H, int32_t M, int32_t D, int32_t b, const float *Wd, const float *bd,
                                 const float *gamma, const float *beta, const void *Wu_bf16_padded, const float *bu,
                                 const float *scale, void *work_wdf, float *work_c, float *work_d, int32_t dbg, void *stream) {

@@ -301,6 +301,13 @@ int ch_convert_bf16(const float *x, int64_t rows, int cols, int cols_pad, bf16_t
 int ch_bn_fold(const float *w, const float *b, const float *mean, const float *var, int n, float eps, float *scale,
                float *shift, hipStream_t s);
 
+// ---- text_model.hip (the two kernels of the CLIP text tower that are its own; D % 128 == 0, D <= 1280) -------------------------
+// H[row] = tok[ids[row]] + pos[row % T] for row < rows, fp32; ids on the device, every one a row of tok (the caller's check)
+int ch_text_embed(const int32_t *ids, int rows, int T, int D, const float *tok, const float *pos, float *H, hipStream_t s);
+// out[r] = LayerNorm(H[src(r)]) in fp32 for r < nrows: src = r * T + eos[r] (eos on the device, each in [0, T)), or r when eos is null
+int ch_text_pool(const float *H, const int32_t *eos, int nrows, int T, int D, const float *w, const float *b, float eps, float *out,
+                 hipStream_t s);
+
 // ---- training step (train_kernels.hip, attention_bwd.hip; orchestration in train.hip) -----------------------------------------
 // fp32 rows -> bf16 copy + per-64-column (sum, sum of squares) partials [rows, D/64, 2] (what the LN-folded GEMMs consume)
 int ch_hb_stats(const float *H, int64_t rows, int D, bf16_t *hb, float *stats, hipStream_t s);

@@ -175,8 +175,7 @@ int run_text(ch_text *m, int B, int T, float *out_pooled, float *out_hidden, hip
     const ch_text_config &c = m->cfg;
     const int D = c.dim, M = c.ffn, rows = B * T;
     const int act_epi = c.act == 0 ? EPI_BIAS_QUICKGELU : EPI_BIAS_GELU;
-    hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, s, m->ids, rows, T, D, m->tok, m->pos, m->H);
-    CH_LAUNCH_CHECK();
+    if (int e = ch_text_embed(m->ids, rows, T, D, m->tok, m->pos, m->H, s)) return e;
     auto gemm = [&](const bf16_t *X, const bf16_t *W, int N, int K, const float *bias, int epi, bf16_t *out, int ldo) {
         GemmParams p{};
         p.X = X; p.W = W; p.M = rows; p.N = N; p.K = K; p.X_rows_alloc = m->rows_alloc; p.bias = bias;
@@ -192,18 +191,31 @@ int run_text(ch_text *m, int B, int T, float *out_pooled, float *out_hidden, hip
         if (int e = gemm(m->Xn, w.fc1_w, M, D, w.fc1_b, act_epi, m->F1, M)) return e;
         if (int e = gemm(m->F1, w.fc2_w, D, M, w.fc2_b, EPI_BIAS_RESID, m->A, D)) return e;
     }
-    hipLaunchKernelGGL(text_pool_kernel, dim3((unsigned)ceil_div64(B, 4)), dim3(256), 0, s, m->H, m->eos, B, T, D, m->fln_w, m->fln_b, c.ln_eps,
-                       out_pooled);
-    CH_LAUNCH_CHECK();
-    if (out_hidden) {
-        hipLaunchKernelGGL(text_pool_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, s, m->H, (const int32_t *)nullptr, rows, T, D,
-                           m->fln_w, m->fln_b, c.ln_eps, out_hidden);
-        CH_LAUNCH_CHECK();
-    }
+    if (int e = ch_text_pool(m->H, m->eos, B, T, D, m->fln_w, m->fln_b, c.ln_eps, out_pooled, s)) return e;
+    if (out_hidden)
+        if (int e = ch_text_pool(m->H, nullptr, rows, T, D, m->fln_w, m->fln_b, c.ln_eps, out_hidden, s)) return e;
     return 0;
 }
 
 }  // namespace
+
+// the launchers of the two kernels (kernels.h): what run_text calls, and what the taps of debug_taps.hip launch on caller buffers
+int ch_text_embed(const int32_t *ids, int rows, int T, int D, const float *tok, const float *pos, float *H, hipStream_t s) {
+    CH_REQUIRE(D > 0 && D % 128 == 0 && D <= 128 * MAXP, "text_embed: D must be a multiple of 128 and <= 1280");
+    CH_REQUIRE(rows >= 1 && T >= 1, "text_embed: rows and T must be >= 1");
+    hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, s, ids, rows, T, D, tok, pos, H);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
+
+int ch_text_pool(const float *H, const int32_t *eos, int nrows, int T, int D, const float *w, const float *b, float eps, float *out,
+                 hipStream_t s) {
+    CH_REQUIRE(D > 0 && D % 128 == 0 && D <= 128 * MAXP, "text_pool: D must be a multiple of 128 and <= 1280");
+    CH_REQUIRE(nrows >= 1 && T >= 1, "text_pool: nrows and T must be >= 1");
+    hipLaunchKernelGGL(text_pool_kernel, dim3((unsigned)ceil_div64(nrows, 4)), dim3(256), 0, s, H, eos, nrows, T, D, w, b, eps, out);
+    CH_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int ch_text_create(const ch_text_config *cfg, const ch_tensor *tensors, int32_t ntensors, ch_text **out) {
     CH_REQUIRE(out != nullptr, "null out pointer");

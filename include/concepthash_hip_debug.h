@@ -172,6 +172,15 @@ int ch_debug_bn_fold(const float *w, const float *b, const float *mean, const fl
 int ch_debug_fold_ln(const float *Wd, const float *bd, const float *gamma, const float *beta, int32_t b, int32_t bpad, int32_t D, void *Wdf,
                      float *c, float *d, void *stream);
 
+/* The two kernels that are the text tower's own (text_model.hip), through the launchers ch_text_encode's chain calls, on caller buffers
+ * (tests/test_text_chain_gpu.py; references in tests/text_chain_ref.py).  D % 128 == 0, D <= 1280.  Device pointers only, and NO range
+ * check of ids / eos (ch_text_encode checks its host arrays): every id must be a row of tok, every eos entry in [0, T).
+ * text_embed: H[row] = tok[ids[row]] + pos[row % T] for row < rows (fp32, one addition).
+ * text_pool: out[r] = LayerNorm(H[eos ? r * T + eos[r] : r]) for r < nrows, fp32 in and out (two-pass mean / variance). */
+int ch_debug_text_embed(const int32_t *ids, int32_t rows, int32_t T, int32_t D, const float *tok, const float *pos, float *H, void *stream);
+int ch_debug_text_pool(const float *H, const int32_t *eos, int32_t nrows, int32_t T, int32_t D, const float *w, const float *b, float eps,
+                       float *out, void *stream);
+
 /* Copy one of the centre arrays a model holds since ch_model_create to `out` (device): which = 0 `center` [C, center_dim] as ingested |
  * 1 center_l2 [C, nbit] (projected, l2-normalised) | 2 center_bin [C, nbit] (its signs / sqrt(nbit)).  tests/test_text_query_gpu.py
  * holds ch_model_project_text + the normalisation launch against 1 and 2, bit for bit. */
