@@ -19,6 +19,19 @@
 // (arithmetic, lossless, CMYK / Adobe RGB, 12 bit, multi-scan sequential, exotic sampling, tiny images, a progressive file whose low
 // coefficients are not fully refined -- libjpeg smooths those) gets a non-zero `status` in its descriptor: the host side of the loader
 // decodes exactly those files with PIL -- the reference's own path -- and counts them.
+// "Bit-equal" covers DAMAGED files too, by flagging instead of guessing after the entropy decode:
+//   * status 13 -- a block outside the DOMAIN in which the restated IDCT is libjpeg-turbo's: every dequantised value coef * quant fits
+//     int16, every pass-1 workspace value fits int16, every pass-2 output before the level shift lies in [-512, 511].  Outside it Pillow's
+//     SIMD IDCT saturates 16-bit lanes where the restated one keeps wide integers and wraps in the range-limit table.  An encoder never
+//     writes such a block; a few overwritten bytes can.  Checked per block while the coefficients are copied out (check_domain_and_copy:
+//     a sufficient bound on the sum of |coef * quant| first, the three conditions in full for the blocks that miss it).  Inside the domain
+//     the kernel's int32 arithmetic cannot overflow: the largest value of a pass before its descale is below 2.006e9 < 2^31.
+//   * status 11 -- besides an invalid code or a run past the block: a data segment (up to a restart marker or the end of a scan) that
+//     ends before its last MCU, so that the decoder consumed bits the file does not have.  libjpeg warns there and recovers (zero bits to
+//     the end of the MCU, then every MCU skipped up to the next restart); the recovery is not restated (BitReader::overran).  The cost: when the overrun lies in the LAST MCU of its segment there is nothing
+//     to skip and libjpeg's pixels are the ones decoded here, yet the file is reported all the same -- 29 of the 824 damaged test files
+//     (3.5 %) that both decoders used to accept went to PIL although they were bit-equal; 180 of the 824 get status 11 for this reason
+//     in all, 44 status 13, 600 stay (tests/test_jpeg.py).
 // This file is plain C++ (no HIP): marker parsing, the Huffman / progressive entropy decode and the batch file reads.  It is compiled into
 // the library by the normal build AND, by tests/test_jpeg.py, into a stand-alone AddressSanitizer + UBSan object that the mutation test of
 // the decoder runs against (the decoder parses bytes from disk).  The GPU half (kernels + ch_jpeg_reconstruct) is jpeg.hip.
@@ -126,7 +139,8 @@ struct Parsed {
 // status codes (also documented in include/concepthash_hip.h)
 enum {
     JS_OK = 0, JS_NOT_JPEG = 1, JS_TRUNCATED = 2, JS_PROGRESSIVE_OR_OTHER_SOF = 3, JS_PRECISION = 4, JS_COMPONENTS = 5,
-    JS_SAMPLING = 6, JS_MULTISCAN = 7, JS_COLORSPACE = 8, JS_TABLES = 9, JS_TINY = 10, JS_CORRUPT = 11, JS_TOO_LARGE = 12
+    JS_SAMPLING = 6, JS_MULTISCAN = 7, JS_COLORSPACE = 8, JS_TABLES = 9, JS_TINY = 10, JS_CORRUPT = 11, JS_TOO_LARGE = 12,
+    JS_OUT_OF_DOMAIN = 13
 };
 // Pillow refuses images of more than 2 x MAX_IMAGE_PIXELS (DecompressionBombError): such a file is left to it, so that the caller sees the
 // reference's error instead of a multi-gigabyte coefficient buffer
@@ -303,6 +317,7 @@ struct BitReader {
     int bits = 0;
     bool marker = false;   // a marker (FF xx, xx != 0) was reached: only zero bits are fed from here on
     bool eof = false;      // ... or the FILE ended inside the entropy-coded data (a truncated file: libjpeg warns, Pillow raises)
+    int pad = 0;           // zero bits appended to `acc` since the marker was reached (they are its LOWEST valid bits)
 
     // callers need at most 31 valid bits at a time (a 16-bit code + a 15-bit magnitude): top up only when fewer than 32 are left
     inline void ensure32() {
@@ -342,12 +357,17 @@ struct BitReader {
                 if (!marker) eof = true;
                 marker = true;
             }
+            if (marker) pad += 8;
             acc |= (uint64_t)b << (56 - bits);
             bits += 8;
         }
     }
     inline unsigned peek(int n) const { return (unsigned)(acc >> (64 - n)); }
     inline void skip(int n) { acc <<= n; bits -= n; }
+    // Did the decoder CONSUME bits that are not in the file -- the zeros fed after a marker?  libjpeg warns there ("premature end of
+    // data segment"), finishes the MCU on zero bits and then SKIPS every MCU up to the next restart marker; that recovery is not restated,
+    // so a segment that ends early is reported (JS_CORRUPT).  Asked at the end of every segment (before a restart marker, after a scan).
+    inline bool overran() const { return pad > bits; }
 };
 
 inline int extend(int v, int s) { return v < (1 << (s - 1)) ? v + (int)((~0u) << s) + 1 : v; }
@@ -433,6 +453,8 @@ struct CompGrid {
 
 // byte-align and consume the expected RSTn; false when it is not there
 inline bool take_restart(BitReader &br, int &next_rst) {
+    if (br.overran()) return false;
+    br.pad = 0;
     br.acc = 0;
     br.bits = 0;
     br.marker = false;
@@ -645,6 +667,7 @@ int decode_progressive(const uint8_t *d, int64_t n, const ch_jpeg_desc &desc, Pa
                     }
                 }
             if (br.eof) return JS_TRUNCATED;
+            if (br.overran()) return JS_CORRUPT;
             // the next marker: the reader never steps over one, so it is at or after br.p
             const uint8_t *q = br.p;
             while (q + 1 < br.end && !(q[0] == 0xFF && q[1] != 0 && q[1] != 0xFF && !(q[1] >= 0xD0 && q[1] <= 0xD7))) ++q;
@@ -681,6 +704,8 @@ int entropy_decode_one(const uint8_t *d, int64_t n, const ch_jpeg_desc &desc, in
             if (P.restart) {
                 if (to_restart == 0) {
                     // byte-align, expect RSTn
+                    if (br.overran()) return JS_CORRUPT;
+                    br.pad = 0;
                     br.acc = 0;
                     br.bits = 0;
                     br.marker = false;
@@ -711,7 +736,112 @@ int entropy_decode_one(const uint8_t *d, int64_t n, const ch_jpeg_desc &desc, in
     }
     // the data ran out before a marker: a truncated file.  What was decoded is zero-padded garbage from there on; Pillow raises on
     // such a file, so it is handed to the caller's decoder, which will say so
-    return br.eof ? JS_TRUNCATED : JS_OK;
+    return br.eof ? JS_TRUNCATED : br.overran() ? JS_CORRUPT : JS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host: the DOMAIN of the restated arithmetic.  jpeg.hip restates the C `jpeg_idct_islow` (32-bit workspace, a range-limit table that
+// WRAPS at 1024); Pillow's libjpeg-turbo runs a SIMD IDCT in 16-bit lanes that SATURATE.  The two give the same samples exactly when,
+// for every block,
+//   (1) every dequantised value coef * quant fits int16,
+//   (2) every pass-1 workspace value fits int16,
+//   (3) every pass-2 output, before the level shift, lies in [-512, 511] (where the wrap table and a saturation agree).
+// An encoder never leaves that domain (its coefficients come from samples in [0, 255]); a damaged-but-decodable file can, and is then
+// reported (JS_OUT_OF_DOMAIN) for the caller's PIL instead of being reconstructed to other pixels than the reference's.  Inside the
+// domain the kernel's int32 arithmetic cannot overflow: a pass is linear in its eight inputs before the descale, the absolute row sum of
+// its integer matrix is at most 61,214 (the IDCT_G table below), so with inputs within int16 every pre-descale value is below
+// 61,214 * 32,768 + 2^17 = 2.006e9 < 2^31.
+//
+// The check is exact but cheap: a sufficient bound passes nearly every block, the others are evaluated in full.  With D = |dequantised
+// DC| and A = the sum of the |dequantised AC| of a block, and G the integer matrix of one pass (G[x][0] = 8192, |G[x][k]| <= 11363):
+//   pass 1:  ws = (G-combination of a column) / 2^11 + e1, |e1| <= 1/2            =>  |ws| <= 4 D + 5.549 A + 1/2
+//   pass 2:  out = (G-combination of a row of ws) / 2^18 + e2, |e2| <= 1/2; the e1 of a row add up to at most 61214 / 2 / 2^18 = 0.117
+//            =>  |out| <= D * 8192^2 / 2^29 + A * 11363^2 / 2^29 + 0.617 = D / 8 + 0.24051 A + 0.617
+// so 32 D + 62 A <= 510 * 256 gives |out| <= 510.7 (3), |ws| <= 16,321 (2) and |coef * quant| <= 4,080 (1).
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int64_t IDCT_G[8][8] = {{8192, 11363, 10703, 9633, 8192, 6437, 4433, 2260},   {8192, 9633, 4433, -2259, -8192, -11362, -10704, -6436},
+                                  {8192, 6437, -4433, -11362, -8192, 2261, 10704, 9633}, {8192, 2260, -10703, -6436, 8192, 9633, -4433, -11363},
+                                  {8192, -2260, -10703, 6436, 8192, -9633, -4433, 11363}, {8192, -6437, -4433, 11362, -8192, -2261, 10704, -9633},
+                                  {8192, -9633, 4433, 2259, -8192, 11362, -10704, 6436}, {8192, -11363, 10703, -9633, 8192, -6437, 4433, -2260}};
+constexpr int kBoundLimit = 510 * 256;
+
+// the three conditions on one block, evaluated in full (64-bit: any int16 coefficient and any uint16 table entry may come in).  jidctint.c
+// sums the products of a pass in another order; before the descale that is the same integer.
+bool block_in_domain_exact(const int16_t *blk, const uint16_t *quant) {
+    int64_t v[64], ws[64];
+    for (int i = 0; i < 64; ++i) {
+        v[i] = (int64_t)blk[i] * quant[i];
+        if (v[i] < -32768 || v[i] > 32767) return false;
+    }
+    for (int c = 0; c < 8; ++c)
+        for (int x = 0; x < 8; ++x) {
+            int64_t a = 0;
+            for (int k = 0; k < 8; ++k) a += IDCT_G[x][k] * v[8 * k + c];
+            a = (a + (1 << 10)) >> 11;
+            if (a < -32768 || a > 32767) return false;
+            ws[8 * x + c] = a;
+        }
+    for (int r = 0; r < 8; ++r)
+        for (int x = 0; x < 8; ++x) {
+            int64_t a = 0;
+            for (int k = 0; k < 8; ++k) a += IDCT_G[x][k] * ws[8 * r + k];
+            a = (a + (1 << 17)) >> 18;
+            if (a < -512 || a > 511) return false;
+        }
+    return true;
+}
+
+struct DomainTable {
+    __m128i q[3][8];   // the component's table as int16 lanes (only when every entry is <= 255)
+    bool cheap[3];     // ... otherwise every block of the component is evaluated in full
+};
+
+// `n` blocks of one component: check each, and copy it to `dst` (with non-temporal stores when `stream`; src and dst are then 16-byte
+// aligned).  The copy already touches every coefficient, so the bound costs eight multiply-adds per block on data that is in registers.
+bool check_and_copy(const int16_t *src, int16_t *dst, int64_t n, const DomainTable &T, int comp, const uint16_t *quant, bool stream) {
+    const __m128i zero = _mm_setzero_si128();
+    for (int64_t b = 0; b < n; ++b, src += 64, dst += 64) {
+        __m128i row[8], acc = zero;
+        for (int r = 0; r < 8; ++r) {
+            row[r] = _mm_loadu_si128((const __m128i *)(src + 8 * r));
+            // |c| (saturating: -32768 -> 32767, far beyond the bound either way) times the table entry, summed in pairs: int32 lanes,
+            // at most 8 * 2 * 32767 * 255 < 2^28 each
+            const __m128i a = _mm_max_epi16(row[r], _mm_subs_epi16(zero, row[r]));
+            acc = _mm_add_epi32(acc, _mm_madd_epi16(a, T.q[comp][r]));
+        }
+        bool ok = false;
+        if (T.cheap[comp]) {
+            acc = _mm_add_epi32(acc, _mm_shuffle_epi32(acc, 0x4E));
+            acc = _mm_add_epi32(acc, _mm_shuffle_epi32(acc, 0xB1));
+            const int64_t l1 = (uint32_t)_mm_cvtsi128_si32(acc);
+            const int64_t dc = (int64_t)(src[0] < 0 ? -(int)src[0] : (int)src[0]) * quant[0];
+            ok = 32 * dc + 62 * (l1 > dc ? l1 - dc : 0) <= kBoundLimit;
+        }
+        if (!ok && !block_in_domain_exact(src, quant)) return false;
+        if (stream) {
+            for (int r = 0; r < 8; ++r) _mm_stream_si128((__m128i *)(dst + 8 * r), row[r]);
+        } else {
+            for (int r = 0; r < 8; ++r) _mm_storeu_si128((__m128i *)(dst + 8 * r), row[r]);
+        }
+    }
+    return true;
+}
+
+// one image: scratch -> destination, JS_OUT_OF_DOMAIN as soon as a block is outside the domain
+int check_domain_and_copy(const int16_t *src, int16_t *dst, const ch_jpeg_desc &d) {
+    DomainTable T;
+    for (int c = 0; c < d.ncomp; ++c) {
+        T.cheap[c] = true;
+        for (int i = 0; i < 64; ++i) T.cheap[c] = T.cheap[c] && d.quant[c][i] <= 255;
+        for (int r = 0; r < 8; ++r) T.q[c][r] = T.cheap[c] ? _mm_loadu_si128((const __m128i *)(d.quant[c] + 8 * r)) : _mm_setzero_si128();
+    }
+    const bool stream = ((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 15) == 0;
+    const int64_t nby = (int64_t)d.mcu_w * d.hs * d.mcu_h * d.vs, nbc = (int64_t)d.mcu_w * d.mcu_h;
+    bool ok = check_and_copy(src, dst, nby, T, 0, d.quant[0], stream);
+    for (int c = 1; ok && c < d.ncomp; ++c)
+        ok = check_and_copy(src + 64 * (nby + (c - 1) * nbc), dst + 64 * (nby + (c - 1) * nbc), nbc, T, c, d.quant[c], stream);
+    if (stream) _mm_sfence();   // weakly ordered stores: visible before this thread signals completion (the DMA engine reads them next)
+    return ok ? JS_OK : JS_OUT_OF_DOMAIN;
 }
 
 }  // namespace
@@ -765,15 +895,8 @@ extern "C" int ch_jpeg_entropy_decode(const uint8_t *const *files, const int64_t
                 desc[i].status = st;   // a corrupt stream: the caller falls back to its host decoder for this file
                 continue;
             }
-            int16_t *dst = coef_host + desc[i].coef_offset;
-            if (((uintptr_t)dst & 15) == 0 && ((uintptr_t)scratch.data() & 15) == 0) {
-                const __m128i *sv = (const __m128i *)scratch.data();
-                __m128i *dv = (__m128i *)dst;
-                for (size_t k = 0; k < ncoef / 8; ++k) _mm_stream_si128(dv + k, _mm_load_si128(sv + k));
-                _mm_sfence();   // weakly ordered stores: visible before this thread signals completion (the DMA engine reads them next)
-            } else {
-                std::memcpy(dst, scratch.data(), ncoef * 2);
-            }
+            // the copy is also the domain check (above): a file with a block outside the domain goes to the caller's host decoder
+            desc[i].status = check_domain_and_copy(scratch.data(), coef_host + desc[i].coef_offset, desc[i]);
         }
     };
     const int nt = std::max(1, std::min<int>(nthreads, n));

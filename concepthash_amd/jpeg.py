@@ -11,7 +11,13 @@ A 20k images/s encoder outruns that on any host, so here the loader only READS t
 leaving decoded RGB bytes in the layout `GpuPreprocess` / `ch_preprocess` consume.  The bytes are BIT-EQUAL to Pillow's
 (tests/test_jpeg.py).  Baseline and progressive Huffman files are covered; files outside the supported subset (CMYK, arithmetic coding,
 exotic sampling, truncated data, ...: `ch_jpeg_desc.status != 0`) are decoded with PIL on the host -- the reference's own path -- and copied
-into their slots; `stats` counts them.  There is no CPU fallback for the
+into their slots; `stats` counts them.  "Bit-equal" holds on damaged files too, because two things are flagged rather than guessed after
+the entropy decode: a data segment that ends before its last MCU (libjpeg warns and recovers; status 11), and a file with a block outside
+the DOMAIN in which the restated integer IDCT is libjpeg-turbo's (status 13): every dequantised value coef * quant fits int16, every
+pass-1 workspace value fits int16, every pass-2 output before the level shift lies in [-512, 511].  Pillow's SIMD IDCT saturates 16-bit
+lanes outside it, the restated one keeps wide integers and wraps in the range-limit table; inside it they agree and the kernel's int32
+arithmetic cannot overflow (a pass's largest value before the descale is below 61,214 * 32,768 + 2^17 = 2.006e9).  An encoder-written
+file never leaves the domain.  There is no CPU fallback for the
 supported files: without the HIP library or a GPU, construction raises."""
 from __future__ import annotations
 
@@ -33,7 +39,7 @@ assert DESC_DTYPE.itemsize == ctypes.sizeof(_lib.JpegDesc)
 
 STATUS = {0: "ok", 1: "not a JPEG", 2: "truncated", 3: "lossless / arithmetic / unfinished progressive", 4: "not 8 bit", 5: "component count",
           6: "sampling factors", 7: "multi-scan", 8: "colour space", 9: "tables", 10: "smaller than 16x16", 11: "corrupt entropy data",
-          12: "beyond Pillow's decompression-bomb limit"}
+          12: "beyond Pillow's decompression-bomb limit", 13: "coefficients outside the range libjpeg's decoders agree on"}
 
 
 _libc = None

@@ -44,14 +44,56 @@ def _idct_1d(v, shift):
     return _descale(out, shift)
 
 
-def idct_blocks(coef: np.ndarray, quant: np.ndarray) -> np.ndarray:
-    """coef [nblocks, 64] int16 (natural order), quant [64] -> samples [nblocks, 8, 8] uint8."""
+def idct_stages(coef: np.ndarray, quant: np.ndarray):
+    """coef [nblocks, 64] int16 (natural order), quant [64] -> (dequantised [n, 8, 8], pass-1 workspace [n, 8, 8], pass-2 output before
+    the level shift and the range limit [n, 8, 8]), all int64: the three places where `in_domain` looks."""
     v = coef.astype(np.int64).reshape(-1, 8, 8) * quant.astype(np.int64).reshape(1, 8, 8)
     ws = _idct_1d(np.swapaxes(v, 1, 2), CONST_BITS - PASS1_BITS)          # pass 1: columns ([block, col, row])
     ws = np.swapaxes(ws, 1, 2)                                            # -> [block, row, col]
-    out = _idct_1d(ws, CONST_BITS + PASS1_BITS + 3)                       # pass 2: rows
+    return v, ws, _idct_1d(ws, CONST_BITS + PASS1_BITS + 3)               # pass 2: rows
+
+
+def idct_blocks(coef: np.ndarray, quant: np.ndarray) -> np.ndarray:
+    """coef [nblocks, 64] int16 (natural order), quant [64] -> samples [nblocks, 8, 8] uint8."""
+    out = idct_stages(coef, quant)[2]
     idx = out & 1023                                                      # post-IDCT range-limit table, level shift included
     return np.where(idx < 128, idx + 128, np.where(idx < 512, 255, np.where(idx < 896, 0, idx - 896))).astype(np.uint8)
+
+
+def _get(desc):
+    return (lambda k: desc[k]) if isinstance(desc, (np.void, dict)) else (lambda k: getattr(desc, k))   # numpy record or ctypes struct
+
+
+def component_blocks(coef: np.ndarray, desc):
+    """-> [(this component's blocks [n, 64], its quant table [64])] in the order of the coefficient buffer."""
+    get = _get(desc)
+    hs, vs, mw, mh = (int(get(k)) for k in ("hs", "vs", "mcu_w", "mcu_h"))
+    q = np.asarray(get("quant"), dtype=np.int64).reshape(3, 64)
+    coef = coef.reshape(-1, 64)
+    nby, nbc = mw * hs * mh * vs, mw * mh
+    if int(get("ncomp")) == 1:
+        return [(coef[:nby], q[0])]
+    return [(coef[:nby], q[0]), (coef[nby:nby + nbc], q[1]), (coef[nby + nbc:nby + 2 * nbc], q[2])]
+
+
+I16_MIN, I16_MAX = -32768, 32767
+
+
+def blocks_in_domain(coef: np.ndarray, quant: np.ndarray) -> np.ndarray:
+    """Per block: is it inside the domain in which this restatement (wide integers, a range-limit table that WRAPS at 1024) and
+    libjpeg-turbo's SIMD `jsimd_idct_islow` (16-bit lanes that saturate) compute the same samples?
+      1. every dequantised value coef * quant fits int16,
+      2. every pass-1 workspace value fits int16,
+      3. every pass-2 output (before the level shift) lies in [-512, 511], where the wrap table and a saturation agree.
+    Encoder-written files are always inside; a damaged-but-decodable file may not be."""
+    v, ws, out = idct_stages(coef, quant)
+    ok = (v >= I16_MIN) & (v <= I16_MAX) & (ws >= I16_MIN) & (ws <= I16_MAX) & (out >= -512) & (out <= 511)
+    return ok.reshape(ok.shape[0], -1).all(axis=1)
+
+
+def in_domain(coef: np.ndarray, desc) -> bool:
+    """coef / desc as for `reconstruct`: every block of every component satisfies `blocks_in_domain`."""
+    return all(bool(blocks_in_domain(c, q).all()) for c, q in component_blocks(coef, desc))
 
 
 def _plane(blocks: np.ndarray, bh: int, bw: int) -> np.ndarray:
@@ -88,7 +130,7 @@ def _h2v2(p: np.ndarray) -> np.ndarray:
 def reconstruct(coef: np.ndarray, desc) -> np.ndarray:
     """coef: this image's int16 coefficients (component 0 blocks row-major, then components 1, 2); desc: its ch_jpeg_desc (any object
     with width, height, ncomp, hs, vs, mcu_w, mcu_h, quant) -> RGB uint8 [height, width, 3]."""
-    get = (lambda k: desc[k]) if isinstance(desc, (np.void, dict)) else (lambda k: getattr(desc, k))   # numpy record or ctypes struct
+    get = _get(desc)
     w, h, hs, vs, mw, mh = (int(get(k)) for k in ("width", "height", "hs", "vs", "mcu_w", "mcu_h"))
     q = np.asarray(get("quant"), dtype=np.int64).reshape(3, 64)
     nby = mw * hs * mh * vs
